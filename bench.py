@@ -14,8 +14,12 @@ MASTER_* exported, rendezvous on 127.0.0.1); under `python -m torch.distributed.
 exist and are used as they are.  Sequences are independent, each rank owns `--batch` of them, there is no data-path
 collective; a barrier brackets the timed region and the max time over ranks is used ("scaling": "weak").
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Beside the headline (`value`) it carries, at N = 1:
-  roofline         - dominant kernel: algorithmic bytes per launch / its mean hipEvent duration, vs 8 TB/s HBM
+Prints ONE JSON line on rank 0: `value` (scans/s) and `ms_per_step` of exactly `--steps` timed steps after `--warmup` untimed ones, with
+  roofline         - dominant kernel: algorithmic bytes per launch / its mean hipEvent duration, vs 8 TB/s HBM (hipEvents of the timed steps;
+                     with --contexts > 1 only under --full, which profiles one context in a pass of its own)
+`--dump-outputs DIR` writes what the last timed step computed (poses of every sequence, clouds of a seeded sample) as DIR/*.npy.
+A plain run does nothing else.  With `--full` the line also carries (all but repeated_blocks at N = 1 only):
+  repeated_blocks  - further identical K-step blocks timed until --repeat-to-seconds are covered (spread; never `value`)
   value_host_input - the same steps fed from pinned HOST memory: one batched H2D copy per step on a copy stream, double-buffered
                      against the kernels (aloam_process_host) — the PCIe-inclusive rate, never the headline
   workloads        - BASELINE.json configs[2] (odometry + laserMapping refinement every sweep) and configs[3] (128 x 2048
@@ -81,7 +85,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=120, help="timed steps of the headline leg (120 x ~9 ms: a timed region above one second); the other legs use min(steps, --extra-steps)")
     ap.add_argument("--extra-steps", type=int, default=30)
-    ap.add_argument("--repeat-to-seconds", type=float, default=1.0, help="after the K timed steps, time further identical K-step blocks until this many seconds are covered (0: off; always off with --no-extras); reported as repeated_blocks, never as `value`")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: repeated K-step blocks, four streams, host-fed rates, latency, "
+                    "accuracy against the oracle, CPU baselines and the configs[2] / [3] legs.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the K timed steps, write what the last of them computed as DIR/<name>.npy: the odometry (and, with "
+                    "--mapping, the refined) pose of every sequence of rank 0 and the published clouds of a fixed, seeded sample of them")
+    ap.add_argument("--repeat-to-seconds", type=float, default=1.0, help="with --full: after the K timed steps, time further identical K-step blocks until this many seconds are covered (0: off; always off with --no-extras); reported as repeated_blocks, never as `value`")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2048, help="independent sequences per GPU of the headline leg (round 6, kernel time per sequence: 1024 -> 8.72 us, 2048 -> 8.27, 4096 -> 8.27; 30 MB of HBM per sequence); the configs[2] / [3] comparison legs stay at min(batch, 1024)")
     ap.add_argument("--frames", type=int, default=6, help="stored sweeps per sequence (replayed ping-pong)")
@@ -93,9 +101,9 @@ def parse_args():
     ap.add_argument("--map-warmup", type=int, default=80, help="untimed steps of the configs[2] workload: 125 m of travel, after which the submap is stationary")
     ap.add_argument("--contexts", type=int, default=1, help="split the batch over this many contexts (= HIP streams) on the same GPU")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each CPU baseline leg (one thread; one process per core)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip host-input rate, configs[2]/[3] sub-workloads and latency")
-    ap.add_argument("--host-input", action="store_true", help="(kept for compatibility: the host-fed rate is part of the default line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the accuracy and CPU baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip repeated blocks, host-input rate, configs[2]/[3] sub-workloads and latency")
+    ap.add_argument("--host-input", action="store_true", help="(kept for compatibility: the host-fed rate is part of the --full line)")
     ap.add_argument("--latency-sweeps", type=int, default=120)
     ap.add_argument("--travel", action="store_true", help="odometry-only workload on the travelling drive (the configs[2] input: 1.6 m per sweep down a street, 120 m range) instead of laps of the 30 m circle; --frames distinct sweeps per sequence")
     ap.add_argument("--reference-order", action="store_true", help="run the workload of this call in the reference's voxel summation order (aloam_set_voxel_sum_order: the validation mode, std::sort replayed on the device) and say so in config")
@@ -233,11 +241,48 @@ def map_state(cx, n_seq=4):
     return out
 
 
-def timed_resident(torch, dist, world, ctxs, wl, steps, warmup, mapping, repeat_to_s=0.0, repeats_out=None, batch=None):
+DUMP_SAMPLE, DUMP_BYTES = 8, 60_000_000     # clouds of at most 8 sequences; all files together stay under 64 MB
+
+
+def dump_outputs(path, ctxs, mapping):
+    """What a caller of aloam_process_device (+ aloam_mapping_step) receives after the last step, as <path>/<name>.npy: the odometry pose
+    (odom_q_w, odom_t_w, odom_q_lc, odom_t_lc; float64, one row per sequence) and with mapping the refined pose (map_*) of EVERY sequence, then the
+    five clouds scan registration publishes (seqNNNN_cloud / sharp / less_sharp / flat / less_flat; float32 x y z intensity) and with mapping the
+    registered sweep (seqNNNN_registered) of a fixed, seeded sample of sequences, as many of the sample as fit into DUMP_BYTES."""
+    binding = importlib.import_module("a-loam_amd.binding")
+    BC = ctxs[0].batch
+    B = BC * len(ctxs)
+    seq = lambda b: (ctxs[b // BC], b % BC)                # sequence b of the batch lives in context b // BC (bench --contexts)
+    out = {}
+    poses = [cx.pose(s) for cx, s in map(seq, range(B))]
+    out.update({f"odom_{k}": np.stack([p[k] for p in poses]) for k in ("q_w", "t_w", "q_lc", "t_lc")})
+    if mapping:
+        poses = [cx.map_pose(s) for cx, s in map(seq, range(B))]
+        out.update({f"map_{k}": np.stack([p[k] for p in poses]) for k in ("q_w", "t_w", "q_wmap_wodom", "t_wmap_wodom")})
+    budget = DUMP_BYTES - sum(a.nbytes for a in out.values())
+    clouds = {"cloud": binding.CLOUD_FULL, "sharp": binding.CLOUD_SHARP, "less_sharp": binding.CLOUD_LESS_SHARP, "flat": binding.CLOUD_FLAT, "less_flat": binding.CLOUD_LESS_FLAT}
+    for b in np.sort(np.random.default_rng(0).choice(B, size=min(DUMP_SAMPLE, B), replace=False)):
+        cx, s = seq(int(b))
+        one = {f"seq{b:04d}_{name}": cx.cloud(which, s) for name, which in clouds.items()}
+        if mapping:
+            one[f"seq{b:04d}_registered"] = cx.map_cloud(binding.MAP_REGISTERED, s)
+        size = sum(a.nbytes for a in one.values())
+        if size > budget:
+            break
+        budget -= size
+        out.update(one)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def timed_resident(torch, dist, world, ctxs, wl, steps, warmup, mapping, repeat_to_s=0.0, repeats_out=None, batch=None, after_timed=None, profile_pass=True):
     """W untimed + exactly K timed steps with the inputs resident in HBM; per-kernel hipEvents on the context's own stream.
+    `after_timed(ctxs)` is called once the K timed steps are done, before anything else runs on the contexts.
     `repeat_to_s` > 0: after the K timed steps (which alone make `value`), further identical blocks of exactly K steps are timed the
     same way (barrier + synchronize on both sides, MAX over ranks) until the blocks add up to that many seconds (at most 24 blocks), and
-    their times are appended to `repeats_out` — the driver's `--steps 20` times 0.2 s, too short to say anything about spread."""
+    their times are appended to `repeats_out` — the driver's `--steps 20` times 0.2 s, too short to say anything about spread.
+    With several contexts the per-kernel profile takes a pass of its own, run only when `profile_pass` is set (otherwise it is None)."""
     NC, BC = len(ctxs), (batch or wl.B) // len(ctxs)       # batch: only the first `batch` sequences of the workload (the comparison legs)
     order = frame_order(wl.T, warmup + steps)
     nin = {(k, c): wl.nin(k, c * BC, (c + 1) * BC) for k in range(wl.T) for c in range(NC)}
@@ -271,6 +316,8 @@ def timed_resident(torch, dist, world, ctxs, wl, steps, warmup, mapping, repeat_
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     snapshot = ctxs[0].profile() if NC == 1 else None      # the per-kernel profile is that of the K contract steps only
+    if after_timed is not None:
+        after_timed(ctxs)
     if repeat_to_s > 0 and repeats_out is not None and elapsed > 0:
         cont = frame_order(wl.T, warmup + steps * 25)[warmup + steps:]          # the ping-pong replay simply goes on
         for r in range(min(24, max(0, int(np.ceil(repeat_to_s / elapsed)) - 1))):   # the same count on every rank: `elapsed` is the MAX over ranks
@@ -289,6 +336,8 @@ def timed_resident(torch, dist, world, ctxs, wl, steps, warmup, mapping, repeat_
                 dist.all_reduce(tm, op=dist.ReduceOp.MAX)
                 el = float(tm.item())
             repeats_out.append(el)
+    if NC > 1 and not profile_pass:
+        return elapsed, None
     if NC > 1:                                             # per-kernel profile from one extra, untimed pass on a single context
         ctxs[0].profile_enable(True)
         for k in order[warmup:]:
@@ -685,10 +734,15 @@ def main():
     if args.mapping:
         for c in ctxs:
             c.mapping_enable(0.4, 0.8, args.map_pool)      # launch/aloam_velodyne_HDL_64.launch: mapping_line / plane_resolution
+    extras = args.full and not args.no_extras
     more = []
-    # (not under --no-extras: that is what the rocprofv3 / counter passes and the A/B scripts run, and they want exactly W + K steps)
-    elapsed, prof = timed_resident(torch, dist, world, ctxs, wl, args.steps, args.warmup, args.mapping, repeat_to_s=0.0 if args.no_extras else args.repeat_to_seconds, repeats_out=more)
-    bscan = survey_b_scan(ctxs[0], wl)
+    # repeated blocks only with --full and without --no-extras: a plain run, the rocprofv3 / counter passes and the A/B scripts want exactly W + K steps
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda cs: dump_outputs(args.dump_outputs, cs, args.mapping)
+    elapsed, prof = timed_resident(torch, dist, world, ctxs, wl, args.steps, args.warmup, args.mapping, repeat_to_s=args.repeat_to_seconds if extras else 0.0, repeats_out=more,
+                                   after_timed=dump, profile_pass=args.full)
+    bscan = survey_b_scan(ctxs[0], wl) if prof is not None else None
     mstate = map_state(ctxs[0]) if args.mapping else None
     free1, _ = torch.cuda.mem_get_info(dev)                # inputs + contexts of THIS rank (of every rank that shares the device under the test hook)
     try:
@@ -705,7 +759,7 @@ def main():
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 features / f64 solve", "data": "synthetic",
            "config": {"workload": wl.describe(args.mapping), "sequences_per_gpu": B, "contexts_per_gpu": NC, "stored_frames": T, "voxel_sum_order": "reference (std::sort replayed, validation mode)" if args.reference_order else "input order (throughput path)",
                       "points_per_sweep": wl.NP, "parallelism": f"{world} x independent sequence shards, no collectives"},
-           "roofline": roofline_of(prof, args.steps, B, args.sensor, args.mapping), "input_generation_s": round(wl.gen_s, 2),
+           "roofline": roofline_of(prof, args.steps, B, args.sensor, args.mapping) if prof is not None else None, "input_generation_s": round(wl.gen_s, 2),
            "timed_region_s": round(elapsed, 3), "library_sha256": lib_sha256(),
            "memory": {"hbm_used_bytes": int(free0 - free1), "hbm_bytes_per_sequence": int((free0 - free1) / max(1, B)), "hbm_total_bytes": int(total_hbm),
                       "host_rss_bytes": rss, "host_ram_bytes": host_ram, "input_bytes": int(B * T * wl.NP * 16)}}
@@ -718,10 +772,11 @@ def main():
                                   "ms_per_step": {"first": round(1e3 * elapsed / args.steps, 4), "median": round(float(np.median(ms)), 4), "min": round(ms[0], 4), "max": round(ms[-1], 4)},
                                   "value_median": round(world * B * args.steps / (float(np.median(blocks))), 2)}
     # whole-path view with SURVEY.md 8(d)'s B_scan (one figure per sweep, measured sizes) next to the sum of the per-kernel floors above
-    out["roofline"]["survey_b_scan"] = dict(bscan, achieved_gbs=round(value / world * bscan["bytes"] / 1e9, 2), frac=round(value / world * bscan["bytes"] / 1e9 / HBM_PEAK_GBS, 5),
-                                            frac_of_measured_copy_peak=round(value / world * bscan["bytes"] / 6.29e12, 5))
+    if bscan is not None:
+        out["roofline"]["survey_b_scan"] = dict(bscan, achieved_gbs=round(value / world * bscan["bytes"] / 1e9, 2), frac=round(value / world * bscan["bytes"] / 1e9 / HBM_PEAK_GBS, 5),
+                                                frac_of_measured_copy_peak=round(value / world * bscan["bytes"] / 6.29e12, 5))
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = extras and rank == 0 and world == 1
     xsteps = min(args.steps, args.extra_steps)            # steps of the secondary legs (host-fed, four contexts, configs[2] / [3])
     if extras and NC == 1 and B % 4 == 0:
         # the same steps with the batch split over four contexts (= four HIP streams): tails and launch gaps of one quarter are
@@ -739,7 +794,7 @@ def main():
         out["host_input_xyz12"] = host_fed(torch, binding, wl, local_rank, xsteps, args.warmup, stride=12)
         out["latency"] = latency(binding, wl, local_rank, args.latency_sweeps, mapping=False)
         out["latency"]["with_hipgraph_odometry_step"] = {k: v for k, v in latency(binding, wl, local_rank, args.latency_sweeps, mapping=False, graph=True).items() if k.endswith(("median", "p95"))}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["accuracy"] = accuracy(binding, wl, local_rank)
         if not args.rough:     # the same legs on KITTI-shaped irregular sweeps (dropouts, ragged rings, noisy sectors, repeated returns)
             wlr = Workload(syn, torch, args.sensor, 2, T, rank, dev, rough=True)

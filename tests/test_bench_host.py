@@ -90,3 +90,48 @@ def test_roofline_objects_attach_only_counters_of_this_library(tmp_path, monkeyp
     monkeypatch.setattr(b, "lib_sha256", lambda: "another build")
     r = b.roofline_of(prof, 10, 1024, "HDL-64", False)
     assert r["traffic"] is None and "valu" not in r and r["bound"] == "hbm" and "not attached" in r["traffic_note"]
+
+
+class _FakeContext:
+    """The getters of binding.Aloam that bench.dump_outputs calls; every value encodes the batch-wide index of its sequence."""
+
+    def __init__(self, batch, first):
+        self.batch, self.first = batch, first
+
+    def pose(self, s):
+        g = float(self.first + s)
+        return {"q_w": np.full(4, g), "t_w": np.full(3, g), "q_lc": np.zeros(4), "t_lc": np.ones(3)}
+
+    def map_pose(self, s):
+        g = float(self.first + s)
+        return {"q_w": np.full(4, -g), "t_w": np.full(3, -g), "q_wmap_wodom": np.zeros(4), "t_wmap_wodom": np.zeros(3)}
+
+    def cloud(self, which, s):
+        return np.full((100000 if which == 0 else 5000, 4), self.first + s, np.float32)
+
+    def map_cloud(self, which, s):
+        return np.full((90000, 4), -(self.first + s), np.float32)
+
+
+def test_dump_outputs_every_pose_and_a_seeded_sample_of_clouds(tmp_path):
+    """--dump-outputs: the pose of every sequence in batch order across contexts (float64), the five published clouds (and with mapping the
+    refined pose and registered sweep) of a seeded sample of sequences (float32), the same files for the same batch, at most 64 MB in all."""
+    b = _bench()
+    for mapping in (False, True):
+        runs = []
+        for r in range(2):
+            d = tmp_path / f"{mapping}_{r}"
+            b.dump_outputs(str(d), [_FakeContext(1024, 0), _FakeContext(1024, 1024)], mapping)
+            runs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])
+        out = runs[0]
+        assert sum(a.nbytes for a in out.values()) <= 64e6 and all(a.dtype in (np.float32, np.float64) for a in out.values())
+        assert out["odom_t_w.npy"].shape == (2048, 3) and np.array_equal(out["odom_t_w.npy"][:, 0], np.arange(2048.0))
+        assert ("map_t_w.npy" in out) == mapping and (not mapping or np.array_equal(out["map_t_w.npy"][:, 0], -np.arange(2048.0)))
+        seqs = sorted({int(f[3:7]) for f in out if f.startswith("seq")})
+        assert 4 <= len(seqs) <= 8 and len({s < 1024 for s in seqs}) == 2     # the sample spans both contexts
+        for s in seqs:
+            kinds = ("cloud", "sharp", "less_sharp", "flat", "less_flat") + (("registered",) if mapping else ())
+            for k in kinds:
+                a = out[f"seq{s:04d}_{k}.npy"]
+                assert a.dtype == np.float32 and a.shape[1] == 4 and np.all(a == (-s if k == "registered" else s))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/gpu_evidence.sh <tag> — the evidence set of a round on the GPU box: parity tests, the default bench line, rocprofv3 kernel
+# tools/gpu_evidence.sh <tag> — the evidence set of a round on the GPU box: parity tests, the --full bench line, rocprofv3 kernel
 # stats of the same command, and the counter passes (FETCH_SIZE / WRITE_SIZE / two SQ groups) for the headline workload, plus
 # FETCH / WRITE for configs[2] (--mapping) and configs[3] (--sensor ROWS128).  Everything lands in gpurun_out/<tag>/.
 TAG=${1:-evidence}
@@ -8,7 +8,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-python bench.py > $O/bench.log 2>&1; tail -c 600 $O/bench.log
+python bench.py --full > $O/bench.log 2>&1; tail -c 600 $O/bench.log
 cd /tmp && export TMPDIR=/tmp
 for cfg in "headline:" "mapping:--mapping" "rows128:--sensor ROWS128 --batch 1024" "travel:--travel --frames 24 --batch 1024"; do   # the comparison workloads keep the batch of the earlier rounds
   name=${cfg%%:*}; args=${cfg#*:}
