@@ -17,6 +17,10 @@ constexpr int kSectors = 6;            // reference src/scanRegistration.cpp:282
 constexpr int kSharpPerSector = 2;     // :301
 constexpr int kLessSharpPerSector = 20;// :307
 constexpr int kFlatPerSector = 4;      // :359
+// Feature capacity of one ring: every [B][R * k...PerRing] feature buffer and the offsets into it follow from these.
+constexpr int kSharpPerRing = kSectors * kSharpPerSector;              // 12
+constexpr int kLessSharpPerRing = kSectors * kLessSharpPerSector;      // 120
+constexpr int kFlatPerRing = kSectors * kFlatPerSector;                // 24
 constexpr int kNnTile = 1024;          // targets staged in LDS per NN workgroup
 
 enum ErrBits { kErrEmpty = 1, kErrRingCap = 2, kErrPointCap = 4, kErrInternal = 8 };   // kErrInternal: a look-back wait of k_ring_features timed out
@@ -69,9 +73,9 @@ struct RegArgs {
   unsigned epoch;            // this launch; never 0 (the buffer starts zeroed)
   int* ring_ticket;          // [B] rings of the sweep handed out so far (k_ring_features takes, k_cloud_sizes resets)
   int store_debug;           // 1: also write curv / label (parity tests); the throughput entries leave them out
-  float4* sharp;             // [B][R*12]
-  float4* less_sharp;        // [B][R*120]   (current buffer)
-  float4* flat;              // [B][R*24]
+  float4* sharp;             // [B][R*kSharpPerRing]
+  float4* less_sharp;        // [B][R*kLessSharpPerRing]   (current buffer)
+  float4* flat;              // [B][R*kFlatPerRing]
   float4* less_flat;         // [B][cap]     (current buffer)
 };
 
@@ -79,12 +83,12 @@ struct OdomArgs {
   int B, cap, R;
   SeqMeta* meta;
   OdomState* state;
-  const float4* sharp;       // [B][R*12]
-  const float4* flat;        // [B][R*24]
-  const float4* corner_last; // [B][R*120]
+  const float4* sharp;       // [B][R*kSharpPerRing]
+  const float4* flat;        // [B][R*kFlatPerRing]
+  const float4* corner_last; // [B][R*kLessSharpPerRing]
   const float4* surf_last;   // [B][cap]
   // spatial hash grids over the last clouds (k_build_grids): index 0 = corner_last, 1 = surf_last
-  float4* grid_sorted3[2];   // [B][R*120] / [B][cap]   entries bucketed by (ix,iy,iz)
+  float4* grid_sorted3[2];   // [B][R*kLessSharpPerRing] / [B][cap]   entries bucketed by (ix,iy,iz)
   float4* grid_sorted2[2];   //                          entries bucketed by (ix,iy,ring key)
   int* grid_start3[2];       // [B][H+1]
   int* grid_start2[2];       // [B][H+1]
@@ -95,10 +99,10 @@ struct OdomArgs {
                              //          2 = not sorted -> literal walks; flags[2] != 0: the coarse level holds 16-bit positions into the fine copy (k_build_grids_fused)
   int* grid_walk[2];         // [B][2][R + 8]   per ring key k: first index with key >= k, last index with key <= k (written for nearly-sorted clouds only)
   int grid_H_corner, grid_H_surf;   // buckets (power of two, multiple of 1024)
-  float4* sel_sharp;         // [B][R*12]  features moved to the start of the sweep with the current pose (k_transform_queries)
-  float4* sel_flat;          // [B][R*24]
-  EdgeRec* edges;            // [B][R*12]
-  PlaneRec* planes;          // [B][R*24]
+  float4* sel_sharp;         // [B][R*kSharpPerRing]  features moved to the start of the sweep with the current pose (k_transform_queries)
+  float4* sel_flat;          // [B][R*kFlatPerRing]
+  EdgeRec* edges;            // [B][R*kSharpPerRing]
+  PlaneRec* planes;          // [B][R*kFlatPerRing]
   int outer;                 // which outer iteration (0/1)
   int last_outer;            // 1: integrate the pose after solving (src/laserOdometry.cpp:504-505)
   int lm_max_iterations;
@@ -113,7 +117,7 @@ struct GridView {
 __device__ __forceinline__ GridView grid_view(const OdomArgs& a, int b, int which) {
   GridView g;
   g.H = which == 0 ? a.grid_H_corner : a.grid_H_surf;
-  const long long per = which == 0 ? (long long)a.R * 120 : (long long)a.cap;
+  const long long per = which == 0 ? (long long)a.R * kLessSharpPerRing : (long long)a.cap;
   g.sorted3 = a.grid_sorted3[which] + b * per;
   g.sorted2 = a.grid_sorted2[which] + b * per;
   g.start3 = a.grid_start3[which] + (long long)b * (g.H + 1);

@@ -276,9 +276,9 @@ __global__ void k_map_stack_segments(MapArgs a, VoxArgs v) {
   if (g >= a.B * 2) return;
   const int b = g >> 1, cls = g & 1;
   VoxSeg s{};
-  s.in = cls == 0 ? a.corner_last + (long long)b * a.R * 120 : a.surf_last + (long long)b * a.cap;
+  s.in = cls == 0 ? a.corner_last + (long long)b * a.R * kLessSharpPerRing : a.surf_last + (long long)b * a.cap;
   s.n = cls == 0 ? a.meta[b].n_corner_last : a.meta[b].n_surf_last;
-  s.out = a.stack[cls] + (long long)b * (cls == 0 ? a.R * 120 : a.cap);
+  s.out = a.stack[cls] + (long long)b * (cls == 0 ? a.R * kLessSharpPerRing : a.cap);
   s.out_count = &a.seq[b].n_stack[cls];
   s.final_out = nullptr;
   s.final_count = nullptr;
@@ -1153,7 +1153,7 @@ __global__ __launch_bounds__(kMapSearchThreads) void k_map_search(MapArgs a, int
   if (b >= a.B) return;
   const MapSeq& ms = a.seq[b];
   const int n = ms.n_stack[CLS];
-  const long long sb = (long long)b * (CLS == 0 ? a.R * 120 : a.cap);
+  const long long sb = (long long)b * (CLS == 0 ? a.R * kLessSharpPerRing : a.cap);
   if (!ms.gate) return;
   double par[7];
 #pragma unroll
@@ -1217,7 +1217,7 @@ __global__ __launch_bounds__(256) void k_map_fit(MapArgs a) {
   const int b = blockIdx.y;
   const MapSeq& ms = a.seq[b];
   const int n = ms.n_stack[CLS];
-  const long long sb = (long long)b * (CLS == 0 ? a.R * 120 : a.cap);
+  const long long sb = (long long)b * (CLS == 0 ? a.R * kLessSharpPerRing : a.cap);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   __shared__ int s_wcnt[4];
   int* tile_cnt = a.rec_tiles + (long long)b * a.rec_tiles_per_seq + (CLS == 0 ? 0 : a.rec_tiles_corner);
@@ -1292,7 +1292,7 @@ __global__ __launch_bounds__(256) void k_map_fit(MapArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { e.a[k] = ra[k]; e.b[k] = rb[k]; }
         e.pad = i;
-        a.edges[(long long)b * a.R * 120 + i0 + rank] = e;
+        a.edges[(long long)b * a.R * kLessSharpPerRing + i0 + rank] = e;
       } else {
         MapNormRec e;
         e.cp[0] = ori.x; e.cp[1] = ori.y; e.cp[2] = ori.z;
@@ -1314,7 +1314,7 @@ template <bool WITH_JAC>
 __device__ void map_evaluate(const MapArgs& a, int b, const int* s_pref, const double q[4], const double t[3], double* acc, int* n_edge, int* n_norm) {
   const int tid = threadIdx.x;
   const MapSeq& ms = a.seq[b];
-  const MapEdgeRec* E = a.edges + (long long)b * a.R * 120;
+  const MapEdgeRec* E = a.edges + (long long)b * a.R * kLessSharpPerRing;
   const MapNormRec* P = a.norms + (long long)b * a.cap;
   int ne = 0, np = 0;
   // records are fetched a few at a time ahead of the f64 work (same per-thread order as a plain strided loop)
@@ -1445,7 +1445,7 @@ __global__ __launch_bounds__(kMapSolveThreads) void k_map_solve(MapArgs a, int i
 __global__ __launch_bounds__(256) void k_map_cubeid(MapArgs a) {
   const int b = blockIdx.y, cls = blockIdx.z;
   const MapSeq& ms = a.seq[b];
-  const long long sb = (long long)b * (cls == 0 ? a.R * 120 : a.cap);
+  const long long sb = (long long)b * (cls == 0 ? a.R * kLessSharpPerRing : a.cap);
   double par[7];
 #pragma unroll
   for (int k = 0; k < 7; ++k) par[k] = ms.par[k];
@@ -1535,7 +1535,7 @@ __global__ __launch_bounds__(64) void k_map_scatter(MapArgs a) {
   int* add = a.addcnt + ((long long)b * 2 + cls) * kMapCubes;
   const int* cur = a.cursor + ((long long)b * 2 + cls) * kMapCubes;
   float4* pool = a.pool[cls] + (long long)b * a.pool_cap;
-  const long long sb = (long long)b * (cls == 0 ? a.R * 120 : a.cap);
+  const long long sb = (long long)b * (cls == 0 ? a.R * kLessSharpPerRing : a.cap);
   __shared__ int s_cur[kMapCubes];                                           // absolute append position of every touched cube (-1: no room, skipped)
   for (int c = lane; c < kMapCubes; c += 64) {
     const int ad = add[c];

@@ -75,7 +75,7 @@ struct MapArgs {
   OdomState* odom;
   MapSeq* seq;
   float line_res, plane_res;
-  const float4* corner_last;     // [B][R*120]  /laser_cloud_corner_last
+  const float4* corner_last;     // [B][R*kLessSharpPerRing]  /laser_cloud_corner_last
   const float4* surf_last;       // [B][cap]    /laser_cloud_surf_last
   const float4* full;            // [B][cap]    /velodyne_cloud_3, dense (set from outside, or made by k_dense_cloud)
   const float4* slabs; int slab; const int* ringstart;   // ... or, straight from scan registration: one slab per ring + the dense start of every ring (slabs == nullptr: use `full`)
@@ -84,7 +84,7 @@ struct MapArgs {
   float4* pool[2];               // [B][pool_cap]
   int pool_cap;
   int* tab;                      // [B][kTabInts]  valid cubes + submap prefixes
-  float4* stack[2];              // [B][R*120] / [B][cap]   laserCloudCornerStack / SurfStack
+  float4* stack[2];              // [B][R*kLessSharpPerRing] / [B][cap]   laserCloudCornerStack / SurfStack
   float4* stack_world[2];        // same shapes: the stacks transformed with the refined pose (:739, :762)
   int* stack_cube[2];            // cube index of every stack point, -1 outside the window
   int* addcnt;                   // [B][2][kMapCubes]
@@ -97,7 +97,7 @@ struct MapArgs {
   int* report_dev;               // [3] ticket of k_map_report, largest corner / surf stack so far
   int* report_host;              // pinned host memory: step, largest live corner / surf, largest stack corner / surf
   float4* knn;                   // [B][cap][4]  the five neighbours of every stack point (search -> fit)
-  MapEdgeRec* edges;             // [B][R*120]
+  MapEdgeRec* edges;             // [B][R*kLessSharpPerRing]
   MapNormRec* norms;             // [B][cap]
   int lm_max_iterations;
   int* rec_tiles;                // [B][rec_tiles_per_seq] valid factor records per tile of 256 stack points: corner tiles, then surf tiles

@@ -6,10 +6,12 @@
 //                 pcl::KdTreeFLANN::setInputCloud (:567-568): LDS counting-sort of each "last" cloud into two spatial
 //                 hash grids (3-D cells on two levels, (x, y, ring) cells) + the flag that says whether the cloud is ring-sorted, which is what turns
 //                 the reference's walk-until-break loops into "ring key within +-2" tests
-//   k_associate_pair (round 4; k_associate = the one-query-per-wave form of rounds 1-3, kept for A/B builds and, as k_associate_flagged, for clouds that
-//                 are not ring-sorted)
+//   k_associate_pair / k_associate_nearly / k_associate_flagged
+//                 every sequence goes to exactly one of the three by the flags of its last cloud: k_associate_pair for ring-sorted clouds,
+//                 k_associate_nearly (the same pair code with the index-range walk window) for nearly ring-sorted ones, k_associate_flagged
+//                 (one query per wave, literal walks) for clouds that are not ring-sorted or hold keys / coordinates out of range.
 //                 nearestKSearch(k=1) (:302,390) + the ring-adjacent second / third neighbour walks (:304-384, :392-482) on the features
-//                 k_transform_queries moved to the sweep start (:111-129), TWO queries per wave: exact 1-NN over the 3x3x3 block of fine hash
+//                 k_transform_queries moved to the sweep start (:111-129); the pair kernels take TWO queries per wave: exact 1-NN over the 3x3x3 block of fine hash
 //                 cells with the f32 distance ((dx*dx+dy*dy)+dz*dz) FLANN's L2_Simple accumulates (lowest index wins exact ties), the walk
 //                 candidates from the keys that block left in registers; coarse shells / the (x, y, ring) grid as tails for the queries whose
 //                 neighbours lie beyond the block.  The association does not depend on aloam_config.distortion (the features arrive
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(1024) void k_build_grids_fused(OdomArgs a) {
   const int b = blockIdx.y, which = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const SeqMeta m = a.meta[b];
   const int n = which == 0 ? m.n_corner_last : m.n_surf_last;
-  const float4* pts = which == 0 ? a.corner_last + (long long)b * a.R * 120 : a.surf_last + (long long)b * a.cap;
+  const float4* pts = which == 0 ? a.corner_last + (long long)b * a.R * kLessSharpPerRing : a.surf_last + (long long)b * a.cap;
   const GridView g = grid_view(a, b, which);
   const int H = g.H;
   if (!fused_takes(n, H)) return;
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(1024, kBgWaves) void k_build_grids(OdomArgs a) {
   const int pass_lo = blockIdx.x % 3, pass_hi = pass_lo + 1;
   const SeqMeta m = a.meta[b];
   const int n = which == 0 ? m.n_corner_last : m.n_surf_last;
-  const float4* pts = which == 0 ? a.corner_last + (long long)b * a.R * 120 : a.surf_last + (long long)b * a.cap;
+  const float4* pts = which == 0 ? a.corner_last + (long long)b * a.R * kLessSharpPerRing : a.surf_last + (long long)b * a.cap;
   const GridView g = grid_view(a, b, which);
   if (fused_takes(n, g.H)) return;        // k_build_grids_fused built this cloud's grids already
   extern __shared__ __attribute__((aligned(16))) int lds[];
@@ -614,7 +616,7 @@ __global__ __launch_bounds__(256) void k_transform_queries(OdomArgs a) {
   if (i >= m.n_sharp + m.n_flat) return;
   const bool plane = i >= m.n_sharp;
   const int qi = plane ? i - m.n_sharp : i;
-  const long long o = plane ? (long long)b * a.R * 24 + qi : (long long)b * a.R * 12 + qi;
+  const long long o = plane ? (long long)b * a.R * kFlatPerRing + qi : (long long)b * a.R * kSharpPerRing + qi;
   const float4 raw = plane ? a.flat[o] : a.sharp[o];
   float4 sel;
   if (DISTORT) {
@@ -648,14 +650,14 @@ template <bool PLANE, bool WIDE> struct SweepRows { static constexpr int value =
 template <bool PLANE, bool WIDE>
 __device__ __forceinline__ void associate_one(const OdomArgs& a, int b, int qi, const SeqMeta& m, const GridView& g, int lane, int* row) {
   constexpr int kSweep = SweepRows<PLANE, WIDE>::value;
-  const int qcap = PLANE ? a.R * 24 : a.R * 12;
+  const int qcap = PLANE ? a.R * kFlatPerRing : a.R * kSharpPerRing;
   const float4* Q = (PLANE ? a.flat : a.sharp) + (long long)b * qcap;
   const float4 raw = Q[qi];
   const float4 sel = ((PLANE ? a.sel_flat : a.sel_sharp) + (long long)b * qcap)[qi];   // k_transform_queries
   const bool bad = g.flags[0] != 0, unsorted = g.flags[1] != 0;
   const float frac = raw.w - (float)(int)raw.w;                              // relTime of the point (:116)
   const int nt = PLANE ? m.n_surf_last : m.n_corner_last;
-  const float4* T = PLANE ? a.surf_last + (long long)b * a.cap : a.corner_last + (long long)b * a.R * 120;
+  const float4* T = PLANE ? a.surf_last + (long long)b * a.cap : a.corner_last + (long long)b * a.R * kLessSharpPerRing;
   int valid = 0;
   Track t1 = {~0ull, 0.f, 0.f, 0.f}, t2 = t1, t3 = t1;
   Kept<kSweep> kept;
@@ -772,7 +774,7 @@ __device__ __forceinline__ void associate_one(const OdomArgs& a, int b, int qi, 
   // the record: lane 0 stores the raw, untransformed point (:365-367 / :460-462) and the flag, the lanes that saw the
   // winners store them (a point seen on two grid levels is stored twice with the same value)
   if (PLANE) {
-    PlaneRec* e = a.planes + (long long)b * a.R * 24 + qi;
+    PlaneRec* e = a.planes + (long long)b * a.R * kFlatPerRing + qi;
     if (lane == 0) {
       e->cp[0] = raw.x; e->cp[1] = raw.y; e->cp[2] = raw.z;
       e->valid = valid; e->pad[0] = __float_as_int(frac); e->pad[1] = e->pad[2] = 0;
@@ -784,7 +786,7 @@ __device__ __forceinline__ void associate_one(const OdomArgs& a, int b, int qi, 
       if (t3.v == best3) { e->m[0] = t3.x; e->m[1] = t3.y; e->m[2] = t3.z; }
     }
   } else {
-    EdgeRec* e = a.edges + (long long)b * a.R * 12 + qi;
+    EdgeRec* e = a.edges + (long long)b * a.R * kSharpPerRing + qi;
     if (lane == 0) {
       e->cp[0] = raw.x; e->cp[1] = raw.y; e->cp[2] = raw.z;
       e->valid = valid; e->pad[0] = __float_as_int(frac); e->pad[1] = 0;
@@ -1146,12 +1148,12 @@ __device__ __forceinline__ void associate_pair(const OdomArgs& a, int b, int qi0
   const int l = lane & 31, hsel = lane >> 5, last4 = (lane | 31) << 2;
   const int qi = qi0 + hsel;
   const bool qact = qi < nq;
-  const int qcap = PLANE ? a.R * 24 : a.R * 12;
+  const int qcap = PLANE ? a.R * kFlatPerRing : a.R * kSharpPerRing;
   const long long qo = (long long)b * qcap + (qact ? qi : qi0);
   const float4 raw = (PLANE ? a.flat : a.sharp)[qo];
   const float4 sel = (PLANE ? a.sel_flat : a.sel_sharp)[qo];                 // k_transform_queries
   const float frac = raw.w - (float)(int)raw.w;                              // relTime of the point (:116)
-  const float4* T = PLANE ? a.surf_last + (long long)b * a.cap : a.corner_last + (long long)b * a.R * 120;
+  const float4* T = PLANE ? a.surf_last + (long long)b * a.cap : a.corner_last + (long long)b * a.R * kLessSharpPerRing;
   const unsigned hm = (unsigned)(g.H - 1), last_index = (unsigned)(nt - 1);
   const float cell = cell3_of(PLANE ? 1 : 0);
   const float2v selxy = {sel.x, sel.y};
@@ -1262,7 +1264,7 @@ __device__ __forceinline__ void associate_pair(const OdomArgs& a, int b, int qi0
   // ring-ordered cloud by index: the grid entries are copies of exactly those points), the next lane the flag and the relTime
   if (qact) {
     constexpr int kPts = PLANE ? 4 : 3;
-    float* e = PLANE ? reinterpret_cast<float*>(a.planes + (long long)b * a.R * 24 + qi) : reinterpret_cast<float*>(a.edges + (long long)b * a.R * 12 + qi);
+    float* e = PLANE ? reinterpret_cast<float*>(a.planes + (long long)b * a.R * kFlatPerRing + qi) : reinterpret_cast<float*>(a.edges + (long long)b * a.R * kSharpPerRing + qi);
     if (l < kPts) {
       float x = raw.x, y = raw.y, z = raw.z;
       if (l > 0) {
@@ -1288,7 +1290,7 @@ __global__ __launch_bounds__(64) void k_associate_pair(OdomArgs a) {
   __shared__ int lds[sweep2_lds_ints<kRows>()];
   // XCD-aware work mapping as in k_associate: XCD x works through sequences x, x + 8, ...
   const int lane = threadIdx.x, L = blockIdx.x, xcd = L & 7, slot = L >> 3;
-  const int pairs = PLANE ? a.R * 12 : a.R * 6;
+  const int pairs = PLANE ? a.R * (kFlatPerRing / 2) : a.R * (kSharpPerRing / 2);
   const int b = (slot / pairs) * 8 + xcd, qi0 = (slot % pairs) * 2;
   if (b >= a.B) return;
   const SeqMeta m = a.meta[b];
@@ -1346,8 +1348,8 @@ template <bool WITH_JAC, bool DISTORT>
 __device__ void evaluate(const OdomArgs& a, int b, const double q[4], const double t[3], double* acc, int* n_edge, int* n_plane) {
   const int tid = threadIdx.x;
   const SeqMeta m = a.meta[b];
-  const EdgeRec* E = a.edges + (long long)b * a.R * 12;
-  const PlaneRec* P = a.planes + (long long)b * a.R * 24;
+  const EdgeRec* E = a.edges + (long long)b * a.R * kSharpPerRing;
+  const PlaneRec* P = a.planes + (long long)b * a.R * kFlatPerRing;
   int ne = 0, np = 0;
   for (int i = tid; i < m.n_sharp; i += kSolveThreads) {
     const EdgeRec e = E[i];
@@ -1493,13 +1495,13 @@ void launch_build_grids(const OdomArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_build_grids, dim3(6, a.B), dim3(1024), build_grids_lds_bytes(a.grid_H_surf, a.R), s, a);
 }
 void launch_transform_queries(const OdomArgs& a, hipStream_t s) {
-  const dim3 grid((a.R * 36 + 255) / 256, a.B);
+  const dim3 grid((a.R * (kSharpPerRing + kFlatPerRing) + 255) / 256, a.B);
   if (a.distortion) hipLaunchKernelGGL(k_transform_queries<true>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_transform_queries<false>, grid, dim3(256), 0, s, a);
 }
 void launch_associate(const OdomArgs& a, bool plane, hipStream_t s) {
   const int by = (a.B + 7) / 8 * 8;      // padded so that every (XCD, sequence slot) pair exists (see k_associate_pair)
-  const int qcap = plane ? a.R * 24 : a.R * 12;   // the kernel decodes (sequence, query) from blockIdx.x with exactly this slot count
+  const int qcap = plane ? a.R * kFlatPerRing : a.R * kSharpPerRing;   // the kernel decodes (sequence, query) from blockIdx.x with exactly this slot count
   // sensors with more than 64 rings: the ring grid's +-2-ring window and the fine blocks hold about twice the candidates, so the
   // waves keep more rows of candidates in flight per sweep round (rows by class AND ring count)
   const bool wide = a.R > 64;

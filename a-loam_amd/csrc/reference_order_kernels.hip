@@ -204,7 +204,7 @@ __global__ __launch_bounds__(kLitThreads) void k_vox_reference_order(VoxArgs v, 
     const int n = sg.n;
     if (n <= n_lo || n > n_hi) continue;
     long long soff;
-    if (stacks) { const int b = g >> 1; soff = (long long)b * ((long long)a.cap + a.R * 120) + ((g & 1) ? a.R * 120 : 0); }
+    if (stacks) { const int b = g >> 1; soff = (long long)b * ((long long)a.cap + a.R * kLessSharpPerRing) + ((g & 1) ? a.R * kLessSharpPerRing : 0); }
     else soff = sg.out - v.tmp;
     Entry* E = n <= lds_entries ? lds_E : reinterpret_cast<Entry*>(v.keys[0]) + soff;
     int* fpos = reinterpret_cast<int*>(v.keys[1] + soff);                    // the two stop lists of a cooperative partition: 2 x 4 bytes per point of the second key buffer

@@ -950,13 +950,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
       const int j = q / kSlots, slot = q % kSlots;
       const int ncorner = s_misc[1 + j] & 0xff, nflat = s_misc[1 + j] >> 8;
       if (slot < kSharpPerSector) {
-        if (slot < ncorner) a.sharp[(long long)b * a.R * 12 + base_sharp + s_misc[16 + j] + slot] = cloud[s_pick[j * kSlots + kSharpPerSector + slot]];
+        if (slot < ncorner) a.sharp[(long long)b * a.R * kSharpPerRing + base_sharp + s_misc[16 + j] + slot] = cloud[s_pick[j * kSlots + kSharpPerSector + slot]];
       } else if (slot < kSharpPerSector + kLessSharpPerSector) {
         const int k = slot - kSharpPerSector;
-        if (k < ncorner) a.less_sharp[(long long)b * a.R * 120 + base_less + s_misc[24 + j] + k] = cloud[s_pick[j * kSlots + slot]];
+        if (k < ncorner) a.less_sharp[(long long)b * a.R * kLessSharpPerRing + base_less + s_misc[24 + j] + k] = cloud[s_pick[j * kSlots + slot]];
       } else {
         const int k = slot - kSharpPerSector - kLessSharpPerSector;
-        if (k < nflat) a.flat[(long long)b * a.R * 24 + base_flat + s_misc[32 + j] + k] = cloud[s_pick[j * kSlots + slot]];
+        if (k < nflat) a.flat[(long long)b * a.R * kFlatPerRing + base_flat + s_misc[32 + j] + k] = cloud[s_pick[j * kSlots + slot]];
       }
     }
   }

@@ -359,3 +359,56 @@ def test_pools_grow_under_asynchronous_steps_without_dropping_a_point(binding, s
         assert {k: v for k, v in ia[b].items() if k != "compactions"} == {k: v for k, v in is_[b].items() if k != "compactions"}, (b, ia[b], is_[b])
         for cls in (0, 1):
             _compare_maps(ca[b][cls], cs[b][cls], (b, cls))
+
+
+def test_context_cycles_release_every_buffer(binding, syn):
+    """The context owns every buffer it allocates: create (all stages), enable mapping with a pool the steps outgrow, run the steps (the
+    host-input staging slabs included), destroy.  After two warm-up cycles three more leave the device's free memory where it was.  (The HIP
+    runtime keeps memory of its own over the first two cycles of a process, measured 26 + 16 MiB on one MI355X; from the third on, free memory
+    returns to the same 2 MiB granule every time.)  A pool-sized set of buffers left behind would be several MiB per cycle."""
+    import torch
+    B, T, cols = 2, 12, 512
+    dev = torch.device("cuda", 0)
+    model = syn.sensor_model("HDL-64", columns=cols, device=dev)
+    NP = model.dirs.shape[0]
+    data = torch.zeros((B, T, NP, 4), dtype=torch.float32, device=dev)
+    counts = np.zeros((B, T), np.int32)
+    for b in range(B):
+        world = syn.make_street_world(80 + b).to(dev)
+        R, t = syn.trajectory_travel(T, step=1.6, seed=80 + b)
+        gen = torch.Generator(device=dev).manual_seed(600 + b)
+        for k in range(T):
+            s = syn.render_scan(world, model, R[k], t[k], 0.02, gen, max_range=syn.STREET_MAX_RANGE, cull=True)
+            counts[b, k] = s.shape[0]
+            data[b, k, : s.shape[0]] = s
+    first = [data[b, 0, : counts[b, 0]].cpu().numpy() for b in range(B)]
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    def cycle():
+        gpu = binding.Aloam(n_scans=64, min_range=5.0, batch=B, max_points=NP)
+        gpu.mapping_enable(0.4, 0.8, pool_points=4096)
+        gpu.scan_register(first)                               # host input: allocates a staging slab
+        gpu.odometry_step()
+        gpu.mapping_step()
+        for k in range(1, T):
+            gpu.process_device(data.data_ptr() + k * NP * 16, T * NP * 16, counts[:, k])
+            gpu.mapping_step()
+        gpu.synchronize()
+        growths, held = gpu.map_pool_info()["growths"], free_bytes()
+        gpu.close()
+        return growths, held
+
+    cycle()                                                    # warm-up of the runtime
+    cycle()
+    base = free_bytes()
+    tol = 4 << 20
+    for i in range(3):
+        growths, held = cycle()
+        after = free_bytes()
+        print(f"cycle {i}: context held {(base - held) / 2**20:.1f} MiB, free memory after destroy {(after - base) / 2**20:+.2f} MiB")
+        assert growths >= 1, growths
+        assert base - held > 4 * tol, (base, held)             # the context's own buffers are far above the tolerance
+        assert abs(after - base) <= tol, (i, base, after)
