@@ -103,6 +103,8 @@ def lib():
         L.aloam_set_last.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
         L.aloam_set_state.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.aloam_set_system_inited.argtypes = [vp, C.c_int]
+        L.aloam_set_active.argtypes = [vp, vp]
+        L.aloam_reset_sequences.argtypes = [vp, vp, C.c_int]
         L.aloam_get_ring_ranges.argtypes = [vp, C.c_int, vp, vp]
         L.aloam_get_curvature.argtypes = [vp, C.c_int, vp, C.c_int]
         L.aloam_get_labels.argtypes = [vp, C.c_int, vp, C.c_int]
@@ -257,6 +259,21 @@ class Aloam:
         a, b, c, d = _f64(para_q), _f64(para_t), _f64(q_w), _f64(t_w)
         self._check(lib().aloam_set_state(self.h, seq, _p(a), _p(b), _p(c), _p(d)))
         self._check(lib().aloam_set_system_inited(self.h, int(inited)))
+
+    # ---- per-sequence lifecycle ---------------------------------------------------------------------------------
+    def set_active(self, mask=None):
+        """Which sequences take part in the calls that follow (one truthy value per sequence); None = all of them."""
+        if mask is None:
+            self._check(lib().aloam_set_active(self.h, None))
+            return
+        m = np.ascontiguousarray([1 if v else 0 for v in mask], dtype=np.int32)
+        assert m.shape == (self.batch,)
+        self._check(lib().aloam_set_active(self.h, _p(m)))
+
+    def reset_sequences(self, seqs):
+        """Put the listed sequences back to the state of a fresh context, in stream order (no synchronisation)."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_reset_sequences(self.h, _p(ids) if len(ids) else None, len(ids)))
 
     def odometry_step(self):
         self._check(lib().aloam_odometry_step(self.h))

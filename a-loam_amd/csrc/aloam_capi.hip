@@ -76,7 +76,8 @@ struct aloam_ctx {
   Stream stream, copy_stream;
   Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
-  // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch per buffer parity
+  // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
+  // solves (no mask), [1] through the staged mask d_mask_odo
   GraphExec odom_graph[2];
   aloam_config cfg{};
   int stages = ALOAM_STAGE_ALL;      // which stages this context has buffers for (aloam_create_stages)
@@ -89,8 +90,16 @@ struct aloam_ctx {
   int in_slot = 0;
   bool in_used[2] = {false, false};
   DevBuf<int> d_nin;
-  PinnedBuf<int> h_nin; int h_nin_slot = 0;         // pinned ring of kNinSlots x B counts: an async H2D copy reads its slot later
+  PinnedBuf<int> h_nin; int h_nin_slot = 0;         // pinned ring of kNinSlots x B ints (counts, masks, reset ids): an async H2D copy reads its slot later
   bool nin_used[kNinSlots] = {};
+  // per-sequence lifecycle (aloam_set_active / aloam_reset_sequences)
+  std::vector<int> active;                          // [B] the mask in force, 0 / 1
+  bool all_active = true;
+  std::vector<int> reg_active;                      // the mask of the last registration, while its odometry step is still to come (reg_pending)
+  bool reg_pending = false;
+  const int* reg_mask = nullptr;                    // what the last registration's kernels were given (nullptr = all); k_dense_cloud reuses it
+  std::vector<int> parity, inited;                  // host mirrors of SeqMeta::parity and OdomState::inited: both change only through host calls
+  DevBuf<int> d_mask_reg, d_mask_odo, d_mask_map, d_reset_ids;   // [B] each: masks as the launches of one stage see them, ids of a reset
   DevBuf<SeqMeta> d_meta;
   DevBuf<float4> d_slabs; int slab = 0;             // ring-ordered points, one slab per (sequence, ring): what k_front writes and the feature kernels read
   DevBuf<unsigned long long> d_front_lb; DevBuf<int> d_front_ticket;
@@ -101,8 +110,7 @@ struct aloam_ctx {
   DevBuf<int> d_ring_ticket;                                       // per sweep: rings handed out to the workgroups of the running k_ring_features
   bool debug_arrays = false;                                       // the last registration wrote curvature / labels
   DevBuf<float4> d_sharp, d_flat;
-  DevBuf<float4> d_less_sharp[2], d_less_flat[2];
-  int cur = 0;                       // which of the double buffers holds the CURRENT sweep's less-sharp / less-flat
+  DevBuf<float4> d_less_sharp[2], d_less_flat[2];   // a sequence's CURRENT sweep is in [parity[b]], its last clouds in [1 - parity[b]]
   DevBuf<OdomState> d_state;
   DevBuf<float4> d_grid_sorted3[2], d_grid_sorted2[2];
   DevBuf<int> d_grid_start3[2], d_grid_start2[2];
@@ -123,8 +131,10 @@ struct aloam_ctx {
   int map_pool_limit = 1 << 26;      // ceiling per sequence and class (aloam_mapping_set_pool_limit); ALOAM_E_CAPACITY only there
   int map_growths = 0;
   long long map_steps = 0;           // mapping steps queued so far
-  int nin_max = 0;                   // largest scan handed to the last registration call (bounds what one step can add to a map)
-  int inject_max = 0;                // largest cloud injected through aloam_set_last since the last mapping step (the same bound for a mapping-only context)
+  // What one mapping step can add to a map is bounded by the largest of: the active rows of the last registration, and the clouds injected
+  // since the last mapping step (aloam_set_last / aloam_set_features).  An injection raises the bound, never lowers it.
+  int nin_max = 0;                   // largest active scan of the last registration call
+  int inject_max = 0;                // largest cloud injected since the last mapping step
   PinnedBuf<volatile int> h_map_report;   // pinned: {step, live corner, live surf, stack corner, stack surf} of the last finished step
   int* d_map_report_host = nullptr;       // the same memory as the device sees it
   DevBuf<int> d_map_report, d_map_live;
@@ -135,7 +145,6 @@ struct aloam_ctx {
   DevBuf<int> d_vox_lists;
   DevBuf<int> d_rec_tiles; int rec_tiles_corner = 0, rec_tiles_per_seq = 0;
   DevBuf<VoxSeg> d_segs; DevBuf<int> d_vox_counters, d_bbox;
-  bool system_inited = false;        // reference src/laserOdometry.cpp:69
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -213,6 +222,30 @@ void prof_resolve(aloam_ctx* c) {
   c->prof_pending.clear();
 }
 
+// n ints to device memory through the pinned ring: returns at once, the H2D copy runs in stream order (the slot is reused kNinSlots calls later,
+// after the copy that read it has run).
+int stage_ints(aloam_ctx* c, const int* src, int n, int* dst) {
+  const int ns = c->h_nin_slot;
+  c->h_nin_slot = (ns + 1) % kNinSlots;
+  int* slot = c->h_nin.get() + (size_t)ns * c->B;
+  if (c->nin_used[ns]) HIP_TRY(c, hipEventSynchronize(c->nin_done[ns]));   // the copy queued kNinSlots launches ago has read it
+  std::memcpy(slot, src, sizeof(int) * n);
+  HIP_TRY(c, hipMemcpyAsync(dst, slot, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->nin_done[ns], c->stream));
+  c->nin_used[ns] = true;
+  return ALOAM_OK;
+}
+
+// The mask in force for one stage's launches: nullptr when every sequence takes part (the kernels then load nothing), else staged into `dst`.
+int stage_mask(aloam_ctx* c, DevBuf<int>& dst, const int** out) {
+  *out = nullptr;
+  if (c->all_active) return ALOAM_OK;
+  if (!dst && dmalloc(c, dst, c->B)) return ALOAM_E_HIP;
+  if (const int rc = stage_ints(c, c->active.data(), c->B, dst.get())) return rc;
+  *out = dst.get();
+  return ALOAM_OK;
+}
+
 RegArgs reg_args(aloam_ctx* c, const void* d_scans, long long seq_stride, int pt_stride) {
   RegArgs a{};
   a.in = (const char*)d_scans; a.seq_stride = seq_stride; a.pt_stride = pt_stride;
@@ -221,7 +254,9 @@ RegArgs reg_args(aloam_ctx* c, const void* d_scans, long long seq_stride, int pt
   a.meta = c->d_meta.get(); a.slabs = c->d_slabs.get(); a.slab = c->slab; a.front_lb = c->d_front_lb.get(); a.front_ticket = c->d_front_ticket.get();
   a.ringstart = c->d_ringstart.get(); a.cloud = c->d_cloud.get(); a.curv = c->d_curv.get(); a.label = c->d_label.get();
   a.lookback = c->d_lookback.get(); a.epoch = c->reg_epoch; a.store_debug = c->debug_arrays ? 1 : 0; a.ring_ticket = c->d_ring_ticket.get();
-  a.sharp = c->d_sharp.get(); a.less_sharp = c->d_less_sharp[c->cur].get(); a.flat = c->d_flat.get(); a.less_flat = c->d_less_flat[c->cur].get();
+  a.sharp = c->d_sharp.get(); a.flat = c->d_flat.get();
+  for (int k = 0; k < 2; ++k) { a.less_sharp[k] = c->d_less_sharp[k].get(); a.less_flat[k] = c->d_less_flat[k].get(); }
+  a.active = c->reg_mask;
   return a;
 }
 
@@ -239,7 +274,7 @@ OdomArgs odom_args(aloam_ctx* c) {
   a.B = c->B; a.cap = c->cap; a.R = c->R;
   a.meta = c->d_meta.get(); a.state = c->d_state.get();
   a.sharp = c->d_sharp.get(); a.flat = c->d_flat.get();
-  a.corner_last = c->d_less_sharp[1 - c->cur].get(); a.surf_last = c->d_less_flat[1 - c->cur].get();
+  for (int k = 0; k < 2; ++k) { a.less_sharp[k] = c->d_less_sharp[k].get(); a.less_flat[k] = c->d_less_flat[k].get(); }
   for (int k = 0; k < 2; ++k) {
     a.grid_sorted3[k] = c->d_grid_sorted3[k].get(); a.grid_sorted2[k] = c->d_grid_sorted2[k].get(); a.grid_start3[k] = c->d_grid_start3[k].get();
     a.grid_sorted3c[k] = c->d_grid_sorted3c[k].get(); a.grid_start3c[k] = c->d_grid_start3c[k].get();
@@ -304,15 +339,14 @@ int check_batch(aloam_ctx* c, const int* n_in, int stride_bytes) {
 // debug_arrays: also write cloudCurvature / cloudLabel (the per-point entry points aloam_get_curvature / aloam_get_labels);
 // the throughput entries (aloam_process_device / aloam_process_host) leave those 5 bytes per point out.  The batch has passed check_batch.
 int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot = -1, bool debug_arrays = true) {
-  c->nin_max = *std::max_element(n_in, n_in + c->B);
-  const int ns = c->h_nin_slot;
-  c->h_nin_slot = (ns + 1) % kNinSlots;
-  int* nin_slot = c->h_nin.get() + (size_t)ns * c->B;
-  if (c->nin_used[ns]) HIP_TRY(c, hipEventSynchronize(c->nin_done[ns]));   // the copy queued kNinSlots launches ago has read it
-  std::memcpy(nin_slot, n_in, sizeof(int) * c->B);
-  HIP_TRY(c, hipMemcpyAsync(c->d_nin.get(), nin_slot, sizeof(int) * c->B, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(c->nin_done[ns], c->stream));
-  c->nin_used[ns] = true;
+  int rc = ALOAM_OK;
+  // A sequence that sits out keeps its dense cloud: made now from its slabs if the last registration's was never asked for (a no-op otherwise)
+  if (!c->all_active && (rc = ensure_dense(c))) return rc;
+  c->nin_max = 0;
+  for (int b = 0; b < c->B; ++b) if (c->all_active || c->active[b]) c->nin_max = std::max(c->nin_max, n_in[b]);
+  if ((rc = stage_ints(c, n_in, c->B, c->d_nin.get()))) return rc;
+  if ((rc = stage_mask(c, c->d_mask_reg, &c->reg_mask))) return rc;
+  if (c->stages & ALOAM_STAGE_ODOMETRY) { c->reg_active = c->active; c->reg_pending = true; }
   c->debug_arrays = debug_arrays || c->sum_order != 0;      // the reference-order pass reads cloudLabel
   if (((++c->reg_epoch) & 0x7fffffffu) == 0) ++c->reg_epoch;                 // 31 bits of it tag the look-back granules; 0 = "never written"
   const RegArgs a = reg_args(c, d_scans, seq_stride, stride_bytes);
@@ -375,6 +409,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->in_consumed[k].h, hipEventDisableTiming));
   }
   c->B = cfg->batch; c->max_points = cfg->max_points; c->R = cfg->n_scans;
+  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0);
   // The per-sequence stride of every [B][cap] buffer is kept OFF the powers of two (131 072 points x 16 B = 2 MiB apart, the workgroups of a launch - one
   // per sequence, all at about the same offset of their sequence - meet on the same memory channels): + 1/32 + 16 points.  Measured on k_build_grids_fused at
   // batch 1024, one box: 1.62 - 1.65 ms at the power-of-two stride, 1.48 - 1.52 ms with 1040 / 4112 / 16 400 points of padding.
@@ -587,8 +622,25 @@ int aloam_odometry_step(aloam_ctx* c) {
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_stage(c, ALOAM_STAGE_ODOMETRY)) return rc;
   if (!c->have_features) { c->err = "aloam_odometry_step before any features were registered / set"; return ALOAM_E_STATE; }
+  // Per sequence: kSeqActive = takes part (swaps), kSeqSolve = takes part and is past its first frame (src/laserOdometry.cpp:267-271).  The
+  // kernels get no mask at all when every sequence solves: the launches of a lock-step batch are those of a context without the feature.
+  std::vector<int> bits(c->B);
+  bool any_solve = false, all_solve = true;
+  for (int b = 0; b < c->B; ++b) {
+    const bool on = c->all_active || c->active[b];
+    bits[b] = on ? (kSeqActive | (c->inited[b] ? kSeqSolve : 0)) : 0;
+    any_solve |= (bits[b] & kSeqSolve) != 0;
+    all_solve &= (bits[b] & kSeqSolve) != 0;
+  }
+  const int* mask = nullptr;
+  if (!all_solve && (any_solve || !c->all_active)) {             // (a first frame of the whole batch needs no mask: k_advance swaps all)
+    if (!c->d_mask_odo && dmalloc(c, c->d_mask_odo, c->B)) return ALOAM_E_HIP;
+    if (const int rc = stage_ints(c, bits.data(), c->B, c->d_mask_odo.get())) return rc;
+    mask = c->d_mask_odo.get();
+  }
   auto launch_all = [&]() {
     OdomArgs a = odom_args(c);
+    a.active = mask;
     { ProfScope p(c, K_BUILD_GRIDS); launch_build_grids(a, c->stream); }          // kd-tree stand-in over the last clouds
     for (int outer = 0; outer < c->cfg.outer_iterations; ++outer) {
       a.outer = outer;
@@ -598,17 +650,19 @@ int aloam_odometry_step(aloam_ctx* c) {
       { ProfScope p(c, K_ASSOC_PLANE); launch_associate(a, true, c->stream); }
       { ProfScope p(c, K_SOLVE); launch_solve(a, c->stream); }
     }
-    { ProfScope p(c, K_ADVANCE); launch_advance(c->d_meta.get(), c->B, c->stream); }   // swap (src/laserOdometry.cpp:554-563)
+    { ProfScope p(c, K_ADVANCE); launch_advance(a, c->stream); }   // swap (src/laserOdometry.cpp:554-563)
   };
-  if (!c->system_inited) {
-    c->system_inited = true;                       // first frame: no solve (src/laserOdometry.cpp:267-271)
-    { ProfScope p(c, K_ADVANCE); launch_advance(c->d_meta.get(), c->B, c->stream); }
+  if (!any_solve) {
+    // first frame of every active sequence: no solve (src/laserOdometry.cpp:267-271)
+    OdomArgs a = odom_args(c);
+    a.active = mask;
+    { ProfScope p(c, K_ADVANCE); launch_advance(a, c->stream); }
   } else if (c->use_graph && !c->prof_on && !c->debug_sync) {
-    // The kernel arguments of a step depend on the buffer parity only (pointer flip of the last clouds), so each parity is captured once
-    // and replayed: one launch instead of ~15.  Measured at batch 1 (bench.py latency leg): 0.418 ms per step against 0.416 ms with separate
-    // launches — the step is bound by the execution of its dependent kernels (one sequence fills a fraction of the chip), not by launching them,
-    // so the path is kept (tested bit for bit) but off by default.
-    GraphExec& ge = c->odom_graph[c->cur];
+    // The kernel arguments of a step are the same every step (the buffer parity is per sequence, on the device; the mask is staged into the
+    // same buffer), so the step is captured once per mask mode and replayed: one launch instead of ~15.  Measured at batch 1 (bench.py latency leg):
+    // 0.418 ms per step against 0.416 ms with separate launches — the step is bound by the execution of its dependent kernels (one sequence fills
+    // a fraction of the chip), not by launching them, so the path is kept (tested bit for bit) but off by default.
+    GraphExec& ge = c->odom_graph[mask ? 1 : 0];
     if (!ge) {
       // A failed capture must not leave the stream in capture mode or leak the graph: the capture is always ended, the graph always
       // destroyed, and on any error this context goes back to separate launches for good (the step itself is then launched normally).
@@ -632,7 +686,8 @@ int aloam_odometry_step(aloam_ctx* c) {
     launch_all();
   }
   HIP_TRY(c, hipGetLastError());
-  c->cur ^= 1;
+  for (int b = 0; b < c->B; ++b) if (bits[b] & kSeqActive) { c->parity[b] ^= 1; c->inited[b] = 1; }
+  c->reg_pending = false;
   return ALOAM_OK;
 }
 
@@ -652,6 +707,7 @@ static int find_cloud(aloam_ctx* c, int seq, int which, const float4** ptr, int*
   SeqMeta m;
   if ((rc = fetch_meta(c, seq, &m))) return rc;
   const size_t b = seq;
+  const int cur = c->parity[seq];
   auto at = [](const DevBuf<float4>& base, size_t off) -> const float4* { return base ? base.get() + off : nullptr; };
   // aloam_odometry_step ends with the reference's pointer swap (src/laserOdometry.cpp:554-560): afterwards the sweep
   // just processed is read through CORNER_LAST / SURF_LAST, exactly like laserCloudCornerLast / laserCloudSurfLast.
@@ -659,10 +715,10 @@ static int find_cloud(aloam_ctx* c, int seq, int which, const float4** ptr, int*
     case ALOAM_CLOUD_FULL: *ptr = at(c->d_cloud, b * c->cap); *n = m.n_cloud; break;
     case ALOAM_CLOUD_SHARP: *ptr = at(c->d_sharp, b * c->R * kSharpPerRing); *n = m.n_sharp; break;
     case ALOAM_CLOUD_FLAT: *ptr = at(c->d_flat, b * c->R * kFlatPerRing); *n = m.n_flat; break;
-    case ALOAM_CLOUD_LESS_SHARP: *ptr = at(c->d_less_sharp[c->cur], b * c->R * kLessSharpPerRing); *n = m.n_less_sharp; break;
-    case ALOAM_CLOUD_LESS_FLAT: *ptr = at(c->d_less_flat[c->cur], b * c->cap); *n = m.n_less_flat; break;
-    case ALOAM_CLOUD_CORNER_LAST: *ptr = at(c->d_less_sharp[1 - c->cur], b * c->R * kLessSharpPerRing); *n = m.n_corner_last; break;
-    case ALOAM_CLOUD_SURF_LAST: *ptr = at(c->d_less_flat[1 - c->cur], b * c->cap); *n = m.n_surf_last; break;
+    case ALOAM_CLOUD_LESS_SHARP: *ptr = at(c->d_less_sharp[cur], b * c->R * kLessSharpPerRing); *n = m.n_less_sharp; break;
+    case ALOAM_CLOUD_LESS_FLAT: *ptr = at(c->d_less_flat[cur], b * c->cap); *n = m.n_less_flat; break;
+    case ALOAM_CLOUD_CORNER_LAST: *ptr = at(c->d_less_sharp[1 - cur], b * c->R * kLessSharpPerRing); *n = m.n_corner_last; break;
+    case ALOAM_CLOUD_SURF_LAST: *ptr = at(c->d_less_flat[1 - cur], b * c->cap); *n = m.n_surf_last; break;
     default: c->err = "unknown cloud id"; return ALOAM_E_ARG;
   }
   if (!*ptr) { c->err = "this context holds no such cloud (see aloam_create_stages)"; return ALOAM_E_STATE; }
@@ -720,13 +776,15 @@ int aloam_set_features(aloam_ctx* c, int seq, const float* sharp, int n_sharp, c
   if (rc) return rc;
   if (n_sharp < 0 || n_sharp > c->R * kSharpPerRing || n_less_sharp < 0 || n_less_sharp > c->R * kLessSharpPerRing || n_flat < 0 || n_flat > c->R * kFlatPerRing ||
       n_less_flat < 0 || n_less_flat > c->max_points) { c->err = "feature cloud larger than the selection rules allow"; return ALOAM_E_CAPACITY; }
-  if (!c->d_sharp || !c->d_less_sharp[c->cur]) { c->err = "this context has no feature buffers (created for the mapping stage only)"; return ALOAM_E_STATE; }
+  const int cur = c->parity[seq];
+  if (!c->d_sharp || !c->d_less_sharp[cur]) { c->err = "this context has no feature buffers (created for the mapping stage only)"; return ALOAM_E_STATE; }
+  c->inject_max = std::max(c->inject_max, std::max(n_less_sharp, n_less_flat));
   const size_t b = seq;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (n_sharp) HIP_TRY(c, hipMemcpy(c->d_sharp.get() + b * c->R * kSharpPerRing, sharp, sizeof(float4) * n_sharp, hipMemcpyHostToDevice));
-  if (n_less_sharp) HIP_TRY(c, hipMemcpy(c->d_less_sharp[c->cur].get() + b * c->R * kLessSharpPerRing, less_sharp, sizeof(float4) * n_less_sharp, hipMemcpyHostToDevice));
+  if (n_less_sharp) HIP_TRY(c, hipMemcpy(c->d_less_sharp[cur].get() + b * c->R * kLessSharpPerRing, less_sharp, sizeof(float4) * n_less_sharp, hipMemcpyHostToDevice));
   if (n_flat) HIP_TRY(c, hipMemcpy(c->d_flat.get() + b * c->R * kFlatPerRing, flat, sizeof(float4) * n_flat, hipMemcpyHostToDevice));
-  if (n_less_flat) HIP_TRY(c, hipMemcpy(c->d_less_flat[c->cur].get() + b * c->cap, less_flat, sizeof(float4) * n_less_flat, hipMemcpyHostToDevice));
+  if (n_less_flat) HIP_TRY(c, hipMemcpy(c->d_less_flat[cur].get() + b * c->cap, less_flat, sizeof(float4) * n_less_flat, hipMemcpyHostToDevice));
   if ((rc = edit_seq(c, c->d_meta.get() + seq, [&](SeqMeta& m) { m.n_sharp = n_sharp; m.n_less_sharp = n_less_sharp; m.n_flat = n_flat; m.n_less_flat = n_less_flat; m.err = 0; }))) return rc;
   c->have_features = true;
   return ALOAM_OK;
@@ -737,12 +795,13 @@ int aloam_set_last(aloam_ctx* c, int seq, const float* corner_last, int n_corner
   int rc = check_seq(c, seq);
   if (rc) return rc;
   if (n_corner < 0 || n_corner > c->R * kLessSharpPerRing || n_surf < 0 || n_surf > c->max_points) { c->err = "last cloud too large"; return ALOAM_E_CAPACITY; }
-  c->inject_max = std::max(c->inject_max, std::max(n_corner, n_surf));
-  if (!c->d_less_sharp[1 - c->cur]) { c->err = "this context has no buffers for the last clouds (created for the registration stage only)"; return ALOAM_E_STATE; }
+  c->inject_max = std::max(c->inject_max, std::max(n_corner, n_surf));   // what the next mapping step may add (never lowers the bound)
+  const int last = 1 - c->parity[seq];
+  if (!c->d_less_sharp[last]) { c->err = "this context has no buffers for the last clouds (created for the registration stage only)"; return ALOAM_E_STATE; }
   const size_t b = seq;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (n_corner) HIP_TRY(c, hipMemcpy(c->d_less_sharp[1 - c->cur].get() + b * c->R * kLessSharpPerRing, corner_last, sizeof(float4) * n_corner, hipMemcpyHostToDevice));
-  if (n_surf) HIP_TRY(c, hipMemcpy(c->d_less_flat[1 - c->cur].get() + b * c->cap, surf_last, sizeof(float4) * n_surf, hipMemcpyHostToDevice));
+  if (n_corner) HIP_TRY(c, hipMemcpy(c->d_less_sharp[last].get() + b * c->R * kLessSharpPerRing, corner_last, sizeof(float4) * n_corner, hipMemcpyHostToDevice));
+  if (n_surf) HIP_TRY(c, hipMemcpy(c->d_less_flat[last].get() + b * c->cap, surf_last, sizeof(float4) * n_surf, hipMemcpyHostToDevice));
   return edit_seq(c, c->d_meta.get() + seq, [&](SeqMeta& m) { m.n_corner_last = n_corner; m.n_surf_last = n_surf; });
 }
 
@@ -759,7 +818,53 @@ int aloam_set_state(aloam_ctx* c, int seq, const double para_q[4], const double 
 int aloam_set_system_inited(aloam_ctx* c, int inited) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  c->system_inited = inited != 0;
+  std::fill(c->inited.begin(), c->inited.end(), inited != 0 ? 1 : 0);
+  launch_set_inited(c->d_state.get(), c->B, inited != 0 ? 1 : 0, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return ALOAM_OK;
+}
+
+// ---- per-sequence lifecycle ----------------------------------------------------------------------------------------
+int aloam_set_active(aloam_ctx* c, const int* active) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  std::vector<int> m(c->B, 1);
+  if (active) for (int b = 0; b < c->B; ++b) m[b] = active[b] != 0 ? 1 : 0;
+  if (c->reg_pending && (c->stages & ALOAM_STAGE_REGISTRATION) && m != c->reg_active) {
+    c->err = "the mask may not change between a registration and the odometry step that consumes it";
+    return ALOAM_E_STATE;
+  }
+  c->all_active = std::find(m.begin(), m.end(), 0) == m.end();
+  c->active = std::move(m);
+  return ALOAM_OK;
+}
+
+int aloam_reset_sequences(aloam_ctx* c, const int* seqs, int n) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (n < 0 || n > c->B || (n > 0 && !seqs)) { c->err = "bad sequence list"; return ALOAM_E_ARG; }
+  std::vector<char> seen(c->B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (seqs[i] < 0 || seqs[i] >= c->B || seen[seqs[i]]) { c->err = "sequence index out of range or repeated"; return ALOAM_E_ARG; }
+    seen[seqs[i]] = 1;
+  }
+  if (n == 0) return ALOAM_OK;
+  if (!c->d_reset_ids && dmalloc(c, c->d_reset_ids, c->B)) return ALOAM_E_HIP;
+  if (const int rc = stage_ints(c, seqs, n, c->d_reset_ids.get())) return rc;
+  ResetArgs r{};
+  r.seqs = c->d_reset_ids.get(); r.n = n; r.R = c->R;
+  r.meta = c->d_meta.get(); r.ringstart = c->d_ringstart.get(); r.state = c->d_state.get();
+  r.edges = c->d_edges.get(); r.planes = c->d_planes.get();
+  for (int k = 0; k < 2; ++k) r.grid_flags[k] = c->d_grid_flags[k].get();
+  for (int k = 0; k < 2; ++k) { r.less_sharp[k] = c->d_less_sharp[k].get(); r.less_flat[k] = c->d_less_flat[k].get(); }
+  r.cap = c->cap;
+  if (c->map_on) { r.mapseq = c->d_mapseq.get(); r.cubes = c->d_cubes.get(); r.addcnt = c->d_addcnt.get(); r.live = c->d_map_live.get(); }
+  launch_reset_sequences(r, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  for (int i = 0; i < n; ++i) {
+    c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0;
+    if ((int)c->map_err_seen.size() == c->B) c->map_err_seen[seqs[i]] = 0;
+  }
   return ALOAM_OK;
 }
 
@@ -930,7 +1035,8 @@ static MapArgs map_args(aloam_ctx* c) {
   a.line_res = c->map_line_res; a.plane_res = c->map_plane_res;
   // after aloam_odometry_step's swap the sweep just processed is the "last" one: exactly what the odometry node publishes
   // as /laser_cloud_corner_last, /laser_cloud_surf_last and /velodyne_cloud_3 (reference src/laserOdometry.cpp:570-591)
-  a.corner_last = c->d_less_sharp[1 - c->cur].get(); a.surf_last = c->d_less_flat[1 - c->cur].get(); a.full = c->d_cloud.get();
+  for (int k = 0; k < 2; ++k) { a.less_sharp[k] = c->d_less_sharp[k].get(); a.less_flat[k] = c->d_less_flat[k].get(); }
+  a.full = c->d_cloud.get();
   if (!c->dense_valid) { a.slabs = c->d_slabs.get(); a.slab = c->slab; a.ringstart = c->d_ringstart.get(); }   // the sweep just registered lives in its ring slabs; the dense copy is made only for who asks
   a.registered = c->d_registered.get();
   a.cubes = c->d_cubes.get(); a.pool_cap = c->map.points; a.tab = c->d_maptab.get();
@@ -1000,7 +1106,8 @@ static int map_alloc_pool(aloam_ctx* c, int pool_points) {
 // bound exceeds the pool: wait for the device (the report is then exact), double the pool until it holds the bound, move the contents.
 static int map_ensure_capacity(aloam_ctx* c) {
   if (c->map.points >= c->map_pool_limit) return ALOAM_OK;     // at the ceiling: nothing to decide (the device counts what does not fit)
-  const int hard[2] = {std::min(c->R * kLessSharpPerRing, c->nin_max ? c->nin_max : c->cap), std::min(c->cap, c->nin_max ? c->nin_max : c->cap)};
+  const int step_max = std::max(c->nin_max, c->inject_max);   // the last registration's active rows and what was injected since the last step
+  const int hard[2] = {std::min(c->R * kLessSharpPerRing, step_max ? step_max : c->cap), std::min(c->cap, step_max ? step_max : c->cap)};
   auto bound = [&](long long lag) {
     const int done = c->h_map_report[0];
     long long worst = 0;
@@ -1117,10 +1224,11 @@ int aloam_mapping_step(aloam_ctx* c) {
   // at most four steps queued ahead of the device: the occupancy report the pools are sized from is never older than that
   hipEvent_t done = c->map_step_done[c->map_steps & 3];
   if (c->map_steps >= 4) HIP_TRY(c, hipEventSynchronize(done));
-  if (c->inject_max > 0) { c->nin_max = c->inject_max; c->inject_max = 0; }   // this step's clouds came through aloam_set_last
   int rc = map_ensure_capacity(c);
   if (rc) return rc;
-  const MapArgs a = map_args(c);
+  c->inject_max = 0;
+  MapArgs a = map_args(c);
+  if ((rc = stage_mask(c, c->d_mask_map, &a.active))) return rc;
   { ProfScope p(c, K_MAP_BEGIN); launch_map_begin(a, c->stream); }
   { ProfScope p(c, K_MAP_VOXEL_STACK);                                      // downSizeFilterCorner / Surf on the incoming clouds (:542-550)
     const VoxArgs v = vox_args(c, c->B * 2, c->map_levels);

@@ -34,7 +34,9 @@ struct alignas(16) SeqMeta {           // one per sequence, device resident
   int err;
   int n_sharp, n_less_sharp, n_flat, n_less_flat;   // current sweep
   int n_corner_last, n_surf_last;                   // previous sweep (laserCloudCornerLast / SurfLast)
-  int pad0, pad1;
+  int parity;                                       // which of the two less-sharp / less-flat buffers holds this sequence's CURRENT sweep
+                                                    // (the other holds its last clouds); k_advance flips it for the sequences it swaps
+  int pad1;
 };
 
 struct alignas(16) OdomState {         // one per sequence, device resident
@@ -46,8 +48,15 @@ struct alignas(16) OdomState {         // one per sequence, device resident
   int lm_iterations[2], lm_successful[2];
   double initial_cost[2], final_cost[2];
   int termination[2];
-  int pad[2];
+  int inited;                          // systemInited of this sequence (src/laserOdometry.cpp:69,267-271); set by k_advance, cleared by k_reset_sequences
+  int pad;
 };
+
+// Which sequences take part in a launch (aloam_set_active): nullptr = all of them, else one int per sequence whose bit kSeqActive says
+// whether it takes part at all and kSeqSolve (odometry only) whether it is an active sequence past its first frame.  One scalar load per
+// workgroup: a sequence that sits out is neither read nor written.
+enum SeqBits { kSeqActive = 1, kSeqSolve = 2 };
+__device__ __forceinline__ bool seq_idle(const int* active, int b, int bit = kSeqActive) { return active && !(active[b] & bit); }
 
 struct EdgeRec { float cp[3], a[3], b[3]; int valid; int pad[2]; };          // 48 B : LidarEdgeFactor ctor args
 struct PlaneRec { float cp[3], j[3], l[3], m[3]; int valid; int pad[3]; };   // 64 B : LidarPlaneFactor ctor args
@@ -74,9 +83,10 @@ struct RegArgs {
   int* ring_ticket;          // [B] rings of the sweep handed out so far (k_ring_features takes, k_cloud_sizes resets)
   int store_debug;           // 1: also write curv / label (parity tests); the throughput entries leave them out
   float4* sharp;             // [B][R*kSharpPerRing]
-  float4* less_sharp;        // [B][R*kLessSharpPerRing]   (current buffer)
+  float4* less_sharp[2];     // [B][R*kLessSharpPerRing]   both buffers: a sequence's current sweep goes to [SeqMeta::parity]
   float4* flat;              // [B][R*kFlatPerRing]
-  float4* less_flat;         // [B][cap]     (current buffer)
+  float4* less_flat[2];      // [B][cap]                   (same)
+  const int* active;         // [B] SeqBits of this registration, nullptr = all sequences
 };
 
 struct OdomArgs {
@@ -85,8 +95,9 @@ struct OdomArgs {
   OdomState* state;
   const float4* sharp;       // [B][R*kSharpPerRing]
   const float4* flat;        // [B][R*kFlatPerRing]
-  const float4* corner_last; // [B][R*kLessSharpPerRing]
-  const float4* surf_last;   // [B][cap]
+  const float4* less_sharp[2];   // [B][R*kLessSharpPerRing]  a sequence's last clouds are in [1 - SeqMeta::parity]
+  const float4* less_flat[2];    // [B][cap]
+  const int* active;         // [B] SeqBits of this step (kSeqSolve: the sequences that solve), nullptr = all sequences
   // spatial hash grids over the last clouds (k_build_grids): index 0 = corner_last, 1 = surf_last
   float4* grid_sorted3[2];   // [B][R*kLessSharpPerRing] / [B][cap]   entries bucketed by (ix,iy,iz)
   float4* grid_sorted2[2];   //                          entries bucketed by (ix,iy,ring key)
@@ -108,6 +119,13 @@ struct OdomArgs {
   int lm_max_iterations;
   int distortion;            // 1: per-point interpolation ratio (reference DISTORTION 1); 0: s = 1
 };
+
+// One row of a double-buffered cloud: buffer `k` (0 / 1) of sequence b, with `per` points per sequence.  A select, not an index into the
+// kernel argument (that would copy the argument struct to scratch).
+template <typename T>
+__device__ __forceinline__ T* row_of(T* const (&buf)[2], int k, int b, long long per) { return (k ? buf[1] : buf[0]) + b * per; }
+__device__ __forceinline__ const float4* corner_last(const OdomArgs& a, int b, int parity) { return row_of(a.less_sharp, parity ^ 1, b, (long long)a.R * kLessSharpPerRing); }
+__device__ __forceinline__ const float4* surf_last(const OdomArgs& a, int b, int parity) { return row_of(a.less_flat, parity ^ 1, b, (long long)a.cap); }
 
 struct GridView {
   int H;

@@ -100,6 +100,7 @@ __device__ __forceinline__ int compact_cap(int n, int mode) { return n <= 0 ? 0 
 
 __global__ __launch_bounds__(256) void k_map_compact_plan(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, tid = threadIdx.x;
+  if (seq_idle(a.active, b)) return;
   MapSeq& ms = a.seq[b];
   int* flag = a.compact_flag + b * 2 + cls;
   const CubeDesc* T = cube_table(a, b, cls);
@@ -156,6 +157,7 @@ __global__ __launch_bounds__(256) void k_map_compact_plan(MapArgs a) {
 template <int PHASE>   // 0: cubes -> staging at their new offsets; 1: staging -> pool, descriptors updated
 __global__ __launch_bounds__(256) void k_map_compact_move(MapArgs a, float4* staging) {
   const int b = blockIdx.y, cls = blockIdx.z, tid = threadIdx.x;
+  if (seq_idle(a.active, b)) return;                                        // (its compact_flag is of an earlier step)
   const int mode = a.compact_flag[b * 2 + cls];
   if (!mode) return;
   CubeDesc* T = cube_table(a, b, cls);
@@ -181,10 +183,11 @@ __global__ __launch_bounds__(256) void k_map_begin(MapArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   MapSeq& ms = a.seq[b];
   __shared__ int s_c[3], s_cen[3];
+  if (b == 0 && tid == 0) { if (a.vox_counters[1]) a.vox_counters[3] += 1; a.vox_counters[1] = 0; }   // batch-wide: also when sequence 0 sits out
+  if (seq_idle(a.active, b)) return;
   if (tid == 0) {
     if (ms.err) ms.err_steps += 1;                                           // capacity flags describe one step; what the previous step
     ms.err = 0;                                                              // raised stays countable for a host that synchronises later
-    if (b == 0) { if (a.vox_counters[1]) a.vox_counters[3] += 1; a.vox_counters[1] = 0; }
     const OdomState& od = a.odom[b];
     double qo[4], to[3], qm[4], q[4], rt[3];
     for (int k = 0; k < 4; ++k) { qo[k] = od.q_w[k]; qm[k] = ms.q_wmap_wodom[k]; ms.q_wodom[k] = qo[k]; }
@@ -276,7 +279,9 @@ __global__ void k_map_stack_segments(MapArgs a, VoxArgs v) {
   if (g >= a.B * 2) return;
   const int b = g >> 1, cls = g & 1;
   VoxSeg s{};
-  s.in = cls == 0 ? a.corner_last + (long long)b * a.R * kLessSharpPerRing : a.surf_last + (long long)b * a.cap;
+  if (seq_idle(a.active, b)) { v.segs[g] = s; return; }                    // an empty segment: nothing filtered, its stack count kept
+  const int last = a.meta[b].parity ^ 1;
+  s.in = cls == 0 ? row_of(a.less_sharp, last, b, (long long)a.R * kLessSharpPerRing) : row_of(a.less_flat, last, b, (long long)a.cap);
   s.n = cls == 0 ? a.meta[b].n_corner_last : a.meta[b].n_surf_last;
   s.out = a.stack[cls] + (long long)b * (cls == 0 ? a.R * kLessSharpPerRing : a.cap);
   s.out_count = &a.seq[b].n_stack[cls];
@@ -294,7 +299,7 @@ __global__ void k_map_cube_segments(MapArgs a, VoxArgs v) {
   const int j = g % kMapValidMax, cls = (g / kMapValidMax) & 1, b = g / (2 * kMapValidMax);
   VoxSeg s{};
   s.leaf = cls == 0 ? a.line_res : a.plane_res;
-  if (j < a.seq[b].n_valid) {
+  if (!seq_idle(a.active, b) && j < a.seq[b].n_valid) {                    // idle: an empty segment, its cubes are not re-filtered
     CubeDesc* d = cube_table(a, b, cls) + a.tab[(long long)b * kTabInts + j];
     s.in = a.pool[cls] + (long long)b * a.pool_cap + d->off;
     s.n = d->cnt;
@@ -923,6 +928,7 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
 // any size; the bucket table is capped at 32768 entries (132 KiB of the CU's 160 KiB) however far the pool has grown.
 __global__ __launch_bounds__(1024) void k_mapgrid_build(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, tid = threadIdx.x;
+  if (seq_idle(a.active, b)) return;
   const MapSeq& ms = a.seq[b];
   const int n = ms.from_total[cls], nv = ms.n_valid, H = a.grid_H;
   const int* tab = a.tab + (long long)b * kTabInts;
@@ -1150,7 +1156,7 @@ __global__ __launch_bounds__(kMapSearchThreads) void k_map_search(MapArgs a, int
   // such that XCD x works through sequences x, x + 8, ...: one L2 fetches a sequence's submap instead of eight.
   const int L = blockIdx.x, xcd = L & 7, slot = L >> 3;
   const int b = (slot / nblk) * 8 + xcd, blk = slot % nblk;
-  if (b >= a.B) return;
+  if (b >= a.B || seq_idle(a.active, b)) return;
   const MapSeq& ms = a.seq[b];
   const int n = ms.n_stack[CLS];
   const long long sb = (long long)b * (CLS == 0 ? a.R * kLessSharpPerRing : a.cap);
@@ -1215,6 +1221,7 @@ __global__ __launch_bounds__(kMapSearchThreads) void k_map_search(MapArgs a, int
 template <int CLS>
 __global__ __launch_bounds__(256) void k_map_fit(MapArgs a) {
   const int b = blockIdx.y;
+  if (seq_idle(a.active, b)) return;
   const MapSeq& ms = a.seq[b];
   const int n = ms.n_stack[CLS];
   const long long sb = (long long)b * (CLS == 0 ? a.R * kLessSharpPerRing : a.cap);
@@ -1395,6 +1402,7 @@ __global__ __launch_bounds__(kMapSolveThreads) void k_map_solve(MapArgs a, int i
   const int b = blockIdx.x, tid = threadIdx.x;
   __shared__ double s_red[(kMapSolveThreads / 64) * 28];
   extern __shared__ int s_pref[];                                            // exclusive prefixes of the valid records per tile: corner, then surf
+  if (seq_idle(a.active, b)) return;
   MapSeq& ms = a.seq[b];
   {
     const int nt0 = (ms.n_stack[0] + 255) >> 8, nt1 = (ms.n_stack[1] + 255) >> 8;
@@ -1444,6 +1452,7 @@ __global__ __launch_bounds__(kMapSolveThreads) void k_map_solve(MapArgs a, int i
 // =======================================================================================================
 __global__ __launch_bounds__(256) void k_map_cubeid(MapArgs a) {
   const int b = blockIdx.y, cls = blockIdx.z;
+  if (seq_idle(a.active, b)) return;
   const MapSeq& ms = a.seq[b];
   const long long sb = (long long)b * (cls == 0 ? a.R * kLessSharpPerRing : a.cap);
   double par[7];
@@ -1473,6 +1482,7 @@ __global__ __launch_bounds__(256) void k_map_cubeid(MapArgs a) {
 // class pool; the old segment is abandoned).  Then the append cursor of every touched cube is published.
 __global__ __launch_bounds__(256) void k_map_reserve(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, tid = threadIdx.x;
+  if (seq_idle(a.active, b)) return;
   CubeDesc* T = cube_table(a, b, cls);
   int* add = a.addcnt + ((long long)b * 2 + cls) * kMapCubes;
   int* cur = a.cursor + ((long long)b * 2 + cls) * kMapCubes;
@@ -1529,6 +1539,7 @@ __global__ __launch_bounds__(256) void k_map_reserve(MapArgs a) {
 // stable append: one wave per (sequence, class) walks the stack in order, 64 points a step
 __global__ __launch_bounds__(64) void k_map_scatter(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, lane = threadIdx.x;
+  if (seq_idle(a.active, b)) return;
   const MapSeq& ms = a.seq[b];
   const int n = ms.n_stack[cls];
   const CubeDesc* T = cube_table(a, b, cls);
@@ -1577,7 +1588,7 @@ __global__ __launch_bounds__(64) void k_map_scatter(MapArgs a) {
 
 __global__ __launch_bounds__(256) void k_map_register(MapArgs a) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.meta[b].n_cloud) return;
+  if (seq_idle(a.active, b) || i >= a.meta[b].n_cloud) return;
   const MapSeq& ms = a.seq[b];
   double par[7];
 #pragma unroll
@@ -1588,6 +1599,7 @@ __global__ __launch_bounds__(256) void k_map_register(MapArgs a) {
 // the same from the ring slabs of scan registration (k_front): ring r of the sweep, written at the ring's place in the dense numbering
 __global__ __launch_bounds__(256) void k_map_register_slabs(MapArgs a) {
   const int r = blockIdx.x, b = blockIdx.y;
+  if (seq_idle(a.active, b)) return;
   const int start = a.ringstart[b * (a.R + 1) + r], n = a.ringstart[b * (a.R + 1) + r + 1] - start;
   const MapSeq& ms = a.seq[b];
   double par[7];
@@ -1609,15 +1621,16 @@ __global__ __launch_bounds__(256) void k_map_report(MapArgs a, int step) {
   const CubeDesc* T = cube_table(a, b, cls);
   __shared__ int s_red[4][4];
   __shared__ int s_last;
+  const bool idle = seq_idle(a.active, b);                                  // an idle sequence only takes its ticket: its live count stands
   int live = 0;
-  for (int c = tid; c < kMapCubes; c += 256) live += T[c].cnt;
+  if (!idle) for (int c = tid; c < kMapCubes; c += 256) live += T[c].cnt;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) live += __shfl_xor(live, d, 64);
   if ((tid & 63) == 0) s_red[0][tid >> 6] = live;
   __syncthreads();
   if (tid == 0) {
     live = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
-    atomicExch(&a.live[b * 2 + cls], live);
+    if (!idle) atomicExch(&a.live[b * 2 + cls], live);
     __threadfence();
     s_last = atomicAdd(&a.report_dev[0], 1) == (int)(gridDim.x * gridDim.y) - 1;
   }
@@ -1646,6 +1659,48 @@ __global__ __launch_bounds__(256) void k_map_report(MapArgs a, int step) {
     h[0] = step;
   }
 }
+
+// =======================================================================================================
+// sequence reset (aloam_reset_sequences)
+// =======================================================================================================
+// One workgroup per listed sequence: SeqMeta, OdomState, the odometry getters' rows (correspondences, last-cloud order, ring ranges, both
+// less-sharp / less-flat buffers: the getters read them past the swap and past what a sweep wrote, which is zeros in a new context) and, with
+// mapping, MapSeq, both classes' cube tables and append counts and the live counts go back to their creation values (src/laserOdometry.cpp:93-98,
+// src/laserMapping.cpp:72-74,109,115).  Cube tables and pool_used at zero release the sequence's pool space.  No allocation, no host wait: a
+// graph-capturable launch in stream order between asynchronous steps.
+__global__ __launch_bounds__(256) void k_reset_sequences(ResetArgs r) {
+  const int b = r.seqs[blockIdx.x], tid = threadIdx.x;
+  if (tid == 0) {
+    r.meta[b] = SeqMeta{};
+    OdomState st{};
+    st.para_q[3] = 1.0; st.q_w[3] = 1.0;
+    r.state[b] = st;
+    if (r.mapseq) {
+      MapSeq ms{};
+      ms.par[3] = 1.0; ms.q_wmap_wodom[3] = 1.0;
+      ms.cen[0] = 10; ms.cen[1] = 10; ms.cen[2] = 5;
+      r.mapseq[b] = ms;
+      r.live[2 * b] = 0; r.live[2 * b + 1] = 0;
+    }
+  }
+  if (r.ringstart) for (int i = tid; i <= r.R; i += 256) r.ringstart[(long long)b * (r.R + 1) + i] = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (r.less_sharp[k]) for (int i = tid; i < r.R * kLessSharpPerRing; i += 256) r.less_sharp[k][(long long)b * r.R * kLessSharpPerRing + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r.less_flat[k]) for (long long i = tid; i < r.cap; i += 256) r.less_flat[k][(long long)b * r.cap + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if (r.edges) {
+    for (int i = tid; i < r.R * kSharpPerRing; i += 256) r.edges[(long long)b * r.R * kSharpPerRing + i] = EdgeRec{};
+    for (int i = tid; i < r.R * kFlatPerRing; i += 256) r.planes[(long long)b * r.R * kFlatPerRing + i] = PlaneRec{};
+    if (tid < 8) r.grid_flags[tid >> 2][b * 4 + (tid & 3)] = 0;
+  }
+  if (r.mapseq) {
+    for (int i = tid; i < 2 * kMapCubes; i += 256) {
+      r.cubes[(long long)b * 2 * kMapCubes + i] = CubeDesc{0, 0, 0, 0};
+      r.addcnt[(long long)b * 2 * kMapCubes + i] = 0;
+    }
+  }
+}
+void launch_reset_sequences(const ResetArgs& r, hipStream_t s) { if (r.n > 0) hipLaunchKernelGGL(k_reset_sequences, dim3(r.n), dim3(256), 0, s, r); }
 
 // =======================================================================================================
 // launchers

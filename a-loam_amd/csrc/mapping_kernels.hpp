@@ -75,8 +75,9 @@ struct MapArgs {
   OdomState* odom;
   MapSeq* seq;
   float line_res, plane_res;
-  const float4* corner_last;     // [B][R*kLessSharpPerRing]  /laser_cloud_corner_last
-  const float4* surf_last;       // [B][cap]    /laser_cloud_surf_last
+  const float4* less_sharp[2];   // [B][R*kLessSharpPerRing]  /laser_cloud_corner_last = row [1 - SeqMeta::parity]
+  const float4* less_flat[2];    // [B][cap]    /laser_cloud_surf_last   (same)
+  const int* active;             // [B] SeqBits of this step, nullptr = all sequences (aloam_set_active)
   const float4* full;            // [B][cap]    /velodyne_cloud_3, dense (set from outside, or made by k_dense_cloud)
   const float4* slabs; int slab; const int* ringstart;   // ... or, straight from scan registration: one slab per ring + the dense start of every ring (slabs == nullptr: use `full`)
   float4* registered;            // [B][cap]    /velodyne_cloud_registered
@@ -118,6 +119,20 @@ void launch_map_solve(const MapArgs& a, int iter, bool last, hipStream_t s);
 void launch_map_insert(const MapArgs& a, float4* staging, hipStream_t s);   // staging: 2 pools per sequence
 void launch_map_register(const MapArgs& a, hipStream_t s);   // reads the slabs when a.slabs is set, the dense cloud otherwise
 void launch_map_report(const MapArgs& a, int step, hipStream_t s);
+
+// aloam_reset_sequences: the listed sequences back to what aloam_create / aloam_mapping_enable hand out.  Null pointers: stage not present.
+struct ResetArgs {
+  const int* seqs; int n;        // [n] distinct sequence ids
+  int R;
+  SeqMeta* meta; int* ringstart; // [B], [B][R+1]
+  OdomState* state;              // [B]
+  EdgeRec* edges; PlaneRec* planes;   // [B][R*kSharpPerRing], [B][R*kFlatPerRing]
+  int* grid_flags[2];            // [B][4]
+  float4* less_sharp[2]; float4* less_flat[2]; int cap;   // the double-buffered clouds, [B][R*kLessSharpPerRing] / [B][cap]: zeros, as in a new
+                                                          // context (the getters read them past the swap, and past what a sweep wrote)
+  MapSeq* mapseq; CubeDesc* cubes; int* addcnt; int* live;   // [B], [B][2][kMapCubes] x 2, [B][2]
+};
+void launch_reset_sequences(const ResetArgs& r, hipStream_t s);
 int prepare_reference_order();                                                                  // reference_order_kernels.hip
 void launch_voxel_filter_reference_order(const VoxArgs& v, const MapArgs& a, bool stacks, hipStream_t s);
 

@@ -207,9 +207,10 @@ __host__ __device__ __forceinline__ bool fused_takes(int n, int H) { return n <=
 __global__ __launch_bounds__(1024) void k_build_grids_fused(OdomArgs a) {
   constexpr int U = 4;
   const int b = blockIdx.y, which = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (seq_idle(a.active, b, kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
   const int n = which == 0 ? m.n_corner_last : m.n_surf_last;
-  const float4* pts = which == 0 ? a.corner_last + (long long)b * a.R * kLessSharpPerRing : a.surf_last + (long long)b * a.cap;
+  const float4* pts = which == 0 ? corner_last(a, b, m.parity) : surf_last(a, b, m.parity);
   const GridView g = grid_view(a, b, which);
   const int H = g.H;
   if (!fused_takes(n, H)) return;
@@ -339,9 +340,10 @@ __global__ __launch_bounds__(1024, kBgWaves) void k_build_grids(OdomArgs a) {
   // overlap each other's load / LDS-atomic / scattered-store phases better than two that run three passes back to back
   const int b = blockIdx.y, which = blockIdx.x / 3, tid = threadIdx.x;      // which: 0 corner_last, 1 surf_last
   const int pass_lo = blockIdx.x % 3, pass_hi = pass_lo + 1;
+  if (seq_idle(a.active, b, kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
   const int n = which == 0 ? m.n_corner_last : m.n_surf_last;
-  const float4* pts = which == 0 ? a.corner_last + (long long)b * a.R * kLessSharpPerRing : a.surf_last + (long long)b * a.cap;
+  const float4* pts = which == 0 ? corner_last(a, b, m.parity) : surf_last(a, b, m.parity);
   const GridView g = grid_view(a, b, which);
   if (fused_takes(n, g.H)) return;        // k_build_grids_fused built this cloud's grids already
   extern __shared__ __attribute__((aligned(16))) int lds[];
@@ -612,6 +614,7 @@ __device__ __forceinline__ unsigned long long wave_nn(const GridView& g, bool ba
 template <bool DISTORT>
 __global__ __launch_bounds__(256) void k_transform_queries(OdomArgs a) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (seq_idle(a.active, b, kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
   if (i >= m.n_sharp + m.n_flat) return;
   const bool plane = i >= m.n_sharp;
@@ -657,7 +660,7 @@ __device__ __forceinline__ void associate_one(const OdomArgs& a, int b, int qi, 
   const bool bad = g.flags[0] != 0, unsorted = g.flags[1] != 0;
   const float frac = raw.w - (float)(int)raw.w;                              // relTime of the point (:116)
   const int nt = PLANE ? m.n_surf_last : m.n_corner_last;
-  const float4* T = PLANE ? a.surf_last + (long long)b * a.cap : a.corner_last + (long long)b * a.R * kLessSharpPerRing;
+  const float4* T = PLANE ? surf_last(a, b, m.parity) : corner_last(a, b, m.parity);
   int valid = 0;
   Track t1 = {~0ull, 0.f, 0.f, 0.f}, t2 = t1, t3 = t1;
   Kept<kSweep> kept;
@@ -1153,7 +1156,8 @@ __device__ __forceinline__ void associate_pair(const OdomArgs& a, int b, int qi0
   const float4 raw = (PLANE ? a.flat : a.sharp)[qo];
   const float4 sel = (PLANE ? a.sel_flat : a.sel_sharp)[qo];                 // k_transform_queries
   const float frac = raw.w - (float)(int)raw.w;                              // relTime of the point (:116)
-  const float4* T = PLANE ? a.surf_last + (long long)b * a.cap : a.corner_last + (long long)b * a.R * kLessSharpPerRing;
+  const int parity = a.meta[b].parity;
+  const float4* T = PLANE ? surf_last(a, b, parity) : corner_last(a, b, parity);
   const unsigned hm = (unsigned)(g.H - 1), last_index = (unsigned)(nt - 1);
   const float cell = cell3_of(PLANE ? 1 : 0);
   const float2v selxy = {sel.x, sel.y};
@@ -1292,7 +1296,7 @@ __global__ __launch_bounds__(64) void k_associate_pair(OdomArgs a) {
   const int lane = threadIdx.x, L = blockIdx.x, xcd = L & 7, slot = L >> 3;
   const int pairs = PLANE ? a.R * (kFlatPerRing / 2) : a.R * (kSharpPerRing / 2);
   const int b = (slot / pairs) * 8 + xcd, qi0 = (slot % pairs) * 2;
-  if (b >= a.B) return;
+  if (b >= a.B || seq_idle(a.active, b, kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
   const int nq = PLANE ? m.n_flat : m.n_sharp;
   if (qi0 >= nq) return;
@@ -1313,6 +1317,7 @@ __global__ __launch_bounds__(64) void k_associate_nearly(OdomArgs a) {
   constexpr int kRows = PairRows<PLANE, WIDE>::value;
   __shared__ int lds[sweep2_lds_ints<kRows>()];
   const int lane = threadIdx.x, b = blockIdx.y;
+  if (seq_idle(a.active, b, kSeqSolve)) return;
   const GridView g = grid_view(a, b, PLANE ? 1 : 0);
   if (g.flags[0] != 0 || g.flags[1] != 1) return;
   const SeqMeta m = a.meta[b];
@@ -1333,6 +1338,7 @@ __global__ __launch_bounds__(256) void k_associate_flagged(OdomArgs a) {
   constexpr int kSweep = SweepRows<PLANE, WIDE>::value;
   __shared__ int rows[4][kSweep * 64];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (seq_idle(a.active, b, kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
   const GridView g = grid_view(a, b, PLANE ? 1 : 0);
   const int nt = PLANE ? m.n_surf_last : m.n_corner_last;
@@ -1431,6 +1437,7 @@ template <bool DISTORT>
 __global__ __launch_bounds__(kSolveThreads) void k_solve(OdomArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   __shared__ double s_red[kSolveWaves * 28];
+  if (seq_idle(a.active, b, kSeqSolve)) return;
   OdomState& st = a.state[b];
   double q[4] = {st.para_q[0], st.para_q[1], st.para_q[2], st.para_q[3]};
   double t[3] = {st.para_t[0], st.para_t[1], st.para_t[2]};
@@ -1469,13 +1476,22 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(OdomArgs a) {
   }
 }
 
-// Cloud swap bookkeeping (reference src/laserOdometry.cpp:554-563): the buffers are swapped by the host (pointer
-// flip), the counts here.
-__global__ void k_advance(SeqMeta* meta, int B) {
+// Cloud swap (reference src/laserOdometry.cpp:554-563) of every active sequence: its buffer parity flips (the sweep just processed becomes
+// the last one), the counts follow, and from now on it is initialised (:267-271: a first frame does nothing else).  Idle sequences keep all three.
+__global__ void k_advance(SeqMeta* meta, OdomState* state, const int* active, int B) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) { meta[b].n_corner_last = meta[b].n_less_sharp; meta[b].n_surf_last = meta[b].n_less_flat; }
+  if (b >= B || seq_idle(active, b)) return;
+  SeqMeta& m = meta[b];
+  m.n_corner_last = m.n_less_sharp; m.n_surf_last = m.n_less_flat; m.parity ^= 1;
+  state[b].inited = 1;
 }
-void launch_advance(SeqMeta* meta, int B, hipStream_t s) { hipLaunchKernelGGL(k_advance, dim3((B + 63) / 64), dim3(64), 0, s, meta, B); }
+// aloam_set_system_inited: the flag of every sequence
+__global__ void k_set_inited(OdomState* state, int B, int inited) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) state[b].inited = inited;
+}
+void launch_set_inited(OdomState* state, int B, int inited, hipStream_t s) { hipLaunchKernelGGL(k_set_inited, dim3((B + 63) / 64), dim3(64), 0, s, state, B, inited); }
+void launch_advance(const OdomArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_advance, dim3((a.B + 63) / 64), dim3(64), 0, s, a.meta, a.state, a.active, a.B); }
 
 // -------------------------------------------------------------------------------------------------------
 size_t build_grids_lds_bytes(int H, int R) { return sizeof(int) * ((size_t)H + 1024 + 2 * (R + 8) + 4); }

@@ -9,5 +9,6 @@ void launch_build_grids(const OdomArgs& a, hipStream_t s);
 void launch_transform_queries(const OdomArgs& a, hipStream_t s);
 void launch_associate(const OdomArgs& a, bool plane, hipStream_t s);
 void launch_solve(const OdomArgs& a, hipStream_t s);
-void launch_advance(SeqMeta* meta, int B, hipStream_t s);
+void launch_advance(const OdomArgs& a, hipStream_t s);             // the swap of every active sequence (a.active bit kSeqActive)
+void launch_set_inited(OdomState* state, int B, int inited, hipStream_t s);
 }  // namespace aloam

@@ -230,6 +230,7 @@ __global__ __launch_bounds__(kLitThreads) void k_vox_reference_order(VoxArgs v, 
 __global__ __launch_bounds__(kLitThreads) void k_less_flat_reference_order(RegArgs a, float leaf, int max_ring) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lit_smem[];
   const int b = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (seq_idle(a.active, b)) return;
   const int start = a.ringstart[b * (a.R + 1) + r];
   const int n = a.ringstart[b * (a.R + 1) + r + 1] - start;
   const int L = n - 11;                                     // elements scanStartInd .. scanEndInd - 1 (:249-251,284-285)
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(kLitThreads) void k_less_flat_reference_order(RegAr
   const int expect = (int)(unsigned)lb[r];
   if (n_mem == 0) return;
   bool unf;
-  float4* out = a.less_flat + (long long)b * a.cap + off;
+  float4* out = row_of(a.less_flat, a.meta[b].parity, b, a.cap) + off;
   const int n_vox = voxel_grid_reference_order([&](int i) { return cloud[member[i]]; }, n_mem, leaf, E, out, s_f, s_i, s_work, kRingWorkMax, s_chunk, kRingChunkMax, fpos, lpos, &unf);
   if (tid == 0 && (unf || n_vox != expect)) atomicOr(&a.meta[b].err, kErrInternal);
 }

@@ -25,6 +25,7 @@ namespace aloam {
 // -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __restrict__ n_in) {
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (seq_idle(a.active, b)) return;                                         // a sequence that sits out: its n_in row is never read
   const int n = n_in[b];
   const char* in = a.in + (long long)b * a.seq_stride;
   __shared__ int s_first, s_last;
@@ -167,6 +168,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   __shared__ int s_cnt[16][kMaxRings];        // [round * 4 + wave][ring]: points of that ring in that wave's round -> offsets inside the ring's slab
   __shared__ int s_half, s_ticket;
+  if (seq_idle(a.active, b)) return;           // before the ticket: nobody waits on the granules of an idle sweep, its ticket stays 0
   if (tid == 0) { s_ticket = atomicAdd(a.front_ticket + b, 1); s_half = 0x7fffffff; }
   for (int q = tid; q < 16 * kMaxRings; q += 256) (&s_cnt[0][0])[q] = 0;
   __syncthreads();
@@ -257,6 +259,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 // reference's dense numbering), the cloud size, the halfPassed index; the block tickets of the next launch.  One wave per sweep.
 __global__ __launch_bounds__(64) void k_ring_starts(RegArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x;
+  if (seq_idle(a.active, b)) return;
   const int n = a.meta[b].n_in < a.cap ? a.meta[b].n_in : a.cap;
   const int nb = (n + kBlockPts - 1) / kBlockPts;
   const unsigned long long* last = a.front_lb + ((long long)b * a.NB + (nb > 0 ? nb - 1 : 0)) * kFrontSlots;
@@ -288,6 +291,7 @@ __global__ __launch_bounds__(64) void k_ring_starts(RegArgs a) {
 // /velodyne_cloud_2 publisher, laserMapping's full-resolution input) - the feature kernels read the slabs.
 __global__ __launch_bounds__(256) void k_dense_cloud(RegArgs a) {
   const int r = blockIdx.x, b = blockIdx.y;
+  if (seq_idle(a.active, b)) return;
   const int start = a.ringstart[b * (a.R + 1) + r], n = a.ringstart[b * (a.R + 1) + r + 1] - start;
   const float4* src = a.slabs + ((long long)b * a.R + r) * a.slab;
   float4* dst = a.cloud + (long long)b * a.cap + start;
@@ -630,6 +634,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_ticket[];
   int* s_ticket = reinterpret_cast<int*>(smem_ticket);                       // first word of the dynamic LDS, free again after the barrier
   typedef __attribute__((address_space(1))) int global_int;                 // a GLOBAL atomic (the generic pointer of the argument struct would make it a flat one)
+  if (seq_idle(a.active, b)) return;                                        // before the ticket (k_cloud_sizes skips the sweep too)
   if (tid == 0) *s_ticket = __hip_atomic_fetch_add((global_int*)(a.ring_ticket + b), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   int r_ = __builtin_amdgcn_readfirstlane(*s_ticket);
@@ -935,7 +940,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
   // 32-bit run keys (voxel index << EB | first element) whenever the voxel box is small enough — most rings: half the LDS
   // traffic and a third fewer VALU instructions in the sort; the 64-bit keys remain for rings whose box has more cells.
   constexpr int EB = NPAD <= 2048 ? 11 : 12;                                  // bits of an element index
-  float4* out = a.less_flat + (long long)b * a.cap;                          // final place: offset = less-flat points of the rings in front
+  const int parity = a.meta[b].parity;
+  float4* out = row_of(a.less_flat, parity, b, a.cap);                      // final place: offset = less-flat points of the rings in front
   if (overflow || cells_in_box <= (1ll << (32 - EB))) {
     // bits of a voxel index: every index is below cells_in_box (or, in PCL's overflow case, the element number itself)
     voxel_runs_tail<NPAD, unsigned, EB>(smem, flags, s_scan, s_misc, cloud, out, L, tid, lane, wave, lb + 3 * a.R, r, a.R, a.epoch, &a.meta[b].err);
@@ -953,7 +959,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
         if (slot < ncorner) a.sharp[(long long)b * a.R * kSharpPerRing + base_sharp + s_misc[16 + j] + slot] = cloud[s_pick[j * kSlots + kSharpPerSector + slot]];
       } else if (slot < kSharpPerSector + kLessSharpPerSector) {
         const int k = slot - kSharpPerSector;
-        if (k < ncorner) a.less_sharp[(long long)b * a.R * kLessSharpPerRing + base_less + s_misc[24 + j] + k] = cloud[s_pick[j * kSlots + slot]];
+        if (k < ncorner) row_of(a.less_sharp, parity, b, (long long)a.R * kLessSharpPerRing)[base_less + s_misc[24 + j] + k] = cloud[s_pick[j * kSlots + slot]];
       } else {
         const int k = slot - kSharpPerSector - kLessSharpPerSector;
         if (k < nflat) a.flat[(long long)b * a.R * kFlatPerRing + base_flat + s_misc[32 + j] + k] = cloud[s_pick[j * kSlots + slot]];
@@ -966,6 +972,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
 // Sizes of the four feature clouds of every sweep = sums of the published ring counts (one wave per sweep).
 __global__ __launch_bounds__(64) void k_cloud_sizes(RegArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x;
+  if (seq_idle(a.active, b)) return;
   const unsigned long long* lb = a.lookback + (long long)b * 4 * a.R;
   int* err = &a.meta[b].err;
   const int n0 = gather_counts(lb + 0 * a.R, a.R, a.epoch, lane, err), n1 = gather_counts(lb + 1 * a.R, a.R, a.epoch, lane, err);

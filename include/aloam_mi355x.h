@@ -8,7 +8,8 @@
  *
  * Conventions
  *   - plain C, no exceptions across the boundary; return 0 = ok, negative = error (aloam_last_error()).
- *   - one aloam_ctx = `batch` independent sequences advanced in lock-step on ONE device and ONE HIP stream
+ *   - one aloam_ctx = `batch` independent sequences advanced in lock-step on ONE device and ONE HIP stream (any of them may sit a step out or
+ *     restart in place: aloam_set_active, aloam_reset_sequences)
  *     (batch = 1 is the reference's single-sensor node).  A context is not thread-safe; distinct contexts
  *     are independent (one per GPU / per process for multi-GPU; no collectives — sequences never exchange data).
  *     Every call runs on the context's device and restores the calling thread's current HIP device before returning.
@@ -171,7 +172,34 @@ int aloam_set_features(aloam_ctx* ctx, int seq, const float* sharp, int n_sharp,
 int aloam_set_last(aloam_ctx* ctx, int seq, const float* corner_last, int n_corner, const float* surf_last, int n_surf); /* laserCloudCornerLast / SurfLast + kd-tree input (src/laserOdometry.cpp:554-568) */
 int aloam_set_state(aloam_ctx* ctx, int seq, const double para_q[4], const double para_t[3], const double q_w_curr[4],
                     const double t_w_curr[3]);                       /* src/laserOdometry.cpp:93-98              */
-int aloam_set_system_inited(aloam_ctx* ctx, int inited);             /* systemInited (src/laserOdometry.cpp:69,267-271) */
+int aloam_set_system_inited(aloam_ctx* ctx, int inited);             /* systemInited (src/laserOdometry.cpp:69,267-271), of every sequence */
+
+/* ---- per-sequence lifecycle: sequences that sit out steps, and restart in place --------------------------------------
+ * Every sequence of a batch has its own lifecycle: its own systemInited flag and its own laserCloudCornerLast / SurfLast buffer
+ * (the swap of src/laserOdometry.cpp:554-563 is per sequence).
+ *
+ * aloam_set_active: which sequences take part in the calls that follow; active[b] != 0 for each of the `batch` sequences, NULL = all
+ * (the default).  Each registration, odometry and mapping call uses the mask in force when it is made.  No synchronisation: the mask
+ * is staged through a pinned ring, like the point counts.
+ *   - In a context with both stages, the mask may not change between a registration and the odometry step that consumes it:
+ *     ALOAM_E_STATE, and the mask in force stays as it was.
+ *   - The mapping step may use another mask than the odometry step of the same frame: a sequence idle in mapping has dropped that frame
+ *     in mapping, as the reference's mapping node drops frames when it falls behind (src/laserMapping.cpp:299-303).
+ *   - An idle sequence is neither read nor written by that call: input, features, dense cloud, curvature and labels, odometry state and
+ *     statistics, correspondences, last clouds, map pose, cubes and pool contents, registered cloud.  Every getter returns the same bits
+ *     before and after an idle step.  Its n_in row must still be in 0 .. max_points; its points are never read (NaN / garbage is fine).
+ *   - An ACTIVE sequence with no surviving point still fails with ALOAM_E_EMPTY.  An all-idle step is legal and changes nothing.
+ *   - An active sequence that is not initialised (new context, aloam_reset_sequences, aloam_set_system_inited(0)) has a first frame
+ *     in its next odometry step: no solve, only the swap (src/laserOdometry.cpp:267-271), while the others solve.
+ *
+ * aloam_reset_sequences: the n listed sequences become exactly what a freshly created context holds, with its mapping configuration and
+ * pool limit kept: identity poses, not initialised, no last clouds, no correspondences; with mapping enabled an empty map (its pool space
+ * released), cen = (10, 10, 5), identity q_wmap_wodom, frame_count 0, error / compaction counters zero.  Queued on the stream with no
+ * host synchronisation (valid between asynchronous steps and with the graph-replayed odometry step).  Out-of-range or repeated ids:
+ * ALOAM_E_ARG, nothing is reset.  The other sequences are not touched.
+ */
+int aloam_set_active(aloam_ctx* ctx, const int* active);
+int aloam_reset_sequences(aloam_ctx* ctx, const int* seqs, int n);
 
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host

@@ -10,6 +10,10 @@ Ground truth is moved into the lidar / "/camera_init" convention exactly like ki
 per sweep, plus the ATE (RMSE of translation, same start, no alignment) against the ground truth when it is present.
 
 KITTI is not part of this repository or image; `--selftest` writes a tiny synthetic sequence in this layout and runs on it.
+
+`--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
+context runs one sequence; when it ends, the slot is reset in place (aloam_reset_sequences) and takes the next one, and slots with nothing
+left sit the step out (aloam_set_active).  Each sequence's output files are byte-identical to running it alone.
 """
 from __future__ import annotations
 
@@ -43,9 +47,34 @@ def read_gt(path):
     return np.einsum("ij,njk->nik", R_TRANSFORM, P[:, :, :3]), P[:, :, 3] @ R_TRANSFORM.T
 
 
-def write_selftest(folder, seq="00", frames=6):
+def schedule(lengths, batch):
+    """Continuous batching of sequences with `lengths` sweeps over `batch` slots, without a device: a list of steps
+    (active, resets, frames) - active[slot] whether the slot takes part, resets = the slots to reset before the step (a new sequence
+    enters them), frames = {slot: (sequence index, frame)} of the active slots.  Sequences enter the slots in order."""
+    assert batch >= 1 and all(n >= 0 for n in lengths)
+    pending = [i for i, n in enumerate(lengths) if n > 0]
+    pending.reverse()
+    slot_seq, slot_next = [None] * batch, [0] * batch
+    steps = []
+    while True:
+        resets, frames = [], {}
+        for s in range(batch):
+            if slot_seq[s] is None or slot_next[s] >= lengths[slot_seq[s]]:
+                slot_seq[s] = pending.pop() if pending else None
+                slot_next[s] = 0
+                if slot_seq[s] is not None:
+                    resets.append(s)
+            if slot_seq[s] is not None:
+                frames[s] = (slot_seq[s], slot_next[s])
+                slot_next[s] += 1
+        if not frames:
+            return steps
+        steps.append(([s in frames for s in range(batch)], resets, frames))
+
+
+def write_selftest(folder, seq="00", frames=6, seed=77):
     syn = importlib.import_module("a-loam_amd.synthetic")
-    scans, R, t, model = syn.make_sequence("HDL-64", frames, seed=77, columns=1024)
+    scans, R, t, model = syn.make_sequence("HDL-64", frames, seed=seed, columns=1024)
     os.makedirs(os.path.join(folder, "sequences", seq), exist_ok=True)
     os.makedirs(os.path.join(folder, "velodyne", "sequences", seq, "velodyne"), exist_ok=True)
     os.makedirs(os.path.join(folder, "results"), exist_ok=True)
@@ -65,6 +94,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", help="dataset_folder of kitti_helper.launch")
     ap.add_argument("--seq", default="00")
+    ap.add_argument("--seqs", nargs="+", help="several sequences, run together by continuous batching over --batch slots")
+    ap.add_argument("--batch", type=int, default=1, help="slots of the context with --seqs")
     ap.add_argument("--out", default="kitti_out")
     ap.add_argument("--mapping", action="store_true")
     ap.add_argument("--max-frames", type=int, default=0)
@@ -72,45 +103,57 @@ def main():
     ap.add_argument("--reference-order", action="store_true", help="sum voxel members in pcl::VoxelGrid's own order (the reference's bits; ~4x slower for one sensor): for runs that are compared pose by pose with A-LOAM's")
     ap.add_argument("--distortion", action="store_true", help="per-point interpolation ratio (the reference's DISTORTION 1; real KITTI sweeps are already de-skewed, so the reference ships 0)")
     args = ap.parse_args()
+    seqs = args.seqs or [args.seq]
     if args.selftest:
         args.dataset = os.path.join(args.out, "selftest_dataset")
-        write_selftest(args.dataset, args.seq)
+        for i, seq in enumerate(seqs):                 # sequences of unequal length, so that slots finish at different steps
+            write_selftest(args.dataset, seq, frames=6 + 2 * (i % 3), seed=77 + i)
     binding = importlib.import_module("a-loam_amd.binding")
-    times = read_times(os.path.join(args.dataset, "sequences", args.seq, "times.txt"))
-    if args.max_frames:
-        times = times[: args.max_frames]
-    gt_path = os.path.join(args.dataset, "results", args.seq + ".txt")
-    gt = read_gt(gt_path) if os.path.exists(gt_path) else None
+    times = []
+    for seq in seqs:
+        ts = read_times(os.path.join(args.dataset, "sequences", seq, "times.txt"))
+        times.append(ts[: args.max_frames] if args.max_frames else ts)
+    batch = args.batch if args.seqs else 1
     # launch/aloam_velodyne_HDL_64.launch: scan_line 64, minimum_range 5, mapping resolutions 0.4 / 0.8
-    gpu = binding.Aloam(n_scans=64, min_range=5.0, max_points=140000, distortion=args.distortion)
+    gpu = binding.Aloam(n_scans=64, min_range=5.0, batch=batch, max_points=140000, distortion=args.distortion)
     if args.reference_order:
         gpu.set_voxel_sum_order(True)
     if args.mapping:
         gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)          # where the map starts: the pools double as it grows (src/laserMapping.cpp:737-783 push_back)
     os.makedirs(args.out, exist_ok=True)
-    odo, mapped = [], []
-    for k, stamp in enumerate(times):
-        pts = read_lidar(os.path.join(args.dataset, "velodyne", "sequences", args.seq, "velodyne", f"{k:06d}.bin"))
-        gpu.scan_register(pts)
+    odo, mapped = [[] for _ in seqs], [[] for _ in seqs]
+    idle = np.zeros((0, 4), np.float32)
+    for active, resets, frames in schedule([len(ts) for ts in times], batch):
+        if resets:
+            gpu.reset_sequences(resets)                # a new sequence enters these slots: a fresh context's state, in place
+        gpu.set_active(None if all(active) else active)
+        scans = [idle] * batch
+        for slot, (i, k) in frames.items():
+            scans[slot] = read_lidar(os.path.join(args.dataset, "velodyne", "sequences", seqs[i], "velodyne", f"{k:06d}.bin"))
+        gpu.scan_register(scans)
         gpu.odometry_step()
-        p = gpu.pose()
-        odo.append([stamp, *p["t_w"], *p["q_w"]])
+        for slot, (i, k) in frames.items():
+            p = gpu.pose(slot)
+            odo[i].append([times[i][k], *p["t_w"], *p["q_w"]])
         if args.mapping:
             gpu.mapping_step()
             gpu.synchronize()
-            m = gpu.map_pose()
-            mapped.append([stamp, *m["t_w"], *m["q_w"]])
-    np.savetxt(os.path.join(args.out, f"{args.seq}_odometry.txt"), np.array(odo), fmt="%.9e")
-    if mapped:
-        np.savetxt(os.path.join(args.out, f"{args.seq}_mapped.txt"), np.array(mapped), fmt="%.9e")
-    if gt is not None:
-        Rg, tg = gt
-        tg = (tg[: len(odo)] - tg[0]) @ Rg[0]          # same start as the estimate (identity at the first sweep)
-        for name, tr in (("odometry", odo), ("mapped", mapped)):
-            if tr:
-                e = np.array(tr)[:, 1:4] - tg
-                print(f"{name}: {len(tr)} sweeps, ATE (RMSE, no alignment) = {np.sqrt((e ** 2).sum(1).mean()):.4f} m, final error = {np.linalg.norm(e[-1]):.4f} m")
+            for slot, (i, k) in frames.items():
+                m = gpu.map_pose(slot)
+                mapped[i].append([times[i][k], *m["t_w"], *m["q_w"]])
     gpu.close()
+    for i, seq in enumerate(seqs):
+        np.savetxt(os.path.join(args.out, f"{seq}_odometry.txt"), np.array(odo[i]), fmt="%.9e")
+        if mapped[i]:
+            np.savetxt(os.path.join(args.out, f"{seq}_mapped.txt"), np.array(mapped[i]), fmt="%.9e")
+        gt_path = os.path.join(args.dataset, "results", seq + ".txt")
+        if os.path.exists(gt_path):
+            Rg, tg = read_gt(gt_path)
+            tg = (tg[: len(odo[i])] - tg[0]) @ Rg[0]   # same start as the estimate (identity at the first sweep)
+            for name, tr in (("odometry", odo[i]), ("mapped", mapped[i])):
+                if tr:
+                    e = np.array(tr)[:, 1:4] - tg
+                    print(f"{seq} {name}: {len(tr)} sweeps, ATE (RMSE, no alignment) = {np.sqrt((e ** 2).sum(1).mean()):.4f} m, final error = {np.linalg.norm(e[-1]):.4f} m")
 
 
 if __name__ == "__main__":
