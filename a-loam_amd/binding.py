@@ -19,7 +19,8 @@ HEADER_PATH = os.path.join(_ROOT, "include", "aloam_mi355x.h")
 
 CLOUD_FULL, CLOUD_SHARP, CLOUD_LESS_SHARP, CLOUD_FLAT, CLOUD_LESS_FLAT, CLOUD_CORNER_LAST, CLOUD_SURF_LAST = range(7)
 E_ARG, E_SCAN_LINES, E_EMPTY, E_CAPACITY, E_HIP, E_STATE = -1, -2, -3, -4, -5, -6
-MAP_REGISTERED, MAP_CORNER_STACK, MAP_SURF_STACK = 2, 3, 4
+MAP_REGISTERED, MAP_CORNER_STACK, MAP_SURF_STACK, MAP_SURROUND, MAP_FULL = 2, 3, 4, 5, 6
+EXPORT_MAP, EXPORT_MAX_IDS = 16, 12                 # export ids: CLOUD_* or EXPORT_MAP + MAP_*
 STAGE_REGISTRATION, STAGE_ODOMETRY, STAGE_MAPPING, STAGE_ALL = 1, 2, 4, 7
 MAP_INFO_KEYS = ("cenW", "cenH", "cenD", "frame_count", "from_map_corner", "from_map_surf", "corner_stack", "surf_stack",
                  "corner_num0", "corner_num1", "surf_num0", "surf_num1", "lm_iterations0", "lm_iterations1", "termination0", "compactions")
@@ -35,6 +36,12 @@ class AloamOdomStats(C.Structure):
     _fields_ = [("corner_corr", C.c_int * 2), ("plane_corr", C.c_int * 2), ("lm_iterations", C.c_int * 2),
                 ("lm_successful", C.c_int * 2), ("initial_cost", C.c_double * 2), ("final_cost", C.c_double * 2),
                 ("termination", C.c_int * 2)]
+
+
+class AloamPoseRecord(C.Structure):
+    _fields_ = [("q_w", C.c_double * 4), ("t_w", C.c_double * 3), ("q_last_curr", C.c_double * 4), ("t_last_curr", C.c_double * 3),
+                ("map_q_w", C.c_double * 4), ("map_t_w", C.c_double * 3), ("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3),
+                ("inited", C.c_int), ("map_frames", C.c_int), ("pad", C.c_int * 2)]
 
 
 class AloamError(RuntimeError):
@@ -122,6 +129,8 @@ def lib():
         L.aloam_map_cube_counts.argtypes = [vp, C.c_int, C.c_int, vp]
         L.aloam_get_map_cube.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
         L.aloam_get_map_cloud.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
+        L.aloam_export_poses.argtypes = [vp, vp]
+        L.aloam_export_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -366,6 +375,24 @@ class Aloam:
         if n:
             self._check(lib().aloam_get_map_cloud(self.h, seq, which, _p(out), n))
         return out
+
+    # ---- batched export (stream-ordered; wait with synchronize()) ------------------------------------------------------------
+    def export_poses(self, dst_ptr):
+        """One AloamPoseRecord per sequence into dst_ptr (device memory of this context's device, or pinned host memory)."""
+        self._check(lib().aloam_export_poses(self.h, C.c_void_p(dst_ptr)))
+
+    def export_clouds(self, ids, dst_ptr, cap_points, offsets_ptr):
+        """Clouds `ids` (CLOUD_* or EXPORT_MAP + MAP_*) of every sequence packed into dst_ptr (16-byte points, at most cap_points of
+        them), segment (i, b) at [offsets[i * batch + b], offsets[i * batch + b + 1]); offsets_ptr receives len(ids) * batch + 1 int64."""
+        a = (C.c_int * max(1, len(ids)))(*[int(v) for v in ids])
+        self._check(lib().aloam_export_clouds(self.h, a, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None, int(cap_points), C.c_void_p(offsets_ptr)))
+
+    def export_segment(self, points, offsets, ids, which, seq):
+        """The points of cloud `which` of sequence `seq` in an export's destination (a torch tensor or numpy array of float32, viewed as
+        (n, 4)) given its offsets (after the export has finished)."""
+        i = list(ids).index(which)
+        lo, hi = int(offsets[i * self.batch + seq]), int(offsets[i * self.batch + seq + 1])
+        return points.reshape(-1, 4)[lo:hi]
 
     # ---- profiling -----------------------------------------------------------------------------------------
     def profile_enable(self, on=True):

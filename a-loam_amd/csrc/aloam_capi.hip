@@ -14,6 +14,7 @@
 
 #include "../../include/aloam_mi355x.h"
 #include "aloam_device.hpp"
+#include "export_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "registration_kernels.hpp"
@@ -23,11 +24,11 @@ using namespace aloam;
 namespace {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register"};
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
 constexpr int kNinSlots = 8;
@@ -145,6 +146,13 @@ struct aloam_ctx {
   DevBuf<int> d_vox_lists;
   DevBuf<int> d_rec_tiles; int rec_tiles_corner = 0, rec_tiles_per_seq = 0;
   DevBuf<VoxSeg> d_segs; DevBuf<int> d_vox_counters, d_bbox;
+  // batched export (aloam_export_clouds, and the cube-list clouds of aloam_get_map_cloud): scratch of count / scan / gather, used in stream order
+  DevBuf<int> d_exp_cnt, d_exp_chunk; DevBuf<long long> d_exp_off;   // [ALOAM_EXPORT_MAX_IDS * B] points and [.. + 1] chunk / point offsets per segment
+  DevBuf<int> d_exp_pref[2];                                         // entry prefixes of the cube lists, [B][151] surround, [B][9703] full map (on first use)
+  int exp_last_segs = 0;                                             // segments of the last export (its algorithmic bytes)
+  int gather_blocks = 2048;                                          // workgroups of the persistent k_export_gather: 8 per CU
+  DevBuf<float4> d_exp_tmp; long long exp_tmp_cap = 0;              // aloam_get_map_cloud(SURROUND / FULL): the segment of one sequence
+  DevBuf<long long> d_exp_tmp_off;
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -429,6 +437,10 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
   if ((rc = dmalloc(c, c->d_meta, B))) return rc;
   if ((rc = dmalloc(c, c->d_state, B))) return rc;
   if ((rc = dmalloc(c, c->d_cloud, B * cap))) return rc;                    // /velodyne_cloud_2 -> _3 -> mapping's full-resolution input
+  if ((rc = dmalloc(c, c->d_exp_cnt, B * ALOAM_EXPORT_MAX_IDS))) return rc;
+  if ((rc = dmalloc(c, c->d_exp_chunk, B * ALOAM_EXPORT_MAX_IDS + 1))) return rc;
+  if ((rc = dmalloc(c, c->d_exp_off, B * ALOAM_EXPORT_MAX_IDS + 1))) return rc;
+  { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) c->gather_blocks = 8 * cus; }
   if (reg) {                                                                 // working set of scan registration
     c->slab = c->npad + 16;                                                  // >= the longest ring k_ring_features accepts (npad + 11)
     if ((rc = dmalloc(c, c->d_slabs, B * R * (size_t)c->slab))) return rc;
@@ -980,7 +992,12 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
   prof_resolve(c);
   if (total_ms) *total_ms = c->prof_ms[kernel];
   if (launches) *launches = c->prof_launches[kernel];
-  if (algorithmic_bytes) {
+  if (algorithmic_bytes && kernel == K_EXPORT) {
+    // the last export: every point read once and written once, one count read and one offset written per segment (DESIGN.md "Batched export")
+    long long total = 0;
+    HIP_TRY(c, hipMemcpy(&total, c->d_exp_off.get() + c->exp_last_segs, sizeof(total), hipMemcpyDeviceToHost));
+    *algorithmic_bytes = 32.0 * total + 16.0 * c->exp_last_segs;
+  } else if (algorithmic_bytes) {
     // per-launch algorithmic traffic from the sizes of the LAST sweep (DESIGN.md "Algorithmic bytes")
     std::vector<SeqMeta> m(c->B);
     HIP_TRY(c, hipMemcpy(m.data(), c->d_meta.get(), sizeof(SeqMeta) * c->B, hipMemcpyDeviceToHost));
@@ -1320,6 +1337,106 @@ static int fetch_mapseq(aloam_ctx* c, int seq, MapSeq* ms) {
   return ALOAM_OK;
 }
 
+// ---- batched export -----------------------------------------------------------------------------------------------------
+// The address a kernel writes `p` through: device memory of the context's device as it is, pinned host memory through its device mapping.
+// Pageable host memory (with XNACK off a kernel store there faults the device), managed memory, another device's memory and NULL are refused.
+static int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out) {
+  hipPointerAttribute_t at{};
+  const bool known = p && hipPointerGetAttributes(&at, p) == hipSuccess;
+  if (!known) (void)hipGetLastError();                    // (pageable memory is an error of the query, not of the context)
+  void* d = nullptr;
+  if (known && !at.isManaged && at.type == hipMemoryTypeDevice && at.device == c->cfg.device) d = const_cast<void*>(p);
+  else if (known && !at.isManaged && at.type == hipMemoryTypeHost && hipHostGetDevicePointer(&d, const_cast<void*>(p), 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
+  if (!d) { c->err = std::string(what) + " must be device memory of the context's device or pinned host memory"; return ALOAM_E_ARG; }
+  if ((uintptr_t)p % align || (uintptr_t)d % align) { c->err = std::string(what) + " must be " + std::to_string(align) + "-byte aligned"; return ALOAM_E_ARG; }
+  *out = d;
+  return ALOAM_OK;
+}
+
+// Where export id `id` (ALOAM_CLOUD_* or ALOAM_EXPORT_MAP + ALOAM_MAP_*) is read from: the buffers and counts of the matching getter, with the
+// checks of find_cloud / aloam_get_map_cloud.  Queues nothing.
+static int export_src(aloam_ctx* c, int id, ExportSrc* s) {
+  *s = ExportSrc{};
+  const int* meta = reinterpret_cast<const int*>(c->d_meta.get());
+  const int* mseq = reinterpret_cast<const int*>(c->d_mapseq.get());
+  const int meta_ints = sizeof(SeqMeta) / sizeof(int), map_ints = sizeof(MapSeq) / sizeof(int);
+  const long long feat = (long long)c->R * kLessSharpPerRing, cap = c->cap;
+  auto plain = [&](const float4* b0, const float4* b1, long long stride, const int* count, int count_stride, int sel) {
+    s->base[0] = b0; s->base[1] = b1; s->stride = stride; s->count = count; s->count_stride = count_stride; s->sel = sel; s->kind = kExportPlain;
+  };
+#define META_FIELD(f) (meta + offsetof(SeqMeta, f) / sizeof(int)), meta_ints
+  switch (id) {
+    case ALOAM_CLOUD_FULL: plain(c->d_cloud.get(), nullptr, cap, META_FIELD(n_cloud), kSelFixed); break;
+    case ALOAM_CLOUD_SHARP: plain(c->d_sharp.get(), nullptr, (long long)c->R * kSharpPerRing, META_FIELD(n_sharp), kSelFixed); break;
+    case ALOAM_CLOUD_FLAT: plain(c->d_flat.get(), nullptr, (long long)c->R * kFlatPerRing, META_FIELD(n_flat), kSelFixed); break;
+    case ALOAM_CLOUD_LESS_SHARP: plain(c->d_less_sharp[0].get(), c->d_less_sharp[1].get(), feat, META_FIELD(n_less_sharp), kSelCurrent); break;
+    case ALOAM_CLOUD_LESS_FLAT: plain(c->d_less_flat[0].get(), c->d_less_flat[1].get(), cap, META_FIELD(n_less_flat), kSelCurrent); break;
+    case ALOAM_CLOUD_CORNER_LAST: plain(c->d_less_sharp[0].get(), c->d_less_sharp[1].get(), feat, META_FIELD(n_corner_last), kSelLast); break;
+    case ALOAM_CLOUD_SURF_LAST: plain(c->d_less_flat[0].get(), c->d_less_flat[1].get(), cap, META_FIELD(n_surf_last), kSelLast); break;
+    case ALOAM_EXPORT_MAP + ALOAM_MAP_REGISTERED: case ALOAM_EXPORT_MAP + ALOAM_MAP_CORNER_STACK: case ALOAM_EXPORT_MAP + ALOAM_MAP_SURF_STACK:
+    case ALOAM_EXPORT_MAP + ALOAM_MAP_SURROUND: case ALOAM_EXPORT_MAP + ALOAM_MAP_FULL:
+      if (!c->map_on) { c->err = "mapping not enabled"; return ALOAM_E_STATE; }
+      if (id == ALOAM_EXPORT_MAP + ALOAM_MAP_REGISTERED) plain(c->d_registered.get(), nullptr, cap, META_FIELD(n_cloud), kSelFixed);
+      else if (id == ALOAM_EXPORT_MAP + ALOAM_MAP_CORNER_STACK) plain(c->d_stack[0].get(), nullptr, feat, mseq + offsetof(MapSeq, n_stack) / sizeof(int), map_ints, kSelFixed);
+      else if (id == ALOAM_EXPORT_MAP + ALOAM_MAP_SURF_STACK) plain(c->d_stack[1].get(), nullptr, cap, mseq + offsetof(MapSeq, n_stack) / sizeof(int) + 1, map_ints, kSelFixed);
+      else s->kind = id == ALOAM_EXPORT_MAP + ALOAM_MAP_SURROUND ? kExportSurround : kExportFull;
+      return ALOAM_OK;
+    default: c->err = "unknown cloud id " + std::to_string(id); return ALOAM_E_ARG;
+  }
+#undef META_FIELD
+  // find_cloud's rule: the row a getter of any sequence would read must exist (aloam_create_stages leaves some buffers out)
+  for (int b = 0; b < c->B; ++b) {
+    const int row = s->sel == kSelFixed ? 0 : s->sel == kSelCurrent ? c->parity[b] : 1 - c->parity[b];
+    if (!s->base[row]) { c->err = "this context holds no such cloud (see aloam_create_stages)"; return ALOAM_E_STATE; }
+  }
+  return ALOAM_OK;
+}
+
+// count -> scan -> gather of n_ids checked sources for sequences seq0 .. seq0 + nseq - 1 into device addresses (dst may be nullptr when cap is 0).
+static int queue_export(aloam_ctx* c, const ExportSrc* src, int n_ids, bool full_cloud, int seq0, int nseq, float4* dst, long long cap, long long* dst_off) {
+  for (int i = 0; i < n_ids; ++i) {
+    const int k = src[i].kind - 1;
+    if (k >= 0 && !c->d_exp_pref[k]) HIP_TRY(c, dalloc(c->d_exp_pref[k], (size_t)c->B * ((k == 0 ? kExportSurroundEntries : kExportFullEntries) + 1)));
+  }
+  if (full_cloud) if (const int rc = ensure_dense(c)) return rc;   // the full cloud is gathered from d_cloud, as aloam_get_cloud reads it
+  ExportArgs a{};
+  a.n_ids = n_ids; a.seq0 = seq0; a.nseq = nseq;
+  for (int i = 0; i < n_ids; ++i) a.src[i] = src[i];
+  a.meta = c->d_meta.get();
+  if (c->map_on) {
+    a.cubes = c->d_cubes.get(); a.tab = c->d_maptab.get(); a.mapseq = c->d_mapseq.get();
+    a.pool[0] = c->map.pool[0].get(); a.pool[1] = c->map.pool[1].get(); a.pool_cap = c->map.points;
+  }
+  a.seg_cnt = c->d_exp_cnt.get(); a.chunk_off = c->d_exp_chunk.get(); a.seg_off = c->d_exp_off.get(); a.dst_off = dst_off;
+  a.cube_pref[0] = c->d_exp_pref[0].get(); a.cube_pref[1] = c->d_exp_pref[1].get();
+  a.dst = dst; a.cap_points = dst ? cap : 0;
+  { ProfScope p(c, K_EXPORT); launch_export_clouds(a, c->gather_blocks, c->stream); }
+  HIP_TRY(c, hipGetLastError());
+  c->exp_last_segs = n_ids * nseq;
+  return ALOAM_OK;
+}
+
+// aloam_get_map_cloud(SURROUND / FULL): the export of one sequence into the context's scratch, then one copy to the caller.
+static int get_cube_list(aloam_ctx* c, int seq, int which, float* out, int cap_points) {
+  ExportSrc src;
+  int rc = export_src(c, ALOAM_EXPORT_MAP + which, &src);
+  if (rc) return rc;
+  if (!c->d_exp_tmp_off) HIP_TRY(c, dalloc(c->d_exp_tmp_off, 2));
+  long long off[2] = {0, 0};
+  for (int pass = 0; pass < 2; ++pass) {                  // a second pass only when the scratch was too small for the points asked for
+    if ((rc = queue_export(c, &src, 1, false, seq, 1, c->d_exp_tmp.get(), c->exp_tmp_cap, c->d_exp_tmp_off.get()))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(off, c->d_exp_tmp_off.get(), sizeof(off), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (cap_points <= 0 || off[1] <= c->exp_tmp_cap) break;
+    c->d_exp_tmp.reset(); c->exp_tmp_cap = 0;
+    HIP_TRY(c, dalloc(c->d_exp_tmp, (size_t)off[1]));
+    c->exp_tmp_cap = off[1];
+  }
+  const long long k = std::min<long long>(off[1], cap_points);
+  if (k > 0) HIP_TRY(c, hipMemcpy(out, c->d_exp_tmp.get(), sizeof(float4) * k, hipMemcpyDeviceToHost));
+  return (int)off[1];
+}
+
 int aloam_get_map_pose(aloam_ctx* c, int seq, double q_w_curr[4], double t_w_curr[3], double q_wmap_wodom[4], double t_wmap_wodom[3]) {
   DeviceScope device_scope(c);
   MapSeq ms;
@@ -1372,6 +1489,7 @@ int aloam_get_map_cloud(aloam_ctx* c, int seq, int which, float* out, int cap_po
   MapSeq ms;
   const int rc = fetch_mapseq(c, seq, &ms);
   if (rc) return rc;
+  if (which == ALOAM_MAP_SURROUND || which == ALOAM_MAP_FULL) return get_cube_list(c, seq, which, out, cap_points);
   const float4* p = nullptr;
   int n = 0;
   if (which == ALOAM_MAP_REGISTERED) {
@@ -1384,6 +1502,38 @@ int aloam_get_map_cloud(aloam_ctx* c, int seq, int which, float* out, int cap_po
   const int k = n < cap_points ? n : cap_points;
   if (k > 0) HIP_TRY(c, hipMemcpy(out, p, sizeof(float4) * k, hipMemcpyDeviceToHost));
   return n;
+}
+
+// Poses of every sequence (/laser_odom_to_init src/laserOdometry.cpp:511-522 with para_q / para_t, /aft_mapped_to_init src/laserMapping.cpp:851-863
+// with q_wmap_wodom / t_wmap_wodom), in stream order.
+int aloam_export_poses(aloam_ctx* c, aloam_pose_record* dst) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  void* d = nullptr;
+  if (const int rc = export_target(c, dst, alignof(aloam_pose_record), "dst", &d)) return rc;
+  launch_export_poses(c->d_state.get(), c->map_on ? c->d_mapseq.get() : nullptr, c->B, static_cast<aloam_pose_record*>(d), c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return ALOAM_OK;
+}
+
+// Clouds ids[0 .. n_ids) of every sequence packed back to back (the cloud topics of src/scanRegistration.cpp:413-441, src/laserOdometry.cpp:574-590,
+// src/laserMapping.cpp:803-846), in stream order.  Every argument is checked before anything is queued.
+int aloam_export_clouds(aloam_ctx* c, const int* ids, int n_ids, float* dst_xyzw, long long cap_points, long long* dst_offsets) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (n_ids < 0 || n_ids > ALOAM_EXPORT_MAX_IDS || (n_ids > 0 && !ids)) { c->err = "n_ids must be 0 .. ALOAM_EXPORT_MAX_IDS"; return ALOAM_E_ARG; }
+  if (cap_points < 0) { c->err = "negative cap_points"; return ALOAM_E_ARG; }
+  ExportSrc src[ALOAM_EXPORT_MAX_IDS];
+  bool full_cloud = false;
+  for (int i = 0; i < n_ids; ++i) {
+    for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) { c->err = "repeated cloud id " + std::to_string(ids[i]); return ALOAM_E_ARG; }
+    if (const int rc = export_src(c, ids[i], &src[i])) return rc;
+    full_cloud |= ids[i] == ALOAM_CLOUD_FULL;
+  }
+  void *d_off = nullptr, *d_pts = nullptr;
+  if (const int rc = export_target(c, dst_offsets, alignof(long long), "dst_offsets", &d_off)) return rc;
+  if ((dst_xyzw || cap_points > 0) && export_target(c, dst_xyzw, 16, "dst_xyzw", &d_pts)) return ALOAM_E_ARG;
+  return queue_export(c, src, n_ids, full_cloud, 0, c->B, static_cast<float4*>(d_pts), cap_points, static_cast<long long*>(d_off));
 }
 
 }  // extern "C"

@@ -47,19 +47,14 @@ nav_msgs::Odometry make_odom(const double q[4], const double t[3], const ros::Ti
   o.pose.pose.position.x = t[0]; o.pose.pose.position.y = t[1]; o.pose.pose.position.z = t[2];
   return o;
 }
-sensor_msgs::PointCloud2 cubes_msg(const int* cubes, int n_cubes, const ros::Time& stamp) {   // corner then surf points per cube (:808-813, :825-829)
-  std::vector<float> all;
-  std::vector<int> cnt(21 * 21 * 11);
-  for (int i = 0; i < n_cubes; ++i)
-    for (int cls = 0; cls < 2; ++cls) {
-      std::vector<float> v(4);
-      const int n = aloam_get_map_cube(g_ctx, 0, cls, cubes[i], v.data(), 0);
-      if (n <= 0) continue;
-      v.resize(4 * static_cast<size_t>(n));
-      aloam_get_map_cube(g_ctx, 0, cls, cubes[i], v.data(), n);
-      all.insert(all.end(), v.begin(), v.end());
-    }
-  return aloam_host::xyzi_to_msg(all.data(), static_cast<int>(all.size() / 4), stamp, "/camera_init");
+sensor_msgs::PointCloud2 map_cloud_msg(int which, const ros::Time& stamp) {   // /laser_cloud_surround (:806-812), /laser_cloud_map (:823-829)
+  std::vector<float> all(4);
+  const int n = aloam_get_map_cloud(g_ctx, 0, which, nullptr, 0);
+  if (n > 0) {
+    all.resize(4 * static_cast<size_t>(n));
+    aloam_get_map_cloud(g_ctx, 0, which, all.data(), n);
+  }
+  return aloam_host::xyzi_to_msg(all.data(), n > 0 ? n : 0, stamp, "/camera_init");
 }
 }  // namespace
 aloam_ctx* aloam_node_context() { return g_ctx; }
@@ -110,9 +105,6 @@ static void process() {
     const double qo[4] = {od->pose.pose.orientation.x, od->pose.pose.orientation.y, od->pose.pose.orientation.z, od->pose.pose.orientation.w};
     const double to[3] = {od->pose.pose.position.x, od->pose.pose.position.y, od->pose.pose.position.z};
     const double id_q[4] = {0, 0, 0, 1}, id_t[3] = {0, 0, 0};
-    double t_guess[3];                                     // t_w_curr of transformAssociateToMap (:142-146): picks the centre cube
-    quat_rot(q_wmap_wodom, to, t_guess);
-    for (int k = 0; k < 3; ++k) t_guess[k] += t_wmap_wodom[k];
     if (aloam_set_last(g_ctx, 0, corner.data(), nCorner, surf.data(), nSurf) != ALOAM_OK || aloam_set_full_cloud(g_ctx, 0, full.data(), nFull) != ALOAM_OK ||
         aloam_set_state(g_ctx, 0, id_q, id_t, qo, to) != ALOAM_OK || aloam_mapping_step(g_ctx) != ALOAM_OK) {
       ROS_WARN("mapping step failed: %s", aloam_last_error(g_ctx));
@@ -129,26 +121,9 @@ static void process() {
     aloam_get_map_pose(g_ctx, 0, q_w, t_w, q_wmap_wodom, t_wmap_wodom);
     const ros::Time stamp = ros::Time().fromSec(tOdom);
 
-    if (frameCount % 5 == 0 || frameCount % 20 == 0) {     // :803-834
-      int info[16];
-      aloam_get_map_info(g_ctx, 0, info);
-      std::vector<int> counts(21 * 21 * 11);
-      if (frameCount % 5 == 0) {
-        // laserCloudSurroundInd = the valid 5 x 5 x 3 window around the centre cube (:512-529)
-        const int cI = static_cast<int>((t_guess[0] + 25.0) / 50.0) + info[0] - (t_guess[0] + 25.0 < 0),
-                  cJ = static_cast<int>((t_guess[1] + 25.0) / 50.0) + info[1] - (t_guess[1] + 25.0 < 0),
-                  cK = static_cast<int>((t_guess[2] + 25.0) / 50.0) + info[2] - (t_guess[2] + 25.0 < 0);
-        std::vector<int> cubes;
-        for (int i = cI - 2; i <= cI + 2; i++) for (int j = cJ - 2; j <= cJ + 2; j++) for (int k = cK - 1; k <= cK + 1; k++)
-          if (i >= 0 && i < 21 && j >= 0 && j < 21 && k >= 0 && k < 11) cubes.push_back(i + 21 * j + 21 * 21 * k);
-        pubLaserCloudSurround.publish(cubes_msg(cubes.data(), static_cast<int>(cubes.size()), stamp));
-      }
-      if (frameCount % 20 == 0) {
-        std::vector<int> cubes(21 * 21 * 11);
-        for (int i = 0; i < 21 * 21 * 11; ++i) cubes[i] = i;
-        pubLaserCloudMap.publish(cubes_msg(cubes.data(), static_cast<int>(cubes.size()), stamp));
-      }
-    }
+    // :803-834: the window of this step (laserCloudSurroundInd, :512-529) and the whole map, assembled on the device
+    if (frameCount % 5 == 0) pubLaserCloudSurround.publish(map_cloud_msg(ALOAM_MAP_SURROUND, stamp));
+    if (frameCount % 20 == 0) pubLaserCloudMap.publish(map_cloud_msg(ALOAM_MAP_FULL, stamp));
     {  // /velodyne_cloud_registered (:836-846)
       std::vector<float> reg(4 * static_cast<size_t>(nFull > 0 ? nFull : 1));
       const int n = aloam_get_map_cloud(g_ctx, 0, ALOAM_MAP_REGISTERED, reg.data(), nFull);

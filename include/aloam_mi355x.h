@@ -158,6 +158,12 @@ int aloam_get_map_info(aloam_ctx* ctx, int seq, int out[16]);
 int aloam_map_cube_counts(aloam_ctx* ctx, int seq, int feature_class, int* out_4851);      /* points per cube of the 21 x 21 x 11 window */
 int aloam_get_map_cube(aloam_ctx* ctx, int seq, int feature_class, int cube, float* out_xyzw, int cap_points);   /* laserCloud*Array[cube] */
 enum { ALOAM_MAP_REGISTERED = 2, ALOAM_MAP_CORNER_STACK = 3, ALOAM_MAP_SURF_STACK = 4 };    /* /velodyne_cloud_registered (:836-846); laserCloud*Stack (:542-550) */
+/* ALOAM_MAP_SURROUND: /laser_cloud_surround = laserCloudSurround (src/laserMapping.cpp:803-821): for every cube of the last step's 5 x 5 x 3
+ * window in the i, j, k order of :512-529, its corner cube then its surf cube, as they are after the step's insert and re-filter; empty
+ * before a sequence's first mapping step.  ALOAM_MAP_FULL: /laser_cloud_map = laserCloudMap (:823-834): all 4851 cubes in index order,
+ * corner then surf for each.  Both are assembled on the device by the same kernels as aloam_export_clouds. */
+enum { ALOAM_MAP_SURROUND = 5, ALOAM_MAP_FULL = 6 };
+/* REGISTERED, CORNER_STACK, SURF_STACK, SURROUND or FULL of one sequence.  Returns the point count; out_xyzw may be NULL when cap_points is 0. */
 int aloam_get_map_cloud(aloam_ctx* ctx, int seq, int which, float* out_xyzw, int cap_points);
 
 /* ---- results (each synchronises the stream) ---------------------------------------------------------------- */
@@ -165,6 +171,43 @@ int aloam_cloud_size(aloam_ctx* ctx, int seq, int which);            /* replaces
 int aloam_get_cloud(aloam_ctx* ctx, int seq, int which, float* out_xyzw, int cap_points);  /* what pcl::toROSMsg publishes (src/scanRegistration.cpp:413-441, src/laserOdometry.cpp:574-590) */
 int aloam_get_pose(aloam_ctx* ctx, int seq, double q_w_curr[4], double t_w_curr[3], double q_last_curr[4], double t_last_curr[3]); /* /laser_odom_to_init (src/laserOdometry.cpp:511-522) + para_q / para_t */
 int aloam_get_odom_stats(aloam_ctx* ctx, int seq, aloam_odom_stats* out);
+
+/* ---- batched export: what the nodes publish, for every sequence, in one asynchronous call ------------------------------
+ * Replaces the publishers of the three nodes read one sequence at a time: /laser_odom_to_init (src/laserOdometry.cpp:511-522), the cloud
+ * topics (src/scanRegistration.cpp:413-441, src/laserOdometry.cpp:574-590), /aft_mapped_to_init (src/laserMapping.cpp:851-863),
+ * /laser_cloud_surround, /laser_cloud_map and /velodyne_cloud_registered (src/laserMapping.cpp:803-846).
+ *
+ * Both calls are queued on the context's stream and return without waiting for the device: they make no host synchronisation and read
+ * nothing back.  They write the state at that point of the stream (a step queued after them does not change what they write); the caller
+ * waits with aloam_synchronize or an event on aloam_stream.  Every value has exactly the bits the matching getter returns after a
+ * synchronise, sequences that sat out the last step and clouds injected through aloam_set_* included.
+ *
+ * Destinations: device memory of the context's device, or pinned host memory (hipHostMalloc, hipHostRegister; the kernels write through
+ * its device mapping).  Every pointer is classified before anything is queued: pageable host memory, another device's memory and NULL are
+ * refused with ALOAM_E_ARG (a kernel store to pageable memory would fault the device).  dst_xyzw must be 16-byte aligned; it may be NULL
+ * when cap_points is 0. */
+typedef struct aloam_pose_record {            /* one per sequence; 240 bytes                                                           */
+  double q_w[4], t_w[3];                      /* /laser_odom_to_init          = aloam_get_pose q_w_curr / t_w_curr                      */
+  double q_last_curr[4], t_last_curr[3];      /* para_q / para_t              = aloam_get_pose                                          */
+  double map_q_w[4], map_t_w[3];              /* /aft_mapped_to_init          = aloam_get_map_pose (zeros without mapping)              */
+  double q_wmap_wodom[4], t_wmap_wodom[3];    /* map <- odom correction       = aloam_get_map_pose (zeros without mapping)              */
+  int inited;                                 /* systemInited of the sequence (src/laserOdometry.cpp:69,267-271)                        */
+  int map_frames;                             /* frameCount of the mapping node (src/laserMapping.cpp:115); -1 without mapping          */
+  int pad[2];
+} aloam_pose_record;
+
+/* Cloud ids of aloam_export_clouds: an ALOAM_CLOUD_* value, or ALOAM_EXPORT_MAP + one of ALOAM_MAP_REGISTERED .. ALOAM_MAP_FULL. */
+enum { ALOAM_EXPORT_MAP = 16, ALOAM_EXPORT_MAX_IDS = 12 };
+
+int aloam_export_poses(aloam_ctx* ctx, aloam_pose_record* dst);   /* dst[batch] */
+/* Segment (i, b) = cloud ids[i] of sequence b, packed at [dst_offsets[i * batch + b], dst_offsets[i * batch + b + 1]) in points of 16 bytes;
+ * dst_offsets[n_ids * batch] is the total.  The device writes dst_offsets (n_ids * batch + 1 values) always, and a segment's points only
+ * when the segment ends at or before cap_points: nothing is ever written past cap_points, cap_points = 0 is the size query, and an overflow
+ * is no error (compare the total with the capacity).  0 <= n_ids <= ALOAM_EXPORT_MAX_IDS; unknown or repeated ids: ALOAM_E_ARG; a map id
+ * without aloam_mapping_enable, or a cloud this context holds no buffer for (aloam_create_stages): ALOAM_E_STATE.  `ids` is read during
+ * the call only.  The full cloud (ALOAM_CLOUD_FULL) is made from the ring slabs first if no consumer has asked for it since the last
+ * registration, as aloam_get_cloud does. */
+int aloam_export_clouds(aloam_ctx* ctx, const int* ids, int n_ids, float* dst_xyzw, long long cap_points, long long* dst_offsets);
 
 /* ---- teacher forcing / state injection (what the topic hand-over between the nodes allows) ----------------- */
 int aloam_set_features(aloam_ctx* ctx, int seq, const float* sharp, int n_sharp, const float* less_sharp, int n_less_sharp,

@@ -18,6 +18,7 @@ left sit the step out (aloam_set_active).  Each sequence's output files are byte
 from __future__ import annotations
 
 import argparse
+import ctypes
 import importlib
 import os
 import sys
@@ -121,6 +122,9 @@ def main():
     if args.mapping:
         gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)          # where the map starts: the pools double as it grows (src/laserMapping.cpp:737-783 push_back)
     os.makedirs(args.out, exist_ok=True)
+    import torch                                       # (after the binding: it loads torch's HIP runtime first)
+    rec_buf = torch.empty(batch * ctypes.sizeof(binding.AloamPoseRecord), dtype=torch.uint8, pin_memory=True)   # the poses of a step, written by the device
+    recs = (binding.AloamPoseRecord * batch).from_address(rec_buf.data_ptr())
     odo, mapped = [[] for _ in seqs], [[] for _ in seqs]
     idle = np.zeros((0, 4), np.float32)
     for active, resets, frames in schedule([len(ts) for ts in times], batch):
@@ -132,15 +136,15 @@ def main():
             scans[slot] = read_lidar(os.path.join(args.dataset, "velodyne", "sequences", seqs[i], "velodyne", f"{k:06d}.bin"))
         gpu.scan_register(scans)
         gpu.odometry_step()
-        for slot, (i, k) in frames.items():
-            p = gpu.pose(slot)
-            odo[i].append([times[i][k], *p["t_w"], *p["q_w"]])
         if args.mapping:
             gpu.mapping_step()
-            gpu.synchronize()
-            for slot, (i, k) in frames.items():
-                m = gpu.map_pose(slot)
-                mapped[i].append([times[i][k], *m["t_w"], *m["q_w"]])
+        gpu.export_poses(rec_buf.data_ptr())           # odometry and mapped poses of every slot in one call
+        gpu.synchronize()
+        for slot, (i, k) in frames.items():
+            r = recs[slot]
+            odo[i].append([times[i][k], *r.t_w, *r.q_w])
+            if args.mapping:
+                mapped[i].append([times[i][k], *r.map_t_w, *r.map_q_w])
     gpu.close()
     for i, seq in enumerate(seqs):
         np.savetxt(os.path.join(args.out, f"{seq}_odometry.txt"), np.array(odo[i]), fmt="%.9e")
