@@ -22,6 +22,8 @@ E_ARG, E_SCAN_LINES, E_EMPTY, E_CAPACITY, E_HIP, E_STATE = -1, -2, -3, -4, -5, -
 MAP_REGISTERED, MAP_CORNER_STACK, MAP_SURF_STACK, MAP_SURROUND, MAP_FULL = 2, 3, 4, 5, 6
 EXPORT_MAP, EXPORT_MAX_IDS = 16, 12                 # export ids: CLOUD_* or EXPORT_MAP + MAP_*
 STAGE_REGISTRATION, STAGE_ODOMETRY, STAGE_MAPPING, STAGE_ALL = 1, 2, 4, 7
+SEQ_RECORD_MAGIC, SEQ_RECORD_VERSION = 0x51534C41, 1
+SEQ_PART_ODOMETRY, SEQ_PART_MAP = 1, 2
 MAP_INFO_KEYS = ("cenW", "cenH", "cenD", "frame_count", "from_map_corner", "from_map_surf", "corner_stack", "surf_stack",
                  "corner_num0", "corner_num1", "surf_num0", "surf_num1", "lm_iterations0", "lm_iterations1", "termination0", "compactions")
 
@@ -42,6 +44,16 @@ class AloamPoseRecord(C.Structure):
     _fields_ = [("q_w", C.c_double * 4), ("t_w", C.c_double * 3), ("q_last_curr", C.c_double * 4), ("t_last_curr", C.c_double * 3),
                 ("map_q_w", C.c_double * 4), ("map_t_w", C.c_double * 3), ("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3),
                 ("inited", C.c_int), ("map_frames", C.c_int), ("pad", C.c_int * 2)]
+
+
+class AloamSeqRecordHeader(C.Structure):
+    """The first 128 bytes of a sequence record (aloam_seq_record_header)."""
+    _fields_ = [("magic", C.c_uint), ("version", C.c_uint), ("bytes", C.c_longlong), ("parts", C.c_int), ("n_scans", C.c_int),
+                ("ring_from_field", C.c_int), ("min_range_bits", C.c_uint), ("distortion", C.c_int), ("lm_max_iterations", C.c_int),
+                ("outer_iterations", C.c_int), ("sum_order", C.c_int), ("line_res_bits", C.c_uint), ("plane_res_bits", C.c_uint),
+                ("inited", C.c_int), ("n_corner_last", C.c_int), ("n_surf_last", C.c_int), ("n_cubes", C.c_int * 2),
+                ("map_points", C.c_int * 2), ("err_events", C.c_int), ("seq_meta_bytes", C.c_int), ("odom_bytes", C.c_int),
+                ("map_seq_bytes", C.c_int), ("pad", C.c_int * 6)]
 
 
 class AloamError(RuntimeError):
@@ -112,6 +124,8 @@ def lib():
         L.aloam_set_system_inited.argtypes = [vp, C.c_int]
         L.aloam_set_active.argtypes = [vp, vp]
         L.aloam_reset_sequences.argtypes = [vp, vp, C.c_int]
+        L.aloam_save_sequences.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
+        L.aloam_load_sequences.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_get_ring_ranges.argtypes = [vp, C.c_int, vp, vp]
         L.aloam_get_curvature.argtypes = [vp, C.c_int, vp, C.c_int]
         L.aloam_get_labels.argtypes = [vp, C.c_int, vp, C.c_int]
@@ -283,6 +297,36 @@ class Aloam:
         """Put the listed sequences back to the state of a fresh context, in stream order (no synchronisation)."""
         ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
         self._check(lib().aloam_reset_sequences(self.h, _p(ids) if len(ids) else None, len(ids)))
+
+    # ---- sequence records ------------------------------------------------------------------------------------------------------------
+    def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):
+        """Queue the records of `seqs` into dst_ptr (device memory or pinned host memory; 0 with cap_bytes 0 = the size query); offsets_ptr
+        receives len(seqs) + 1 int64 byte offsets.  Stream-ordered: wait with synchronize()."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_save_sequences(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None,
+                                               int(cap_bytes), C.c_void_p(offsets_ptr) if offsets_ptr else None))
+
+    def save_sequences(self, seqs, pinned=True):
+        """Records of `seqs`: a size query, one allocation (pinned host memory, or device memory with pinned=False), the save and a
+        synchronise.  Returns (blob, offsets): blob a uint8 numpy array (pinned) or torch tensor (device), offsets int64 numpy [len(seqs) + 1]."""
+        import torch
+        off = torch.zeros(len(seqs) + 1, dtype=torch.int64, pin_memory=True)
+        self.save_sequences_into(seqs, 0, 0, off.data_ptr())
+        self.synchronize()
+        total = int(off[-1])
+        blob = torch.empty(max(total, 16), dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.save_sequences_into(seqs, blob.data_ptr(), total, off.data_ptr())
+        self.synchronize()
+        return (blob[:total].numpy() if pinned else blob[:total]), off.numpy().copy()
+
+    def load_sequences(self, slots, blob, offsets):
+        """Record i of blob (numpy array - pageable or a pinned view - or torch tensor on this device or pinned), at
+        [offsets[i], offsets[i + 1]), into slots[i].  The blob is kept referenced until the next load (the copy is stream-ordered)."""
+        ids = np.ascontiguousarray([int(v) for v in slots], dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ptr = blob.data_ptr() if hasattr(blob, "data_ptr") else blob.ctypes.data
+        self._load_keep = (blob, off)
+        self._check(lib().aloam_load_sequences(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(ptr) if ptr else None, _p(off)))
 
     def odometry_step(self):
         self._check(lib().aloam_odometry_step(self.h))

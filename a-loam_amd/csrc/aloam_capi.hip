@@ -14,6 +14,7 @@
 
 #include "../../include/aloam_mi355x.h"
 #include "aloam_device.hpp"
+#include "checkpoint_kernels.hpp"
 #include "export_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -24,11 +25,12 @@ using namespace aloam;
 namespace {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_SAVE, K_LOAD, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds"};
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "save_sequences",
+                                    "load_sequences"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
 constexpr int kNinSlots = 8;
@@ -100,6 +102,7 @@ struct aloam_ctx {
   bool reg_pending = false;
   const int* reg_mask = nullptr;                    // what the last registration's kernels were given (nullptr = all); k_dense_cloud reuses it
   std::vector<int> parity, inited;                  // host mirrors of SeqMeta::parity and OdomState::inited: both change only through host calls
+  std::vector<char> needs_odom;                     // [B] loaded by aloam_load_sequences and not yet through an odometry step: may not map
   DevBuf<int> d_mask_reg, d_mask_odo, d_mask_map, d_reset_ids;   // [B] each: masks as the launches of one stage see them, ids of a reset
   DevBuf<SeqMeta> d_meta;
   DevBuf<float4> d_slabs; int slab = 0;             // ring-ordered points, one slab per (sequence, ring): what k_front writes and the feature kernels read
@@ -153,6 +156,12 @@ struct aloam_ctx {
   int gather_blocks = 2048;                                          // workgroups of the persistent k_export_gather: 8 per CU
   DevBuf<float4> d_exp_tmp; long long exp_tmp_cap = 0;              // aloam_get_map_cloud(SURROUND / FULL): the segment of one sequence
   DevBuf<long long> d_exp_tmp_off;
+  // sequence records (aloam_save_sequences / aloam_load_sequences): scratch sized for `batch` records on first use, used in stream order
+  DevBuf<int> d_ck_seqs, d_ck_info, d_ck_units, d_ck_chunk, d_ck_pref; DevBuf<long long> d_ck_uoff;   // save: ids, counts, lengths, prefixes
+  PinnedBuf<char> h_ck; char* d_ck_host = nullptr;                  // load: headers read back, then the staged offsets / chunks / counts (pinned, mapped)
+  DevBuf<char> d_ck_load;                                           // load: the same staged arrays in device memory
+  DevBuf<char> d_ck_stage; size_t ck_stage_bytes = 0;               // load: records from pageable host memory
+  int ck_save_n = 0; long long ck_load_bytes = 0;                   // the last save / load (algorithmic bytes)
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -417,7 +426,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->in_consumed[k].h, hipEventDisableTiming));
   }
   c->B = cfg->batch; c->max_points = cfg->max_points; c->R = cfg->n_scans;
-  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0);
+  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0);
   // The per-sequence stride of every [B][cap] buffer is kept OFF the powers of two (131 072 points x 16 B = 2 MiB apart, the workgroups of a launch - one
   // per sequence, all at about the same offset of their sequence - meet on the same memory channels): + 1/32 + 16 points.  Measured on k_build_grids_fused at
   // batch 1024, one box: 1.62 - 1.65 ms at the power-of-two stride, 1.48 - 1.52 ms with 1040 / 4112 / 16 400 points of padding.
@@ -698,7 +707,7 @@ int aloam_odometry_step(aloam_ctx* c) {
     launch_all();
   }
   HIP_TRY(c, hipGetLastError());
-  for (int b = 0; b < c->B; ++b) if (bits[b] & kSeqActive) { c->parity[b] ^= 1; c->inited[b] = 1; }
+  for (int b = 0; b < c->B; ++b) if (bits[b] & kSeqActive) { c->parity[b] ^= 1; c->inited[b] = 1; c->needs_odom[b] = 0; }
   c->reg_pending = false;
   return ALOAM_OK;
 }
@@ -851,15 +860,10 @@ int aloam_set_active(aloam_ctx* c, const int* active) {
   return ALOAM_OK;
 }
 
-int aloam_reset_sequences(aloam_ctx* c, const int* seqs, int n) {
-  DeviceScope device_scope(c);
-  if (!c) return ALOAM_E_ARG;
-  if (n < 0 || n > c->B || (n > 0 && !seqs)) { c->err = "bad sequence list"; return ALOAM_E_ARG; }
-  std::vector<char> seen(c->B, 0);
-  for (int i = 0; i < n; ++i) {
-    if (seqs[i] < 0 || seqs[i] >= c->B || seen[seqs[i]]) { c->err = "sequence index out of range or repeated"; return ALOAM_E_ARG; }
-    seen[seqs[i]] = 1;
-  }
+}  // extern "C"
+
+// The reset of aloam_reset_sequences on checked ids, queued, with its host mirrors.
+static int queue_reset(aloam_ctx* c, const int* seqs, int n) {
   if (n == 0) return ALOAM_OK;
   if (!c->d_reset_ids && dmalloc(c, c->d_reset_ids, c->B)) return ALOAM_E_HIP;
   if (const int rc = stage_ints(c, seqs, n, c->d_reset_ids.get())) return rc;
@@ -874,11 +878,26 @@ int aloam_reset_sequences(aloam_ctx* c, const int* seqs, int n) {
   launch_reset_sequences(r, c->stream);
   HIP_TRY(c, hipGetLastError());
   for (int i = 0; i < n; ++i) {
-    c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0;
+    c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0;
     if ((int)c->map_err_seen.size() == c->B) c->map_err_seen[seqs[i]] = 0;
   }
   return ALOAM_OK;
 }
+
+extern "C" {
+
+int aloam_reset_sequences(aloam_ctx* c, const int* seqs, int n) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (n < 0 || n > c->B || (n > 0 && !seqs)) { c->err = "bad sequence list"; return ALOAM_E_ARG; }
+  std::vector<char> seen(c->B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (seqs[i] < 0 || seqs[i] >= c->B || seen[seqs[i]]) { c->err = "sequence index out of range or repeated"; return ALOAM_E_ARG; }
+    seen[seqs[i]] = 1;
+  }
+  return queue_reset(c, seqs, n);
+}
+
 
 // ---- intermediate arrays ---------------------------------------------------------------------------------------
 int aloam_get_ring_ranges(aloam_ctx* c, int seq, int* start, int* count) {
@@ -997,6 +1016,11 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
     long long total = 0;
     HIP_TRY(c, hipMemcpy(&total, c->d_exp_off.get() + c->exp_last_segs, sizeof(total), hipMemcpyDeviceToHost));
     *algorithmic_bytes = 32.0 * total + 16.0 * c->exp_last_segs;
+  } else if (algorithmic_bytes && (kernel == K_SAVE || kernel == K_LOAD)) {
+    // the last save / load: every record byte - points, fixed sections, cube lists - read once and written once
+    long long units = 0;
+    if (kernel == K_SAVE && c->d_ck_uoff) HIP_TRY(c, hipMemcpy(&units, c->d_ck_uoff.get() + c->ck_save_n, sizeof(units), hipMemcpyDeviceToHost));
+    *algorithmic_bytes = 2.0 * (kernel == K_SAVE ? 16.0 * units : (double)c->ck_load_bytes);
   } else if (algorithmic_bytes) {
     // per-launch algorithmic traffic from the sizes of the LAST sweep (DESIGN.md "Algorithmic bytes")
     std::vector<SeqMeta> m(c->B);
@@ -1238,6 +1262,11 @@ int aloam_mapping_step(aloam_ctx* c) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
   if (!c->map_on) { c->err = "aloam_mapping_step before aloam_mapping_enable"; return ALOAM_E_STATE; }
+  for (int b = 0; b < c->B; ++b)
+    if (c->needs_odom[b] && (c->all_active || c->active[b])) {
+      c->err = "sequence " + std::to_string(b) + " was loaded (aloam_load_sequences) and has not had its odometry step yet: it may not map";
+      return ALOAM_E_STATE;
+    }
   // at most four steps queued ahead of the device: the occupancy report the pools are sized from is never older than that
   hipEvent_t done = c->map_step_done[c->map_steps & 3];
   if (c->map_steps >= 4) HIP_TRY(c, hipEventSynchronize(done));
@@ -1534,6 +1563,245 @@ int aloam_export_clouds(aloam_ctx* c, const int* ids, int n_ids, float* dst_xyzw
   if (const int rc = export_target(c, dst_offsets, alignof(long long), "dst_offsets", &d_off)) return rc;
   if ((dst_xyzw || cap_points > 0) && export_target(c, dst_xyzw, 16, "dst_xyzw", &d_pts)) return ALOAM_E_ARG;
   return queue_export(c, src, n_ids, full_cloud, 0, c->B, static_cast<float4*>(d_pts), cap_points, static_cast<long long*>(d_off));
+}
+
+// ---- sequence records ------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+// The header fields a record carries from its context (the counts are the device's): what a load compares.
+static aloam_seq_record_header record_template(const aloam_ctx* c) {
+  aloam_seq_record_header h{};
+  h.magic = ALOAM_SEQ_RECORD_MAGIC; h.version = ALOAM_SEQ_RECORD_VERSION;
+  h.parts = ((c->stages & ALOAM_STAGE_ODOMETRY) ? ALOAM_SEQ_PART_ODOMETRY : 0) | (c->map_on ? ALOAM_SEQ_PART_MAP : 0);
+  h.n_scans = c->cfg.n_scans; h.ring_from_field = c->cfg.ring_from_field != 0;
+  std::memcpy(&h.min_range_bits, &c->cfg.min_range, 4);
+  h.distortion = c->cfg.distortion != 0; h.lm_max_iterations = c->cfg.lm_max_iterations; h.outer_iterations = c->cfg.outer_iterations;
+  h.sum_order = c->sum_order;
+  if (c->map_on) { std::memcpy(&h.line_res_bits, &c->map_line_res, 4); std::memcpy(&h.plane_res_bits, &c->map_plane_res, 4); }
+  h.seq_meta_bytes = sizeof(SeqMeta); h.odom_bytes = sizeof(OdomState); h.map_seq_bytes = sizeof(MapSeq);
+  return h;
+}
+
+// n distinct ids in 0 .. B-1 (slots of a load, sequences of a save).
+static int check_ids(aloam_ctx* c, const int* ids, int n) {
+  if (n < 0 || n > c->B || (n > 0 && !ids)) { c->err = "bad sequence list"; return ALOAM_E_ARG; }
+  std::vector<char> seen(c->B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= c->B || seen[ids[i]]) { c->err = "sequence index out of range or repeated"; return ALOAM_E_ARG; }
+    seen[ids[i]] = 1;
+  }
+  return ALOAM_OK;
+}
+
+// Scratch of both calls, sized for `batch` records, allocated once (then only ever used in stream order).
+static int ck_scratch(aloam_ctx* c) {
+  const size_t B = c->B;
+  if (!c->d_ck_seqs) {
+    HIP_TRY(c, dalloc(c->d_ck_seqs, B)); HIP_TRY(c, dalloc(c->d_ck_info, B * kRecInfo)); HIP_TRY(c, dalloc(c->d_ck_units, B));
+    HIP_TRY(c, dalloc(c->d_ck_chunk, B + 1)); HIP_TRY(c, dalloc(c->d_ck_uoff, B + 1));
+  }
+  if (c->map_on && !c->d_ck_pref) HIP_TRY(c, dalloc(c->d_ck_pref, B * 2 * (kMapCubes + 1)));
+  return ALOAM_OK;
+}
+
+// Load staging, pinned and in device memory: [B + 1] offsets, [B + 1] chunk offsets, [B][kRecInfo] counts.  The pinned copy first holds the
+// offsets and, behind them, the headers of records in device memory.
+static size_t ck_stage_layout(size_t B, size_t* chunk_at, size_t* info_at) {
+  *chunk_at = 8 * (B + 1);
+  *info_at = (*chunk_at + 4 * (B + 1) + 15) & ~(size_t)15;
+  return std::max(*info_at + 4 * kRecInfo * B, *chunk_at + sizeof(aloam_seq_record_header) * B);
+}
+static int ck_load_scratch(aloam_ctx* c) {
+  if (c->h_ck) return ALOAM_OK;
+  size_t ca, ia;
+  const size_t bytes = ck_stage_layout(c->B, &ca, &ia);
+  char* p = nullptr;
+  HIP_TRY(c, hipHostMalloc((void**)&p, bytes, hipHostMallocMapped));
+  c->h_ck.reset(p);
+  HIP_TRY(c, hipHostGetDevicePointer((void**)&c->d_ck_host, p, 0));
+  HIP_TRY(c, dalloc(c->d_ck_load, bytes));
+  return ALOAM_OK;
+}
+
+// Where a load reads `p` from: device memory of the context's device or pinned host memory (*dev = the address the kernels use), or
+// pageable host memory (*dev = nullptr: read by the host, staged).  Another device's memory, managed memory and NULL are refused.
+static int load_source(aloam_ctx* c, const void* p, const char* what, const void** dev, bool* on_host) {
+  hipPointerAttribute_t at{};
+  *dev = nullptr; *on_host = true;
+  if (!p) { c->err = std::string(what) + " is NULL"; return ALOAM_E_ARG; }
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return ALOAM_OK; }   // pageable host memory
+  if (at.isManaged) { c->err = std::string(what) + " must be device memory of the context's device, pinned or pageable host memory"; return ALOAM_E_ARG; }
+  if (at.type == hipMemoryTypeDevice) {
+    if (at.device != c->cfg.device) { c->err = std::string(what) + " is memory of another device"; return ALOAM_E_ARG; }
+    *dev = p; *on_host = false;
+    return ALOAM_OK;
+  }
+  void* d = nullptr;
+  if (at.type == hipMemoryTypeHost && hipHostGetDevicePointer(&d, const_cast<void*>(p), 0) == hipSuccess) *dev = d;
+  else (void)hipGetLastError();
+  return ALOAM_OK;                                       // pinned host memory: readable by the host and (through *dev) by the kernels
+}
+
+// Checks one header against this context; names the first field that differs.
+static int check_header(aloam_ctx* c, int i, const aloam_seq_record_header& h, long long len, const aloam_seq_record_header& want) {
+  auto fail = [&](int rc, const std::string& what) { c->err = "record " + std::to_string(i) + ": " + what; return rc; };
+  if (h.magic != ALOAM_SEQ_RECORD_MAGIC) return fail(ALOAM_E_ARG, "bad magic (not a sequence record)");
+  if (h.version != ALOAM_SEQ_RECORD_VERSION) return fail(ALOAM_E_ARG, "record version " + std::to_string(h.version) + ", this library reads version " + std::to_string(ALOAM_SEQ_RECORD_VERSION));
+  if (h.bytes != len) return fail(ALOAM_E_ARG, "record length " + std::to_string(h.bytes) + " differs from the offsets' " + std::to_string(len));
+  if (h.seq_meta_bytes != want.seq_meta_bytes || h.odom_bytes != want.odom_bytes || h.map_seq_bytes != want.map_seq_bytes) return fail(ALOAM_E_ARG, "section sizes differ");
+  struct { const char* name; long long got, ctx; } fields[] = {
+      {"n_scans", h.n_scans, want.n_scans}, {"ring_from_field", h.ring_from_field, want.ring_from_field},
+      {"min_range", h.min_range_bits, want.min_range_bits}, {"distortion", h.distortion, want.distortion},
+      {"lm_max_iterations", h.lm_max_iterations, want.lm_max_iterations}, {"outer_iterations", h.outer_iterations, want.outer_iterations},
+      {"voxel sum order", h.sum_order, want.sum_order},
+      {"odometry part (ALOAM_STAGE_ODOMETRY)", h.parts & ALOAM_SEQ_PART_ODOMETRY, want.parts & ALOAM_SEQ_PART_ODOMETRY},
+      {"map part (mapping enabled)", h.parts & ALOAM_SEQ_PART_MAP, want.parts & ALOAM_SEQ_PART_MAP},
+      {"mapping_line_resolution", h.line_res_bits, want.line_res_bits}, {"mapping_plane_resolution", h.plane_res_bits, want.plane_res_bits}};
+  for (const auto& f : fields)
+    if (f.got != f.ctx) return fail(ALOAM_E_ARG, std::string(f.name) + " differs from this context's (record " + std::to_string(f.got) + ", context " + std::to_string(f.ctx) + ")");
+  if (h.parts & ~(ALOAM_SEQ_PART_ODOMETRY | ALOAM_SEQ_PART_MAP)) return fail(ALOAM_E_ARG, "unknown parts");
+  const bool odo = h.parts & ALOAM_SEQ_PART_ODOMETRY, map = h.parts & ALOAM_SEQ_PART_MAP;
+  if (h.n_corner_last < 0 || h.n_surf_last < 0 || (!odo && (h.n_corner_last || h.n_surf_last))) return fail(ALOAM_E_ARG, "bad last-cloud sizes");
+  for (int k = 0; k < 2; ++k)
+    if (h.n_cubes[k] < 0 || h.n_cubes[k] > kMapCubes || h.map_points[k] < 0 || (!map && (h.n_cubes[k] || h.map_points[k]))) return fail(ALOAM_E_ARG, "bad cube counts");
+  if (rec_layout(map, h.n_corner_last, h.n_surf_last, h.n_cubes, h.map_points).bytes != h.bytes) return fail(ALOAM_E_ARG, "record length disagrees with its counts");
+  if (h.n_corner_last > c->R * kLessSharpPerRing || h.n_surf_last > c->max_points)
+    return fail(ALOAM_E_CAPACITY, "its last clouds (" + std::to_string(h.n_corner_last) + " / " + std::to_string(h.n_surf_last) + " points) exceed this context's max_points");
+  for (int k = 0; k < 2; ++k)
+    if (h.map_points[k] > c->map_pool_limit) return fail(ALOAM_E_CAPACITY, "its map (" + std::to_string(h.map_points[k]) + " points of one class) exceeds the pool limit");
+  return ALOAM_OK;
+}
+
+extern "C" {
+
+int aloam_save_sequences(aloam_ctx* c, const int* seqs, int n, void* dst, long long cap_bytes, long long* dst_offsets) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (const int rc = check_ids(c, seqs, n)) return rc;
+  if (cap_bytes < 0) { c->err = "negative cap_bytes"; return ALOAM_E_ARG; }
+  if (c->reg_pending) { c->err = "a registration waits for its odometry step: records are saved between frames"; return ALOAM_E_STATE; }
+  void *d_off = nullptr, *d_dst = nullptr;
+  if (const int rc = export_target(c, dst_offsets, alignof(long long), "dst_offsets", &d_off)) return rc;
+  if ((dst || cap_bytes > 0) && export_target(c, dst, 16, "dst", &d_dst)) return ALOAM_E_ARG;
+  if (const int rc = ck_scratch(c)) return rc;
+  if (n > 0) if (const int rc = stage_ints(c, seqs, n, c->d_ck_seqs.get())) return rc;
+  CkptSaveArgs a{};
+  a.seqs = c->d_ck_seqs.get(); a.n = n; a.R = c->R; a.cap = c->cap;
+  a.meta = c->d_meta.get(); a.state = c->d_state.get();
+  if (c->stages & ALOAM_STAGE_ODOMETRY)
+    for (int k = 0; k < 2; ++k) { a.less_sharp[k] = c->d_less_sharp[k].get(); a.less_flat[k] = c->d_less_flat[k].get(); }
+  if (c->map_on) {
+    a.mapseq = c->d_mapseq.get(); a.cubes = c->d_cubes.get(); a.tab = c->d_maptab.get(); a.live = c->d_map_live.get();
+    a.pool[0] = c->map.pool[0].get(); a.pool[1] = c->map.pool[1].get(); a.pool_cap = c->map.points;
+  }
+  a.hdr = record_template(c);
+  a.info = c->d_ck_info.get(); a.units = c->d_ck_units.get(); a.chunk_off = c->d_ck_chunk.get(); a.unit_off = c->d_ck_uoff.get();
+  a.cube_pref = c->d_ck_pref.get();
+  a.dst_off = static_cast<long long*>(d_off); a.dst = static_cast<char*>(d_dst); a.cap_bytes = d_dst ? cap_bytes : 0;
+  { ProfScope p(c, K_SAVE); launch_save_sequences(a, c->gather_blocks, c->stream); }
+  HIP_TRY(c, hipGetLastError());
+  c->ck_save_n = n;
+  return ALOAM_OK;
+}
+
+int aloam_load_sequences(aloam_ctx* c, const int* slots, int n, const void* src, const long long* src_offsets) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (const int rc = check_ids(c, slots, n)) return rc;
+  if (c->reg_pending) { c->err = "a registration waits for its odometry step: records are loaded between frames"; return ALOAM_E_STATE; }
+  const void *d_src = nullptr, *d_offs = nullptr;   // (the offsets are read by the host, then staged with the counts)
+  bool src_host = false, offs_host = false;
+  if (const int rc = load_source(c, src_offsets, "src_offsets", &d_offs, &offs_host)) return rc;
+  if (n == 0) return ALOAM_OK;
+  if (const int rc = load_source(c, src, "src", &d_src, &src_host)) return rc;
+  if ((uintptr_t)src % 16) { c->err = "src must be 16-byte aligned"; return ALOAM_E_ARG; }
+  if (const int rc = ck_load_scratch(c)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));          // the one host wait: the pools are sized from the headers
+  std::vector<long long> off(n + 1);
+  if (offs_host) std::memcpy(off.data(), src_offsets, sizeof(long long) * (n + 1));
+  else HIP_TRY(c, hipMemcpy(off.data(), src_offsets, sizeof(long long) * (n + 1), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i)
+    if (off[i] < 0 || off[i] % 16 || off[i + 1] - off[i] < (long long)sizeof(aloam_seq_record_header) || (off[i + 1] - off[i]) % kRecAlign) {
+      c->err = "record " + std::to_string(i) + ": offsets must rise by whole records (multiples of " + std::to_string(kRecAlign) + " bytes)";
+      return ALOAM_E_ARG;
+    }
+  std::vector<aloam_seq_record_header> hdr(n);
+  if (src_host) {
+    for (int i = 0; i < n; ++i) std::memcpy(&hdr[i], static_cast<const char*>(src) + off[i], sizeof(aloam_seq_record_header));
+  } else {                                                // records in device memory: one small gather of the headers into pinned memory
+    long long* h_off = reinterpret_cast<long long*>(c->h_ck.get());
+    for (int i = 0; i < n; ++i) h_off[i] = off[i];
+    launch_read_headers(static_cast<const char*>(d_src), reinterpret_cast<const long long*>(c->d_ck_host), n, reinterpret_cast<aloam_seq_record_header*>(c->d_ck_host + 8 * (c->B + 1)), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::memcpy(hdr.data(), c->h_ck.get() + 8 * (c->B + 1), sizeof(aloam_seq_record_header) * n);
+  }
+  const aloam_seq_record_header want = record_template(c);
+  long long need = 0;
+  for (int i = 0; i < n; ++i) {
+    if (const int rc = check_header(c, i, hdr[i], off[i + 1] - off[i], want)) return rc;
+    need = std::max<long long>(need, std::max(hdr[i].map_points[0], hdr[i].map_points[1]));
+  }
+  // Everything is checked: from here on the load changes the context.
+  if (c->map_on && need > c->map.points) {
+    long long np = c->map.points;
+    while (np < need) np *= 2;
+    np = std::min<long long>(np, c->map_pool_limit);
+    if (const int rc = map_alloc_pool(c, (int)np)) return rc;
+    c->map_growths += 1;
+  }
+  const char* base = static_cast<const char*>(d_src);
+  if (!base) {                                            // pageable host memory: staged into device memory (the span of the n records)
+    const size_t span = (size_t)(off[n] - off[0]);
+    if (c->ck_stage_bytes < span) {
+      c->d_ck_stage.reset(); c->ck_stage_bytes = 0;
+      HIP_TRY(c, dalloc(c->d_ck_stage, span));
+      c->ck_stage_bytes = span;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_ck_stage.get(), static_cast<const char*>(src) + off[0], span, hipMemcpyHostToDevice, c->stream));
+    base = c->d_ck_stage.get() - off[0];
+  }
+  size_t chunk_at, info_at;
+  ck_stage_layout(c->B, &chunk_at, &info_at);
+  char* h = c->h_ck.get();
+  long long* s_off = reinterpret_cast<long long*>(h);
+  int* s_chunk = reinterpret_cast<int*>(h + chunk_at);
+  int* s_info = reinterpret_cast<int*>(h + info_at);
+  int chunks = 0;
+  for (int i = 0; i < n; ++i) {
+    const aloam_seq_record_header& r = hdr[i];
+    s_off[i] = off[i];
+    s_chunk[i] = chunks;
+    chunks += (int)((r.bytes / 16 + kExportChunk - 1) / kExportChunk);
+    const int info[kRecInfo] = {r.n_corner_last, r.n_surf_last, r.n_cubes[0], r.n_cubes[1], r.map_points[0], r.map_points[1], slots[i], 0};
+    std::memcpy(s_info + (size_t)i * kRecInfo, info, sizeof(info));
+  }
+  s_off[n] = off[n]; s_chunk[n] = chunks;
+  HIP_TRY(c, hipMemcpyAsync(c->d_ck_load.get(), h, info_at + sizeof(int) * kRecInfo * n, hipMemcpyHostToDevice, c->stream));
+  if (const int rc = queue_reset(c, slots, n)) return rc;
+  CkptLoadArgs a{};
+  a.src = base; a.off = reinterpret_cast<const long long*>(c->d_ck_load.get());
+  a.chunk_off = reinterpret_cast<const int*>(c->d_ck_load.get() + chunk_at); a.info = reinterpret_cast<const int*>(c->d_ck_load.get() + info_at);
+  a.n = n; a.R = c->R; a.cap = c->cap;
+  a.meta = c->d_meta.get(); a.state = c->d_state.get();
+  if (c->stages & ALOAM_STAGE_ODOMETRY) { a.corner_last = c->d_less_sharp[1].get(); a.surf_last = c->d_less_flat[1].get(); }
+  if (c->map_on) {
+    a.mapseq = c->d_mapseq.get(); a.cubes = c->d_cubes.get(); a.tab = c->d_maptab.get(); a.live = c->d_map_live.get();
+    a.pool[0] = c->map.pool[0].get(); a.pool[1] = c->map.pool[1].get(); a.pool_cap = c->map.points;
+  }
+  { ProfScope p(c, K_LOAD); launch_load_sequences(a, c->gather_blocks, c->stream); }
+  HIP_TRY(c, hipGetLastError());
+  // host mirrors: parity 0 (the reset), systemInited from the header, capacity events already seen, no mapping before the next odometry step
+  if ((int)c->map_err_seen.size() != c->B) c->map_err_seen.assign(c->B, 0);
+  c->ck_load_bytes = off[n] - off[0];
+  for (int i = 0; i < n; ++i) {
+    const int s = slots[i];
+    c->inited[s] = hdr[i].inited != 0;
+    c->map_err_seen[s] = hdr[i].err_events;
+    c->needs_odom[s] = (c->stages & ALOAM_STAGE_ODOMETRY) ? 1 : 0;
+    if (c->map_on) for (int k = 0; k < 2; ++k) c->h_map_report[1 + k] = std::max((int)c->h_map_report[1 + k], hdr[i].map_points[k]);
+  }
+  return ALOAM_OK;
 }
 
 }  // extern "C"

@@ -29,26 +29,6 @@ __global__ __launch_bounds__(64) void k_export_poses(const OdomState* odom, cons
 }
 
 // ---- clouds ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ceil_chunks(int n) { return (n + kExportChunk - 1) / kExportChunk; }
-
-// Exclusive prefix over the NT threads of a workgroup (Hillis-Steele in LDS); *total = the sum of all.
-template <typename T, int NT>
-__device__ T block_exclusive_scan(T v, T* lds, T* total) {
-  const int tid = threadIdx.x;
-  lds[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < NT; d <<= 1) {
-    const T add = tid >= d ? lds[tid - d] : T(0);
-    __syncthreads();
-    lds[tid] += add;
-    __syncthreads();
-  }
-  const T incl = lds[tid];
-  *total = lds[NT - 1];
-  __syncthreads();                                       // the caller may reuse lds
-  return incl - v;
-}
-
 // Points of every plain segment: the getters' own counts (SeqMeta for the ALOAM_CLOUD_* ids and REGISTERED, MapSeq::n_stack for the stacks).
 __global__ __launch_bounds__(256) void k_export_count(ExportArgs a) {
   const int g = blockIdx.x * 256 + threadIdx.x;
@@ -106,27 +86,6 @@ __global__ __launch_bounds__(1024) void k_export_scan(ExportArgs a) {
   if (tid == 0) { a.seg_off[S] = total_p; a.dst_off[S] = total_p; a.chunk_off[S] = total_c; }
 }
 
-// n points from s to d: tiles of 8 x 256 points with the 8 loads of a thread in flight before its stores (named registers: a local array
-// indexed in an unrolled loop was left in scratch memory), the rest point by point.  Consecutive lanes take consecutive points.
-__device__ __forceinline__ void copy_points(float4* d, const float4* s, int n) {
-  const int tid = threadIdx.x;
-  int base = 0;
-  for (; base + 8 * 256 <= n; base += 8 * 256) {
-    const float4* sp = s + base + tid;
-    float4* dp = d + base + tid;
-    const float4 v0 = sp[0], v1 = sp[256], v2 = sp[512], v3 = sp[768], v4 = sp[1024], v5 = sp[1280], v6 = sp[1536], v7 = sp[1792];
-    dp[0] = v0; dp[256] = v1; dp[512] = v2; dp[768] = v3; dp[1024] = v4; dp[1280] = v5; dp[1536] = v6; dp[1792] = v7;
-  }
-  for (int k = base + tid; k < n; k += 256) d[k] = s[k];
-}
-
-// Last index j in [lo, hi) with v[j] <= x (v non-decreasing, v[lo] <= x).
-template <typename T>
-__device__ __forceinline__ int last_le(const T* v, int lo, int hi, long long x) {
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (v[mid] <= x) lo = mid; else hi = mid; }
-  return lo;
-}
-
 // Persistent segmented copy: the workgroups take chunks of <= kExportChunk points in turn; a chunk finds its segment by binary search over the
 // chunk offsets (the segments of one workgroup's chunks only move forward).  A segment that does not end at or before cap_points is skipped whole.
 __global__ __launch_bounds__(256) void k_export_gather(ExportArgs a) {
@@ -165,6 +124,8 @@ __global__ __launch_bounds__(256) void k_export_gather(ExportArgs a) {
 void launch_export_poses(const OdomState* odom, const MapSeq* mapseq, int B, aloam_pose_record* dst, hipStream_t s) {
   hipLaunchKernelGGL(k_export_poses, dim3((B + 63) / 64), dim3(64), 0, s, odom, mapseq, B, dst);
 }
+
+void launch_export_scan(const ExportArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(1024), 0, s, a); }
 
 void launch_export_clouds(const ExportArgs& a, int gather_blocks, hipStream_t s) {
   const int S = a.n_ids * a.nseq;

@@ -244,6 +244,65 @@ int aloam_set_system_inited(aloam_ctx* ctx, int inited);             /* systemIn
 int aloam_set_active(aloam_ctx* ctx, const int* active);
 int aloam_reset_sequences(aloam_ctx* ctx, const int* seqs, int n);
 
+/* ---- sequence records: save and restore whole sequences, in batched stream-ordered calls ------------------------------
+ * A sequence record is everything that makes up a sequence between two frames - odometry pose and statistics, systemInited, the last
+ * clouds (laserCloudCornerLast / SurfLast, src/laserOdometry.cpp:554-563), and with mapping the map pose, window centre, frame count,
+ * counters, the last step's window and every non-empty cube (src/laserMapping.cpp:72-116) - in a position-independent byte layout.  A
+ * sequence loaded into a slot of any context whose configuration is compatible (below) continues bit for bit as if it had never left.
+ *
+ * aloam_save_sequences: records of the n sequences seqs[0 .. n) (distinct, in range; idle and never-initialised sequences too), queued on
+ * the context's stream with no host synchronisation and no read-back, holding the state at that point of the stream.  dst and dst_offsets:
+ * device memory of the context's device or pinned host memory (as for aloam_export_clouds; pageable memory, another device's memory and
+ * NULL are refused with ALOAM_E_ARG before anything is queued; dst may be NULL when cap_bytes is 0), dst 16-byte aligned.  The device always
+ * writes dst_offsets[0 .. n] in bytes: record i lies at [dst_offsets[i], dst_offsets[i + 1]), every record a multiple of 256 bytes.  A
+ * record is written whole, and only when it ends at or before cap_bytes: nothing is ever written past cap_bytes, and cap_bytes = 0 is the
+ * size query.
+ *
+ * aloam_load_sequences: record i of src (at [src_offsets[i], src_offsets[i + 1])) into slot slots[i], for n distinct slots (one record
+ * may go to several slots: a fork).  src and src_offsets may be device memory of the context's device, pinned host memory, or pageable
+ * host memory (staged through context scratch, so a record read from a file loads directly); src 16-byte aligned.  The call synchronises
+ * the context's stream once and reads the n headers (the map pools are sized on the host; records in device memory: one small gather
+ * kernel and a second wait); every header is checked before anything is
+ * queued - magic, version, length equal to the offsets' difference, the parts held and the compatibility fields - and a failed load
+ * changes nothing.  The rest is asynchronous: src must stay unchanged until aloam_synchronize or an event on aloam_stream.  A loaded slot
+ * first becomes what aloam_reset_sequences makes of it, then receives the record; the active mask is not changed.
+ *   - Compatibility: n_scans, ring_from_field, min_range, distortion, lm_max_iterations, outer_iterations, the voxel sum order, the parts
+ *     held (odometry: the context has ALOAM_STAGE_ODOMETRY; map: mapping is enabled) and the two mapping resolutions must equal the saving
+ *     context's, else ALOAM_E_ARG with the field named by aloam_last_error.  Batch, device, max_points, pool size and pool limit may
+ *     differ: a last cloud larger than the target's max_points, or a map class above its pool limit, is ALOAM_E_CAPACITY; a map above its
+ *     pool size grows the pools first.
+ *   - Frame boundaries: both calls fail with ALOAM_E_STATE between a registration and the odometry step that consumes it.  A sequence
+ *     saved after a frame's odometry step but before its mapping step has dropped that frame in mapping (src/laserMapping.cpp:299-303).
+ *     In a context with ALOAM_STAGE_ODOMETRY a loaded slot takes part in one registration and odometry step before it may be active in a
+ *     mapping step; until then aloam_mapping_step returns ALOAM_E_STATE and queues nothing.
+ *   - The per-step scratch of a sequence (current sweep and its features, dense cloud, curvature, labels, ring starts, correspondences,
+ *     search grids, stacks, registered cloud) is not part of a record: it reads as after aloam_reset_sequences until the next step.  Nor
+ *     is the residue of older sweeps that ALOAM_CLOUD_LESS_SHARP / LESS_FLAT return past the previous last clouds after an odometry step.
+ *     The cubes are packed back to back in the target's pool; aloam_get_map_info's compaction count is kept.
+ * Records of another version are refused; the payload carries no checksum. */
+enum { ALOAM_SEQ_RECORD_MAGIC = 0x51534c41, ALOAM_SEQ_RECORD_VERSION = 1 };   /* magic: the bytes "ALSQ" */
+enum { ALOAM_SEQ_PART_ODOMETRY = 1, ALOAM_SEQ_PART_MAP = 2 };
+typedef struct aloam_seq_record_header {     /* first 128 bytes of a record                                                      */
+  unsigned int magic;                        /* ALOAM_SEQ_RECORD_MAGIC                                                            */
+  unsigned int version;                      /* ALOAM_SEQ_RECORD_VERSION                                                          */
+  long long bytes;                           /* whole record, a multiple of 256                                                   */
+  int parts;                                 /* ALOAM_SEQ_PART_* held                                                             */
+  int n_scans, ring_from_field;              /* the saving context's configuration (aloam_config) ...                            */
+  unsigned int min_range_bits;               /* ... min_range as its IEEE-754 bits                                                */
+  int distortion, lm_max_iterations, outer_iterations;
+  int sum_order;                             /* ALOAM_SUM_*                                                                       */
+  unsigned int line_res_bits, plane_res_bits;   /* mapping resolutions as bits; 0 without the map part                           */
+  int inited;                                /* systemInited of the sequence                                                      */
+  int n_corner_last, n_surf_last;            /* points of the last clouds (0 without the odometry part)                          */
+  int n_cubes[2];                            /* non-empty cubes, corner / surf                                                    */
+  int map_points[2];                         /* points of those cubes, corner / surf                                              */
+  int err_events;                            /* map-pool capacity events of the sequence so far (not reported again after a load) */
+  int seq_meta_bytes, odom_bytes, map_seq_bytes;   /* sizes of the fixed sections that follow the header                         */
+  int pad[6];
+} aloam_seq_record_header;
+int aloam_save_sequences(aloam_ctx* ctx, const int* seqs, int n, void* dst, long long cap_bytes, long long* dst_offsets);
+int aloam_load_sequences(aloam_ctx* ctx, const int* slots, int n, const void* src, const long long* src_offsets);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

@@ -13,7 +13,9 @@ KITTI is not part of this repository or image; `--selftest` writes a tiny synthe
 
 `--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
 context runs one sequence; when it ends, the slot is reset in place (aloam_reset_sequences) and takes the next one, and slots with nothing
-left sit the step out (aloam_set_active).  Each sequence's output files are byte-identical to running it alone.
+left sit the step out (aloam_set_active).  `--slice K` time-slices more sequences than slots (schedule_sliced()): after K frames a sequence
+is saved (aloam_save_sequences) and the longest-waiting one loaded (aloam_load_sequences).  Each sequence's output files are byte-identical
+to running it alone.
 """
 from __future__ import annotations
 
@@ -73,6 +75,41 @@ def schedule(lengths, batch):
         steps.append(([s in frames for s in range(batch)], resets, frames))
 
 
+def schedule_sliced(lengths, batch, k):
+    """Time-sliced continuous batching, without a device: like schedule(), but a resident sequence that has run `k` frames since it entered
+    its slot leaves it for the longest-waiting sequence, if one waits.  A list of steps (active, resets, frames, saves, loads): saves = the
+    (slot, sequence) pairs to save before the step (the sequence leaves with frames left), then resets = the slots a new sequence enters,
+    loads = the (slot, sequence) pairs whose saved record is loaded (the sequence resumes).  Waiting sequences enter in first-in first-out
+    order, new ones in order.  With k >= the longest sequence no sequence is preempted and (active, resets, frames) are schedule()'s."""
+    assert batch >= 1 and k >= 1 and all(n >= 0 for n in lengths)
+    waiting = [i for i, n in enumerate(lengths) if n > 0]
+    started = set()
+    slot_seq, slot_run, nxt = [None] * batch, [0] * batch, [0] * len(lengths)
+    steps = []
+    while True:
+        saves, resets, loads, frames = [], [], [], {}
+        room = len(waiting)                                  # preempt no more sequences than wait
+        for s in range(batch):
+            i = slot_seq[s]
+            if i is not None and nxt[i] >= lengths[i]:
+                slot_seq[s] = None                           # finished
+            elif i is not None and slot_run[s] >= k and room > 0:
+                saves.append((s, i)); waiting.append(i); slot_seq[s] = None; room -= 1
+        for s in range(batch):
+            if slot_seq[s] is None and waiting:
+                i = slot_seq[s] = waiting.pop(0)
+                slot_run[s] = 0
+                (loads.append((s, i)) if i in started else resets.append(s))
+                started.add(i)
+            if slot_seq[s] is not None:
+                i = slot_seq[s]
+                frames[s] = (i, nxt[i])
+                nxt[i] += 1; slot_run[s] += 1
+        if not frames:
+            return steps
+        steps.append(([s in frames for s in range(batch)], resets, frames, saves, loads))
+
+
 def write_selftest(folder, seq="00", frames=6, seed=77):
     syn = importlib.import_module("a-loam_amd.synthetic")
     scans, R, t, model = syn.make_sequence("HDL-64", frames, seed=seed, columns=1024)
@@ -97,6 +134,8 @@ def main():
     ap.add_argument("--seq", default="00")
     ap.add_argument("--seqs", nargs="+", help="several sequences, run together by continuous batching over --batch slots")
     ap.add_argument("--batch", type=int, default=1, help="slots of the context with --seqs")
+    ap.add_argument("--slice", type=int, default=0, help="with --seqs: time slices of this many frames; a preempted sequence is saved into pinned host "
+                                                        "memory (aloam_save_sequences) and later loaded into whichever slot is free (schedule_sliced)")
     ap.add_argument("--out", default="kitti_out")
     ap.add_argument("--mapping", action="store_true")
     ap.add_argument("--max-frames", type=int, default=0)
@@ -127,7 +166,16 @@ def main():
     recs = (binding.AloamPoseRecord * batch).from_address(rec_buf.data_ptr())
     odo, mapped = [[] for _ in seqs], [[] for _ in seqs]
     idle = np.zeros((0, 4), np.float32)
-    for active, resets, frames in schedule([len(ts) for ts in times], batch):
+    lengths = [len(ts) for ts in times]
+    plan = schedule_sliced(lengths, batch, args.slice) if args.slice > 0 else [(*st, [], []) for st in schedule(lengths, batch)]
+    parked = {}                                        # sequence -> (record bytes in pinned host memory, offsets)
+    for active, resets, frames, saves, loads in plan:
+        if saves:
+            blob, off = gpu.save_sequences([s for s, _ in saves])
+            for j, (_, i) in enumerate(saves):
+                parked[i] = (blob[off[j]:off[j + 1]], np.array([0, off[j + 1] - off[j]], np.int64))
+        for s, i in loads:
+            gpu.load_sequences([s], *parked.pop(i))
         if resets:
             gpu.reset_sequences(resets)                # a new sequence enters these slots: a fresh context's state, in place
         gpu.set_active(None if all(active) else active)
