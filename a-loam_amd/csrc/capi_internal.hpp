@@ -1,0 +1,274 @@
+// a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
+// error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
+// aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/aloam_mi355x.h"
+#include "aloam_device.hpp"
+#include "checkpoint_kernels.hpp"
+#include "export_kernels.hpp"
+#include "mapping_kernels.hpp"
+#include "odometry_kernels.hpp"
+#include "registration_kernels.hpp"
+
+using namespace aloam;
+
+namespace aloam {
+enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
+                K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_SAVE, K_LOAD, K_COUNT };
+const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
+                                    "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
+                                    "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "save_sequences",
+                                    "load_sequences"};
+static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
+struct ProfRec { int kernel; hipEvent_t e0, e1; };
+constexpr int kNinSlots = 8;
+
+// Owners of everything the context allocates: released by their destructors when the context is deleted, so a failed
+// allocation or copy half way through leaks nothing.
+struct DeviceFree { void operator()(void* p) const { (void)hipFree(p); } };
+struct PinnedFree { void operator()(const volatile void* p) const { (void)hipHostFree(const_cast<void*>(p)); } };
+template <typename T> using DevBuf = std::unique_ptr<T[], DeviceFree>;
+template <typename T> using PinnedBuf = std::unique_ptr<T[], PinnedFree>;
+// A stream, event or graph: converts to the raw handle, so call sites read as with the handle itself.
+template <typename H, hipError_t (*Destroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}   // (no copies, no assignment)
+  ~Handle() { reset(); }
+  void reset() { if (h) (void)Destroy(h); h = nullptr; }
+  operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
+
+template <typename T>
+hipError_t dalloc(DevBuf<T>& p, size_t count) {
+  T* raw = nullptr;
+  const hipError_t e = hipMalloc((void**)&raw, count * sizeof(T));
+  p.reset(raw);
+  return e;
+}
+
+// Everything whose size follows the map pool (map_alloc_pool): built fresh and committed with one move when the pool grows.
+struct MapPool {
+  int points = 0, H = 0;             // pool points per sequence and class, buckets of the submap grid
+  int cube_levels = 0, tile_cap = 0, tile_bound = 0;   // general voxel path: merge levels of a cube, tile list capacity, tiles of the per-cube pass
+  long long key_cap = 0;
+  DevBuf<float4> pool[2], grid_sorted[2], voxtmp;
+  DevBuf<int> grid_start[2], tile_seg, tile_heads, tile_pref;
+  DevBuf<unsigned long long> keys[2];
+};
+}  // namespace aloam
+
+struct aloam_ctx {
+  // Streams and events first: members are destroyed in reverse order, so every buffer is released before them.
+  Stream stream, copy_stream;
+  Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
+  std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
+  // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
+  // solves (no mask), [1] through the staged mask d_mask_odo
+  GraphExec odom_graph[2];
+  aloam_config cfg{};
+  int stages = ALOAM_STAGE_ALL;      // which stages this context has buffers for (aloam_create_stages)
+  int B = 0, cap = 0, R = 0, NB = 0, npad = 0;   // cap: points per sequence the big buffers are laid out for = max_points + padding (below)
+  int max_points = 0;                   // what the caller may hand in (aloam_config.max_points)
+  std::string err;
+  // input staging (host-input path only)
+  // two device slabs: the H2D copy of call k + 1 (copy stream) overlaps the kernels of call k (compute stream)
+  DevBuf<char> d_in[2]; size_t d_in_bytes[2] = {0, 0};
+  int in_slot = 0;
+  bool in_used[2] = {false, false};
+  DevBuf<int> d_nin;
+  PinnedBuf<int> h_nin; int h_nin_slot = 0;         // pinned ring of kNinSlots x B ints (counts, masks, reset ids): an async H2D copy reads its slot later
+  bool nin_used[kNinSlots] = {};
+  // per-sequence lifecycle (aloam_set_active / aloam_reset_sequences)
+  std::vector<int> active;                          // [B] the mask in force, 0 / 1
+  bool all_active = true;
+  std::vector<int> reg_active;                      // the mask of the last registration, while its odometry step is still to come (reg_pending)
+  bool reg_pending = false;
+  const int* reg_mask = nullptr;                    // what the last registration's kernels were given (nullptr = all); k_dense_cloud reuses it
+  std::vector<int> parity, inited;                  // host mirrors of SeqMeta::parity and OdomState::inited: both change only through host calls
+  std::vector<char> needs_odom;                     // [B] loaded by aloam_load_sequences and not yet through an odometry step: may not map
+  DevBuf<int> d_mask_reg, d_mask_odo, d_mask_map, d_reset_ids;   // [B] each: masks as the launches of one stage see them, ids of a reset
+  DevBuf<SeqMeta> d_meta;
+  DevBuf<float4> d_slabs; int slab = 0;             // ring-ordered points, one slab per (sequence, ring): what k_front writes and the feature kernels read
+  DevBuf<unsigned long long> d_front_lb; DevBuf<int> d_front_ticket;
+  bool dense_valid = true;                          // d_cloud holds the dense concatenation of the current slabs (k_dense_cloud, on demand)
+  DevBuf<int> d_ringstart;
+  DevBuf<float4> d_cloud; DevBuf<float> d_curv; DevBuf<int8_t> d_label;
+  DevBuf<unsigned long long> d_lookback; unsigned reg_epoch = 0;   // ring-count granules of k_ring_features, launch counter
+  DevBuf<int> d_ring_ticket;                                       // per sweep: rings handed out to the workgroups of the running k_ring_features
+  bool debug_arrays = false;                                       // the last registration wrote curvature / labels
+  DevBuf<float4> d_sharp, d_flat;
+  DevBuf<float4> d_less_sharp[2], d_less_flat[2];   // a sequence's CURRENT sweep is in [parity[b]], its last clouds in [1 - parity[b]]
+  DevBuf<OdomState> d_state;
+  DevBuf<float4> d_grid_sorted3[2], d_grid_sorted2[2];
+  DevBuf<int> d_grid_start3[2], d_grid_start2[2];
+  DevBuf<float4> d_grid_sorted3c[2];   // coarse level of the 3-D grid
+  DevBuf<int> d_grid_start3c[2];
+  DevBuf<int> d_grid_flags[2], d_grid_walk[2];
+  int grid_H[2] = {4096, 16384};
+  DevBuf<EdgeRec> d_edges; DevBuf<PlaneRec> d_planes;
+  DevBuf<float4> d_sel_sharp, d_sel_flat;
+  // scan-to-map refinement (allocated by aloam_mapping_enable)
+  bool map_on = false;
+  long long map_err_reported = 0;    // voxel-scratch capacity events (vox counters[3]) aloam_synchronize has already returned
+  std::vector<long long> map_err_seen;   // per sequence: pool capacity events (MapSeq.err_steps) already returned
+  float map_line_res = 0.4f, map_plane_res = 0.8f;
+  int map_levels = 0, map_stack_tile_bound = 0, map_nsegs_max = 0;   // general voxel path over the incoming clouds: merge levels, tiles
+  MapPool map;                       // the pool-sized state (map_alloc_pool)
+  // pool growth (map_ensure_capacity): the reference's cubes are std::vectors that grow without bound (src/laserMapping.cpp:737-783)
+  int map_pool_limit = 1 << 26;      // ceiling per sequence and class (aloam_mapping_set_pool_limit); ALOAM_E_CAPACITY only there
+  int map_growths = 0;
+  long long map_steps = 0;           // mapping steps queued so far
+  // What one mapping step can add to a map is bounded by the largest of: the active rows of the last registration, and the clouds injected
+  // since the last mapping step (aloam_set_last / aloam_set_features).  An injection raises the bound, never lowers it.
+  int nin_max = 0;                   // largest active scan of the last registration call
+  int inject_max = 0;                // largest cloud injected since the last mapping step
+  PinnedBuf<volatile int> h_map_report;   // pinned: {step, live corner, live surf, stack corner, stack surf} of the last finished step
+  int* d_map_report_host = nullptr;       // the same memory as the device sees it
+  DevBuf<int> d_map_report, d_map_live;
+  DevBuf<MapSeq> d_mapseq; DevBuf<CubeDesc> d_cubes; DevBuf<int> d_maptab;
+  DevBuf<float4> d_stack[2], d_stack_world[2]; DevBuf<int> d_stack_cube[2];
+  DevBuf<int> d_addcnt, d_cursor, d_compact_flag;
+  DevBuf<MapEdgeRec> d_medges; DevBuf<MapNormRec> d_mnorms; DevBuf<float4> d_registered, d_knn;
+  DevBuf<int> d_vox_lists;
+  DevBuf<int> d_rec_tiles; int rec_tiles_corner = 0, rec_tiles_per_seq = 0;
+  DevBuf<VoxSeg> d_segs; DevBuf<int> d_vox_counters, d_bbox;
+  // batched export (aloam_export_clouds, and the cube-list clouds of aloam_get_map_cloud): scratch of count / scan / gather, used in stream order
+  DevBuf<int> d_exp_cnt, d_exp_chunk; DevBuf<long long> d_exp_off;   // [ALOAM_EXPORT_MAX_IDS * B] points and [.. + 1] chunk / point offsets per segment
+  DevBuf<int> d_exp_pref[2];                                         // entry prefixes of the cube lists, [B][151] surround, [B][9703] full map (on first use)
+  int exp_last_segs = 0;                                             // segments of the last export (its algorithmic bytes)
+  int gather_blocks = 2048;                                          // workgroups of the persistent k_export_gather: 8 per CU
+  DevBuf<float4> d_exp_tmp; long long exp_tmp_cap = 0;              // aloam_get_map_cloud(SURROUND / FULL): the segment of one sequence
+  DevBuf<long long> d_exp_tmp_off;
+  // sequence records (aloam_save_sequences / aloam_load_sequences): scratch sized for `batch` records on first use, used in stream order
+  DevBuf<int> d_ck_seqs, d_ck_info, d_ck_units, d_ck_chunk, d_ck_pref; DevBuf<long long> d_ck_uoff;   // save: ids, counts, lengths, prefixes
+  PinnedBuf<char> h_ck; char* d_ck_host = nullptr;                  // load: headers read back, then the staged offsets / chunks / counts (pinned, mapped)
+  DevBuf<char> d_ck_load;                                           // load: the same staged arrays in device memory
+  DevBuf<char> d_ck_stage; size_t ck_stage_bytes = 0;               // load: records from pageable host memory
+  int ck_save_n = 0; long long ck_load_bytes = 0;                   // the last save / load (algorithmic bytes)
+  int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
+  bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
+  bool have_features = false;
+  // profiling
+  bool prof_on = false;
+  bool debug_sync = false;           // environment ALOAM_DEBUG_SYNC, read once at creation
+  std::vector<ProfRec> prof_pending;
+  std::vector<hipEvent_t> prof_free;
+  double prof_ms[K_COUNT] = {0};
+  long long prof_launches[K_COUNT] = {0};
+};
+
+#define HIP_TRY(ctx, expr)                                                                                   \
+  do {                                                                                                       \
+    hipError_t e__ = (expr);                                                                                 \
+    if (e__ != hipSuccess) {                                                                                 \
+      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                                       \
+      return ALOAM_E_HIP;                                                                                    \
+    }                                                                                                        \
+  } while (0)
+
+namespace aloam {
+
+// allocate and zero on the context's stream: the kernels rely on zeroed look-back granules, tickets and counters
+template <typename T>
+int dmalloc(aloam_ctx* c, DevBuf<T>& p, size_t count) {
+  HIP_TRY(c, dalloc(p, count));
+  HIP_TRY(c, hipMemsetAsync(p.get(), 0, count * sizeof(T), c->stream));
+  return ALOAM_OK;
+}
+
+hipEvent_t prof_event(aloam_ctx* c);
+struct ProfScope {
+  aloam_ctx* c; int k; hipEvent_t e0 = nullptr;
+  ProfScope(aloam_ctx* c_, int k_) : c(c_), k(k_) {
+    if (c->prof_on) { e0 = prof_event(c); (void)hipEventRecord(e0, c->stream); }
+  }
+  ~ProfScope() {
+    if (c->prof_on) { hipEvent_t e1 = prof_event(c); (void)hipEventRecord(e1, c->stream); c->prof_pending.push_back({k, e0, e1}); }
+    if (c->debug_sync) {   // ALOAM_DEBUG_SYNC=1: wait after every stage and name it, so that a device fault can be pinned on a kernel
+      const hipError_t e = hipStreamSynchronize(c->stream);
+      std::fprintf(stderr, "[aloam] %-22s %s\n", kKernelNames[k], e == hipSuccess ? "ok" : hipGetErrorString(e));
+    }
+  }
+};
+// Every entry point runs on the context's device whatever the calling thread's current device is, and leaves the caller's
+// choice as it found it (several contexts on several devices in one process; frameworks that switch devices behind our back).
+struct DeviceScope {
+  int prev = -1;
+  explicit DeviceScope(const aloam_ctx* c) {
+    int cur = -1;
+    if (c && hipGetDevice(&cur) == hipSuccess && cur != c->cfg.device && hipSetDevice(c->cfg.device) == hipSuccess) prev = cur;
+  }
+  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+  DeviceScope(const DeviceScope&) = delete;
+  DeviceScope& operator=(const DeviceScope&) = delete;
+};
+
+// The per-sequence struct at `dev` (SeqMeta, OdomState, MapSeq, a count in one of them) read back after the stream has drained.
+template <typename T>
+int read_seq(aloam_ctx* c, const T* dev, T* out) {
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(out, dev, sizeof(T), hipMemcpyDeviceToHost));
+  return ALOAM_OK;
+}
+
+// The per-sequence struct at `dev` read back (read_seq), changed by `edit`, written again.
+template <typename T, typename Edit>
+int edit_seq(aloam_ctx* c, T* dev, Edit edit) {
+  T v;
+  if (const int rc = read_seq(c, dev, &v)) return rc;
+  edit(v);
+  HIP_TRY(c, hipMemcpy(dev, &v, sizeof(T), hipMemcpyHostToDevice));
+  return ALOAM_OK;
+}
+
+// A scratch buffer of `have` elements grown to hold `need`; the old one is released first: its contents are not needed.
+template <typename T, typename N>
+int grow_scratch(aloam_ctx* c, DevBuf<T>& p, N& have, N need) {
+  if (have >= need) return ALOAM_OK;
+  have = 0;
+  p.reset();
+  HIP_TRY(c, dalloc(p, (size_t)need));
+  have = need;
+  return ALOAM_OK;
+}
+
+// The row of sequence `seq` that a getter reads through `s` (cloud_desc): base[0 / parity / 1 - parity] + seq * stride; nullptr when this
+// context has no buffer for it (aloam_create_stages leaves some out).  Writable: the setters fill the context's own buffers through it.
+inline float4* cloud_row(const aloam_ctx* c, const ExportSrc& s, int seq) {
+  const int r = s.sel == kSelFixed ? 0 : s.sel == kSelCurrent ? c->parity[seq] : 1 - c->parity[seq];
+  return s.base[r] ? const_cast<float4*>(s.base[r]) + (size_t)seq * s.stride : nullptr;
+}
+
+// aloam_capi.hip
+int stage_ints(aloam_ctx* c, const int* src, int n, int* dst);
+int stage_mask(aloam_ctx* c, DevBuf<int>& dst, const int** out);
+int check_seq(aloam_ctx* c, int seq);
+int require_stage(aloam_ctx* c, int stage);
+int check_ids(aloam_ctx* c, const int* ids, int n);
+int queue_reset(aloam_ctx* c, const int* seqs, int n);
+// capi_odometry.hip
+int ensure_dense(aloam_ctx* c);
+long long cloud_desc(const aloam_ctx* c, int id, ExportSrc* s);
+int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n);
+// capi_mapping.hip
+int grow_map_pool(aloam_ctx* c, long long want, bool clamp);
+// capi_records.hip
+int get_cube_list(aloam_ctx* c, int seq, int which, float* out, int cap_points);
+
+}  // namespace aloam
