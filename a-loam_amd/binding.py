@@ -124,6 +124,7 @@ def lib():
         L.aloam_set_system_inited.argtypes = [vp, C.c_int]
         L.aloam_set_active.argtypes = [vp, vp]
         L.aloam_reset_sequences.argtypes = [vp, vp, C.c_int]
+        L.aloam_set_map_frozen.argtypes = [vp, vp]
         L.aloam_save_sequences.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_load_sequences.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_get_ring_ranges.argtypes = [vp, C.c_int, vp, vp]
@@ -297,6 +298,16 @@ class Aloam:
         """Put the listed sequences back to the state of a fresh context, in stream order (no synchronisation)."""
         ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
         self._check(lib().aloam_reset_sequences(self.h, _p(ids) if len(ids) else None, len(ids)))
+
+    def set_map_frozen(self, mask=None):
+        """Which sequences localize against their map instead of extending it in the mapping steps that follow (one truthy value per
+        sequence); None = none of them."""
+        if mask is None:
+            self._check(lib().aloam_set_map_frozen(self.h, None))
+            return
+        m = np.ascontiguousarray([1 if v else 0 for v in mask], dtype=np.int32)
+        assert m.shape == (self.batch,)
+        self._check(lib().aloam_set_map_frozen(self.h, _p(m)))
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

@@ -53,9 +53,10 @@ struct alignas(16) OdomState {         // one per sequence, device resident
 };
 
 // Which sequences take part in a launch (aloam_set_active): nullptr = all of them, else one int per sequence whose bit kSeqActive says
-// whether it takes part at all and kSeqSolve (odometry only) whether it is an active sequence past its first frame.  One scalar load per
-// workgroup: a sequence that sits out is neither read nor written.
-enum SeqBits { kSeqActive = 1, kSeqSolve = 2 };
+// whether it takes part at all, kSeqSolve (odometry only) whether it is an active sequence past its first frame and kSeqMapGrow (mapping
+// only) whether it is an active sequence that extends its map (aloam_set_map_frozen: clear = it localizes against a frozen map).  One
+// scalar load per workgroup: a sequence that sits out is neither read nor written.
+enum SeqBits { kSeqActive = 1, kSeqSolve = 2, kSeqMapGrow = 4 };
 __device__ __forceinline__ bool seq_idle(const int* active, int b, int bit = kSeqActive) { return active && !(active[b] & bit); }
 
 struct EdgeRec { float cp[3], a[3], b[3]; int valid; int pad[2]; };          // 48 B : LidarEdgeFactor ctor args

@@ -102,6 +102,8 @@ struct aloam_ctx {
   const int* reg_mask = nullptr;                    // what the last registration's kernels were given (nullptr = all); k_dense_cloud reuses it
   std::vector<int> parity, inited;                  // host mirrors of SeqMeta::parity and OdomState::inited: both change only through host calls
   std::vector<char> needs_odom;                     // [B] loaded by aloam_load_sequences and not yet through an odometry step: may not map
+  std::vector<char> frozen;                         // [B] aloam_set_map_frozen: localizes against its map in the mapping steps, does not extend it
+  bool any_frozen = false;
   DevBuf<int> d_mask_reg, d_mask_odo, d_mask_map, d_reset_ids;   // [B] each: masks as the launches of one stage see them, ids of a reset
   DevBuf<SeqMeta> d_meta;
   DevBuf<float4> d_slabs; int slab = 0;             // ring-ordered points, one slab per (sequence, ring): what k_front writes and the feature kernels read
@@ -142,6 +144,7 @@ struct aloam_ctx {
   int* d_map_report_host = nullptr;       // the same memory as the device sees it
   DevBuf<int> d_map_report, d_map_live;
   DevBuf<MapSeq> d_mapseq; DevBuf<CubeDesc> d_cubes; DevBuf<int> d_maptab;
+  DevBuf<MapGridSig> d_grid_sig;     // [B][2] what each submap grid was last built from (grid reuse of frozen sequences)
   DevBuf<float4> d_stack[2], d_stack_world[2]; DevBuf<int> d_stack_cube[2];
   DevBuf<int> d_addcnt, d_cursor, d_compact_flag;
   DevBuf<MapEdgeRec> d_medges; DevBuf<MapNormRec> d_mnorms; DevBuf<float4> d_registered, d_knn;

@@ -22,7 +22,7 @@ static MapArgs map_args(aloam_ctx* c) {
     a.pool[k] = c->map.pool[k].get(); a.stack[k] = c->d_stack[k].get(); a.stack_world[k] = c->d_stack_world[k].get(); a.stack_cube[k] = c->d_stack_cube[k].get();
     a.grid_sorted[k] = c->map.grid_sorted[k].get(); a.grid_start[k] = c->map.grid_start[k].get();
   }
-  a.grid_H = c->map.H; a.live = c->d_map_live.get(); a.report_dev = c->d_map_report.get(); a.report_host = c->d_map_report_host;
+  a.grid_H = c->map.H; a.grid_sig = c->d_grid_sig.get(); a.live = c->d_map_live.get(); a.report_dev = c->d_map_report.get(); a.report_host = c->d_map_report_host;
   a.addcnt = c->d_addcnt.get(); a.cursor = c->d_cursor.get(); a.compact_flag = c->d_compact_flag.get();
   a.edges = c->d_medges.get(); a.norms = c->d_mnorms.get(); a.knn = c->d_knn.get();
   a.lm_max_iterations = c->cfg.lm_max_iterations;
@@ -70,6 +70,7 @@ static int map_alloc_pool(aloam_ctx* c, int pool_points) {
     else HIP_TRY(c, hipMemsetAsync(n.pool[k].get(), 0, sizeof(float4) * B * pool, c->stream));
     HIP_TRY(c, hipMemsetAsync(n.grid_start[k].get(), 0, sizeof(int) * B * ((size_t)n.H + 1), c->stream));
   }
+  if (c->d_grid_sig) HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get(), 0, sizeof(MapGridSig) * B * 2, c->stream));   // the grids are not moved
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->map = std::move(n);
   return ALOAM_OK;
@@ -82,6 +83,7 @@ static int map_alloc_pool(aloam_ctx* c, int pool_points) {
 // (a stack is a filtered subset of one sweep) until a step has reported, then twice the largest stack any step has produced so far - a
 // step that breaks that bound AND fills the pool drops points and raises ALOAM_E_CAPACITY like a full pool at the ceiling does.  When the
 // bound exceeds the pool: wait for the device (the report is then exact), double the pool until it holds the bound, move the contents.
+// Not called for a step whose active sequences are all frozen (aloam_set_map_frozen): such a step adds nothing to any map.
 static int map_ensure_capacity(aloam_ctx* c) {
   if (c->map.points >= c->map_pool_limit) return ALOAM_OK;     // at the ceiling: nothing to decide (the device counts what does not fit)
   const int step_max = std::max(c->nin_max, c->inject_max);   // the last registration's active rows and what was injected since the last step
@@ -144,6 +146,7 @@ int aloam_mapping_enable(aloam_ctx* c, float line_res, float plane_res, int pool
   if ((rc = dmalloc(c, c->d_mapseq, B))) return rc;
   if ((rc = dmalloc(c, c->d_cubes, B * 2 * kMapCubes))) return rc;
   if ((rc = dmalloc(c, c->d_maptab, B * kTabInts))) return rc;
+  if ((rc = dmalloc(c, c->d_grid_sig, B * 2))) return rc;               // zeros: no grid is valid
   if ((rc = dmalloc(c, c->d_addcnt, B * 2 * kMapCubes))) return rc;
   if ((rc = dmalloc(c, c->d_cursor, B * 2 * kMapCubes))) return rc;
   if ((rc = dmalloc(c, c->d_compact_flag, B * 2))) return rc;
@@ -219,14 +222,32 @@ int aloam_mapping_step(aloam_ctx* c) {
       c->err = "sequence " + std::to_string(b) + " was loaded (aloam_load_sequences) and has not had its odometry step yet: it may not map";
       return ALOAM_E_STATE;
     }
+  // Per sequence: kSeqActive = takes part, kSeqMapGrow = takes part and extends its map (not frozen).  The kernels get no mask at all when
+  // every sequence grows: the launches of a lock-step batch are those of a context without aloam_set_active / aloam_set_map_frozen.
+  const int* mask = nullptr;
+  bool any_active = c->all_active, any_grow = !c->any_frozen;
+  if (!c->all_active || c->any_frozen) {
+    std::vector<int> bits(c->B);
+    any_grow = false;
+    for (int b = 0; b < c->B; ++b) {
+      const bool on = c->all_active || c->active[b];
+      bits[b] = on ? (kSeqActive | (c->frozen[b] ? 0 : kSeqMapGrow)) : 0;
+      any_active |= on;
+      any_grow |= (bits[b] & kSeqMapGrow) != 0;
+    }
+    if (!c->d_mask_map && dmalloc(c, c->d_mask_map, c->B)) return ALOAM_E_HIP;
+    if (const int rc = stage_ints(c, bits.data(), c->B, c->d_mask_map.get())) return rc;
+    mask = c->d_mask_map.get();
+  }
+  const bool sizes_pools = any_grow || !any_active;       // every active sequence frozen: nothing is inserted, the pools are neither sized nor waited for
   // at most four steps queued ahead of the device: the occupancy report the pools are sized from is never older than that
   hipEvent_t done = c->map_step_done[c->map_steps & 3];
-  if (c->map_steps >= 4) HIP_TRY(c, hipEventSynchronize(done));
-  int rc = map_ensure_capacity(c);
+  if (sizes_pools && c->map_steps >= 4) HIP_TRY(c, hipEventSynchronize(done));
+  int rc = sizes_pools ? map_ensure_capacity(c) : ALOAM_OK;
   if (rc) return rc;
   c->inject_max = 0;
   MapArgs a = map_args(c);
-  if ((rc = stage_mask(c, c->d_mask_map, &a.active))) return rc;
+  a.active = mask;
   { ProfScope p(c, K_MAP_BEGIN); launch_map_begin(a, c->stream); }
   { ProfScope p(c, K_MAP_VOXEL_STACK);                                      // downSizeFilterCorner / Surf on the incoming clouds (:542-550)
     const VoxArgs v = vox_args(c, c->B * 2, c->map_levels);
@@ -234,13 +255,13 @@ int aloam_mapping_step(aloam_ctx* c) {
     launch_map_stack_segments(a, v, c->stream);
     if (c->sum_order) launch_voxel_filter_reference_order(v, a, true, c->stream);
     else launch_voxel_filter(v, c->map_stack_tile_bound, c->stream); }
-  { ProfScope p(c, K_MAP_GRID); launch_map_grid(a, c->stream); }            // kdtree*FromMap->setInputCloud (:558-559)
+  { ProfScope p(c, K_MAP_GRID); launch_map_grid(a, c->stream); }            // kdtree*FromMap->setInputCloud (:558-559); kept by frozen sequences whose submap is unchanged
   for (int iter = 0; iter < 2; ++iter) {                                    // :562
     { ProfScope p(c, K_MAP_ASSOC); launch_map_associate(a, iter, c->stream); }
     { ProfScope p(c, K_MAP_SOLVE); launch_map_solve(a, iter, iter == 1, c->stream); }
   }
-  { ProfScope p(c, K_MAP_INSERT); launch_map_insert(a, c->map.voxtmp.get(), c->stream); }        // :737-783
-  { ProfScope p(c, K_MAP_VOXEL_CUBES);                                      // per-cube re-filter (:788-801)
+  { ProfScope p(c, K_MAP_INSERT); launch_map_insert(a, c->map.voxtmp.get(), c->stream); }        // :737-783 (not for frozen sequences)
+  { ProfScope p(c, K_MAP_VOXEL_CUBES);                                      // per-cube re-filter (:788-801; frozen: empty segments)
     const VoxArgs v = vox_args(c, c->B * 2 * kMapValidMax, c->map.cube_levels);
     HIP_TRY(c, hipMemsetAsync(c->d_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));
     launch_map_cube_segments(a, v, c->stream);
@@ -272,6 +293,7 @@ int aloam_set_map(aloam_ctx* c, int seq, int cls, const int* cube_ids, const int
   if (total && !points_xyzw) return ALOAM_E_ARG;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (total > c->map.points && (rc = grow_map_pool(c, total, false))) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // another submap: its grids are built anew
   HIP_TRY(c, hipMemcpy(c->d_cubes.get() + ((size_t)seq * 2 + cls) * kMapCubes, d.data(), sizeof(CubeDesc) * kMapCubes, hipMemcpyHostToDevice));
   if (total) HIP_TRY(c, hipMemcpy(c->map.pool[cls].get() + (size_t)seq * c->map.points, points_xyzw, sizeof(float4) * (size_t)total, hipMemcpyHostToDevice));
   if ((rc = edit_seq(c, c->d_mapseq.get() + seq, [&](MapSeq& ms) { ms.pool_used[cls] = (int)total; }))) return rc;
@@ -285,11 +307,25 @@ int aloam_set_map_frame(aloam_ctx* c, int seq, const int cen[3], const double q_
   if (rc) return rc;
   if (!c->map_on) { c->err = "mapping not enabled"; return ALOAM_E_STATE; }
   if (!cen || !q_wmap_wodom || !t_wmap_wodom) return ALOAM_E_ARG;
-  return edit_seq(c, c->d_mapseq.get() + seq, [&](MapSeq& ms) {
-    for (int k = 0; k < 3; ++k) { ms.cen[k] = cen[k]; ms.t_wmap_wodom[k] = t_wmap_wodom[k]; }
-    for (int k = 0; k < 4; ++k) ms.q_wmap_wodom[k] = q_wmap_wodom[k];
-    ms.frame_count = frame_count;
-  });
+  if ((rc = edit_seq(c, c->d_mapseq.get() + seq, [&](MapSeq& ms) {
+         for (int k = 0; k < 3; ++k) { ms.cen[k] = cen[k]; ms.t_wmap_wodom[k] = t_wmap_wodom[k]; }
+         for (int k = 0; k < 4; ++k) ms.q_wmap_wodom[k] = q_wmap_wodom[k];
+         ms.frame_count = frame_count;
+       }))) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // a new frame: the grids are built anew
+  return ALOAM_OK;
+}
+
+int aloam_set_map_frozen(aloam_ctx* c, const int* frozen) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (const int rc = require_stage(c, ALOAM_STAGE_MAPPING)) return rc;
+  if (!c->map_on) { c->err = "aloam_set_map_frozen before aloam_mapping_enable"; return ALOAM_E_STATE; }
+  std::vector<char> m(c->B, 0);
+  if (frozen) for (int b = 0; b < c->B; ++b) m[b] = frozen[b] != 0 ? 1 : 0;
+  c->any_frozen = std::find(m.begin(), m.end(), 1) != m.end();
+  c->frozen = std::move(m);
+  return ALOAM_OK;
 }
 
 static int fetch_mapseq(aloam_ctx* c, int seq, MapSeq* ms) {

@@ -5,7 +5,8 @@
 //   k_map_compact_*    (no counterpart: the reference's cubes are std::vectors) packs the class pools when a frame's growth
 //                      no longer fits behind the bump pointer
 //   k_map_begin        :142-146 transformAssociateToMap, :311-321 centre cube, :323-507 window shifts (the 21 x 21 x 11
-//                      pointer grid becomes a table of cube descriptors), :509-539 valid cubes + submap prefixes
+//                      pointer grid becomes a table of cube descriptors), :509-539 valid cubes + submap prefixes; for a frozen
+//                      sequence (kSeqMapGrow clear) whether its submap grid is still exact (MapGridSig)
 //   k_vox_lds          pcl::VoxelGrid::filter (:542-550 incoming clouds, :788-801 per-cube re-filter) of one segment by one workgroup:
 //                      run heads -> (voxel, first point) keys -> stable radix sort in registers / LDS -> centroids in input order
 //   k_vox_*            the same through global memory for segments that do not fit (tile sort + rank-merge levels)
@@ -15,7 +16,7 @@
 //                      eigen-decomposition) / plane fit (5x3 least squares), valid factor records compacted per tile of 256 points
 //   k_map_solve        :565-572,712-720 ceres::Solve over LidarEdgeFactor + LidarPlaneNormFactor blocks (shared LM loop,
 //                      lm_device.hpp), then :148-152 transformUpdate
-//   k_map_cubeid / k_map_reserve / k_map_scatter   :737-783 map insertion (stable append per cube)
+//   k_map_cubeid / k_map_reserve / k_map_scatter   :737-783 map insertion (stable append per cube); not for frozen sequences
 //   k_map_register     :836-846 /velodyne_cloud_registered
 // Everything is integer / f32 / f64 scalar work on 16-byte point records: HBM- and latency-bound, no MFMA.
 #include "mapping_kernels.hpp"
@@ -100,7 +101,7 @@ __device__ __forceinline__ int compact_cap(int n, int mode) { return n <= 0 ? 0 
 
 __global__ __launch_bounds__(256) void k_map_compact_plan(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, tid = threadIdx.x;
-  if (seq_idle(a.active, b)) return;
+  if (seq_idle(a.active, b, kSeqMapGrow)) return;                          // idle or frozen: no insertion
   MapSeq& ms = a.seq[b];
   int* flag = a.compact_flag + b * 2 + cls;
   const CubeDesc* T = cube_table(a, b, cls);
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(256) void k_map_compact_plan(MapArgs a) {
 template <int PHASE>   // 0: cubes -> staging at their new offsets; 1: staging -> pool, descriptors updated
 __global__ __launch_bounds__(256) void k_map_compact_move(MapArgs a, float4* staging) {
   const int b = blockIdx.y, cls = blockIdx.z, tid = threadIdx.x;
-  if (seq_idle(a.active, b)) return;                                        // (its compact_flag is of an earlier step)
+  if (seq_idle(a.active, b, kSeqMapGrow)) return;                          // (its compact_flag is of an earlier step)
   const int mode = a.compact_flag[b * 2 + cls];
   if (!mode) return;
   CubeDesc* T = cube_table(a, b, cls);
@@ -183,8 +184,11 @@ __global__ __launch_bounds__(256) void k_map_begin(MapArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   MapSeq& ms = a.seq[b];
   __shared__ int s_c[3], s_cen[3];
+  __shared__ int2 s_sig[2][kMapValidMax];                                     // frozen: the new window's grid signature per class
+  __shared__ int s_nsig[2];
   if (b == 0 && tid == 0) { if (a.vox_counters[1]) a.vox_counters[3] += 1; a.vox_counters[1] = 0; }   // batch-wide: also when sequence 0 sits out
   if (seq_idle(a.active, b)) return;
+  const bool frozen = seq_idle(a.active, b, kSeqMapGrow);                   // active, localizing against a map it does not change
   if (tid == 0) {
     if (ms.err) ms.err_steps += 1;                                           // capacity flags describe one step; what the previous step
     ms.err = 0;                                                              // raised stays countable for a host that synchronises later
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(256) void k_map_begin(MapArgs a) {
     int* tab = a.tab + (long long)b * kTabInts;
     const CubeDesc* Tc = cube_table(a, b, 0);
     const CubeDesc* Ts = cube_table(a, b, 1);
-    int nvld = 0, pc = 0, ps = 0;
+    int nvld = 0, pc = 0, ps = 0, nc = 0, ns = 0;
     for (int i = s_c[0] - 2; i <= s_c[0] + 2; i++)
       for (int j = s_c[1] - 2; j <= s_c[1] + 2; j++)
         for (int k = s_c[2] - 1; k <= s_c[2] + 1; k++)
@@ -245,10 +249,20 @@ __global__ __launch_bounds__(256) void k_map_begin(MapArgs a) {
             tab[nvld] = ind;
             tab[80 + nvld] = pc;
             tab[160 + nvld] = ps;
-            pc += Tc[ind].cnt;
-            ps += Ts[ind].cnt;
+            if (frozen) {
+              const CubeDesc dc = Tc[ind], ds = Ts[ind];
+              if (dc.cnt) s_sig[0][nc++] = make_int2(dc.off, dc.cnt);
+              if (ds.cnt) s_sig[1][ns++] = make_int2(ds.off, ds.cnt);
+              pc += dc.cnt;
+              ps += ds.cnt;
+            } else {
+              pc += Tc[ind].cnt;
+              ps += Ts[ind].cnt;
+            }
             ++nvld;
           }
+    s_nsig[0] = nc;
+    s_nsig[1] = ns;
     tab[80 + nvld] = pc;
     tab[160 + nvld] = ps;
     ms.n_valid = nvld;
@@ -257,6 +271,24 @@ __global__ __launch_bounds__(256) void k_map_begin(MapArgs a) {
     ms.gate = (pc > 10 && ps > 50) ? 1 : 0;                                 // :554
     for (int k = 0; k < 3; ++k) { ms.cen[k] = s_cen[k]; ms.center[k] = s_c[k]; }
     for (int it = 0; it < 2; ++it) { ms.factor_num[it][0] = ms.factor_num[it][1] = 0; ms.lm_iterations[it] = 0; ms.lm_termination[it] = 4; }
+    if (!frozen) {                                                           // this step's insert changes the submap: no grid survives it
+      MapGridSig* g = a.grid_sig + (long long)b * 2;
+      g[0].valid = 0; g[0].reuse = 0; g[1].valid = 0; g[1].reuse = 0;
+    }
+  }
+  if (!frozen) return;
+  // Grid reuse of a frozen sequence: the grid rows are exact when they were built from the same submap - same (off, cnt) list - since the
+  // last invalidation.  Every thread compares one entry; the barrier of __syncthreads_or orders those reads before the new signature is
+  // written over the old one.
+  __syncthreads();
+  for (int cls = 0; cls < 2; ++cls) {
+    MapGridSig& g = a.grid_sig[(long long)b * 2 + cls];
+    const int n = s_nsig[cls];
+    const bool same = g.valid && g.n == n;
+    const int2 want = tid < n ? s_sig[cls][tid] : make_int2(0, 0);
+    const bool differs = __syncthreads_or(tid < n && same && (g.cube[tid].x != want.x || g.cube[tid].y != want.y));
+    if (tid < n) g.cube[tid] = want;
+    if (tid == 0) { g.reuse = same && !differs; g.n = n; g.valid = 1; }       // built (or kept) from this signature by k_mapgrid_build
   }
 }
 
@@ -299,7 +331,7 @@ __global__ void k_map_cube_segments(MapArgs a, VoxArgs v) {
   const int j = g % kMapValidMax, cls = (g / kMapValidMax) & 1, b = g / (2 * kMapValidMax);
   VoxSeg s{};
   s.leaf = cls == 0 ? a.line_res : a.plane_res;
-  if (!seq_idle(a.active, b) && j < a.seq[b].n_valid) {                    // idle: an empty segment, its cubes are not re-filtered
+  if (!seq_idle(a.active, b, kSeqMapGrow) && j < a.seq[b].n_valid) {      // idle or frozen: an empty segment, its cubes are not re-filtered
     CubeDesc* d = cube_table(a, b, cls) + a.tab[(long long)b * kTabInts + j];
     s.in = a.pool[cls] + (long long)b * a.pool_cap + d->off;
     s.n = d->cnt;
@@ -926,9 +958,14 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
 // Built by ONE 1024-thread workgroup per (sequence, class) with an LDS counting sort (count -> scan -> fill), the way k_build_grids
 // builds the odometry grids: no global atomics, no zero-fill of a count table, one launch.  32-bit counters, so the submap may be of
 // any size; the bucket table is capped at 32768 entries (132 KiB of the CU's 160 KiB) however far the pool has grown.
+// The order of the points inside a bucket follows the LDS atomics of the fill pass and is not deterministic; k_map_search ranks its
+// candidates by (distance, submap index) and reads coordinates through the entry it kept, so its result does not depend on that order.
+// A frozen sequence whose submap is that of the last build (MapGridSig, decided by k_map_begin) keeps its grid: only this kernel writes
+// grid_sorted / grid_start and only k_map_search reads them.
 __global__ __launch_bounds__(1024) void k_mapgrid_build(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, tid = threadIdx.x;
   if (seq_idle(a.active, b)) return;
+  if (a.active && a.grid_sig[(long long)b * 2 + cls].reuse) return;         // frozen, same submap as the last build: the grid is exact
   const MapSeq& ms = a.seq[b];
   const int n = ms.from_total[cls], nv = ms.n_valid, H = a.grid_H;
   const int* tab = a.tab + (long long)b * kTabInts;
@@ -1452,7 +1489,7 @@ __global__ __launch_bounds__(kMapSolveThreads) void k_map_solve(MapArgs a, int i
 // =======================================================================================================
 __global__ __launch_bounds__(256) void k_map_cubeid(MapArgs a) {
   const int b = blockIdx.y, cls = blockIdx.z;
-  if (seq_idle(a.active, b)) return;
+  if (seq_idle(a.active, b, kSeqMapGrow)) return;                          // idle or frozen: its addcnt stays zero
   const MapSeq& ms = a.seq[b];
   const long long sb = (long long)b * (cls == 0 ? a.R * kLessSharpPerRing : a.cap);
   double par[7];
@@ -1482,7 +1519,7 @@ __global__ __launch_bounds__(256) void k_map_cubeid(MapArgs a) {
 // class pool; the old segment is abandoned).  Then the append cursor of every touched cube is published.
 __global__ __launch_bounds__(256) void k_map_reserve(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, tid = threadIdx.x;
-  if (seq_idle(a.active, b)) return;
+  if (seq_idle(a.active, b, kSeqMapGrow)) return;
   CubeDesc* T = cube_table(a, b, cls);
   int* add = a.addcnt + ((long long)b * 2 + cls) * kMapCubes;
   int* cur = a.cursor + ((long long)b * 2 + cls) * kMapCubes;
@@ -1539,7 +1576,7 @@ __global__ __launch_bounds__(256) void k_map_reserve(MapArgs a) {
 // stable append: one wave per (sequence, class) walks the stack in order, 64 points a step
 __global__ __launch_bounds__(64) void k_map_scatter(MapArgs a) {
   const int b = blockIdx.x, cls = blockIdx.y, lane = threadIdx.x;
-  if (seq_idle(a.active, b)) return;
+  if (seq_idle(a.active, b, kSeqMapGrow)) return;
   const MapSeq& ms = a.seq[b];
   const int n = ms.n_stack[cls];
   const CubeDesc* T = cube_table(a, b, cls);
@@ -1665,7 +1702,7 @@ __global__ __launch_bounds__(256) void k_map_report(MapArgs a, int step) {
 // =======================================================================================================
 // One workgroup per listed sequence: SeqMeta, OdomState, the odometry getters' rows (correspondences, last-cloud order, ring ranges, both
 // less-sharp / less-flat buffers: the getters read them past the swap and past what a sweep wrote, which is zeros in a new context) and, with
-// mapping, MapSeq, both classes' cube tables and append counts and the live counts go back to their creation values (src/laserOdometry.cpp:93-98,
+// mapping, MapSeq, both classes' cube tables, append counts, live counts and grid signatures go back to their creation values (src/laserOdometry.cpp:93-98,
 // src/laserMapping.cpp:72-74,109,115).  Cube tables and pool_used at zero release the sequence's pool space.  No allocation, no host wait: a
 // graph-capturable launch in stream order between asynchronous steps.
 __global__ __launch_bounds__(256) void k_reset_sequences(ResetArgs r) {
@@ -1698,6 +1735,7 @@ __global__ __launch_bounds__(256) void k_reset_sequences(ResetArgs r) {
       r.cubes[(long long)b * 2 * kMapCubes + i] = CubeDesc{0, 0, 0, 0};
       r.addcnt[(long long)b * 2 * kMapCubes + i] = 0;
     }
+    if (tid < 2) { r.grid_sig[(long long)b * 2 + tid].valid = 0; r.grid_sig[(long long)b * 2 + tid].reuse = 0; }   // the submap grid is built anew
   }
 }
 void launch_reset_sequences(const ResetArgs& r, hipStream_t s) { if (r.n > 0) hipLaunchKernelGGL(k_reset_sequences, dim3(r.n), dim3(256), 0, s, r); }

@@ -14,6 +14,19 @@ enum MapErrBits { kMapErrPool = 1, kMapErrKeys = 2, kMapErrSegment = 4 };
 
 struct CubeDesc { int off, cnt, cap, pad; };             // one map cube of one class: segment [off, off + cap) of the class pool
 
+// What the submap grid of one (sequence, class) was last built from (k_map_begin records it, k_mapgrid_build skips the build when it says
+// so).  Pool segments are disjoint and a frozen map is never written, so an equal signature - (off, cnt) of every non-empty valid cube in
+// window order - means the same submap points in the same order: the grid of the last build is exact.  Kept out of MapSeq, whose bytes are
+// a record's: this is per-step scratch of the context.
+struct MapGridSig {
+  int valid;                                             // the grid_sorted / grid_start rows hold the build of `cube`; cleared by a
+                                                         // growing step, k_reset_sequences, aloam_set_map, aloam_set_map_frame, map_alloc_pool
+  int reuse;                                             // this step: the grid is exact, k_mapgrid_build returns at once
+  int n;                                                 // non-empty valid cubes
+  int pad;
+  int2 cube[kMapValidMax];                               // their (off, cnt), in window order
+};
+
 struct alignas(16) MapSeq {                              // one per sequence
   double par[7];                                         // `parameters`: q_w_curr (x,y,z,w), t_w_curr      (:109-111)
   double q_wmap_wodom[4], t_wmap_wodom[3];               // (:115-116)
@@ -77,8 +90,8 @@ struct MapArgs {
   float line_res, plane_res;
   const float4* less_sharp[2];   // [B][R*kLessSharpPerRing]  /laser_cloud_corner_last = row [1 - SeqMeta::parity]
   const float4* less_flat[2];    // [B][cap]    /laser_cloud_surf_last   (same)
-  const int* active;             // [B] SeqBits of this step, nullptr = all sequences (aloam_set_active)
-  const float4* full;            // [B][cap]    /velodyne_cloud_3, dense (set from outside, or made by k_dense_cloud)
+  const int* active;             // [B] SeqBits of this step (kSeqMapGrow: the sequences that extend their map), nullptr = all sequences grow
+  const float4* full;           // [B][cap]    /velodyne_cloud_3, dense (set from outside, or made by k_dense_cloud)
   const float4* slabs; int slab; const int* ringstart;   // ... or, straight from scan registration: one slab per ring + the dense start of every ring (slabs == nullptr: use `full`)
   float4* registered;            // [B][cap]    /velodyne_cloud_registered
   CubeDesc* cubes;               // [B][2][kMapCubes]
@@ -104,6 +117,7 @@ struct MapArgs {
   int* rec_tiles;                // [B][rec_tiles_per_seq] valid factor records per tile of 256 stack points: corner tiles, then surf tiles
   int rec_tiles_per_seq, rec_tiles_corner;
   int* vox_counters;             // VoxArgs::counters: [1] capacity flag of this step's voxel filters, [3] earlier steps that raised it
+  MapGridSig* grid_sig;          // [B][2]  what the submap grid rows were last built from (frozen sequences reuse an exact grid)
 };
 constexpr int kTabInts = 256;   // [0..74] valid cube ids, [80..155] corner prefix, [160..235] surf prefix
 
@@ -131,6 +145,7 @@ struct ResetArgs {
   float4* less_sharp[2]; float4* less_flat[2]; int cap;   // the double-buffered clouds, [B][R*kLessSharpPerRing] / [B][cap]: zeros, as in a new
                                                           // context (the getters read them past the swap, and past what a sweep wrote)
   MapSeq* mapseq; CubeDesc* cubes; int* addcnt; int* live;   // [B], [B][2][kMapCubes] x 2, [B][2]
+  MapGridSig* grid_sig;                                      // [B][2]
 };
 void launch_reset_sequences(const ResetArgs& r, hipStream_t s);
 int prepare_reference_order();                                                                  // reference_order_kernels.hip

@@ -4,8 +4,22 @@
 // frames are processed in the spin loop instead of a second thread: with the work on the GPU the node is never behind, so
 // the reference's "drop queued frames" branch (:299-303) is kept but does not fire in practice.
 #include <cstdio>
+#include <fstream>
+#include <iterator>
 #include <mutex>
 #include <queue>
+#include <string>
+#include <vector>
+#include <cmath>
+// Pinned memory for the record of `save_map`: the HIP runtime API (a build that finds its headers links libamdhip64, e.g. CMake's
+// hip::host; hipcc and hip::host define the platform, a plain compiler gets it here).
+#if __has_include(<hip/hip_runtime_api.h>)
+#if !defined(__HIP_PLATFORM_AMD__) && !defined(__HIP_PLATFORM_NVIDIA__)
+#define __HIP_PLATFORM_AMD__ 1
+#endif
+#include <hip/hip_runtime_api.h>
+#define ALOAM_NODE_HAVE_HIP 1
+#endif
 
 #include <geometry_msgs/PoseStamped.h>
 #include <nav_msgs/Odometry.h>
@@ -149,6 +163,57 @@ static void process() {
   }
 }
 
+// String parameters through NodeHandle::getParam where the ROS API has it (roscpp); a stand-in without string parameters leaves them unset.
+template <class NH> auto string_param(const NH& nh, const std::string& name, std::string& out, int) -> decltype(nh.getParam(name, out)) {
+  return nh.getParam(name, out);
+}
+template <class NH> bool string_param(const NH&, const std::string&, std::string&, long) { return false; }
+
+// `prior_map`: a sequence record (aloam_save_sequences of a mapping-only context: the map part only) loaded into slot 0.  The record carries
+// the first session's map <- odom correction and frame count; a new drive starts its odometry afresh, so the correction becomes the drive's
+// start pose in the map (`initial_pose`: x, y, z, yaw; default the map origin) and the frame count 0.  The window centre stays the record's.
+bool load_record(const std::string& path, const double initial_pose[4]) {
+  std::ifstream f(path, std::ios::binary);
+  std::vector<char> rec((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  const int slot = 0;
+  const long long off[2] = {0, static_cast<long long>(rec.size())};
+  if (!f.good() && !f.eof()) { ROS_ERROR("prior_map %s: cannot read", path.c_str()); return false; }
+  if (aloam_load_sequences(g_ctx, &slot, 1, rec.data(), off) != ALOAM_OK || aloam_synchronize(g_ctx) != ALOAM_OK) {   // pageable memory: staged by the call
+    ROS_ERROR("prior_map %s: %s", path.c_str(), aloam_last_error(g_ctx));
+    return false;
+  }
+  int info[16];
+  const double q[4] = {0.0, 0.0, std::sin(initial_pose[3] / 2), std::cos(initial_pose[3] / 2)};
+  if (aloam_get_map_info(g_ctx, 0, info) != ALOAM_OK || aloam_set_map_frame(g_ctx, 0, info, q, initial_pose, 0) != ALOAM_OK) {   // info[0..2]: cen
+    ROS_ERROR("prior_map %s: %s", path.c_str(), aloam_last_error(g_ctx));
+    return false;
+  }
+  return true;
+}
+
+// `save_map`: the record of slot 0 written to a file on shutdown (pinned memory: the device writes offsets and record).
+void save_record(const std::string& path) {
+#ifdef ALOAM_NODE_HAVE_HIP
+  const int seq = 0;
+  long long* off = nullptr;
+  void* rec = nullptr;
+  bool ok = hipHostMalloc(reinterpret_cast<void**>(&off), 2 * sizeof(long long), 0) == hipSuccess &&
+            aloam_save_sequences(g_ctx, &seq, 1, nullptr, 0, off) == ALOAM_OK && aloam_synchronize(g_ctx) == ALOAM_OK &&   // size query
+            hipHostMalloc(&rec, static_cast<size_t>(off[1]), 0) == hipSuccess &&
+            aloam_save_sequences(g_ctx, &seq, 1, rec, off[1], off) == ALOAM_OK && aloam_synchronize(g_ctx) == ALOAM_OK;
+  if (ok) {
+    std::ofstream f(path, std::ios::binary);
+    f.write(static_cast<const char*>(rec), off[1]);
+    ok = f.good();
+  }
+  if (!ok) ROS_ERROR("save_map %s failed: %s", path.c_str(), aloam_last_error(g_ctx));
+  if (rec) (void)hipHostFree(rec);
+  if (off) (void)hipHostFree(off);
+#else
+  ROS_ERROR("save_map %s: this build of the node has no HIP runtime headers (pinned memory for the record)", path.c_str());
+#endif
+}
+
 int main(int argc, char** argv) {
   ros::init(argc, argv, "laserMapping");
   ros::NodeHandle nh;
@@ -172,6 +237,23 @@ int main(int argc, char** argv) {
   int reference_sum_order = 0;                             // 1: pcl::VoxelGrid's own summation order in the stack / cube filters (validation: ~80 ms per HDL-64 frame)
   nh.param<int>("reference_sum_order", reference_sum_order, 0);
   if (reference_sum_order) aloam_set_voxel_sum_order(g_ctx, ALOAM_SUM_REFERENCE_ORDER);
+  // Localization against a prior map: `prior_map` = a record written by `save_map` of an earlier run, `localization_only` = 1 freezes the
+  // sequence (aloam_set_map_frozen): every frame is localized in the map, which stays as loaded.
+  std::string prior_map, save_map;
+  string_param(nh, "prior_map", prior_map, 0);
+  string_param(nh, "save_map", save_map, 0);
+  int localization_only = 0;
+  nh.param<int>("localization_only", localization_only, 0);
+  double initial_pose[4] = {0.0, 0.0, 0.0, 0.0};          // with prior_map: where this drive starts in the map (metres, yaw in radians)
+  nh.param<double>("initial_pose_x", initial_pose[0], 0.0);
+  nh.param<double>("initial_pose_y", initial_pose[1], 0.0);
+  nh.param<double>("initial_pose_z", initial_pose[2], 0.0);
+  nh.param<double>("initial_pose_yaw", initial_pose[3], 0.0);
+  if (!prior_map.empty() && !load_record(prior_map, initial_pose)) return 1;
+  if (localization_only) {
+    const int frozen = 1;
+    if (aloam_set_map_frozen(g_ctx, &frozen) != ALOAM_OK) { ROS_ERROR("localization_only: %s", aloam_last_error(g_ctx)); return 1; }
+  }
   ros::Subscriber subLaserCloudCornerLast = nh.subscribe<sensor_msgs::PointCloud2>("/laser_cloud_corner_last", 100, laserCloudCornerLastHandler);
   ros::Subscriber subLaserCloudSurfLast = nh.subscribe<sensor_msgs::PointCloud2>("/laser_cloud_surf_last", 100, laserCloudSurfLastHandler);
   ros::Subscriber subLaserOdometry = nh.subscribe<nav_msgs::Odometry>("/laser_odom_to_init", 100, laserOdometryHandler);
@@ -189,6 +271,7 @@ int main(int argc, char** argv) {
     process();
     rate.sleep();
   }
+  if (!save_map.empty()) save_record(save_map);
   aloam_destroy(g_ctx);
   g_ctx = nullptr;
   return 0;

@@ -244,6 +244,30 @@ int aloam_set_system_inited(aloam_ctx* ctx, int inited);             /* systemIn
 int aloam_set_active(aloam_ctx* ctx, const int* active);
 int aloam_reset_sequences(aloam_ctx* ctx, const int* seqs, int n);
 
+/* ---- localization against a frozen prior map --------------------------------------------------------------------------------
+ * aloam_set_map_frozen: which sequences localize against their map instead of extending it, in the mapping steps that follow.
+ * frozen[b] != 0 for each of the `batch` sequences; NULL = none (the default).
+ *   - A frozen, active sequence's mapping step does everything up to and including the pose: transformAssociateToMap
+ *     (src/laserMapping.cpp:142-146, called at :309), the centre cube and window shifts (:311-507; the slab that falls off is emptied, as in
+ *     a normal step), the valid cubes and submap (:509-539), the stack voxel filters (:542-550), the 5-NN search, line and plane fits and
+ *     the solve (:554-733), transformUpdate (:148-152, called at :734), /velodyne_cloud_registered (:836-846) and frameCount++ (:888).  It
+ *     skips the insertion (:737-783) and the per-cube re-filter (:788-801).
+ *   - Its map afterwards: every cube holds the same points, in the same order and with the same bits; the cube table has only moved by
+ *     the shift permutation of that step.  pool_used does not change and no compaction runs.  ALOAM_MAP_SURROUND and ALOAM_MAP_FULL show
+ *     that unchanged map.
+ *   - Pose bits: the pose, statistics and registered cloud of a frozen step are bit-identical to what a normal step computes from the same
+ *     state (in the reference the solve comes before the insert).  The submap search grid of a frozen sequence is rebuilt only when its
+ *     submap changes (the sensor entered another 50 m cube, or the map / frame was replaced), with the same results.
+ *   - The mask behaves like the active mask: host state staged per call, no synchronisation; each mapping step uses the mask in force when
+ *     it is queued; independent of aloam_set_active (an idle sequence is idle, frozen or not); not changed by aloam_reset_sequences or
+ *     aloam_load_sequences; not part of a sequence record (ALOAM_SEQ_RECORD_VERSION, MapSeq and aloam_pose_record are unchanged).
+ *   - A step whose active sequences are all frozen adds nothing to any map: it never grows the map pools nor waits for the device to size them.
+ *   - The initial guess in the map frame is set with aloam_set_map_frame (q_wmap_wodom, t_wmap_wodom: map <- odometry); the factor counts
+ *     of aloam_get_map_info (corner / surf factors per iteration) are the per-sequence localization score, e.g. to rank several guesses of
+ *     one map loaded into several slots.
+ *   - ALOAM_E_STATE in a context without ALOAM_STAGE_MAPPING or before aloam_mapping_enable; argument errors as for aloam_set_active. */
+int aloam_set_map_frozen(aloam_ctx* ctx, const int* frozen);
+
 /* ---- sequence records: save and restore whole sequences, in batched stream-ordered calls ------------------------------
  * A sequence record is everything that makes up a sequence between two frames - odometry pose and statistics, systemInited, the last
  * clouds (laserCloudCornerLast / SurfLast, src/laserOdometry.cpp:554-563), and with mapping the map pose, window centre, frame count,

@@ -11,6 +11,11 @@ per sweep, plus the ATE (RMSE of translation, same start, no alignment) against 
 
 KITTI is not part of this repository or image; `--selftest` writes a tiny synthetic sequence in this layout and runs on it.
 
+Localization against a prior map (one --seq): `--mapping --save-map m.npz` writes the map of the run (both classes' cubes, window centre and
+frame count) at its end; a later `--prior-map m.npz` run injects it into a fresh context (aloam_set_map / aloam_set_map_frame, identity
+correction or --initial-pose), freezes the sequence (aloam_set_map_frozen) and writes <out>/<seq>_localized.txt: every sweep localized in
+that map, which it leaves unchanged.  The file is a map, not a sequence record: the second run starts its odometry fresh.
+
 `--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
 context runs one sequence; when it ends, the slot is reset in place (aloam_reset_sequences) and takes the next one, and slots with nothing
 left sit the step out (aloam_set_active).  `--slice K` time-slices more sequences than slots (schedule_sliced()): after K frames a sequence
@@ -128,6 +133,36 @@ def write_selftest(folder, seq="00", frames=6, seed=77):
         s.numpy().astype(np.float32).tofile(os.path.join(folder, "velodyne", "sequences", seq, "velodyne", f"{k:06d}.bin"))
 
 
+def save_map(gpu, path):
+    """The map of sequence 0 (aloam_map_cube_counts / aloam_get_map_cube of both classes) with its window centre and frame count."""
+    info = gpu.map_info(0)
+    out = {"cen": np.array([info["cenW"], info["cenH"], info["cenD"]], np.int32), "frames": np.int32(info["frame_count"])}
+    for cls in (0, 1):
+        cubes = gpu.map_cubes(cls, 0)
+        ids = np.array(sorted(cubes), np.int32)
+        out[f"ids{cls}"] = ids
+        out[f"counts{cls}"] = np.array([len(cubes[int(i)]) for i in ids], np.int32)
+        out[f"points{cls}"] = np.concatenate([cubes[int(i)] for i in ids]) if len(ids) else np.zeros((0, 4), np.float32)
+    with open(path, "wb") as f:
+        np.savez(f, **out)
+
+
+def load_prior_map(gpu, path, initial_pose=None):
+    """Inject a save_map() file into sequence 0 of a fresh context: its cubes, its window centre, the correction map <- odometry (identity,
+    or initial_pose = (tx, ty, tz, yaw)), frame count 0; then freeze the sequence."""
+    m = np.load(path)
+    for cls in (0, 1):
+        ids, cnt, pts = m[f"ids{cls}"], m[f"counts{cls}"], m[f"points{cls}"]
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        gpu.set_map({int(i): pts[off[j]:off[j + 1]] for j, i in enumerate(ids)}, cls, seq=0)
+    q, t = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3)
+    if initial_pose is not None:
+        tx, ty, tz, yaw = initial_pose
+        q, t = np.array([0.0, 0.0, np.sin(yaw / 2), np.cos(yaw / 2)]), np.array([tx, ty, tz])
+    gpu.set_map_frame(m["cen"], q, t, 0, seq=0)
+    gpu.set_map_frozen([1])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", help="dataset_folder of kitti_helper.launch")
@@ -142,7 +177,20 @@ def main():
     ap.add_argument("--selftest", action="store_true")
     ap.add_argument("--reference-order", action="store_true", help="sum voxel members in pcl::VoxelGrid's own order (the reference's bits; ~4x slower for one sensor): for runs that are compared pose by pose with A-LOAM's")
     ap.add_argument("--distortion", action="store_true", help="per-point interpolation ratio (the reference's DISTORTION 1; real KITTI sweeps are already de-skewed, so the reference ships 0)")
+    ap.add_argument("--save-map", metavar="FILE.npz", help="with --mapping, one --seq: write the map of the run (cubes of both classes, cen, frame count) at its end")
+    ap.add_argument("--prior-map", metavar="FILE.npz", help="one --seq: localize every sweep against this --save-map file, frozen (the map is not "
+                                                            "changed); writes <seq>_localized.txt")
+    ap.add_argument("--initial-pose", nargs=4, type=float, metavar=("TX", "TY", "TZ", "YAW"), help="with --prior-map: the first guess of the map <- odometry "
+                                                                                                  "correction (metres, radians); default identity")
     args = ap.parse_args()
+    if (args.save_map or args.prior_map) and args.seqs:
+        ap.error("--save-map / --prior-map take one --seq, not --seqs")
+    if args.save_map and not args.mapping:
+        ap.error("--save-map needs --mapping")
+    if args.initial_pose and not args.prior_map:
+        ap.error("--initial-pose needs --prior-map")
+    if args.prior_map:
+        args.mapping = True
     seqs = args.seqs or [args.seq]
     if args.selftest:
         args.dataset = os.path.join(args.out, "selftest_dataset")
@@ -165,6 +213,7 @@ def main():
     rec_buf = torch.empty(batch * ctypes.sizeof(binding.AloamPoseRecord), dtype=torch.uint8, pin_memory=True)   # the poses of a step, written by the device
     recs = (binding.AloamPoseRecord * batch).from_address(rec_buf.data_ptr())
     odo, mapped = [[] for _ in seqs], [[] for _ in seqs]
+    factors = []                                       # --prior-map: last-iteration factors of every sweep (aloam_get_map_info), the fit to the map
     idle = np.zeros((0, 4), np.float32)
     lengths = [len(ts) for ts in times]
     plan = schedule_sliced(lengths, batch, args.slice) if args.slice > 0 else [(*st, [], []) for st in schedule(lengths, batch)]
@@ -178,6 +227,8 @@ def main():
             gpu.load_sequences([s], *parked.pop(i))
         if resets:
             gpu.reset_sequences(resets)                # a new sequence enters these slots: a fresh context's state, in place
+            if args.prior_map:                         # (one --seq: only slot 0, at the first step) the map goes in after that reset
+                load_prior_map(gpu, args.prior_map, args.initial_pose)
         gpu.set_active(None if all(active) else active)
         scans = [idle] * batch
         for slot, (i, k) in frames.items():
@@ -193,16 +244,24 @@ def main():
             odo[i].append([times[i][k], *r.t_w, *r.q_w])
             if args.mapping:
                 mapped[i].append([times[i][k], *r.map_t_w, *r.map_q_w])
+        if args.prior_map:
+            info = gpu.map_info(0)
+            factors.append(info["corner_num1"] + info["surf_num1"])
+    if args.save_map:
+        save_map(gpu, args.save_map)
     gpu.close()
+    mapped_name = "localized" if args.prior_map else "mapped"
+    if factors:
+        print(f"{seqs[0]} localized: factors per sweep (last iteration) min {min(factors)}, mean {np.mean(factors):.0f}")
     for i, seq in enumerate(seqs):
         np.savetxt(os.path.join(args.out, f"{seq}_odometry.txt"), np.array(odo[i]), fmt="%.9e")
         if mapped[i]:
-            np.savetxt(os.path.join(args.out, f"{seq}_mapped.txt"), np.array(mapped[i]), fmt="%.9e")
+            np.savetxt(os.path.join(args.out, f"{seq}_{mapped_name}.txt"), np.array(mapped[i]), fmt="%.9e")
         gt_path = os.path.join(args.dataset, "results", seq + ".txt")
         if os.path.exists(gt_path):
             Rg, tg = read_gt(gt_path)
             tg = (tg[: len(odo[i])] - tg[0]) @ Rg[0]   # same start as the estimate (identity at the first sweep)
-            for name, tr in (("odometry", odo[i]), ("mapped", mapped[i])):
+            for name, tr in (("odometry", odo[i]), (mapped_name, mapped[i])):
                 if tr:
                     e = np.array(tr)[:, 1:4] - tg
                     print(f"{seq} {name}: {len(tr)} sweeps, ATE (RMSE, no alignment) = {np.sqrt((e ** 2).sum(1).mean()):.4f} m, final error = {np.linalg.norm(e[-1]):.4f} m")
