@@ -46,6 +46,31 @@ class AloamPoseRecord(C.Structure):
                 ("inited", C.c_int), ("map_frames", C.c_int), ("pad", C.c_int * 2)]
 
 
+class AloamMapCorrection(C.Structure):
+    """One candidate map <- odometry correction (aloam_map_correction, 64 bytes)."""
+    _fields_ = [("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3), ("pad", C.c_double)]
+
+
+class AloamMapScore(C.Structure):
+    """The score of one (sequence, candidate) pair (aloam_map_score, 32 bytes)."""
+    _fields_ = [("corner_factors", C.c_int), ("surf_factors", C.c_int), ("corner_found", C.c_int), ("surf_found", C.c_int),
+                ("cost", C.c_double), ("pad", C.c_int * 2)]
+
+
+MAP_CORRECTION_DTYPE = np.dtype([("q_wmap_wodom", np.float64, 4), ("t_wmap_wodom", np.float64, 3), ("pad", np.float64)])
+MAP_SCORE_DTYPE = np.dtype([("corner_factors", np.int32), ("surf_factors", np.int32), ("corner_found", np.int32), ("surf_found", np.int32),
+                            ("cost", np.float64), ("pad", np.int32, 2)])
+
+
+def map_corrections(q, t):
+    """Candidates as the C ABI takes them: q [K, 4] (x, y, z, w) and t [K, 3] -> structured array [K] of MAP_CORRECTION_DTYPE."""
+    q, t = np.asarray(q, np.float64).reshape(-1, 4), np.asarray(t, np.float64).reshape(-1, 3)
+    assert len(q) == len(t)
+    c = np.zeros(len(q), MAP_CORRECTION_DTYPE)
+    c["q_wmap_wodom"], c["t_wmap_wodom"] = q, t
+    return c
+
+
 class AloamSeqRecordHeader(C.Structure):
     """The first 128 bytes of a sequence record (aloam_seq_record_header)."""
     _fields_ = [("magic", C.c_uint), ("version", C.c_uint), ("bytes", C.c_longlong), ("parts", C.c_int), ("n_scans", C.c_int),
@@ -125,6 +150,8 @@ def lib():
         L.aloam_set_active.argtypes = [vp, vp]
         L.aloam_reset_sequences.argtypes = [vp, vp, C.c_int]
         L.aloam_set_map_frozen.argtypes = [vp, vp]
+        L.aloam_score_map_corrections.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
+        L.aloam_apply_map_corrections.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
         L.aloam_save_sequences.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_load_sequences.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_get_ring_ranges.argtypes = [vp, C.c_int, vp, vp]
@@ -246,7 +273,9 @@ class Aloam:
         self._check(lib().aloam_input_consumed(self.h))
 
     def synchronize(self):
-        self._check(lib().aloam_synchronize(self.h))
+        rc = lib().aloam_synchronize(self.h)
+        self._apply_keep = []                                 # (the stream has drained: the device has read every choice buffer)
+        self._check(rc)
 
     def cloud(self, which, seq=0):
         n = self._check(lib().aloam_cloud_size(self.h, seq, which))
@@ -308,6 +337,43 @@ class Aloam:
         m = np.ascontiguousarray([1 if v else 0 for v in mask], dtype=np.int32)
         assert m.shape == (self.batch,)
         self._check(lib().aloam_set_map_frozen(self.h, _p(m)))
+
+    # ---- map-pose hypotheses (stream-ordered; wait with synchronize()) --------------------------------------------------------------
+    def score_map_corrections_into(self, seqs, cand_ptr, K, scores_ptr, best_ptr=0):
+        """Queue the scoring of the K candidates at cand_ptr (device, pinned or pageable host memory) for `seqs`; scores_ptr receives
+        len(seqs) * K aloam_map_score records, best_ptr (0 = not wanted) len(seqs) int32 - both device memory or pinned host memory."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_score_map_corrections(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(cand_ptr) if cand_ptr else None, int(K),
+                                                      C.c_void_p(scores_ptr) if scores_ptr else None, C.c_void_p(best_ptr) if best_ptr else None))
+
+    def score_map_corrections(self, seqs, cand, pinned=True):
+        """Scores of the candidates `cand` (structured array of MAP_CORRECTION_DTYPE, see map_corrections) for `seqs`, after a synchronise.
+        Returns (scores, best): a structured array [len(seqs), K] of MAP_SCORE_DTYPE and int32 [len(seqs)]; with pinned=False the
+        destinations are device memory, copied back afterwards."""
+        import torch
+        cand = np.ascontiguousarray(cand, dtype=MAP_CORRECTION_DTYPE)
+        n, K = len(seqs), len(cand)
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        sc = torch.zeros(max(1, n * K) * 32, dtype=torch.uint8, **where)
+        best = torch.zeros(max(1, n), dtype=torch.int32, **where)
+        self.score_map_corrections_into(seqs, cand.ctypes.data, K, sc.data_ptr(), best.data_ptr())
+        self.synchronize()
+        return sc.cpu().numpy()[:n * K * 32].view(MAP_SCORE_DTYPE).reshape(n, K).copy(), best.cpu().numpy()[:n].copy()
+
+    def apply_map_corrections_from(self, seqs, cand_ptr, K, choice_ptr):
+        """Queue q_wmap_wodom, t_wmap_wodom := cand[choice[i]] for seqs[i]; choice_ptr: int32 in device memory or pinned host memory, read
+        on the device in stream order (the `best` of a scoring call queued before this one may be passed straight in)."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_apply_map_corrections(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(cand_ptr) if cand_ptr else None, int(K),
+                                                      C.c_void_p(choice_ptr) if choice_ptr else None))
+
+    def apply_map_corrections(self, seqs, cand, choice):
+        """Install cand[choice[i]] as the correction of seqs[i] (choice: one int per listed sequence), in stream order."""
+        import torch
+        cand = np.ascontiguousarray(cand, dtype=MAP_CORRECTION_DTYPE)
+        ch = torch.tensor([int(v) for v in choice], dtype=torch.int32).pin_memory() if len(seqs) else torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._apply_keep = getattr(self, "_apply_keep", []) + [ch]   # read by the device later: kept until the next synchronize()
+        self.apply_map_corrections_from(seqs, cand.ctypes.data, len(cand), ch.data_ptr())
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

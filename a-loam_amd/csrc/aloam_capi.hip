@@ -81,7 +81,7 @@ int queue_reset(aloam_ctx* c, const int* seqs, int n) {
   if (c->map_on) { r.mapseq = c->d_mapseq.get(); r.cubes = c->d_cubes.get(); r.addcnt = c->d_addcnt.get(); r.live = c->d_map_live.get(); r.grid_sig = c->d_grid_sig.get(); }
   launch_reset_sequences(r, c->stream);
   HIP_TRY(c, hipGetLastError());
-  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; }
+  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); }
   return ALOAM_OK;
 }
 
@@ -149,7 +149,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->in_consumed[k].h, hipEventDisableTiming));
   }
   c->B = cfg->batch; c->max_points = cfg->max_points; c->R = cfg->n_scans;
-  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0);
+  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0); c->scorable.assign(c->B, 0);
   c->map_err_seen.assign(c->B, 0);
   // The per-sequence stride of every [B][cap] buffer is kept OFF the powers of two (131 072 points x 16 B = 2 MiB apart, the workgroups of a launch - one
   // per sequence, all at about the same offset of their sequence - meet on the same memory channels): + 1/32 + 16 points.  Measured on k_build_grids_fused at
@@ -272,6 +272,16 @@ int aloam_synchronize(aloam_ctx* c) {
       c->err += "; the points that did not fit were not inserted (raise pool_points)";
       return ALOAM_E_CAPACITY;
     }
+    if (c->d_rl_bad) {                                    // choices k_apply_corrections found outside 0 .. K-1: reported once, like the capacity events
+      int bad = 0;
+      HIP_TRY(c, hipMemcpy(&bad, c->d_rl_bad.get(), sizeof(bad), hipMemcpyDeviceToHost));
+      const long long fresh = bad - c->rl_bad_reported;
+      c->rl_bad_reported = bad;
+      if (fresh > 0) {
+        c->err = "aloam_apply_map_corrections, since the last aloam_synchronize: " + std::to_string(fresh) + " choice(s) outside 0 .. K-1; those sequences were left untouched";
+        return ALOAM_E_ARG;
+      }
+    }
   }
   return ALOAM_OK;
 }
@@ -370,6 +380,13 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
         }
       }
     }
+    // the last scoring / apply call: candidates in, scores out, and per listed sequence its stacks and bucketed submap once
+    // (what the K candidates re-read comes from L2; the kernel is latency- and issue-bound, not byte-bound).
+    if (c->map_on && kernel == K_SCORE) {
+      bytes = 64.0 * c->rl_last_K + 32.0 * c->rl_last_seqs.size() * c->rl_last_K;
+      for (const int b : c->rl_last_seqs) bytes += 16.0 * (ms[b].n_stack[0] + ms[b].n_stack[1]) + 16.0 * (ms[b].from_total[0] + ms[b].from_total[1]) + 8.0 * c->map.H;
+    }
+    if (kernel == K_APPLY) bytes = c->rl_apply_n * (4.0 + 4.0 + 64.0 + 56.0);   // id, choice, candidate in, correction out
     *algorithmic_bytes = bytes;
   }
   return ALOAM_OK;

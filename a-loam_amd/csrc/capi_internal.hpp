@@ -18,18 +18,19 @@
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "registration_kernels.hpp"
+#include "relocalize_kernels.hpp"
 
 using namespace aloam;
 
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_SAVE, K_LOAD, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
                                     "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "save_sequences",
-                                    "load_sequences"};
+                                    "load_sequences", "score_corrections", "apply_corrections"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
 constexpr int kNinSlots = 8;
@@ -164,6 +165,14 @@ struct aloam_ctx {
   DevBuf<char> d_ck_load;                                           // load: the same staged arrays in device memory
   DevBuf<char> d_ck_stage; size_t ck_stage_bytes = 0;               // load: records from pageable host memory
   int ck_save_n = 0; long long ck_load_bytes = 0;                   // the last save / load (algorithmic bytes)
+  // map-pose hypotheses (aloam_score_map_corrections / aloam_apply_map_corrections)
+  std::vector<char> scorable;                                       // [B] last took part in a mapping step frozen, and its search grid has not been invalidated since
+  DevBuf<int> d_rl_seqs, d_rl_bad;                                  // [B] listed ids; [1] choices found outside 0 .. K-1 by k_apply_corrections
+  DevBuf<ScorePartial> d_rl_part; long long rl_part_cap = 0;        // [n][K][kScoreParts] per-workgroup partials
+  DevBuf<aloam_map_correction> d_rl_cand; long long rl_cand_cap = 0;   // candidates handed in as pageable host memory
+  long long rl_bad_reported = 0;                                    // of d_rl_bad, already returned by aloam_synchronize
+  std::vector<int> rl_last_seqs; int rl_last_K = 0;                 // the last scoring call: its listed sequences and K (algorithmic bytes)
+  int rl_apply_n = 0;
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -270,8 +279,12 @@ int ensure_dense(aloam_ctx* c);
 long long cloud_desc(const aloam_ctx* c, int id, ExportSrc* s);
 int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n);
 // capi_mapping.hip
+inline void clear_scorable(aloam_ctx* c, int seq) { c->scorable[seq] = 0; }   // the search grid of `seq` is no longer that of its stacks
 int grow_map_pool(aloam_ctx* c, long long want, bool clamp);
 // capi_records.hip
+enum CallerMem { kMemPageable, kMemDevice, kMemPinned, kMemManaged, kMemOtherDevice };
+CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev);
+int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out);
 int get_cube_list(aloam_ctx* c, int seq, int which, float* out, int cap_points);
 
 }  // namespace aloam

@@ -73,6 +73,7 @@ static int map_alloc_pool(aloam_ctx* c, int pool_points) {
   if (c->d_grid_sig) HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get(), 0, sizeof(MapGridSig) * B * 2, c->stream));   // the grids are not moved
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->map = std::move(n);
+  for (int b = 0; b < c->B; ++b) clear_scorable(c, b);
   return ALOAM_OK;
 }
 
@@ -272,6 +273,8 @@ int aloam_mapping_step(aloam_ctx* c) {
     launch_map_report(a, (int)c->map_steps, c->stream); }
   HIP_TRY(c, hipEventRecord(done, c->stream));
   HIP_TRY(c, hipGetLastError());
+  for (int b = 0; b < c->B; ++b)                          // what aloam_score_map_corrections may read: the stacks and grid of a frozen step
+    if (c->all_active || c->active[b]) c->scorable[b] = c->frozen[b];
   return ALOAM_OK;
 }
 
@@ -294,6 +297,7 @@ int aloam_set_map(aloam_ctx* c, int seq, int cls, const int* cube_ids, const int
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (total > c->map.points && (rc = grow_map_pool(c, total, false))) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // another submap: its grids are built anew
+  clear_scorable(c, seq);
   HIP_TRY(c, hipMemcpy(c->d_cubes.get() + ((size_t)seq * 2 + cls) * kMapCubes, d.data(), sizeof(CubeDesc) * kMapCubes, hipMemcpyHostToDevice));
   if (total) HIP_TRY(c, hipMemcpy(c->map.pool[cls].get() + (size_t)seq * c->map.points, points_xyzw, sizeof(float4) * (size_t)total, hipMemcpyHostToDevice));
   if ((rc = edit_seq(c, c->d_mapseq.get() + seq, [&](MapSeq& ms) { ms.pool_used[cls] = (int)total; }))) return rc;
@@ -313,6 +317,7 @@ int aloam_set_map_frame(aloam_ctx* c, int seq, const int cen[3], const double q_
          ms.frame_count = frame_count;
        }))) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // a new frame: the grids are built anew
+  clear_scorable(c, seq);
   return ALOAM_OK;
 }
 

@@ -9,8 +9,8 @@
 // What a caller's pointer is to the context's device.  *dev is the address its kernels reach `p` through: device memory of the context's
 // device as it is, pinned host memory through its device mapping; nullptr for the rest.  kMemPageable: host memory without a device mapping
 // (or NULL), which the kernels cannot reach.
-enum CallerMem { kMemPageable, kMemDevice, kMemPinned, kMemManaged, kMemOtherDevice };
-static CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev) {
+namespace aloam {
+CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev) {
   hipPointerAttribute_t at{};
   *dev = nullptr;
   if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return kMemPageable; }   // (pageable memory is an error of the query, not of the context)
@@ -28,7 +28,7 @@ static CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev)
 
 // The address a kernel writes `p` through: device memory of the context's device as it is, pinned host memory through its device mapping.
 // Pageable host memory (with XNACK off a kernel store there faults the device), managed memory, another device's memory and NULL are refused.
-static int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out) {
+int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out) {
   void* d = nullptr;
   (void)classify_pointer(c, p, &d);                       // (d is set for device memory of this device and pinned host memory only)
   if (!d) { c->err = std::string(what) + " must be device memory of the context's device or pinned host memory"; return ALOAM_E_ARG; }
@@ -36,6 +36,7 @@ static int export_target(aloam_ctx* c, const void* p, size_t align, const char* 
   *out = d;
   return ALOAM_OK;
 }
+}  // namespace aloam
 
 // Where export id `id` (ALOAM_CLOUD_* or ALOAM_EXPORT_MAP + ALOAM_MAP_*) is read from: the buffers and counts the getters read (cloud_desc),
 // with their checks.  Queues nothing.

@@ -268,6 +268,62 @@ int aloam_reset_sequences(aloam_ctx* ctx, const int* seqs, int n);
  *   - ALOAM_E_STATE in a context without ALOAM_STAGE_MAPPING or before aloam_mapping_enable; argument errors as for aloam_set_active. */
 int aloam_set_map_frozen(aloam_ctx* ctx, const int* frozen);
 
+/* ---- scoring and applying batches of map-pose hypotheses ---------------------------------------------------------------------
+ * A frozen mapping step refines a guess that is already close (about 1 m and 2.5 deg of yaw).  A coarser guess is searched:
+ * many candidate corrections (map <- odometry, as aloam_set_map_frame takes them) are scored against the state one frozen step has left on
+ * the device, the best one is installed, and the next frozen steps refine it.  No step, no map copy and no slot per hypothesis.
+ *
+ * aloam_score_map_corrections: for each listed sequence seqs[i] and each candidate cand[c], scores[i * K + c] :=
+ *   - What a score is.  The state the sequence's last mapping step left is read: its laserCloudCornerStack / SurfStack
+ *     (ALOAM_MAP_CORNER_STACK / ALOAM_MAP_SURF_STACK), the odometry pose that step started from, and the search grid of its submap.  The
+ *     start pose is transformAssociateToMap (src/laserMapping.cpp:142-146) with the candidate in place of the sequence's correction; then
+ *     every stack point goes through the first data association of a mapping step (:554-687: pointAssociateToMap, the five nearest
+ *     submap points, the line fit and the plane fit with their tests), and every factor's residual is evaluated once at the start pose
+ *     (src/lidarFactor.hpp:36-51, :116-123, under HuberLoss(0.1) as :565).  Nothing of the sequence is written.
+ *   - Exactness.  corner_factors / surf_factors equal, as integers, the corner / surf factors of iteration 0 that aloam_get_map_info
+ *     reports after a frozen mapping step of the same frame started from aloam_set_map_frame(same cen, cand, same frame_count), whenever
+ *     that step keeps the same window (same cen and centre cube afterwards): the same device functions run in the same order.  A
+ *     candidate that moves the sensor into another 50 m cube is still scored, against the submap that is there (the window of the last
+ *     step), not the one a step from that candidate would select.
+ *   - Which sequences.  Each listed sequence must have been active AND frozen in its last mapping step, with nothing since that
+ *     invalidates its search grid: a mapping step in which it grew its map, aloam_reset_sequences, aloam_load_sequences, aloam_set_map,
+ *     aloam_set_map_frame, a reallocation of the map pools (by any sequence).  All of these are host calls, so a per-sequence host flag
+ *     decides without a synchronise: otherwise ALOAM_E_STATE and nothing is queued.  Steps the sequence sat out, odometry steps and
+ *     aloam_apply_map_corrections keep it.  A sequence whose step failed the gate (submap of <= 10 corner or <= 50 surf points, :554)
+ *     scores zeros.  seqs distinct and in range, n >= 0, K >= 1: else ALOAM_E_ARG.  ALOAM_E_STATE before aloam_mapping_enable.  Allowed
+ *     between asynchronous steps; the active and frozen masks in force play no part.
+ *   - Candidates are shared by all listed sequences (cand[K]); a host that wants another grid per sequence calls once per group of
+ *     sequences.  Quaternions are used as given (not normalised), like aloam_set_map_frame's.
+ *   - best[i] (may be NULL): the candidate with the most corner_factors + surf_factors; ties: the lower cost; ties: the lower index.
+ *     A cost that is NaN (a non-finite candidate) ranks as +infinity.  n * K <= 2^18 pairs per call, else ALOAM_E_ARG (split the candidates).
+ *   - Determinism.  Counts are integer sums.  cost is summed in a fixed order that depends on the stacks alone (per-workgroup partials in
+ *     fixed slots, then one ordered pass; no floating-point atomics): two calls on the same state return the same bits, whatever n, K
+ *     and the position of the candidate in cand.
+ *
+ * aloam_apply_map_corrections: for each listed sequence, q_wmap_wodom, t_wmap_wodom := cand[choice[i]], with choice read ON THE DEVICE
+ * in stream order: the `best` of a scoring call queued before it can be passed straight in, with no synchronise in between.  Every getter
+ * and aloam_export_poses then return the bits aloam_set_map_frame(current cen, that candidate, current frame_count) would give (that call
+ * leaves q_w_curr / t_w_curr as the last step left them; so does this one), with one difference: aloam_set_map_frame synchronises and
+ * invalidates the search grid, this call does neither - the window has not moved, the grid stays valid, and the next frozen step may reuse
+ * it.  Any sequence may be listed (no frozen step is required).  A choice[i] outside 0 .. K-1 on the device leaves that sequence untouched
+ * and is counted; the next aloam_synchronize returns ALOAM_E_ARG for it, once.
+ *
+ * Both calls are queued on the context's stream, make no host synchronisation and read nothing back (the first scoring call, and one
+ * with a larger n * K than any before, allocates its scratch).  scores, best and choice: device memory of the context's device or pinned
+ * host memory, classified before anything is queued as aloam_export_clouds classifies its destinations (pageable, managed, another
+ * device's memory and NULL: ALOAM_E_ARG); 8- / 4-byte aligned.  cand: those two, or pageable host memory, which is staged with one copy
+ * (it may be reused when the call returns; device and pinned candidates must stay unchanged until the call has run). */
+typedef struct aloam_map_correction { double q_wmap_wodom[4], t_wmap_wodom[3], pad; } aloam_map_correction;   /* 64 bytes */
+typedef struct aloam_map_score {                /* 32 bytes                                                                                  */
+  int corner_factors, surf_factors;             /* factors the FIRST association of a frozen mapping step counts from this correction       */
+  int corner_found, surf_found;                 /* stack points whose 5th neighbour is closer than 1 m (src/laserMapping.cpp:582,650)        */
+  double cost;                                  /* sum over those factors of 0.5 * HuberLoss(0.1) of the squared residual, at the start pose */
+  int pad[2];
+} aloam_map_score;
+int aloam_score_map_corrections(aloam_ctx* ctx, const int* seqs, int n, const aloam_map_correction* cand, int K,
+                                aloam_map_score* scores /* [n][K] */, int* best /* [n], may be NULL */);
+int aloam_apply_map_corrections(aloam_ctx* ctx, const int* seqs, int n, const aloam_map_correction* cand, int K, const int* choice /* [n] */);
+
 /* ---- sequence records: save and restore whole sequences, in batched stream-ordered calls ------------------------------
  * A sequence record is everything that makes up a sequence between two frames - odometry pose and statistics, systemInited, the last
  * clouds (laserCloudCornerLast / SurfLast, src/laserOdometry.cpp:554-563), and with mapping the map pose, window centre, frame count,

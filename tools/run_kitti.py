@@ -13,7 +13,8 @@ KITTI is not part of this repository or image; `--selftest` writes a tiny synthe
 
 Localization against a prior map (one --seq): `--mapping --save-map m.npz` writes the map of the run (both classes' cubes, window centre and
 frame count) at its end; a later `--prior-map m.npz` run injects it into a fresh context (aloam_set_map / aloam_set_map_frame, identity
-correction or --initial-pose), freezes the sequence (aloam_set_map_frozen) and writes <out>/<seq>_localized.txt: every sweep localized in
+correction or --initial-pose; `--relocalize RADIUS_M YAW_DEG` searches a grid of corrections around that guess after the first frozen step
+and installs the best, aloam_score_map_corrections / aloam_apply_map_corrections), freezes the sequence (aloam_set_map_frozen) and writes <out>/<seq>_localized.txt: every sweep localized in
 that map, which it leaves unchanged.  The file is a map, not a sequence record: the second run starts its odometry fresh.
 
 `--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
@@ -161,6 +162,7 @@ def load_prior_map(gpu, path, initial_pose=None):
         q, t = np.array([0.0, 0.0, np.sin(yaw / 2), np.cos(yaw / 2)]), np.array([tx, ty, tz])
     gpu.set_map_frame(m["cen"], q, t, 0, seq=0)
     gpu.set_map_frozen([1])
+    return q, t
 
 
 def main():
@@ -182,7 +184,11 @@ def main():
                                                             "changed); writes <seq>_localized.txt")
     ap.add_argument("--initial-pose", nargs=4, type=float, metavar=("TX", "TY", "TZ", "YAW"), help="with --prior-map: the first guess of the map <- odometry "
                                                                                                   "correction (metres, radians); default identity")
+    ap.add_argument("--relocalize", nargs=2, type=float, metavar=("RADIUS_M", "YAW_DEG"), help="with --prior-map: after the first frozen step, score a grid of "
+                    "corrections of this half-width (0.5 m, 2.5 deg cells) around the first guess on the device, install the best, continue")
     args = ap.parse_args()
+    if args.relocalize and not args.prior_map:
+        ap.error("--relocalize needs --prior-map")
     if (args.save_map or args.prior_map) and args.seqs:
         ap.error("--save-map / --prior-map take one --seq, not --seqs")
     if args.save_map and not args.mapping:
@@ -218,6 +224,7 @@ def main():
     lengths = [len(ts) for ts in times]
     plan = schedule_sliced(lengths, batch, args.slice) if args.slice > 0 else [(*st, [], []) for st in schedule(lengths, batch)]
     parked = {}                                        # sequence -> (record bytes in pinned host memory, offsets)
+    guess = None                                       # --prior-map: the first guess, until --relocalize has searched around it
     for active, resets, frames, saves, loads in plan:
         if saves:
             blob, off = gpu.save_sequences([s for s, _ in saves])
@@ -228,7 +235,7 @@ def main():
         if resets:
             gpu.reset_sequences(resets)                # a new sequence enters these slots: a fresh context's state, in place
             if args.prior_map:                         # (one --seq: only slot 0, at the first step) the map goes in after that reset
-                load_prior_map(gpu, args.prior_map, args.initial_pose)
+                guess = load_prior_map(gpu, args.prior_map, args.initial_pose)
         gpu.set_active(None if all(active) else active)
         scans = [idle] * batch
         for slot, (i, k) in frames.items():
@@ -237,6 +244,13 @@ def main():
         gpu.odometry_step()
         if args.mapping:
             gpu.mapping_step()
+        if args.relocalize and guess is not None:      # the first frozen step has left its stacks and submap grid: search around the first guess
+            relocalize = importlib.import_module("a-loam_amd.relocalize")
+            found = relocalize.relocalize(gpu, [0], radius_m=args.relocalize[0], step_m=0.5, yaw_deg=args.relocalize[1], yaw_step_deg=2.5, guesses={0: guess})[0]
+            b, node = found["scores"][found["best"]], found["nodes"][found["best"]]
+            print(f"{seqs[0]} relocalized: {len(found['nodes'])} corrections scored, best node ({node[0]:+.1f} m, {node[1]:+.1f} m, {node[2]:+.1f} deg) "
+                  f"with {int(b['corner_factors']) + int(b['surf_factors'])} factors")
+            guess = None
         gpu.export_poses(rec_buf.data_ptr())           # odometry and mapped poses of every slot in one call
         gpu.synchronize()
         for slot, (i, k) in frames.items():
