@@ -4,5 +4,6 @@ csrc/       HIP kernels (gfx950) + the C-ABI host side -> lib/libaloam_mi355x.so
 host/       the three ROS node shims that keep the aloam_velodyne topic surface and call the C ABI
 binding.py  ctypes stub of the C ABI (tests, bench.py); no second implementation
 synthetic.py  seeded synthetic sweeps (regular and KITTI-shaped rough ones); shard.py  sequence -> rank assignment
+atlas.py    map tiles on the host (numpy): what the map spill drains, files, the window-shift model
 KITTI-layout input and ground-truth evaluation live in tools/run_kitti.py.
 """

@@ -57,6 +57,12 @@ class AloamMapScore(C.Structure):
                 ("cost", C.c_double), ("pad", C.c_int * 2)]
 
 
+class AloamMapTile(C.Structure):
+    """One cube of one class with absolute cube coordinates (aloam_map_tile, 32 bytes)."""
+    _fields_ = [("cube", C.c_int * 3), ("feature_class", C.c_int), ("count", C.c_int), ("frame", C.c_int), ("first_point", C.c_longlong)]
+
+
+MAP_TILE_DTYPE = np.dtype([("cube", np.int32, 3), ("feature_class", np.int32), ("count", np.int32), ("frame", np.int32), ("first_point", np.int64)])
 MAP_CORRECTION_DTYPE = np.dtype([("q_wmap_wodom", np.float64, 4), ("t_wmap_wodom", np.float64, 3), ("pad", np.float64)])
 MAP_SCORE_DTYPE = np.dtype([("corner_factors", np.int32), ("surf_factors", np.int32), ("corner_found", np.int32), ("surf_found", np.int32),
                             ("cost", np.float64), ("pad", np.int32, 2)])
@@ -152,6 +158,12 @@ def lib():
         L.aloam_set_map_frozen.argtypes = [vp, vp]
         L.aloam_score_map_corrections.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
         L.aloam_apply_map_corrections.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
+        L.aloam_map_spill_enable.argtypes = [vp, C.c_int, C.c_int]
+        L.aloam_export_map_spill.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_int]
+        L.aloam_get_map_spill_info.argtypes = [vp, C.c_int, vp]
+        L.aloam_atlas_load.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong]
+        L.aloam_atlas_attach.argtypes = [vp, vp]
+        L.aloam_atlas_info.argtypes = [vp, vp]
         L.aloam_save_sequences.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_load_sequences.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_get_ring_ranges.argtypes = [vp, C.c_int, vp, vp]
@@ -374,6 +386,68 @@ class Aloam:
         ch = torch.tensor([int(v) for v in choice], dtype=torch.int32).pin_memory() if len(seqs) else torch.zeros(1, dtype=torch.int32).pin_memory()
         self._apply_keep = getattr(self, "_apply_keep", []) + [ch]   # read by the device later: kept until the next synchronize()
         self.apply_map_corrections_from(seqs, cand.ctypes.data, len(cand), ch.data_ptr())
+
+    # ---- map spill: the cubes that leave the window (stream-ordered; wait with synchronize()) -------------------------------------
+    def map_spill_enable(self, max_tiles, max_points):
+        """Keep what the window shifts of the mapping steps empty: per sequence and class up to max_tiles tiles / max_points points."""
+        self._check(lib().aloam_map_spill_enable(self.h, int(max_tiles), int(max_points)))
+
+    def export_map_spill_into(self, seqs, tiles_ptr, cap_tiles, points_ptr, cap_points, offsets_ptr, clear=True):
+        """Queue the drain of the spills of `seqs`: tiles_ptr receives up to cap_tiles aloam_map_tile records, points_ptr up to cap_points
+        float4 points, offsets_ptr 2 * (len(seqs) + 1) int64 (tile offsets, then point offsets) - device memory or pinned host memory; 0
+        pointers with caps of 0 = the size query.  clear: empty the sequences that were written."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_export_map_spill(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(tiles_ptr) if tiles_ptr else None, int(cap_tiles),
+                                                 C.c_void_p(points_ptr) if points_ptr else None, int(cap_points),
+                                                 C.c_void_p(offsets_ptr) if offsets_ptr else None, 1 if clear else 0))
+
+    def export_map_spill(self, seqs, clear=True, pinned=True):
+        """The spills of `seqs`: a size query, one allocation (pinned host memory, or device memory with pinned=False), the drain and a
+        synchronise.  Returns (tiles, points, offsets): a structured array of MAP_TILE_DTYPE, float32 [n, 4] and int64 [2, len(seqs) + 1]."""
+        import torch
+        n = len(seqs)
+        off = torch.zeros(2 * (n + 1), dtype=torch.int64, pin_memory=True)
+        self.export_map_spill_into(seqs, 0, 0, 0, 0, off.data_ptr(), clear=False)
+        self.synchronize()
+        nt, npts = int(off[n]), int(off[2 * n + 1])
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, **where)
+        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **where)
+        self.export_map_spill_into(seqs, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), clear=clear)
+        self.synchronize()
+        return (tiles.cpu().numpy()[:nt * 32].view(MAP_TILE_DTYPE).copy(), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy())
+
+    def map_spill_info(self, seq=0):
+        v = np.zeros(8, np.int32)
+        self._check(lib().aloam_get_map_spill_info(self.h, seq, _p(v)))
+        return {"tiles": v[0:2].tolist(), "points": v[2:4].tolist(), "dropped_tiles": int(v[4]), "dropped_points": int(v[5]),
+                "max_tiles": int(v[6]), "max_points": int(v[7])}
+
+    # ---- the atlas: one tile store per context, shared by the attached (frozen) sequences ---------------------------------------------
+    def atlas_load(self, tiles, points):
+        """tiles: structured array of MAP_TILE_DTYPE, points: (n, 4) float32 - numpy arrays, or torch tensors on this device (tiles as
+        uint8).  Synchronous.  No tiles = unload."""
+        if hasattr(tiles, "data_ptr"):
+            nt, npts, tp, pp = tiles.numel() // 32, points.shape[0], tiles.data_ptr(), points.data_ptr()
+        else:
+            tiles, points = np.ascontiguousarray(tiles, dtype=MAP_TILE_DTYPE), _f32(np.asarray(points).reshape(-1, 4))
+            nt, npts, tp, pp = len(tiles), len(points), tiles.ctypes.data, points.ctypes.data
+        self._check(lib().aloam_atlas_load(self.h, C.c_void_p(tp) if nt else None, nt, C.c_void_p(pp) if npts else None, npts))
+
+    def atlas_attach(self, mask=None):
+        """Which sequences take their window from the atlas (one truthy value per sequence); None = none."""
+        if mask is None:
+            self._check(lib().aloam_atlas_attach(self.h, None))
+            return
+        m = np.ascontiguousarray([1 if v else 0 for v in mask], dtype=np.int32)
+        assert m.shape == (self.batch,)
+        self._check(lib().aloam_atlas_attach(self.h, _p(m)))
+
+    def atlas_info(self):
+        v = np.zeros(12, np.int64)
+        self._check(lib().aloam_atlas_info(self.h, _p(v)))
+        return {"tiles": int(v[0]), "cubes": v[1:3].tolist(), "points": v[3:5].tolist(), "extent": v[5:8].tolist(), "largest_window": v[8:10].tolist(),
+                "exact": bool(v[10]), "device_bytes": int(v[11])}
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

@@ -82,6 +82,7 @@ int queue_reset(aloam_ctx* c, const int* seqs, int n) {
   launch_reset_sequences(r, c->stream);
   HIP_TRY(c, hipGetLastError());
   for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); }
+  for (int i = 0; i < n; ++i) if (const int rc = mark_window_stale(c, seqs[i])) return rc;   // an attached slot keeps its attachment
   return ALOAM_OK;
 }
 
@@ -270,6 +271,12 @@ int aloam_synchronize(aloam_ctx* c) {
       if (fresh_pool) c->err += " " + std::to_string(fresh_pool) + " (sequence, step) pair(s) ran out of map pool (first: sequence " + std::to_string(first_seq) + ")";
       if (fresh_vox) c->err += std::string(fresh_pool ? " and" : "") + " " + std::to_string(fresh_vox) + " step(s) ran out of voxel-filter scratch";
       c->err += "; the points that did not fit were not inserted (raise pool_points)";
+      return ALOAM_E_CAPACITY;
+    }
+    long long fresh_spill = 0;                            // tiles k_map_spill could not keep: reported once, like the capacity events above
+    if (const int rc = spill_dropped_since(c, &fresh_spill)) return rc;
+    if (fresh_spill > 0) {
+      c->err = "map spill full: " + std::to_string(fresh_spill) + " tile(s) dropped since the last aloam_synchronize (drain more often or raise max_tiles / max_points)";
       return ALOAM_E_CAPACITY;
     }
     if (c->d_rl_bad) {                                    // choices k_apply_corrections found outside 0 .. K-1: reported once, like the capacity events

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records).
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 
 #include "../../include/aloam_mi355x.h"
 #include "aloam_device.hpp"
+#include "atlas_kernels.hpp"
 #include "checkpoint_kernels.hpp"
 #include "export_kernels.hpp"
 #include "mapping_kernels.hpp"
@@ -173,6 +174,20 @@ struct aloam_ctx {
   long long rl_bad_reported = 0;                                    // of d_rl_bad, already returned by aloam_synchronize
   std::vector<int> rl_last_seqs; int rl_last_K = 0;                 // the last scoring call: its listed sequences and K (algorithmic bytes)
   int rl_apply_n = 0;
+  // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
+  bool spill_on = false;
+  int spill_max_tiles = 0, spill_max_points = 0;
+  DevBuf<aloam_map_tile> d_sp_tiles; DevBuf<float4> d_sp_points;   // [B][2][max_tiles], [B][2][max_points]
+  DevBuf<int> d_sp_counters;                                        // [B][kSpillInts]
+  DevBuf<int> d_sp_seqs, d_sp_cnt, d_sp_chunk; DevBuf<long long> d_sp_off;   // the drain: listed ids, [2][B] counts, [2][B + 1] chunk / element offsets (tiles, points)
+  // atlas (aloam_atlas_load / aloam_atlas_attach): one immutable tile store, shared by the attached sequences
+  bool atlas_on = false;
+  std::vector<char> attached; bool any_attached = false;            // [B] host mirror of d_at_attached
+  DevBuf<int> d_at_attached, d_at_stale;                            // [B] each; stale != 0: the next step cuts the window anew
+  DevBuf<AtlasEntry> d_at_dir[2]; int at_dir_mask[2] = {0, 0};      // per class: directory absolute cube -> (first, count)
+  DevBuf<float4> d_at_points[2];
+  long long at_info[12] = {0};                                      // what aloam_atlas_info returns
+  long long spill_dropped_reported = 0;                             // dropped tiles aloam_synchronize has already returned
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -281,6 +296,14 @@ int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n);
 // capi_mapping.hip
 inline void clear_scorable(aloam_ctx* c, int seq) { c->scorable[seq] = 0; }   // the search grid of `seq` is no longer that of its stacks
 int grow_map_pool(aloam_ctx* c, long long want, bool clamp);
+// capi_atlas.hip
+void queue_map_spill(aloam_ctx* c, const int* mask);
+int spill_dropped_since(aloam_ctx* c, long long* fresh);
+int mark_window_stale(aloam_ctx* c, int seq);            // the map, frame or slot of `seq` was replaced: an attached sequence cuts its window anew
+int atlas_step_check(aloam_ctx* c);                      // ALOAM_E_STATE when an attached sequence that is active in this step is not frozen
+bool queue_atlas_window(aloam_ctx* c, const int* mask);  // k_atlas_window when an attached sequence takes part
+// capi_mapping.hip
+VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);
 // capi_records.hip
 enum CallerMem { kMemPageable, kMemDevice, kMemPinned, kMemManaged, kMemOtherDevice };
 CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev);

@@ -30,13 +30,15 @@ static MapArgs map_args(aloam_ctx* c) {
   a.rec_tiles = c->d_rec_tiles.get(); a.rec_tiles_per_seq = c->rec_tiles_per_seq; a.rec_tiles_corner = c->rec_tiles_corner;
   return a;
 }
-static VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels) {
+namespace aloam {
+VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels) {
   VoxArgs v{};
   v.segs = c->d_segs.get(); v.n_segs = n_segs; v.tile_seg = c->map.tile_seg.get(); v.tile_heads = c->map.tile_heads.get(); v.tile_pref = c->map.tile_pref.get();
   v.counters = c->d_vox_counters.get(); v.keys[0] = c->map.keys[0].get(); v.keys[1] = c->map.keys[1].get(); v.tmp = c->map.voxtmp.get(); v.bbox = c->d_bbox.get();
   v.tile_cap = c->map.tile_cap; v.key_cap = c->map.key_cap; v.levels = levels; v.lists = c->d_vox_lists.get();
   return v;
 }
+}  // namespace aloam
 
 // Everything whose size follows the pool: the two class pools (contents kept when growing), the bucketed copy of the submap, the scratch of
 // the general voxel path (keys, staging = 2 pools per sequence, tile lists) and the bucket tables.  A fresh MapPool is allocated and filled,
@@ -223,6 +225,7 @@ int aloam_mapping_step(aloam_ctx* c) {
       c->err = "sequence " + std::to_string(b) + " was loaded (aloam_load_sequences) and has not had its odometry step yet: it may not map";
       return ALOAM_E_STATE;
     }
+  if (const int rc = atlas_step_check(c)) return rc;
   // Per sequence: kSeqActive = takes part, kSeqMapGrow = takes part and extends its map (not frozen).  The kernels get no mask at all when
   // every sequence grows: the launches of a lock-step batch are those of a context without aloam_set_active / aloam_set_map_frozen.
   const int* mask = nullptr;
@@ -249,7 +252,10 @@ int aloam_mapping_step(aloam_ctx* c) {
   c->inject_max = 0;
   MapArgs a = map_args(c);
   a.active = mask;
-  { ProfScope p(c, K_MAP_BEGIN); launch_map_begin(a, c->stream); }
+  { ProfScope p(c, K_MAP_BEGIN);
+    if (c->spill_on) queue_map_spill(c, mask);                              // the cubes this step's shift empties, while they are still there
+    if (c->any_attached) queue_atlas_window(c, mask);                       // attached sequences: the window cut from the atlas where it is stale or about to shift
+    launch_map_begin(a, c->stream); }
   { ProfScope p(c, K_MAP_VOXEL_STACK);                                      // downSizeFilterCorner / Surf on the incoming clouds (:542-550)
     const VoxArgs v = vox_args(c, c->B * 2, c->map_levels);
     HIP_TRY(c, hipMemsetAsync(c->d_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));   // general-path count, the two LDS-filter lists
@@ -298,6 +304,7 @@ int aloam_set_map(aloam_ctx* c, int seq, int cls, const int* cube_ids, const int
   if (total > c->map.points && (rc = grow_map_pool(c, total, false))) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // another submap: its grids are built anew
   clear_scorable(c, seq);
+  if ((rc = mark_window_stale(c, seq))) return rc;
   HIP_TRY(c, hipMemcpy(c->d_cubes.get() + ((size_t)seq * 2 + cls) * kMapCubes, d.data(), sizeof(CubeDesc) * kMapCubes, hipMemcpyHostToDevice));
   if (total) HIP_TRY(c, hipMemcpy(c->map.pool[cls].get() + (size_t)seq * c->map.points, points_xyzw, sizeof(float4) * (size_t)total, hipMemcpyHostToDevice));
   if ((rc = edit_seq(c, c->d_mapseq.get() + seq, [&](MapSeq& ms) { ms.pool_used[cls] = (int)total; }))) return rc;
@@ -318,7 +325,7 @@ int aloam_set_map_frame(aloam_ctx* c, int seq, const int cen[3], const double q_
        }))) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // a new frame: the grids are built anew
   clear_scorable(c, seq);
-  return ALOAM_OK;
+  return mark_window_stale(c, seq);
 }
 
 int aloam_set_map_frozen(aloam_ctx* c, const int* frozen) {

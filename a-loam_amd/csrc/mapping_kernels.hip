@@ -23,6 +23,7 @@
 
 #include "lm_device.hpp"
 #include "map_search_device.hpp"
+#include "map_window_device.hpp"
 
 namespace aloam {
 
@@ -30,15 +31,6 @@ namespace {
 
 __device__ __forceinline__ int f2o(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }   // order-preserving
 __device__ __forceinline__ float o2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-// int((v + 25.0) / 50.0) + cen, minus one when v + 25 < 0  (:312-321, :741-750)
-__device__ __forceinline__ int cube_coord(double v, int cen) {
-  int c = (int)((v + 25.0) / 50.0) + cen;
-  if (v + 25.0 < 0) c--;
-  return c;
-}
-
-__device__ __forceinline__ CubeDesc* cube_table(const MapArgs& a, int b, int cls) { return a.cubes + ((long long)b * 2 + cls) * kMapCubes; }
 
 // submap lookup: g-th point of the concatenated valid cubes of class cls (laserCloudCornerFromMap / SurfFromMap order)
 __device__ __forceinline__ float4 submap_point(const MapArgs& a, int b, int cls, const int* tab, int n_valid, int g) {
@@ -256,17 +248,7 @@ __global__ __launch_bounds__(256) void k_map_begin(MapArgs a) {
 // =======================================================================================================
 // pcl::VoxelGrid for any number of independent segments
 // =======================================================================================================
-// Which filter takes a segment: the single-workgroup LDS filter (k_vox_lds; list 2: <= kVoxTinyN points, one wave; list 0: <= kVoxSmallN
-// points, 256 threads; list 1: up to kVoxBigN points, 1024 threads) or, for anything larger, the general tile-sort / rank-merge path
-// through global memory.
-__device__ __forceinline__ void vox_enlist(const VoxArgs& v, int seg, int n) {
-  if (n <= 0) return;
-  if (n <= kVoxTinyN) v.lists[2 * (long long)v.n_segs + atomicAdd(&v.counters[7], 1)] = seg;
-  else if (n <= kVoxSmallN) v.lists[atomicAdd(&v.counters[5], 1)] = seg;
-  else if (n <= kVoxBigN) v.lists[v.n_segs + atomicAdd(&v.counters[6], 1)] = seg;
-  else atomicAdd(&v.counters[4], 1);
-}
-
+// Which filter takes a segment is decided by vox_enlist (map_window_device.hpp).
 __global__ void k_map_stack_segments(MapArgs a, VoxArgs v) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= a.B * 2) return;

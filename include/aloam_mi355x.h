@@ -324,6 +324,92 @@ int aloam_score_map_corrections(aloam_ctx* ctx, const int* seqs, int n, const al
                                 aloam_map_score* scores /* [n][K] */, int* best /* [n], may be NULL */);
 int aloam_apply_map_corrections(aloam_ctx* ctx, const int* seqs, int n, const aloam_map_correction* cand, int K, const int* choice /* [n] */);
 
+/* ---- map tiles and the map spill: keeping the cubes that leave the window ------------------------------------------------------
+ * A map is the 21 x 21 x 11 window of 50 m cubes around the sensor (src/laserMapping.cpp:72-80).  When the sensor comes within three
+ * cubes of an edge the window shifts, and the slab that falls off is cleared and re-enters empty at the other side (:323-507): in the
+ * reference, and in aloam_mapping_step, those points are gone.  The spill keeps them.  It changes nothing a mapping step computes: a
+ * re-entered cube still starts empty; the cubes are only copied out before they are emptied.
+ *
+ * aloam_map_tile: one cube of one class with absolute coordinates.  cube[] is the window index (i, j, k) minus the window centre
+ * (laserCloudCenWidth / Height / Depth) = int((t + 25) / 50), minus one when t + 25 < 0 (:312-321), of the coordinates of its points, so a
+ * tile does not depend on the window it was cut from.  first_point indexes the array of 16-byte points (x, y, z, intensity) that goes with
+ * a tile array.
+ *
+ * aloam_map_spill_enable: after aloam_mapping_enable, once.  Allocates, per sequence and class, a row of max_tiles tiles and a row of
+ * max_points points, and counters.  From then on every aloam_mapping_step queues one more kernel in front of its first one: for every
+ * ACTIVE sequence, growing or frozen, that computes the shift this step is about to make (the same arithmetic on the same state:
+ * transformAssociateToMap :142-146, the centre cube :311-321, the shift loop) and, when there is one, appends every non-empty cube that the
+ * shift empties to the sequence's rows as a tile: class 0 (corner) and class 1 (surf) rows apart, each in ascending window index
+ * i + 21 j + 441 k, cube = index minus the centre BEFORE the step, frame = frameCount before the step, the points in the cube's order and
+ * bits.  Idle sequences spill nothing.  A context that never calls this launches exactly what it launched before.
+ *   - A tile is kept whole or not at all.  One that does not fit what is left of its rows is dropped and counted (later, smaller tiles
+ *     of the same step are still kept); the next aloam_synchronize returns ALOAM_E_CAPACITY once, "map spill full".  Drain often enough.
+ *   - aloam_reset_sequences and aloam_load_sequences do not touch a slot's spill: the host drains a slot before it reuses it.  The spill
+ *     is not part of a sequence record (ALOAM_SEQ_RECORD_VERSION, MapSeq and aloam_pose_record are unchanged).
+ *   - max_tiles in 1 .. 2^20, max_points in 1 .. 2^26: else ALOAM_E_ARG.  ALOAM_E_STATE before aloam_mapping_enable or when already enabled.
+ *
+ * aloam_export_map_spill: the drain.  Queued on the context's stream, no host synchronisation, nothing read back.  For the n listed
+ * sequences (distinct, in range) the device always writes dst_offsets[0 .. n] (tiles) and dst_offsets[n + 1 .. 2 n + 1] (points):
+ * sequence seqs[i]'s tiles - its corner row, then its surf row - go to tiles_dst[dst_offsets[i] .. dst_offsets[i + 1]) and their points to
+ * points_dst[dst_offsets[n + 1 + i] .. dst_offsets[n + 2 + i]), with first_point rewritten to index points_dst.  A sequence's tiles and
+ * points are written only when BOTH ranges end inside cap_tiles / cap_points; nothing is ever written past the caps, and caps of 0 are the
+ * size query (tiles_dst / points_dst may then be NULL).  With clear != 0 the sequences that were written are emptied, in stream order; the
+ * others keep their spill.  Destinations are classified like aloam_export_clouds': device memory of the context's device or pinned host
+ * memory; pageable, managed, another device's memory and NULL are refused with ALOAM_E_ARG before anything is queued.
+ *
+ * aloam_get_map_spill_info (synchronises): out = tiles held (corner, surf), points held (corner, surf), tiles dropped so far, points
+ * dropped so far, max_tiles, max_points. */
+typedef struct aloam_map_tile {      /* 32 bytes */
+  int cube[3];                       /* absolute cube (see above) */
+  int feature_class;                 /* 0 corner, 1 surf */
+  int count;                         /* points */
+  int frame;                         /* frameCount of the sequence when the tile was cut; 0 for tiles of other origin */
+  long long first_point;             /* index of its first point in the points array that goes with the tile array */
+} aloam_map_tile;
+int aloam_map_spill_enable(aloam_ctx* ctx, int max_tiles, int max_points);
+int aloam_export_map_spill(aloam_ctx* ctx, const int* seqs, int n, aloam_map_tile* tiles_dst, long long cap_tiles, float* points_dst_xyzw,
+                           long long cap_points, long long* dst_offsets /* [2][n + 1] */, int clear);
+int aloam_get_map_spill_info(aloam_ctx* ctx, int seq, int out[8]);
+
+/* ---- the atlas: a frozen sequence's window served from a map of any extent ----------------------------------------------------
+ * One immutable tile store per context, shared by all its sequences.  A sequence attached to it localizes (aloam_set_map_frozen) in a
+ * map larger than the 21 x 21 x 11 window: whenever its window is stale or about to shift (src/laserMapping.cpp:323-507), the window is
+ * cut fresh from the atlas, so it never loses a cube and cubes more than a window away from where it started are there when it arrives.
+ *
+ * aloam_atlas_load: tiles[n_tiles] and the points[n_points] they index (what aloam_export_map_spill and a-loam_amd/atlas.py produce),
+ * from pageable or pinned host memory or device memory of the context's device (managed / another device's memory: ALOAM_E_ARG).
+ * Synchronous, like aloam_mapping_enable.  Every tile is validated before anything changes: class 0 / 1, count >= 0, its range inside
+ * n_points, cube coordinates in -512 .. 511 (else ALOAM_E_ARG).  n_tiles = 0 unloads.  Replacing or unloading while a sequence is attached:
+ * ALOAM_E_STATE.  ALOAM_E_STATE before aloam_mapping_enable.
+ *   - Per class the points are packed and an open-addressing directory absolute cube -> (first, count) is built on the host (16-byte
+ *     entries, load factor <= 1/2) and uploaded once.
+ *   - Several tiles of one (cube, class) - a cube that left the window, was re-entered and left again, or two sessions - are concatenated
+ *     in array order and filtered once with that class's pcl::VoxelGrid leaf (mapping_line_resolution / mapping_plane_resolution): what
+ *     the per-cube re-filter (:788-801) would have made of them had they been one cube.  Always the input-order sum, whatever
+ *     aloam_set_voxel_sum_order says.  A cube with one tile is taken as it is.  A concatenation larger than a map pool row grows the pools
+ *     first, or is ALOAM_E_CAPACITY at the pool limit; nothing is truncated.  (The pools are grown before the new atlas is installed: when
+ *     a later allocation of the load fails, the atlas stays as it was but the pools - contents kept - may already be larger.)
+ *
+ * aloam_atlas_attach: attached[b] != 0 for each of the `batch` sequences; NULL = none.  Host state staged per call like the frozen mask.
+ * Attaching needs a loaded atlas (ALOAM_E_STATE) and grows the map pools until a row holds the largest window of the atlas
+ * (ALOAM_E_CAPACITY above the pool limit, nothing changed).  Newly attached sequences are marked stale, in stream order; aloam_set_map,
+ * aloam_set_map_frame, aloam_reset_sequences and aloam_load_sequences keep the attachment and mark the sequences they touch stale, so
+ * aloam_set_map_frame(cen, guess, 0) is how a localization starts.  aloam_apply_map_corrections does not (the window has not moved).
+ *   - An attached sequence that is active in a mapping step must be frozen: otherwise aloam_mapping_step returns ALOAM_E_STATE and queues
+ *     nothing.
+ *   - In such a step, before the window shifts would run: not stale and no shift - nothing happens.  Otherwise, for the centre the shift
+ *     leads to, each of the 4851 cubes is looked up in the directory, the descriptors are packed back to back from the start of the pool
+ *     row (as after aloam_load_sequences) and the points copied; cen becomes the new centre, pool_used the totals, the search grids are
+ *     rebuilt.  The step itself then shifts nothing.  ALOAM_MAP_SURROUND / ALOAM_MAP_FULL, the getters, records, scoring and apply work on
+ *     the window as they do without an atlas.  The map spill skips attached sequences (nothing is lost).
+ *
+ * aloam_atlas_info: out = tiles given; cubes (corner, surf) and points (corner, surf) after merging; extent of the bounding box in cubes
+ * (x, y, z); the largest number of points any 21 x 21 x 11 box of cubes holds (corner, surf); 1 when that is exact (sliding sums over the
+ * bounding box), 0 when it is the class total (bounding box above 2^24 cells); device bytes.  Zeros when no atlas is loaded. */
+int aloam_atlas_load(aloam_ctx* ctx, const aloam_map_tile* tiles, long long n_tiles, const float* points_xyzw, long long n_points);
+int aloam_atlas_attach(aloam_ctx* ctx, const int* attached /* [batch], NULL = none */);
+int aloam_atlas_info(aloam_ctx* ctx, long long out[12]);
+
 /* ---- sequence records: save and restore whole sequences, in batched stream-ordered calls ------------------------------
  * A sequence record is everything that makes up a sequence between two frames - odometry pose and statistics, systemInited, the last
  * clouds (laserCloudCornerLast / SurfLast, src/laserOdometry.cpp:554-563), and with mapping the map pose, window centre, frame count,

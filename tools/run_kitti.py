@@ -16,6 +16,9 @@ frame count) at its end; a later `--prior-map m.npz` run injects it into a fresh
 correction or --initial-pose; `--relocalize RADIUS_M YAW_DEG` searches a grid of corrections around that guess after the first frozen step
 and installs the best, aloam_score_map_corrections / aloam_apply_map_corrections), freezes the sequence (aloam_set_map_frozen) and writes <out>/<seq>_localized.txt: every sweep localized in
 that map, which it leaves unchanged.  The file is a map, not a sequence record: the second run starts its odometry fresh.
+`--save-map` holds the final 21 x 21 x 11 window only; `--mapping --save-atlas a.npz` also keeps every cube that left the window on the way
+(aloam_map_spill_enable, drained with aloam_export_map_spill after every step) and writes the whole map as tiles (a-loam_amd/atlas.py);
+`--prior-atlas a.npz` localizes in such a map of any extent (aloam_atlas_load, aloam_atlas_attach), with --initial-pose / --relocalize as above.
 
 `--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
 context runs one sequence; when it ends, the slot is reset in place (aloam_reset_sequences) and takes the next one, and slots with nothing
@@ -134,6 +137,9 @@ def write_selftest(folder, seq="00", frames=6, seed=77):
         s.numpy().astype(np.float32).tofile(os.path.join(folder, "velodyne", "sequences", seq, "velodyne", f"{k:06d}.bin"))
 
 
+SPILL_TILES, SPILL_POINTS = 2048, 1 << 20              # --save-atlas: room per class for what one step's shift empties (it is drained after every step)
+
+
 def save_map(gpu, path):
     """The map of sequence 0 (aloam_map_cube_counts / aloam_get_map_cube of both classes) with its window centre and frame count."""
     info = gpu.map_info(0)
@@ -165,6 +171,22 @@ def load_prior_map(gpu, path, initial_pose=None):
     return q, t
 
 
+def load_prior_atlas(gpu, path, initial_pose=None):
+    """Load a --save-atlas file into the context's atlas and attach sequence 0 to it: its window is cut from the atlas wherever it goes.
+    Correction and frame count as load_prior_map; the first step cuts the window around the guess."""
+    atlas = importlib.import_module("a-loam_amd.atlas")
+    tiles, points = atlas.load_atlas(path)
+    gpu.atlas_load(tiles, points)
+    q, t = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3)
+    if initial_pose is not None:
+        tx, ty, tz, yaw = initial_pose
+        q, t = np.array([0.0, 0.0, np.sin(yaw / 2), np.cos(yaw / 2)]), np.array([tx, ty, tz])
+    gpu.set_map_frozen([1])
+    gpu.atlas_attach([1])
+    gpu.set_map_frame((10, 10, 5), q, t, 0, seq=0)
+    return q, t
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", help="dataset_folder of kitti_helper.launch")
@@ -180,19 +202,32 @@ def main():
     ap.add_argument("--reference-order", action="store_true", help="sum voxel members in pcl::VoxelGrid's own order (the reference's bits; ~4x slower for one sensor): for runs that are compared pose by pose with A-LOAM's")
     ap.add_argument("--distortion", action="store_true", help="per-point interpolation ratio (the reference's DISTORTION 1; real KITTI sweeps are already de-skewed, so the reference ships 0)")
     ap.add_argument("--save-map", metavar="FILE.npz", help="with --mapping, one --seq: write the map of the run (cubes of both classes, cen, frame count) at its end")
+    ap.add_argument("--save-atlas", metavar="FILE.npz", help="with --mapping, one --seq: write the whole map of the run as tiles (a-loam_amd/atlas.py): every cube "
+                                                             "that left the 21 x 21 x 11 window on the way (the map spill, drained after every step) and the final window")
     ap.add_argument("--prior-map", metavar="FILE.npz", help="one --seq: localize every sweep against this --save-map file, frozen (the map is not "
                                                             "changed); writes <seq>_localized.txt")
+    ap.add_argument("--prior-atlas", metavar="FILE.npz", help="one --seq: like --prior-map, against a --save-atlas file of any extent (aloam_atlas_load / "
+                                                              "aloam_atlas_attach: the window is cut from the atlas wherever the sensor goes)")
     ap.add_argument("--initial-pose", nargs=4, type=float, metavar=("TX", "TY", "TZ", "YAW"), help="with --prior-map: the first guess of the map <- odometry "
                                                                                                   "correction (metres, radians); default identity")
     ap.add_argument("--relocalize", nargs=2, type=float, metavar=("RADIUS_M", "YAW_DEG"), help="with --prior-map: after the first frozen step, score a grid of "
                     "corrections of this half-width (0.5 m, 2.5 deg cells) around the first guess on the device, install the best, continue")
     args = ap.parse_args()
+    if args.prior_atlas and args.prior_map:
+        ap.error("--prior-atlas and --prior-map exclude each other")
+    prior_atlas = args.prior_atlas
+    if prior_atlas:                                    # everything else treats it as a prior map
+        args.prior_map = prior_atlas
     if args.relocalize and not args.prior_map:
         ap.error("--relocalize needs --prior-map")
     if (args.save_map or args.prior_map) and args.seqs:
-        ap.error("--save-map / --prior-map take one --seq, not --seqs")
+        ap.error("--save-map / --prior-map / --prior-atlas take one --seq, not --seqs")
     if args.save_map and not args.mapping:
         ap.error("--save-map needs --mapping")
+    if args.save_atlas and not args.mapping:
+        ap.error("--save-atlas needs --mapping")
+    if args.save_atlas and (args.seqs or args.prior_map):
+        ap.error("--save-atlas takes one --seq that maps (no --seqs, no --prior-map)")
     if args.initial_pose and not args.prior_map:
         ap.error("--initial-pose needs --prior-map")
     if args.prior_map:
@@ -219,6 +254,12 @@ def main():
     rec_buf = torch.empty(batch * ctypes.sizeof(binding.AloamPoseRecord), dtype=torch.uint8, pin_memory=True)   # the poses of a step, written by the device
     recs = (binding.AloamPoseRecord * batch).from_address(rec_buf.data_ptr())
     odo, mapped = [[] for _ in seqs], [[] for _ in seqs]
+    spill = None                                       # --save-atlas: the pinned destinations of the drain that follows every mapping step
+    if args.save_atlas:
+        atlas = importlib.import_module("a-loam_amd.atlas")
+        gpu.map_spill_enable(SPILL_TILES, SPILL_POINTS)
+        spill = {"tiles": torch.zeros(2 * SPILL_TILES * 32, dtype=torch.uint8, pin_memory=True), "points": torch.zeros((2 * SPILL_POINTS, 4), dtype=torch.float32, pin_memory=True),
+                 "off": torch.zeros(4, dtype=torch.int64, pin_memory=True), "log": atlas.TileLog()}
     factors = []                                       # --prior-map: last-iteration factors of every sweep (aloam_get_map_info), the fit to the map
     idle = np.zeros((0, 4), np.float32)
     lengths = [len(ts) for ts in times]
@@ -235,7 +276,7 @@ def main():
         if resets:
             gpu.reset_sequences(resets)                # a new sequence enters these slots: a fresh context's state, in place
             if args.prior_map:                         # (one --seq: only slot 0, at the first step) the map goes in after that reset
-                guess = load_prior_map(gpu, args.prior_map, args.initial_pose)
+                guess = (load_prior_atlas if prior_atlas else load_prior_map)(gpu, args.prior_map, args.initial_pose)
         gpu.set_active(None if all(active) else active)
         scans = [idle] * batch
         for slot, (i, k) in frames.items():
@@ -244,6 +285,8 @@ def main():
         gpu.odometry_step()
         if args.mapping:
             gpu.mapping_step()
+        if spill:                                      # stream-ordered, no synchronise of its own: read after the step's synchronize() below
+            gpu.export_map_spill_into([0], spill["tiles"].data_ptr(), 2 * SPILL_TILES, spill["points"].data_ptr(), 2 * SPILL_POINTS, spill["off"].data_ptr(), clear=True)
         if args.relocalize and guess is not None:      # the first frozen step has left its stacks and submap grid: search around the first guess
             relocalize = importlib.import_module("a-loam_amd.relocalize")
             found = relocalize.relocalize(gpu, [0], radius_m=args.relocalize[0], step_m=0.5, yaw_deg=args.relocalize[1], yaw_step_deg=2.5, guesses={0: guess})[0]
@@ -252,17 +295,30 @@ def main():
                   f"with {int(b['corner_factors']) + int(b['surf_factors'])} factors")
             guess = None
         gpu.export_poses(rec_buf.data_ptr())           # odometry and mapped poses of every slot in one call
-        gpu.synchronize()
+        try:
+            gpu.synchronize()
+        except binding.AloamError as e:
+            if spill and "map spill full" in str(e):
+                sys.exit(f"--save-atlas: one step's window shift emptied more than {SPILL_TILES} cubes or {SPILL_POINTS} points of one class; the atlas would be "
+                         f"incomplete.  Raise SPILL_TILES / SPILL_POINTS in tools/run_kitti.py.  ({e})")
+            raise
         for slot, (i, k) in frames.items():
             r = recs[slot]
             odo[i].append([times[i][k], *r.t_w, *r.q_w])
             if args.mapping:
                 mapped[i].append([times[i][k], *r.map_t_w, *r.map_q_w])
+        if spill and int(spill["off"][1]):             # (the rows hold at most what the destinations hold: a drain is always written)
+            nt, npts = int(spill["off"][1]), int(spill["off"][3])
+            spill["log"].add(spill["tiles"].numpy()[:nt * 32].view(atlas.TILE_DTYPE), spill["points"].numpy()[:npts])
         if args.prior_map:
             info = gpu.map_info(0)
             factors.append(info["corner_num1"] + info["surf_num1"])
     if args.save_map:
         save_map(gpu, args.save_map)
+    if args.save_atlas:
+        tiles, points = spill["log"].result(atlas.window_tiles(gpu, 0))
+        atlas.save_atlas(args.save_atlas, tiles, points)
+        print(f"{seqs[0]} atlas: {len(tiles)} tiles, {len(points)} points ({sum(len(t) for t, _ in spill['log'].parts)} tiles left the window on the way)")
     gpu.close()
     mapped_name = "localized" if args.prior_map else "mapped"
     if factors:
