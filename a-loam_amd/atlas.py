@@ -115,8 +115,18 @@ class TileLog:
         return concatenate(self.parts + list(more))
 
 
-def save_atlas(path, tiles, points):
-    np.savez_compressed(path, tiles=np.asarray(tiles, TILE_DTYPE), points=np.asarray(points, np.float32).reshape(-1, 4))
+def save_atlas(path, tiles, points, places=None):
+    """places: the stored places that go with the map (structured array of binding.PLACE_DTYPE, aloam_places_export), kept as raw bytes."""
+    extra = {} if places is None else {"places": np.ascontiguousarray(places).view(np.uint8).reshape(-1)}
+    np.savez_compressed(path, tiles=np.asarray(tiles, TILE_DTYPE), points=np.asarray(points, np.float32).reshape(-1, 4), **extra)
+
+
+def load_atlas_places(path):
+    """The places of a save_atlas file (binding.PLACE_DTYPE); none when it was written without them."""
+    from .binding import PLACE_DTYPE
+    with np.load(path) as z:
+        raw = np.asarray(z["places"], np.uint8) if "places" in z.files else np.zeros(0, np.uint8)
+    return raw.view(PLACE_DTYPE).copy()
 
 
 def load_atlas(path):

@@ -62,6 +62,21 @@ class AloamMapTile(C.Structure):
     _fields_ = [("cube", C.c_int * 3), ("feature_class", C.c_int), ("count", C.c_int), ("frame", C.c_int), ("first_point", C.c_longlong)]
 
 
+class AloamPlace(C.Structure):
+    """One stored place (aloam_place, 4880 bytes): the 60 x 20 sector-major cells of its descriptor and the tag."""
+    _fields_ = [("cells", (C.c_float * 20) * 60), ("q", C.c_double * 4), ("t", C.c_double * 3), ("slot", C.c_int), ("frame", C.c_int),
+                ("n_points", C.c_int), ("pad", C.c_int * 3)]
+
+
+class AloamPlaceMatch(C.Structure):
+    """One result of aloam_places_match (aloam_place_match, 16 bytes)."""
+    _fields_ = [("entry", C.c_int), ("shift", C.c_int), ("distance", C.c_float), ("pad", C.c_int)]
+
+
+PLACE_RINGS, PLACE_SECTORS = 20, 60
+PLACE_DTYPE = np.dtype([("cells", np.float32, (60, 20)), ("q", np.float64, 4), ("t", np.float64, 3), ("slot", np.int32), ("frame", np.int32),
+                        ("n_points", np.int32), ("pad", np.int32, 3)])
+PLACE_MATCH_DTYPE = np.dtype([("entry", np.int32), ("shift", np.int32), ("distance", np.float32), ("pad", np.int32)])
 MAP_TILE_DTYPE = np.dtype([("cube", np.int32, 3), ("feature_class", np.int32), ("count", np.int32), ("frame", np.int32), ("first_point", np.int64)])
 MAP_CORRECTION_DTYPE = np.dtype([("q_wmap_wodom", np.float64, 4), ("t_wmap_wodom", np.float64, 3), ("pad", np.float64)])
 MAP_SCORE_DTYPE = np.dtype([("corner_factors", np.int32), ("surf_factors", np.int32), ("corner_found", np.int32), ("surf_found", np.int32),
@@ -164,6 +179,13 @@ def lib():
         L.aloam_atlas_load.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong]
         L.aloam_atlas_attach.argtypes = [vp, vp]
         L.aloam_atlas_info.argtypes = [vp, vp]
+        L.aloam_places_enable.argtypes = [vp, C.c_int, C.c_float, C.c_float]
+        L.aloam_places_add.argtypes = [vp, vp, C.c_int]
+        L.aloam_places_match.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
+        L.aloam_places_export.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.aloam_places_load.argtypes = [vp, vp, C.c_int]
+        L.aloam_places_clear.argtypes = [vp]
+        L.aloam_places_info.argtypes = [vp, vp]
         L.aloam_save_sequences.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_load_sequences.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_get_ring_ranges.argtypes = [vp, C.c_int, vp, vp]
@@ -448,6 +470,76 @@ class Aloam:
         self._check(lib().aloam_atlas_info(self.h, _p(v)))
         return {"tiles": int(v[0]), "cubes": v[1:3].tolist(), "points": v[3:5].tolist(), "extent": v[5:8].tolist(), "largest_window": v[8:10].tolist(),
                 "exact": bool(v[10]), "device_bytes": int(v[11])}
+
+    # ---- place recognition (stream-ordered; wait with synchronize()) -------------------------------------------------------------------
+    def places_enable(self, capacity, max_range=80.0, sensor_height=2.0):
+        """One place store of `capacity` entries for this context, and one scan-context descriptor per sequence (made on first use)."""
+        self._check(lib().aloam_places_enable(self.h, int(capacity), float(max_range), float(sensor_height)))
+
+    def places_add(self, seqs):
+        """Append the place of each listed sequence (descriptor of the sweep it holds + its pose at this point of the stream).  Returns the
+        store index of the first one; the others follow in listed order."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        first = self.places_info()["count"]
+        self._check(lib().aloam_places_add(self.h, _p(ids) if len(ids) else None, len(ids)))
+        return first
+
+    def places_match_into(self, seqs, ranges, T, dst_ptr):
+        """Queue the match of the listed sequences' descriptors, each against the store entries [ranges[i][0], ranges[i][1]); dst_ptr
+        receives len(seqs) * T aloam_place_match records (device memory or pinned host memory)."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        rg = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 2)
+        assert len(rg) == len(ids)
+        self._check(lib().aloam_places_match(self.h, _p(ids) if len(ids) else None, len(ids), _p(rg) if len(ids) else None, int(T),
+                                             C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def places_match(self, seqs, ranges=None, T=1, pinned=True):
+        """The T best stored places for each listed sequence, after a synchronise: a structured array [len(seqs), T] of PLACE_MATCH_DTYPE.
+        ranges: one (lo, hi) per sequence, or None = the whole store."""
+        import torch
+        n = len(seqs)
+        if ranges is None:
+            ranges = [(0, self.places_info()["count"])] * n
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        dst = torch.zeros(max(1, n * T) * 16, dtype=torch.uint8, **where)
+        self.places_match_into(seqs, ranges, T, dst.data_ptr())
+        self.synchronize()
+        return dst.cpu().numpy()[:n * T * 16].view(PLACE_MATCH_DTYPE).reshape(n, T).copy()
+
+    def places_export_into(self, first, count, dst_ptr):
+        self._check(lib().aloam_places_export(self.h, int(first), int(count), C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def places_export(self, first=0, count=None, pinned=True):
+        """Store entries [first, first + count) (default: all that follow first) as a structured array of PLACE_DTYPE, after a synchronise."""
+        import torch
+        if count is None:
+            count = self.places_info()["count"] - first
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        dst = torch.zeros(max(1, count) * PLACE_DTYPE.itemsize, dtype=torch.uint8, **where)
+        self.places_export_into(first, count, dst.data_ptr())
+        self.synchronize()
+        return dst.cpu().numpy()[:count * PLACE_DTYPE.itemsize].view(PLACE_DTYPE).copy()
+
+    def places_load(self, places):
+        """Append stored places: a structured array of PLACE_DTYPE (pageable host memory), or a torch uint8 tensor on this device or pinned.
+        Returns the store index of the first one.  The source is kept referenced until the next load (the copy is stream-ordered)."""
+        first = self.places_info()["count"]
+        if hasattr(places, "data_ptr"):
+            n, ptr = places.numel() // PLACE_DTYPE.itemsize, places.data_ptr()
+        else:
+            places = np.ascontiguousarray(places, dtype=PLACE_DTYPE)
+            n, ptr = len(places), places.ctypes.data
+        self._places_keep = places
+        self._check(lib().aloam_places_load(self.h, C.c_void_p(ptr) if n else None, n))
+        return first
+
+    def places_clear(self):
+        self._check(lib().aloam_places_clear(self.h))
+
+    def places_info(self):
+        v = np.zeros(4, np.int32)
+        self._check(lib().aloam_places_info(self.h, _p(v)))
+        return {"count": int(v[0]), "capacity": int(v[1]), "max_range": float(v[2:3].view(np.float32)[0]), "sensor_height": float(v[3:4].view(np.float32)[0])}
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

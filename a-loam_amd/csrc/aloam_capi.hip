@@ -81,7 +81,7 @@ int queue_reset(aloam_ctx* c, const int* seqs, int n) {
   if (c->map_on) { r.mapseq = c->d_mapseq.get(); r.cubes = c->d_cubes.get(); r.addcnt = c->d_addcnt.get(); r.live = c->d_map_live.get(); r.grid_sig = c->d_grid_sig.get(); }
   launch_reset_sequences(r, c->stream);
   HIP_TRY(c, hipGetLastError());
-  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); }
+  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); place_sweep_dropped(c, seqs[i]); }
   for (int i = 0; i < n; ++i) if (const int rc = mark_window_stale(c, seqs[i])) return rc;   // an attached slot keeps its attachment
   return ALOAM_OK;
 }
@@ -150,7 +150,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->in_consumed[k].h, hipEventDisableTiming));
   }
   c->B = cfg->batch; c->max_points = cfg->max_points; c->R = cfg->n_scans;
-  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0); c->scorable.assign(c->B, 0);
+  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0); c->scorable.assign(c->B, 0); c->pl_has_sweep.assign(c->B, 0); c->pl_desc_valid.assign(c->B, 0);
   c->map_err_seen.assign(c->B, 0);
   // The per-sequence stride of every [B][cap] buffer is kept OFF the powers of two (131 072 points x 16 B = 2 MiB apart, the workgroups of a launch - one
   // per sequence, all at about the same offset of their sequence - meet on the same memory channels): + 1/32 + 16 points.  Measured on k_build_grids_fused at

@@ -1,7 +1,8 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas).
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// capi_places.hip (place recognition).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,7 @@
 #include "export_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
+#include "places_kernels.hpp"
 #include "registration_kernels.hpp"
 #include "relocalize_kernels.hpp"
 
@@ -188,6 +190,16 @@ struct aloam_ctx {
   DevBuf<float4> d_at_points[2];
   long long at_info[12] = {0};                                      // what aloam_atlas_info returns
   long long spill_dropped_reported = 0;                             // dropped tiles aloam_synchronize has already returned
+  // place recognition (aloam_places_enable): one descriptor per sequence, one store per context
+  bool places_on = false;
+  int pl_capacity = 0, pl_count = 0;                                // entries the store holds / has; the count is host state (adds are stream-ordered)
+  float pl_max_range = 80.f, pl_height = 2.f;
+  std::vector<char> pl_has_sweep, pl_desc_valid;                    // [B] holds a registered sweep (since creation / reset / load); d_pl_desc[b] is that sweep's
+  DevBuf<PlaceDesc> d_pl_desc;                                      // [B]
+  DevBuf<aloam_place> d_pl_store;                                   // [capacity]
+  DevBuf<float> d_pl_unit; DevBuf<unsigned long long> d_pl_masks;   // [capacity][1200] unit-normalised columns, [capacity] non-zero columns
+  DevBuf<int> d_pl_seqs, d_pl_wanted, d_pl_lo, d_pl_hi;             // [B] each: listed ids, descriptors to make, the ranges of a match
+  DevBuf<int2> d_pl_pairs; long long pl_pairs_cap = 0;              // [n][longest range] per-entry results of a match
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -302,6 +314,9 @@ int spill_dropped_since(aloam_ctx* c, long long* fresh);
 int mark_window_stale(aloam_ctx* c, int seq);            // the map, frame or slot of `seq` was replaced: an attached sequence cuts its window anew
 int atlas_step_check(aloam_ctx* c);                      // ALOAM_E_STATE when an attached sequence that is active in this step is not frozen
 bool queue_atlas_window(aloam_ctx* c, const int* mask);  // k_atlas_window when an attached sequence takes part
+// capi_places.hip
+inline void place_sweep_registered(aloam_ctx* c, int seq) { c->pl_has_sweep[seq] = 1; c->pl_desc_valid[seq] = 0; }   // a new sweep: its descriptor is still to be made
+inline void place_sweep_dropped(aloam_ctx* c, int seq) { c->pl_has_sweep[seq] = 0; c->pl_desc_valid[seq] = 0; }       // reset or loaded: nothing to describe
 // capi_mapping.hip
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);
 // capi_records.hip

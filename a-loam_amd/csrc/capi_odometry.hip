@@ -71,6 +71,7 @@ int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, con
   { ProfScope p(c, K_FRONT); launch_front(a, c->stream); }
   { ProfScope p(c, K_RING_STARTS); launch_ring_starts(a, c->stream); }
   c->dense_valid = false;
+  for (int b = 0; b < c->B; ++b) if (c->all_active || c->active[b]) place_sweep_registered(c, b);
   if (slot >= 0) { HIP_TRY(c, hipEventRecord(c->in_consumed[slot], c->stream)); c->in_used[slot] = true; }   // the raw sweep is not read after this
   { ProfScope p(c, K_RING_FEATURES); launch_ring_features(a, c->npad, 0.2f, c->stream);     // leaf 0.2 (src/scanRegistration.cpp:404)
     if (c->sum_order) launch_less_flat_reference_order(reg_args(c, d_scans, seq_stride, stride_bytes), c->npad, 0.2f, c->stream); }

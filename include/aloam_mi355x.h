@@ -410,6 +410,73 @@ int aloam_atlas_load(aloam_ctx* ctx, const aloam_map_tile* tiles, long long n_ti
 int aloam_atlas_attach(aloam_ctx* ctx, const int* attached /* [batch], NULL = none */);
 int aloam_atlas_info(aloam_ctx* ctx, long long out[12]);
 
+/* ---- place recognition: scan-context descriptors and batched matching ------------------------------------------------------------
+ * Stands beside the reference, like the frozen map, the hypotheses and the atlas: A-LOAM has no place recognition.  A frozen step refines
+ * a guess that is about 1 m and 2.5 deg off, aloam_score_map_corrections searches a grid of a few metres around one; this section finds
+ * the guess with no prior at all.  The signature of a sweep is Scan Context (G. Kim, A. Kim, "Scan Context: Egocentric Spatial Descriptor
+ * for Place Recognition within 3D Point Cloud Map", IROS 2018): a polar grid of ALOAM_PLACE_RINGS x ALOAM_PLACE_SECTORS cells around the
+ * sensor, each the greatest height of its points.  A turn of the sensor about z is a cyclic shift of the sectors, so one match returns a
+ * stored place and a yaw.  Opt-in: a context that never calls aloam_places_enable launches exactly what it launched before.
+ *
+ * The descriptor is a function of the set of points of a sequence's ALOAM_CLOUD_FULL (the points scan registration keeps, in the
+ * sensor frame; their order plays no part), every operation a separately rounded f32 operation:
+ *     rho = sqrtf(x * x + y * y);  r = (int)(rho * (20.f / max_range));  points with r >= 20 are skipped
+ *     theta = atan2f(y, x) + (float)M_PI   (atan2f with glibc's bits);  s = min((int)(theta * (float)(60 / (2 pi))), 59)
+ *     D[r][s] = max over its points of max(z + sensor_height, 0);  empty cells are 0
+ * It is made from the ring slabs (the dense cloud is not assembled for it), at most once per registered sweep, by the first
+ * aloam_places_add / aloam_places_match that lists the sequence.
+ *
+ * aloam_places_enable: once per context; allocates the store (capacity in 1 .. 2^20 entries) and one descriptor per sequence.
+ * max_range > 0 and sensor_height finite (80 m and 2 m suit a car-mounted HDL-64), else ALOAM_E_ARG.  Contexts without
+ * ALOAM_STAGE_REGISTRATION: ALOAM_E_STATE, here and in every other call of this section.
+ *
+ * aloam_places_add: appends one entry per listed sequence (distinct, in range), in listed order and in stream order; no host
+ * synchronisation.  The store index of entry i is the count before the call + i, so the host knows it when the call returns.  The tag is
+ * read on the device at that point of the stream: map_q_w / map_t_w as aloam_export_poses would write them with mapping enabled, else
+ * q_w / t_w; frame = map_frames, or -1 without mapping; slot = the sequence; n_points = the points of the sweep.  A store that cannot take
+ * all n: ALOAM_E_CAPACITY, nothing is queued.
+ *
+ * Which sequences may be listed (add and match): those that have registered a sweep since the context was created or since the slot
+ * was last reset or loaded (a host flag, like the one of aloam_score_map_corrections); otherwise ALOAM_E_STATE and nothing is queued.  A
+ * sequence that sat out the last registration uses the sweep it still holds.
+ *
+ * aloam_places_match: for each listed sequence i (its descriptor Q) the T best entries of [ranges[2 i], ranges[2 i + 1]) go to
+ * dst[i * T ..], best first; entry = -1 (shift -1, distance 0) fills what the range does not provide.  For an entry C and a shift:
+ *     d(shift) = 1 - (1 / cnt) * sum over the columns j where C[:, j] and Q[:, (j - shift) mod 60] are both non-zero of their cosine
+ * cnt = the number of such columns (a shift with cnt = 0 is skipped; an entry with no valid shift is never returned).  The entry's distance
+ * is the minimum over the 60 shifts, ties to the lower shift; entries rank by (distance, index).  A match with shift s means: the sensor
+ * stands at the stored pose turned by +s * 6 deg about its own z.  1 <= T <= 8, 0 <= lo <= hi <= count at the time of the call: else
+ * ALOAM_E_ARG.  Stream-ordered, no host synchronisation (the first call, and one with more (sequence, entry) pairs than any before,
+ * allocates scratch); `ranges` is read during the call only; dst: device memory of the context's device or pinned host memory, classified
+ * like the destinations of aloam_export_clouds.  All 60 shifts of a query against a tile of entries are one 64 x 1200 x tile product
+ * of unit-normalised columns on the f32-input matrix cores, in a fixed K order: a (query, entry) result has the same bits whatever n, T,
+ * the range and the position in the list.
+ *
+ * aloam_places_export / aloam_places_load: entries [first, first + count) to dst (device or pinned), and count records appended from src
+ * (device, pinned, or pageable through one staged copy); both stream-ordered.  A load validates every record before anything changes
+ * (cells finite and non-negative, else ALOAM_E_ARG; records in device memory are read back once for that).  aloam_places_clear empties the
+ * store in stream order.  aloam_places_info: out = count, capacity, max_range bits, sensor_height bits (IEEE-754).
+ *
+ * The store is not part of a sequence record (ALOAM_SEQ_RECORD_VERSION, MapSeq and aloam_pose_record are unchanged);
+ * aloam_reset_sequences and aloam_load_sequences leave it alone. */
+enum { ALOAM_PLACE_RINGS = 20, ALOAM_PLACE_SECTORS = 60 };
+typedef struct aloam_place {                  /* 4880 bytes */
+  float cells[ALOAM_PLACE_SECTORS][ALOAM_PLACE_RINGS];   /* sector-major: a yaw shift is an offset */
+  double q[4], t[3];                          /* pose of the sensor when the place was stored */
+  int slot;                                   /* the sequence that stored it */
+  int frame;                                  /* its map_frames then; -1 without mapping */
+  int n_points;                               /* points of the sweep */
+  int pad[3];
+} aloam_place;
+typedef struct aloam_place_match { int entry, shift; float distance; int pad; } aloam_place_match;   /* 16 bytes */
+int aloam_places_enable(aloam_ctx* ctx, int capacity, float max_range, float sensor_height);
+int aloam_places_add(aloam_ctx* ctx, const int* seqs, int n);
+int aloam_places_match(aloam_ctx* ctx, const int* seqs, int n, const int* ranges /* [n][2] */, int T, aloam_place_match* dst /* [n][T] */);
+int aloam_places_export(aloam_ctx* ctx, int first, int count, aloam_place* dst);
+int aloam_places_load(aloam_ctx* ctx, const aloam_place* src, int count);
+int aloam_places_clear(aloam_ctx* ctx);
+int aloam_places_info(aloam_ctx* ctx, int out[4]);
+
 /* ---- sequence records: save and restore whole sequences, in batched stream-ordered calls ------------------------------
  * A sequence record is everything that makes up a sequence between two frames - odometry pose and statistics, systemInited, the last
  * clouds (laserCloudCornerLast / SurfLast, src/laserOdometry.cpp:554-563), and with mapping the map pose, window centre, frame count,

@@ -19,6 +19,10 @@ that map, which it leaves unchanged.  The file is a map, not a sequence record: 
 `--save-map` holds the final 21 x 21 x 11 window only; `--mapping --save-atlas a.npz` also keeps every cube that left the window on the way
 (aloam_map_spill_enable, drained with aloam_export_map_spill after every step) and writes the whole map as tiles (a-loam_amd/atlas.py);
 `--prior-atlas a.npz` localizes in such a map of any extent (aloam_atlas_load, aloam_atlas_attach), with --initial-pose / --relocalize as above.
+`--save-atlas` also stores a place - the scan-context descriptor of the sweep with its mapped pose, aloam_places_add - every --place-spacing
+metres of travel, in the same file; `--prior-atlas a.npz --global-relocalize` then needs no --initial-pose: the first sweep is matched
+against the stored places (aloam_places_match), the pose and yaw of the best one become the first guess (a-loam_amd/places.py
+guess_from_match), one frozen step is taken from it, relocalize() searches its default grid around it, and the run continues.
 
 `--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
 context runs one sequence; when it ends, the slot is reset in place (aloam_reset_sequences) and takes the next one, and slots with nothing
@@ -137,6 +141,7 @@ def write_selftest(folder, seq="00", frames=6, seed=77):
         s.numpy().astype(np.float32).tofile(os.path.join(folder, "velodyne", "sequences", seq, "velodyne", f"{k:06d}.bin"))
 
 
+PLACE_CAPACITY = 16384                                # --save-atlas: places of one run (about 10 KB of device memory each; 49 km at the default spacing)
 SPILL_TILES, SPILL_POINTS = 2048, 1 << 20              # --save-atlas: room per class for what one step's shift empties (it is drained after every step)
 
 
@@ -187,6 +192,21 @@ def load_prior_atlas(gpu, path, initial_pose=None):
     return q, t
 
 
+def global_guess(gpu, stored):
+    """The first guess of --global-relocalize, with no prior: sequence 0's sweep (registered, odometry step taken) matched against the
+    stored places; the best one's pose and yaw as the map <- odometry correction, installed for the first frozen step."""
+    places = importlib.import_module("a-loam_amd.places")
+    m = gpu.places_match([0])[0, 0]
+    if m["entry"] < 0:
+        sys.exit("--global-relocalize: no stored place matches the first sweep (an empty sweep, or an atlas without places)")
+    odom = gpu.pose(0)
+    q, t = places.guess_from_match(stored["q"][m["entry"]], stored["t"][m["entry"]], int(m["shift"]), odom["q_w"], odom["t_w"])
+    gpu.set_map_frame((10, 10, 5), q, t, 0, seq=0)
+    print(f"matched place {int(m['entry'])} of {len(stored)} (frame {int(stored['frame'][m['entry']])}), shift {int(m['shift'])} "
+          f"({int(m['shift']) * places.SECTOR_DEG:.0f} deg), distance {float(m['distance']):.3f}")
+    return q, t
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", help="dataset_folder of kitti_helper.launch")
@@ -212,7 +232,15 @@ def main():
                                                                                                   "correction (metres, radians); default identity")
     ap.add_argument("--relocalize", nargs=2, type=float, metavar=("RADIUS_M", "YAW_DEG"), help="with --prior-map: after the first frozen step, score a grid of "
                     "corrections of this half-width (0.5 m, 2.5 deg cells) around the first guess on the device, install the best, continue")
+    ap.add_argument("--place-spacing", type=float, default=3.0, metavar="METRES", help="with --save-atlas: also store a place (scan-context descriptor + mapped "
+                    "pose) every this many metres of travel, in the same file; 0 stores none")
+    ap.add_argument("--global-relocalize", action="store_true", help="with --prior-atlas, instead of --initial-pose: match the first sweep against the places "
+                    "stored in the atlas file, start from the best one's pose and yaw, then search relocalize()'s default grid around it")
     args = ap.parse_args()
+    if args.global_relocalize and not args.prior_atlas:
+        ap.error("--global-relocalize needs --prior-atlas")
+    if args.global_relocalize and (args.initial_pose or args.relocalize):
+        ap.error("--global-relocalize replaces --initial-pose and --relocalize")
     if args.prior_atlas and args.prior_map:
         ap.error("--prior-atlas and --prior-map exclude each other")
     prior_atlas = args.prior_atlas
@@ -260,6 +288,16 @@ def main():
         gpu.map_spill_enable(SPILL_TILES, SPILL_POINTS)
         spill = {"tiles": torch.zeros(2 * SPILL_TILES * 32, dtype=torch.uint8, pin_memory=True), "points": torch.zeros((2 * SPILL_POINTS, 4), dtype=torch.float32, pin_memory=True),
                  "off": torch.zeros(4, dtype=torch.int64, pin_memory=True), "log": atlas.TileLog()}
+        if args.place_spacing > 0:
+            gpu.places_enable(PLACE_CAPACITY)
+    last_place = None                                  # --save-atlas: mapped position of the last stored place
+    stored = None                                      # --global-relocalize: the places of the atlas file
+    if args.global_relocalize:
+        stored = importlib.import_module("a-loam_amd.atlas").load_atlas_places(prior_atlas)
+        if not len(stored):
+            sys.exit(f"--global-relocalize: {prior_atlas} holds no places (written without --place-spacing?)")
+        gpu.places_enable(len(stored))
+        gpu.places_load(stored)
     factors = []                                       # --prior-map: last-iteration factors of every sweep (aloam_get_map_info), the fit to the map
     idle = np.zeros((0, 4), np.float32)
     lengths = [len(ts) for ts in times]
@@ -283,13 +321,16 @@ def main():
             scans[slot] = read_lidar(os.path.join(args.dataset, "velodyne", "sequences", seqs[i], "velodyne", f"{k:06d}.bin"))
         gpu.scan_register(scans)
         gpu.odometry_step()
+        if stored is not None and guess is not None:   # the first sweep: its best stored place is the first guess
+            guess = global_guess(gpu, stored)
         if args.mapping:
             gpu.mapping_step()
         if spill:                                      # stream-ordered, no synchronise of its own: read after the step's synchronize() below
             gpu.export_map_spill_into([0], spill["tiles"].data_ptr(), 2 * SPILL_TILES, spill["points"].data_ptr(), 2 * SPILL_POINTS, spill["off"].data_ptr(), clear=True)
-        if args.relocalize and guess is not None:      # the first frozen step has left its stacks and submap grid: search around the first guess
+        if (args.relocalize or stored is not None) and guess is not None:   # the first frozen step has left its stacks and submap grid: search around the first guess
             relocalize = importlib.import_module("a-loam_amd.relocalize")
-            found = relocalize.relocalize(gpu, [0], radius_m=args.relocalize[0], step_m=0.5, yaw_deg=args.relocalize[1], yaw_step_deg=2.5, guesses={0: guess})[0]
+            grid = dict(radius_m=args.relocalize[0], step_m=0.5, yaw_deg=args.relocalize[1], yaw_step_deg=2.5) if args.relocalize else {}
+            found = relocalize.relocalize(gpu, [0], guesses={0: guess}, **grid)[0]
             b, node = found["scores"][found["best"]], found["nodes"][found["best"]]
             print(f"{seqs[0]} relocalized: {len(found['nodes'])} corrections scored, best node ({node[0]:+.1f} m, {node[1]:+.1f} m, {node[2]:+.1f} deg) "
                   f"with {int(b['corner_factors']) + int(b['surf_factors'])} factors")
@@ -310,6 +351,11 @@ def main():
         if spill and int(spill["off"][1]):             # (the rows hold at most what the destinations hold: a drain is always written)
             nt, npts = int(spill["off"][1]), int(spill["off"][3])
             spill["log"].add(spill["tiles"].numpy()[:nt * 32].view(atlas.TILE_DTYPE), spill["points"].numpy()[:npts])
+        if spill and args.place_spacing > 0 and gpu.places_info()["count"] < PLACE_CAPACITY:
+            here = np.array(recs[0].map_t_w)
+            if last_place is None or np.linalg.norm(here - last_place) >= args.place_spacing:
+                gpu.places_add([0])                    # the sweep just mapped, with the pose the step has given it
+                last_place = here
         if args.prior_map:
             info = gpu.map_info(0)
             factors.append(info["corner_num1"] + info["surf_num1"])
@@ -317,8 +363,9 @@ def main():
         save_map(gpu, args.save_map)
     if args.save_atlas:
         tiles, points = spill["log"].result(atlas.window_tiles(gpu, 0))
-        atlas.save_atlas(args.save_atlas, tiles, points)
-        print(f"{seqs[0]} atlas: {len(tiles)} tiles, {len(points)} points ({sum(len(t) for t, _ in spill['log'].parts)} tiles left the window on the way)")
+        stored_now = gpu.places_export() if args.place_spacing > 0 else None
+        atlas.save_atlas(args.save_atlas, tiles, points, places=stored_now)
+        print(f"{seqs[0]} atlas: {len(tiles)} tiles, {len(points)} points, {0 if stored_now is None else len(stored_now)} places ({sum(len(t) for t, _ in spill['log'].parts)} tiles left the window on the way)")
     gpu.close()
     mapped_name = "localized" if args.prior_map else "mapped"
     if factors:
