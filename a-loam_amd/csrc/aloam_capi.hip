@@ -75,13 +75,13 @@ int queue_reset(aloam_ctx* c, const int* seqs, int n) {
   r.seqs = c->d_reset_ids.get(); r.n = n; r.R = c->R;
   r.meta = c->d_meta.get(); r.ringstart = c->d_ringstart.get(); r.state = c->d_state.get();
   r.edges = c->d_edges.get(); r.planes = c->d_planes.get();
-  for (int k = 0; k < 2; ++k) r.grid_flags[k] = c->d_grid_flags[k].get();
+  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2; ++k) r.grid_flags[p][k] = c->d_grid_flags[p][k].get();
   for (int k = 0; k < 2; ++k) { r.less_sharp[k] = c->d_less_sharp[k].get(); r.less_flat[k] = c->d_less_flat[k].get(); }
   r.cap = c->cap;
   if (c->map_on) { r.mapseq = c->d_mapseq.get(); r.cubes = c->d_cubes.get(); r.addcnt = c->d_addcnt.get(); r.live = c->d_map_live.get(); r.grid_sig = c->d_grid_sig.get(); }
   launch_reset_sequences(r, c->stream);
   HIP_TRY(c, hipGetLastError());
-  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); place_sweep_dropped(c, seqs[i]); }
+  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->grid_built[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); place_sweep_dropped(c, seqs[i]); }
   for (int i = 0; i < n; ++i) if (const int rc = mark_window_stale(c, seqs[i])) return rc;   // an attached slot keeps its attachment
   return ALOAM_OK;
 }
@@ -150,13 +150,16 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->in_consumed[k].h, hipEventDisableTiming));
   }
   c->B = cfg->batch; c->max_points = cfg->max_points; c->R = cfg->n_scans;
-  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0); c->scorable.assign(c->B, 0); c->pl_has_sweep.assign(c->B, 0); c->pl_desc_valid.assign(c->B, 0);
+  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0); c->scorable.assign(c->B, 0); c->grid_built.assign(c->B, 0); c->pl_has_sweep.assign(c->B, 0); c->pl_desc_valid.assign(c->B, 0);
   c->map_err_seen.assign(c->B, 0);
   // The per-sequence stride of every [B][cap] buffer is kept OFF the powers of two (131 072 points x 16 B = 2 MiB apart, the workgroups of a launch - one
   // per sequence, all at about the same offset of their sequence - meet on the same memory channels): + 1/32 + 16 points.  Measured on k_build_grids_fused at
   // batch 1024, one box: 1.62 - 1.65 ms at the power-of-two stride, 1.48 - 1.52 ms with 1040 / 4112 / 16 400 points of padding.
   c->cap = cfg->max_points + (((cfg->max_points / 32 + 15) & ~15) + 16);
   { const char* e = std::getenv("ALOAM_GRAPH_MAX_BATCH"); c->use_graph = c->B <= (e ? std::atoi(e) : 0); }   // off unless asked for: measured no gain (below)
+  // The next step's search grids are built beside the association and the solve (aloam_odometry_step) unless ALOAM_GRID_OVERLAP=0 asks for the serial
+  // build at the start of every step; a captured step stays a single chain, and a step that waits after every stage has nothing to run beside.
+  { const char* e = std::getenv("ALOAM_GRID_OVERLAP"); c->grid_overlap = !(e && e[0] == '0') && !c->use_graph && !c->debug_sync; }
   c->NB = (c->cap + kBlockPts - 1) / kBlockPts;
   c->npad = cfg->max_ring_points <= 2059 ? 2048 : 4096;
   const size_t B = c->B, cap = c->cap, R = c->R, NB = c->NB;
@@ -197,16 +200,21 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     if ((rc = dmalloc(c, c->d_less_flat[k], B * cap))) return rc;
   }
   if (odo) {
-    for (int k = 0; k < 2; ++k) {
+    for (int p = 0; p < 2; ++p) for (int k = 0; k < 2; ++k) {       // one set of grids per cloud buffer
       const size_t per = k == 0 ? R * kLessSharpPerRing : cap;
-      if ((rc = dmalloc(c, c->d_grid_sorted3[k], B * per))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_sorted2[k], B * per))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_start3[k], B * (c->grid_H[k] + 1)))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_start2[k], B * (c->grid_H[k] + 1)))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_sorted3c[k], B * per))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_start3c[k], B * (c->grid_H[k] + 1)))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_flags[k], B * 4))) return rc;
-      if ((rc = dmalloc(c, c->d_grid_walk[k], B * 2 * (R + 8)))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_sorted3[p][k], B * per))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_sorted2[p][k], B * per))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_start3[p][k], B * (c->grid_H[k] + 1)))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_start2[p][k], B * (c->grid_H[k] + 1)))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_sorted3c[p][k], B * per))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_start3c[p][k], B * (c->grid_H[k] + 1)))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_flags[p][k], B * 4))) return rc;
+      if ((rc = dmalloc(c, c->d_grid_walk[p][k], B * 2 * (R + 8)))) return rc;
+    }
+    if (c->grid_overlap) {
+      HIP_TRY(c, hipStreamCreateWithFlags(&c->grid_stream.h, hipStreamNonBlocking));
+      HIP_TRY(c, hipEventCreateWithFlags(&c->grid_fork.h, hipEventDisableTiming));
+      HIP_TRY(c, hipEventCreateWithFlags(&c->grids_done.h, hipEventDisableTiming));
     }
     if ((rc = dmalloc(c, c->d_edges, B * R * kSharpPerRing))) return rc;
     if ((rc = dmalloc(c, c->d_planes, B * R * kFlatPerRing))) return rc;
@@ -228,6 +236,7 @@ void aloam_destroy(aloam_ctx* c) {
   if (!c) return;
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->grid_stream) (void)hipStreamSynchronize(c->grid_stream);
   prof_resolve(c);
   delete c;                                       // the owners release buffers, then graphs, events and streams, on this device
 }

@@ -99,17 +99,19 @@ struct OdomArgs {
   const float4* less_sharp[2];   // [B][R*kLessSharpPerRing]  a sequence's last clouds are in [1 - SeqMeta::parity]
   const float4* less_flat[2];    // [B][cap]
   const int* active;         // [B] SeqBits of this step (kSeqSolve: the sequences that solve), nullptr = all sequences
-  // spatial hash grids over the last clouds (k_build_grids): index 0 = corner_last, 1 = surf_last
-  float4* grid_sorted3[2];   // [B][R*kLessSharpPerRing] / [B][cap]   entries bucketed by (ix,iy,iz)
-  float4* grid_sorted2[2];   //                          entries bucketed by (ix,iy,ring key)
-  int* grid_start3[2];       // [B][H+1]
-  int* grid_start2[2];       // [B][H+1]
-  float4* grid_sorted3c[2];  // coarse levels of the same two grids: they bound the search of far queries
-  int* grid_start3c[2];      // [B][H+1]
-  int* grid_flags[2];        // [B][4]   flags[0] != 0: keys / coordinates out of range -> literal brute-force path; flags[1]: 0 = ring-sorted, 1 = NEARLY ring-sorted
-                             //          (no key more than 2 below an earlier one: the reference's walks still visit one index range, grid_walk holds its ends),
-                             //          2 = not sorted -> literal walks; flags[2] != 0: the coarse level holds 16-bit positions into the fine copy (k_build_grids_fused)
-  int* grid_walk[2];         // [B][2][R + 8]   per ring key k: first index with key >= k, last index with key <= k (written for nearly-sorted clouds only)
+  // spatial hash grids over the double-buffered clouds (k_build_grids), [set][class]: grid set p of a sequence describes its cloud buffer p (the
+  // search reads set 1 - SeqMeta::parity, the grids of the last clouds, while the build of the sweep just registered may fill set parity beside it);
+  // class 0 = corner, 1 = surf
+  float4* grid_sorted3[2][2];   // [B][R*kLessSharpPerRing] / [B][cap]   entries bucketed by (ix,iy,iz)
+  float4* grid_sorted2[2][2];   //                          entries bucketed by (ix,iy,ring key)
+  int* grid_start3[2][2];       // [B][H+1]
+  int* grid_start2[2][2];       // [B][H+1]
+  float4* grid_sorted3c[2][2];  // coarse levels of the same two grids: they bound the search of far queries
+  int* grid_start3c[2][2];      // [B][H+1]
+  int* grid_flags[2][2];        // [B][4]   flags[0] != 0: keys / coordinates out of range -> literal brute-force path; flags[1]: 0 = ring-sorted, 1 = NEARLY ring-sorted
+                                //          (no key more than 2 below an earlier one: the reference's walks still visit one index range, grid_walk holds its ends),
+                                //          2 = not sorted -> literal walks; flags[2] != 0: the coarse level holds 16-bit positions into the fine copy (k_build_grids_fused)
+  int* grid_walk[2][2];         // [B][2][R + 8]   per ring key k: first index with key >= k, last index with key <= k (written for nearly-sorted clouds only)
   int grid_H_corner, grid_H_surf;   // buckets (power of two, multiple of 1024)
   float4* sel_sharp;         // [B][R*kSharpPerRing]  features moved to the start of the sweep with the current pose (k_transform_queries)
   float4* sel_flat;          // [B][R*kFlatPerRing]
@@ -133,18 +135,24 @@ struct GridView {
   float4 *sorted3, *sorted2, *sorted3c;
   int *start3, *start2, *start3c, *flags, *walk;
 };
-__device__ __forceinline__ GridView grid_view(const OdomArgs& a, int b, int which) {
+// One of the four [set][class] pointers of a grid array, by selects (see row_of).
+template <typename T>
+__device__ __forceinline__ T* grid_ptr(T* const (&buf)[2][2], int set, int which) {
+  return set ? (which ? buf[1][1] : buf[1][0]) : (which ? buf[0][1] : buf[0][0]);
+}
+// The grids of class `which` over cloud buffer `set` of sequence b.
+__device__ __forceinline__ GridView grid_view(const OdomArgs& a, int b, int which, int set) {
   GridView g;
   g.H = which == 0 ? a.grid_H_corner : a.grid_H_surf;
   const long long per = which == 0 ? (long long)a.R * kLessSharpPerRing : (long long)a.cap;
-  g.sorted3 = a.grid_sorted3[which] + b * per;
-  g.sorted2 = a.grid_sorted2[which] + b * per;
-  g.start3 = a.grid_start3[which] + (long long)b * (g.H + 1);
-  g.start2 = a.grid_start2[which] + (long long)b * (g.H + 1);
-  g.sorted3c = a.grid_sorted3c[which] + b * per;
-  g.start3c = a.grid_start3c[which] + (long long)b * (g.H + 1);
-  g.flags = a.grid_flags[which] + b * 4;
-  g.walk = a.grid_walk[which] + (long long)b * 2 * (a.R + 8);
+  g.sorted3 = grid_ptr(a.grid_sorted3, set, which) + b * per;
+  g.sorted2 = grid_ptr(a.grid_sorted2, set, which) + b * per;
+  g.start3 = grid_ptr(a.grid_start3, set, which) + (long long)b * (g.H + 1);
+  g.start2 = grid_ptr(a.grid_start2, set, which) + (long long)b * (g.H + 1);
+  g.sorted3c = grid_ptr(a.grid_sorted3c, set, which) + b * per;
+  g.start3c = grid_ptr(a.grid_start3c, set, which) + (long long)b * (g.H + 1);
+  g.flags = grid_ptr(a.grid_flags, set, which) + b * 4;
+  g.walk = grid_ptr(a.grid_walk, set, which) + (long long)b * 2 * (a.R + 8);
   return g;
 }
 

@@ -80,7 +80,9 @@ struct MapPool {
 struct aloam_ctx {
   // Streams and events first: members are destroyed in reverse order, so every buffer is released before them.
   Stream stream, copy_stream;
+  Stream grid_stream;                // the build of the next step's search grids runs here, beside the association and the solve (aloam_odometry_step)
   Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
+  Event grid_fork, grids_done;       // main stream -> grid stream at the start of a step, grid stream -> main stream before k_advance
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
   // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
   // solves (no mask), [1] through the staged mask d_mask_odo
@@ -121,12 +123,16 @@ struct aloam_ctx {
   DevBuf<float4> d_sharp, d_flat;
   DevBuf<float4> d_less_sharp[2], d_less_flat[2];   // a sequence's CURRENT sweep is in [parity[b]], its last clouds in [1 - parity[b]]
   DevBuf<OdomState> d_state;
-  DevBuf<float4> d_grid_sorted3[2], d_grid_sorted2[2];
-  DevBuf<int> d_grid_start3[2], d_grid_start2[2];
-  DevBuf<float4> d_grid_sorted3c[2];   // coarse level of the 3-D grid
-  DevBuf<int> d_grid_start3c[2];
-  DevBuf<int> d_grid_flags[2], d_grid_walk[2];
+  // search grids, [set][class]: set p of a sequence describes its cloud buffer p (OdomArgs)
+  DevBuf<float4> d_grid_sorted3[2][2], d_grid_sorted2[2][2];
+  DevBuf<int> d_grid_start3[2][2], d_grid_start2[2][2];
+  DevBuf<float4> d_grid_sorted3c[2][2];   // coarse level of the 3-D grid
+  DevBuf<int> d_grid_start3c[2][2];
+  DevBuf<int> d_grid_flags[2][2], d_grid_walk[2][2];
   int grid_H[2] = {4096, 16384};
+  bool grid_overlap = false;         // environment ALOAM_GRID_OVERLAP (default on), read once at creation; off with use_graph / debug_sync
+  std::vector<char> grid_built;      // [B] the grid set of the sequence's LAST clouds holds their grids: set by the step that made them the last ones
+                                     // (it built them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
   DevBuf<EdgeRec> d_edges; DevBuf<PlaneRec> d_planes;
   DevBuf<float4> d_sel_sharp, d_sel_flat;
   // scan-to-map refinement (allocated by aloam_mapping_enable)
@@ -233,14 +239,15 @@ int dmalloc(aloam_ctx* c, DevBuf<T>& p, size_t count) {
 
 hipEvent_t prof_event(aloam_ctx* c);
 struct ProfScope {
-  aloam_ctx* c; int k; hipEvent_t e0 = nullptr;
-  ProfScope(aloam_ctx* c_, int k_) : c(c_), k(k_) {
-    if (c->prof_on) { e0 = prof_event(c); (void)hipEventRecord(e0, c->stream); }
+  aloam_ctx* c; int k; hipStream_t s; hipEvent_t e0 = nullptr;
+  // `on`: the stream the scope's launches go to (default: the context's; the grid stream records intervals that overlap the main stream's)
+  ProfScope(aloam_ctx* c_, int k_, hipStream_t on = nullptr) : c(c_), k(k_), s(on ? on : (hipStream_t)c_->stream) {
+    if (c->prof_on) { e0 = prof_event(c); (void)hipEventRecord(e0, s); }
   }
   ~ProfScope() {
-    if (c->prof_on) { hipEvent_t e1 = prof_event(c); (void)hipEventRecord(e1, c->stream); c->prof_pending.push_back({k, e0, e1}); }
+    if (c->prof_on) { hipEvent_t e1 = prof_event(c); (void)hipEventRecord(e1, s); c->prof_pending.push_back({k, e0, e1}); }
     if (c->debug_sync) {   // ALOAM_DEBUG_SYNC=1: wait after every stage and name it, so that a device fault can be pinned on a kernel
-      const hipError_t e = hipStreamSynchronize(c->stream);
+      const hipError_t e = hipStreamSynchronize(s);
       std::fprintf(stderr, "[aloam] %-22s %s\n", kKernelNames[k], e == hipSuccess ? "ok" : hipGetErrorString(e));
     }
   }

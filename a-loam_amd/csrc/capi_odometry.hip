@@ -27,11 +27,11 @@ OdomArgs odom_args(aloam_ctx* c) {
   a.meta = c->d_meta.get(); a.state = c->d_state.get();
   a.sharp = c->d_sharp.get(); a.flat = c->d_flat.get();
   for (int k = 0; k < 2; ++k) { a.less_sharp[k] = c->d_less_sharp[k].get(); a.less_flat[k] = c->d_less_flat[k].get(); }
-  for (int k = 0; k < 2; ++k) {
-    a.grid_sorted3[k] = c->d_grid_sorted3[k].get(); a.grid_sorted2[k] = c->d_grid_sorted2[k].get(); a.grid_start3[k] = c->d_grid_start3[k].get();
-    a.grid_sorted3c[k] = c->d_grid_sorted3c[k].get(); a.grid_start3c[k] = c->d_grid_start3c[k].get();
-    a.grid_start2[k] = c->d_grid_start2[k].get();
-    a.grid_flags[k] = c->d_grid_flags[k].get(); a.grid_walk[k] = c->d_grid_walk[k].get();
+  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2; ++k) {
+    a.grid_sorted3[p][k] = c->d_grid_sorted3[p][k].get(); a.grid_sorted2[p][k] = c->d_grid_sorted2[p][k].get(); a.grid_start3[p][k] = c->d_grid_start3[p][k].get();
+    a.grid_sorted3c[p][k] = c->d_grid_sorted3c[p][k].get(); a.grid_start3c[p][k] = c->d_grid_start3c[p][k].get();
+    a.grid_start2[p][k] = c->d_grid_start2[p][k].get();
+    a.grid_flags[p][k] = c->d_grid_flags[p][k].get(); a.grid_walk[p][k] = c->d_grid_walk[p][k].get();
   }
   a.grid_H_corner = c->grid_H[0]; a.grid_H_surf = c->grid_H[1];
   a.edges = c->d_edges.get(); a.planes = c->d_planes.get();
@@ -243,11 +243,32 @@ int aloam_odometry_step(aloam_ctx* c) {
     if (const int rc = stage_ints(c, bits.data(), c->B, c->d_mask_odo.get())) return rc;
     mask = c->d_mask_odo.get();
   }
+  // The kd-tree stand-in of a step (launch_build_grids) covers clouds that were complete before the step began, so it need not wait for the step
+  // that searches it.  With grid_overlap every step builds, on the grid stream and beside its own association and solve, the grids of the sweep it
+  // is about to make the last one (the "next" form, into the grid set of that cloud buffer); the step after it finds them built (grid_built) and
+  // starts with the association.  The build is forked from and joined into the main stream inside this call, in front of k_advance, so nothing
+  // else has to know about the grid stream.  A solving sequence whose last clouds came from somewhere else (aloam_set_last, a loaded record)
+  // sends the step through the serial "last" build first, which is also the whole schedule without grid_overlap.
+  const bool overlap = c->grid_overlap;
+  bool build_last = !overlap;
+  if (overlap) for (int b = 0; b < c->B; ++b) build_last |= (bits[b] & kSeqSolve) && !c->grid_built[b];
+  hipError_t join_err = hipSuccess;
+  const int cus = c->gather_blocks / 8;                                           // (aloam_create: eight gather workgroups per CU)
   auto launch_all = [&]() {
     OdomArgs a = odom_args(c);
     a.active = mask;
-    { ProfScope p(c, K_BUILD_GRIDS); launch_build_grids(a, c->stream); }          // kd-tree stand-in over the last clouds
-    for (int outer = 0; outer < c->cfg.outer_iterations; ++outer) {
+    if (overlap) {
+      hipError_t e = hipEventRecord(c->grid_fork, c->stream);                     // everything registered so far, and the staged mask, are in front of it
+      if (e == hipSuccess) e = hipStreamWaitEvent(c->grid_stream, c->grid_fork, 0);
+      { ProfScope p(c, K_BUILD_GRIDS, c->grid_stream); launch_build_grids(a, true, cus, c->grid_stream); }
+      if (e == hipSuccess) e = hipEventRecord(c->grids_done, c->grid_stream);
+      join_err = e;
+    }
+    if (any_solve && build_last) {
+      if (overlap) launch_build_grids(a, false, cus, c->stream);                       // (K_BUILD_GRIDS stays the one launch per step on the grid stream)
+      else { ProfScope p(c, K_BUILD_GRIDS); launch_build_grids(a, false, cus, c->stream); }   // kd-tree stand-in over the last clouds
+    }
+    for (int outer = 0; any_solve && outer < c->cfg.outer_iterations; ++outer) {  // (a first frame of every active sequence: no solve, src/laserOdometry.cpp:267-271)
       a.outer = outer;
       a.last_outer = outer == c->cfg.outer_iterations - 1;
       { ProfScope p(c, K_TRANSFORM); launch_transform_queries(a, c->stream); }    // TransformToStart of the features (:300, :388)
@@ -255,13 +276,11 @@ int aloam_odometry_step(aloam_ctx* c) {
       { ProfScope p(c, K_ASSOC_PLANE); launch_associate(a, true, c->stream); }
       { ProfScope p(c, K_SOLVE); launch_solve(a, c->stream); }
     }
+    if (overlap && join_err == hipSuccess) join_err = hipStreamWaitEvent(c->stream, c->grids_done, 0);
     { ProfScope p(c, K_ADVANCE); launch_advance(a, c->stream); }   // swap (src/laserOdometry.cpp:554-563)
   };
   if (!any_solve) {
-    // first frame of every active sequence: no solve (src/laserOdometry.cpp:267-271)
-    OdomArgs a = odom_args(c);
-    a.active = mask;
-    { ProfScope p(c, K_ADVANCE); launch_advance(a, c->stream); }
+    launch_all();
   } else if (c->use_graph && !c->prof_on && !c->debug_sync) {
     // The kernel arguments of a step are the same every step (the buffer parity is per sequence, on the device; the mask is staged into the
     // same buffer), so the step is captured once per mask mode and replayed: one launch instead of ~15.  Measured at batch 1 (bench.py latency leg):
@@ -290,8 +309,9 @@ int aloam_odometry_step(aloam_ctx* c) {
   } else {
     launch_all();
   }
+  HIP_TRY(c, join_err);
   HIP_TRY(c, hipGetLastError());
-  for (int b = 0; b < c->B; ++b) if (bits[b] & kSeqActive) { c->parity[b] ^= 1; c->inited[b] = 1; c->needs_odom[b] = 0; }
+  for (int b = 0; b < c->B; ++b) if (bits[b] & kSeqActive) { c->parity[b] ^= 1; c->inited[b] = 1; c->needs_odom[b] = 0; c->grid_built[b] = overlap; }
   c->reg_pending = false;
   return ALOAM_OK;
 }
@@ -373,6 +393,7 @@ int aloam_set_last(aloam_ctx* c, int seq, const float* corner_last, int n_corner
   for (auto& x : in) if (!cloud_row(c, x.s, seq)) { c->err = "this context has no buffers for the last clouds (created for the registration stage only)"; return ALOAM_E_STATE; }
   c->inject_max = std::max(c->inject_max, std::max(n_corner, n_surf));   // what the next mapping step may add (never lowers the bound)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->grid_built[seq] = 0;                                                // other last clouds: the next step builds their grids before it searches
   for (auto& x : in) if (x.n) HIP_TRY(c, hipMemcpy(cloud_row(c, x.s, seq), x.pts, sizeof(float4) * x.n, hipMemcpyHostToDevice));
   return edit_seq(c, c->d_meta.get() + seq, [&](SeqMeta& m) { m.n_corner_last = n_corner; m.n_surf_last = n_surf; });
 }
@@ -449,17 +470,19 @@ int aloam_get_labels(aloam_ctx* c, int seq, int* out, int cap) {
   return m.n_cloud;
 }
 
-// Which association kernels own the sequence's last clouds (k_build_grids_fused): per cloud 0 = ring-sorted keys (pair kernel), 1 = nearly
+// Which association kernels owned the clouds the sequence's last step searched (k_build_grids_fused): per cloud 0 = ring-sorted keys (pair kernel), 1 = nearly
 // ring-sorted (pair kernel with the index-range walk window), 2 = not sorted (literal walks), -1 = keys / coordinates out of range (literal search).
 int aloam_get_last_cloud_order(aloam_ctx* c, int seq, int out[2]) {
   DeviceScope device_scope(c);
   int rc = check_seq(c, seq);
   if (rc) return rc;
-  if (!c->d_grid_flags[0]) { c->err = "this context has no odometry stage"; return ALOAM_E_STATE; }
+  if (!c->d_grid_flags[0][0]) { c->err = "this context has no odometry stage"; return ALOAM_E_STATE; }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // The step searched the grids of cloud buffer 1 - parity and flipped the parity afterwards: that set is the one of the buffer `parity` names now.
+  const int set = c->parity[seq];
   for (int k = 0; k < 2; ++k) {
     int f[4];
-    HIP_TRY(c, hipMemcpy(f, c->d_grid_flags[k].get() + (size_t)seq * 4, sizeof(f), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(f, c->d_grid_flags[set][k].get() + (size_t)seq * 4, sizeof(f), hipMemcpyDeviceToHost));
     out[k] = f[0] ? -1 : f[1];
   }
   return ALOAM_OK;

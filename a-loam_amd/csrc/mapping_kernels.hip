@@ -1521,7 +1521,7 @@ __global__ __launch_bounds__(256) void k_reset_sequences(ResetArgs r) {
   if (r.edges) {
     for (int i = tid; i < r.R * kSharpPerRing; i += 256) r.edges[(long long)b * r.R * kSharpPerRing + i] = EdgeRec{};
     for (int i = tid; i < r.R * kFlatPerRing; i += 256) r.planes[(long long)b * r.R * kFlatPerRing + i] = PlaneRec{};
-    if (tid < 8) r.grid_flags[tid >> 2][b * 4 + (tid & 3)] = 0;
+    if (tid < 16) r.grid_flags[tid >> 3][(tid >> 2) & 1][b * 4 + (tid & 3)] = 0;
   }
   if (r.mapseq) {
     for (int i = tid; i < 2 * kMapCubes; i += 256) {

@@ -141,7 +141,7 @@ struct ResetArgs {
   SeqMeta* meta; int* ringstart; // [B], [B][R+1]
   OdomState* state;              // [B]
   EdgeRec* edges; PlaneRec* planes;   // [B][R*kSharpPerRing], [B][R*kFlatPerRing]
-  int* grid_flags[2];            // [B][4]
+  int* grid_flags[2][2];         // [set][class][B][4]
   float4* less_sharp[2]; float4* less_flat[2]; int cap;   // the double-buffered clouds, [B][R*kLessSharpPerRing] / [B][cap]: zeros, as in a new
                                                           // context (the getters read them past the swap, and past what a sweep wrote)
   MapSeq* mapseq; CubeDesc* cubes; int* addcnt; int* live;   // [B], [B][2][kMapCubes] x 2, [B][2]

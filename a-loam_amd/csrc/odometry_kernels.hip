@@ -204,14 +204,30 @@ __device__ __forceinline__ void walk_tables(const float4* __restrict__ pts, int 
 }
 __host__ __device__ __forceinline__ bool fused_takes(int n, int H) { return n <= kFusedMaxN && H <= kFusedMaxH; }
 
-__global__ __launch_bounds__(1024) void k_build_grids_fused(OdomArgs a) {
+// Which clouds a build covers.  The "last" form is the kd-tree of the step itself: the last clouds (buffer 1 - parity) of the sequences that solve.
+// The "next" form builds beside the association and the solve of a step what the NEXT step will search: the sweep just registered (buffer parity,
+// sizes n_less_*) of every sequence that swaps in this step - a first frame leaves a grid behind for the second one - into the grid set of that buffer.
+template <bool NEXT>
+struct BuildSrc {
+  int n, set;
+  const float4* pts;
+  __device__ __forceinline__ BuildSrc(const OdomArgs& a, const SeqMeta& m, int b, int which) {
+    set = NEXT ? m.parity : m.parity ^ 1;
+    n = which == 0 ? (NEXT ? m.n_less_sharp : m.n_corner_last) : (NEXT ? m.n_less_flat : m.n_surf_last);
+    pts = which == 0 ? row_of(a.less_sharp, set, b, (long long)a.R * kLessSharpPerRing) : row_of(a.less_flat, set, b, (long long)a.cap);
+  }
+};
+
+template <bool NEXT>
+__device__ __forceinline__ void build_grids_fused(const OdomArgs& a, int b, int which) {
   constexpr int U = 4;
-  const int b = blockIdx.y, which = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (seq_idle(a.active, b, kSeqSolve)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (seq_idle(a.active, b, NEXT ? kSeqActive : kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
-  const int n = which == 0 ? m.n_corner_last : m.n_surf_last;
-  const float4* pts = which == 0 ? corner_last(a, b, m.parity) : surf_last(a, b, m.parity);
-  const GridView g = grid_view(a, b, which);
+  const BuildSrc<NEXT> src(a, m, b, which);
+  const int n = src.n;
+  const float4* pts = src.pts;
+  const GridView g = grid_view(a, b, which, src.set);
   const int H = g.H;
   if (!fused_takes(n, H)) return;
   extern __shared__ __attribute__((aligned(16))) int lds[];
@@ -332,19 +348,36 @@ __global__ __launch_bounds__(1024) void k_build_grids_fused(OdomArgs a) {
 #endif
 }
 
+__global__ __launch_bounds__(1024) void k_build_grids_fused(OdomArgs a) { build_grids_fused<false>(a, blockIdx.y, blockIdx.x); }
+// The "next" form runs beside the association, whose one-wave workgroups take every wave slot the moment it falls free: a 1024-thread workgroup
+// that has to be PLACED while they run waits for sixteen free slots and 98 KB of LDS on one CU at the same time, and gets them when the
+// association drains (measured at batch 2048: one workgroup per cloud stretched the 2.8 ms build over the 9.3 ms of association and solve and
+// hid 0.4 ms of it).  So this form is persistent: an even number of workgroups (launch_build_grids), placed once when the step begins, walk
+// through the 2 B clouds; in round r workgroup w takes cloud r G + w, and the class bit flips from round to round so that every workgroup
+// gets corner and surf clouds in turn (with 2 B <= G this is one workgroup per cloud, the grid of the "last" form).
+__global__ __launch_bounds__(1024) void k_build_grids_fused_next(OdomArgs a) {
+  const int G = gridDim.x;
+  for (int r = 0, i = blockIdx.x; i < 2 * a.B; ++r, i += G) {
+    build_grids_fused<true>(a, i >> 1, (i ^ r) & 1);
+    __syncthreads();                                    // the tables of this cloud are done with before the next one clears them
+  }
+}
+
 constexpr int kBgWaves = 4;   // waves per SIMD the register budget is sized for
 constexpr int kBgUnroll = 4;
-__global__ __launch_bounds__(1024, kBgWaves) void k_build_grids(OdomArgs a) {
+template <bool NEXT>
+__device__ __forceinline__ void build_grids(const OdomArgs& a) {
   constexpr int U = kBgUnroll;                                     // loads in flight per thread
   // one workgroup per (sequence, cloud, grid): the three grids of a cloud are independent, and six workgroups per sequence
   // overlap each other's load / LDS-atomic / scattered-store phases better than two that run three passes back to back
   const int b = blockIdx.y, which = blockIdx.x / 3, tid = threadIdx.x;      // which: 0 corner_last, 1 surf_last
   const int pass_lo = blockIdx.x % 3, pass_hi = pass_lo + 1;
-  if (seq_idle(a.active, b, kSeqSolve)) return;
+  if (seq_idle(a.active, b, NEXT ? kSeqActive : kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
-  const int n = which == 0 ? m.n_corner_last : m.n_surf_last;
-  const float4* pts = which == 0 ? corner_last(a, b, m.parity) : surf_last(a, b, m.parity);
-  const GridView g = grid_view(a, b, which);
+  const BuildSrc<NEXT> src(a, m, b, which);
+  const int n = src.n;
+  const float4* pts = src.pts;
+  const GridView g = grid_view(a, b, which, src.set);
   if (fused_takes(n, g.H)) return;        // k_build_grids_fused built this cloud's grids already
   extern __shared__ __attribute__((aligned(16))) int lds[];
   int* cnt = lds;                         // [H]
@@ -443,6 +476,9 @@ __global__ __launch_bounds__(1024, kBgWaves) void k_build_grids(OdomArgs a) {
     }
   }
 }
+
+__global__ __launch_bounds__(1024, kBgWaves) void k_build_grids(OdomArgs a) { build_grids<false>(a); }
+__global__ __launch_bounds__(1024, kBgWaves) void k_build_grids_next(OdomArgs a) { build_grids<true>(a); }
 
 __device__ __forceinline__ float walk_dist(const float4& p, const float4& sel) {     // f32 expression (:322-327)
   return (p.x - sel.x) * (p.x - sel.x) + (p.y - sel.y) * (p.y - sel.y) + (p.z - sel.z) * (p.z - sel.z);
@@ -1300,7 +1336,7 @@ __global__ __launch_bounds__(64) void k_associate_pair(OdomArgs a) {
   const SeqMeta m = a.meta[b];
   const int nq = PLANE ? m.n_flat : m.n_sharp;
   if (qi0 >= nq) return;
-  const GridView g = grid_view(a, b, PLANE ? 1 : 0);
+  const GridView g = grid_view(a, b, PLANE ? 1 : 0, m.parity ^ 1);
   const int nt = PLANE ? m.n_surf_last : m.n_corner_last;
   if (g.flags[0] != 0 || g.flags[1] != 0 || nt <= 0) return;                 // k_associate_nearly / k_associate_flagged own this sequence
   // (128-ring sensors: the paired tails would take the planar class from 79 to 85 registers, six waves per SIMD to five, for their ~1 %)
@@ -1318,9 +1354,9 @@ __global__ __launch_bounds__(64) void k_associate_nearly(OdomArgs a) {
   __shared__ int lds[sweep2_lds_ints<kRows>()];
   const int lane = threadIdx.x, b = blockIdx.y;
   if (seq_idle(a.active, b, kSeqSolve)) return;
-  const GridView g = grid_view(a, b, PLANE ? 1 : 0);
-  if (g.flags[0] != 0 || g.flags[1] != 1) return;
   const SeqMeta m = a.meta[b];
+  const GridView g = grid_view(a, b, PLANE ? 1 : 0, m.parity ^ 1);
+  if (g.flags[0] != 0 || g.flags[1] != 1) return;
   const int nq = PLANE ? m.n_flat : m.n_sharp, nt = PLANE ? m.n_surf_last : m.n_corner_last;
   if (nt <= 0) return;
   for (int k = 0; k < kPairsPerWave; ++k) {
@@ -1340,7 +1376,7 @@ __global__ __launch_bounds__(256) void k_associate_flagged(OdomArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (seq_idle(a.active, b, kSeqSolve)) return;
   const SeqMeta m = a.meta[b];
-  const GridView g = grid_view(a, b, PLANE ? 1 : 0);
+  const GridView g = grid_view(a, b, PLANE ? 1 : 0, m.parity ^ 1);
   const int nt = PLANE ? m.n_surf_last : m.n_corner_last;
   if (!(g.flags[0] != 0 || g.flags[1] == 2 || nt <= 0)) return;
   const int nq = PLANE ? m.n_flat : m.n_sharp;
@@ -1499,16 +1535,27 @@ static size_t build_grids_fused_lds_bytes(int H) { return sizeof(int) * (3 * (si
 // The surf grid needs > 64 KiB of dynamic LDS: the attribute belongs to the function ON the current device; aloam_create sets it
 // once per context (no process-global state).
 int prepare_build_grids(int H_surf) {
-  if (hipFuncSetAttribute((const void*)k_build_grids_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)build_grids_fused_lds_bytes(kFusedMaxH)) != hipSuccess) return -1;
-  return hipFuncSetAttribute((const void*)k_build_grids, hipFuncAttributeMaxDynamicSharedMemorySize, (int)build_grids_lds_bytes(H_surf, kMaxRings)) == hipSuccess ? 0 : -1;
+  const int fused = (int)build_grids_fused_lds_bytes(kFusedMaxH), per_grid = (int)build_grids_lds_bytes(H_surf, kMaxRings);
+  if (hipFuncSetAttribute((const void*)k_build_grids_fused, hipFuncAttributeMaxDynamicSharedMemorySize, fused) != hipSuccess) return -1;
+  if (hipFuncSetAttribute((const void*)k_build_grids_fused_next, hipFuncAttributeMaxDynamicSharedMemorySize, fused) != hipSuccess) return -1;
+  if (hipFuncSetAttribute((const void*)k_build_grids, hipFuncAttributeMaxDynamicSharedMemorySize, per_grid) != hipSuccess) return -1;
+  return hipFuncSetAttribute((const void*)k_build_grids_next, hipFuncAttributeMaxDynamicSharedMemorySize, per_grid) == hipSuccess ? 0 : -1;
 }
-void launch_build_grids(const OdomArgs& a, hipStream_t s) {
+// next: the grids of the sweep just registered, for the step after this one (BuildSrc); else those of the last clouds, for this step
+void launch_build_grids(const OdomArgs& a, bool next, int cus, hipStream_t s) {
   // clouds of up to 65535 points: all three grids by one workgroup from two reads; the per-grid workgroups below return at once for those
   // (always launched: which kernel owns a cloud is decided per cloud by fused_takes() in both kernels; LDS sized for the larger table
   // that can be fused)
   const int hc = a.grid_H_corner <= kFusedMaxH ? a.grid_H_corner : 0, hs = a.grid_H_surf <= kFusedMaxH ? a.grid_H_surf : 0;
-  if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused, dim3(2, a.B), dim3(1024), build_grids_fused_lds_bytes(hc > hs ? hc : hs), s, a);
-  hipLaunchKernelGGL(k_build_grids, dim3(6, a.B), dim3(1024), build_grids_lds_bytes(a.grid_H_surf, a.R), s, a);
+  const size_t fused = build_grids_fused_lds_bytes(hc > hs ? hc : hs), per_grid = build_grids_lds_bytes(a.grid_H_surf, a.R);
+  if (next) {
+    const int wgs = cus / 2 >= 2 ? (cus / 2) & ~1 : 2;
+    if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused_next, dim3(2 * a.B < wgs ? 2 * a.B : wgs), dim3(1024), fused, s, a);
+    hipLaunchKernelGGL(k_build_grids_next, dim3(6, a.B), dim3(1024), per_grid, s, a);
+  } else {
+    if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused, dim3(2, a.B), dim3(1024), fused, s, a);
+    hipLaunchKernelGGL(k_build_grids, dim3(6, a.B), dim3(1024), per_grid, s, a);
+  }
 }
 void launch_transform_queries(const OdomArgs& a, hipStream_t s) {
   const dim3 grid((a.R * (kSharpPerRing + kFlatPerRing) + 255) / 256, a.B);
