@@ -1,6 +1,6 @@
 // a-loam_amd/csrc/aloam_capi.hip — host side of libaloam_mi355x.so: context creation and teardown, the pinned staging ring, per-sequence
-// lifecycle and profiling.  The other entry points of include/aloam_mi355x.h are in capi_odometry.hip, capi_mapping.hip and capi_records.hip
-// (what they share: capi_internal.hpp).  There is no CPU fallback anywhere: without a HIP device every entry point fails with ALOAM_E_HIP.
+// lifecycle and profiling.  The other entry points of include/aloam_mi355x.h are in the other capi_*.hip files
+// (what they share, and which file holds what: capi_internal.hpp).  There is no CPU fallback anywhere: without a HIP device every entry point fails with ALOAM_E_HIP.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -32,16 +32,6 @@ int stage_ints(aloam_ctx* c, const int* src, int n, int* dst) {
   return ALOAM_OK;
 }
 
-// The mask in force for one stage's launches: nullptr when every sequence takes part (the kernels then load nothing), else staged into `dst`.
-int stage_mask(aloam_ctx* c, DevBuf<int>& dst, const int** out) {
-  *out = nullptr;
-  if (c->all_active) return ALOAM_OK;
-  if (!dst && dmalloc(c, dst, c->B)) return ALOAM_E_HIP;
-  if (const int rc = stage_ints(c, c->active.data(), c->B, dst.get())) return rc;
-  *out = dst.get();
-  return ALOAM_OK;
-}
-
 int check_seq(aloam_ctx* c, int seq) {
   if (!c) return ALOAM_E_ARG;
   if (seq < 0 || seq >= c->B) { c->err = "sequence index out of range"; return ALOAM_E_ARG; }
@@ -63,26 +53,6 @@ int check_ids(aloam_ctx* c, const int* ids, int n) {
     if (ids[i] < 0 || ids[i] >= c->B || seen[ids[i]]) { c->err = "sequence index out of range or repeated"; return ALOAM_E_ARG; }
     seen[ids[i]] = 1;
   }
-  return ALOAM_OK;
-}
-
-// The reset of aloam_reset_sequences on checked ids, queued, with its host mirrors.
-int queue_reset(aloam_ctx* c, const int* seqs, int n) {
-  if (n == 0) return ALOAM_OK;
-  if (!c->d_reset_ids && dmalloc(c, c->d_reset_ids, c->B)) return ALOAM_E_HIP;
-  if (const int rc = stage_ints(c, seqs, n, c->d_reset_ids.get())) return rc;
-  ResetArgs r{};
-  r.seqs = c->d_reset_ids.get(); r.n = n; r.R = c->R;
-  r.meta = c->d_meta.get(); r.ringstart = c->d_ringstart.get(); r.state = c->d_state.get();
-  r.edges = c->d_edges.get(); r.planes = c->d_planes.get();
-  for (int p = 0; p < 2; ++p) for (int k = 0; k < 2; ++k) r.grid_flags[p][k] = c->d_grid_flags[p][k].get();
-  for (int k = 0; k < 2; ++k) { r.less_sharp[k] = c->d_less_sharp[k].get(); r.less_flat[k] = c->d_less_flat[k].get(); }
-  r.cap = c->cap;
-  if (c->map_on) { r.mapseq = c->d_mapseq.get(); r.cubes = c->d_cubes.get(); r.addcnt = c->d_addcnt.get(); r.live = c->d_map_live.get(); r.grid_sig = c->d_grid_sig.get(); }
-  launch_reset_sequences(r, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  for (int i = 0; i < n; ++i) { c->parity[seqs[i]] = 0; c->inited[seqs[i]] = 0; c->grid_built[seqs[i]] = 0; c->needs_odom[seqs[i]] = 0; c->map_err_seen[seqs[i]] = 0; clear_scorable(c, seqs[i]); place_sweep_dropped(c, seqs[i]); }
-  for (int i = 0; i < n; ++i) if (const int rc = mark_window_stale(c, seqs[i])) return rc;   // an attached slot keeps its attachment
   return ALOAM_OK;
 }
 
@@ -150,8 +120,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->in_consumed[k].h, hipEventDisableTiming));
   }
   c->B = cfg->batch; c->max_points = cfg->max_points; c->R = cfg->n_scans;
-  c->active.assign(c->B, 1); c->parity.assign(c->B, 0); c->inited.assign(c->B, 0); c->needs_odom.assign(c->B, 0); c->frozen.assign(c->B, 0); c->scorable.assign(c->B, 0); c->grid_built.assign(c->B, 0); c->pl_has_sweep.assign(c->B, 0); c->pl_desc_valid.assign(c->B, 0);
-  c->map_err_seen.assign(c->B, 0);
+  c->seq.assign(c->B, SeqHost{});
   // The per-sequence stride of every [B][cap] buffer is kept OFF the powers of two (131 072 points x 16 B = 2 MiB apart, the workgroups of a launch - one
   // per sequence, all at about the same offset of their sequence - meet on the same memory channels): + 1/32 + 16 points.  Measured on k_build_grids_fused at
   // batch 1024, one box: 1.62 - 1.65 ms at the power-of-two stride, 1.48 - 1.52 ms with 1040 / 4112 / 16 400 points of padding.
@@ -270,8 +239,8 @@ int aloam_synchronize(aloam_ctx* c) {
     int first_seq = -1;
     for (int b = 0; b < c->B; ++b) {
       const long long n = ms[b].err_steps + ((ms[b].err & kMapErrPool) ? 1 : 0);
-      if (n > c->map_err_seen[b]) { fresh_pool += n - c->map_err_seen[b]; if (first_seq < 0) first_seq = b; }
-      c->map_err_seen[b] = n;
+      const long long fresh = on_pool_events_reported(c, b, n);
+      if (fresh > 0) { fresh_pool += fresh; if (first_seq < 0) first_seq = b; }
     }
     const long long vox = vc[3] + (vc[1] ? 1 : 0), fresh_vox = vox > c->map_err_reported ? vox - c->map_err_reported : 0;
     c->map_err_reported = vox;
@@ -306,14 +275,13 @@ int aloam_synchronize(aloam_ctx* c) {
 int aloam_set_active(aloam_ctx* c, const int* active) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  std::vector<int> m(c->B, 1);
-  if (active) for (int b = 0; b < c->B; ++b) m[b] = active[b] != 0 ? 1 : 0;
-  if (c->reg_pending && (c->stages & ALOAM_STAGE_REGISTRATION) && m != c->reg_active) {
-    c->err = "the mask may not change between a registration and the odometry step that consumes it";
-    return ALOAM_E_STATE;
-  }
-  c->all_active = std::find(m.begin(), m.end(), 0) == m.end();
-  c->active = std::move(m);
+  if (c->reg_pending && (c->stages & ALOAM_STAGE_REGISTRATION))
+    for (int b = 0; b < c->B; ++b)
+      if ((!active || active[b] != 0) != (c->seq[b].reg_active != 0)) {
+        c->err = "the mask may not change between a registration and the odometry step that consumes it";
+        return ALOAM_E_STATE;
+      }
+  on_active_mask_set(c, active);
   return ALOAM_OK;
 }
 
@@ -321,7 +289,7 @@ int aloam_reset_sequences(aloam_ctx* c, const int* seqs, int n) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
   if (const int rc = check_ids(c, seqs, n)) return rc;
-  return queue_reset(c, seqs, n);
+  return on_slots_reset(c, seqs, n);
 }
 
 // ---- profiling -----------------------------------------------------------------------------------------------

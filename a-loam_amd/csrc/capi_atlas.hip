@@ -32,16 +32,10 @@ int spill_dropped_since(aloam_ctx* c, long long* fresh) {
   return ALOAM_OK;
 }
 
-int mark_window_stale(aloam_ctx* c, int seq) {
-  if (!c->any_attached || !c->attached[seq]) return ALOAM_OK;
-  HIP_TRY(c, hipMemsetAsync(c->d_at_stale.get() + seq, 1, sizeof(int), c->stream));   // any non-zero value
-  return ALOAM_OK;
-}
-
 int atlas_step_check(aloam_ctx* c) {
   if (!c->any_attached) return ALOAM_OK;
   for (int b = 0; b < c->B; ++b)
-    if (c->attached[b] && (c->all_active || c->active[b]) && !(c->any_frozen && c->frozen[b])) {
+    if (c->seq[b].attached && takes_part(c, b) && !(c->any_frozen && c->seq[b].frozen)) {
       c->err = "sequence " + std::to_string(b) + " is attached to the atlas and active but not frozen (aloam_set_map_frozen): an attached window is never extended";
       return ALOAM_E_STATE;
     }
@@ -50,7 +44,7 @@ int atlas_step_check(aloam_ctx* c) {
 
 bool queue_atlas_window(aloam_ctx* c, const int* mask) {
   bool any = false;
-  for (int b = 0; b < c->B; ++b) any |= c->attached[b] && (c->all_active || c->active[b]);
+  for (int b = 0; b < c->B; ++b) any |= c->seq[b].attached && takes_part(c, b);
   if (!any) return false;
   AtlasArgs a{};
   a.B = c->B; a.active = mask; a.attached = c->d_at_attached.get(); a.stale = c->d_at_stale.get();
@@ -303,7 +297,7 @@ int aloam_atlas_attach(aloam_ctx* c, const int* attached) {
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_stage(c, ALOAM_STAGE_MAPPING)) return rc;
   if (!c->map_on) { c->err = "aloam_atlas_attach before aloam_mapping_enable"; return ALOAM_E_STATE; }
-  std::vector<char> m(c->B, 0);
+  std::vector<int> m(c->B, 0);
   if (attached) for (int b = 0; b < c->B; ++b) m[b] = attached[b] != 0 ? 1 : 0;
   const bool any = std::find(m.begin(), m.end(), 1) != m.end();
   if (any && !c->atlas_on) { c->err = "no atlas is loaded (aloam_atlas_load)"; return ALOAM_E_STATE; }
@@ -315,15 +309,8 @@ int aloam_atlas_attach(aloam_ctx* c, const int* attached) {
     }
   }
   if (!c->d_at_attached) { if (const int rc = dmalloc(c, c->d_at_attached, c->B)) return rc; if (const int rc = dmalloc(c, c->d_at_stale, c->B)) return rc; }
-  std::vector<int> bits(c->B);
-  for (int b = 0; b < c->B; ++b) bits[b] = m[b];
-  if (const int rc = stage_ints(c, bits.data(), c->B, c->d_at_attached.get())) return rc;
-  const std::vector<char> old = c->attached.empty() ? std::vector<char>(c->B, 0) : c->attached;
-  c->attached = std::move(m);
-  c->any_attached = any;
-  for (int b = 0; b < c->B; ++b)
-    if (c->attached[b] && !old[b]) { if (const int rc = mark_window_stale(c, b)) return rc; clear_scorable(c, b); }
-  return ALOAM_OK;
+  if (const int rc = stage_ints(c, m.data(), c->B, c->d_at_attached.get())) return rc;
+  return on_atlas_attached(c, m);
 }
 
 int aloam_atlas_info(aloam_ctx* c, long long out[12]) {

@@ -2,7 +2,7 @@
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
 // setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
-// capi_places.hip (place recognition).
+// capi_places.hip (place recognition), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +75,23 @@ struct MapPool {
   DevBuf<int> grid_start[2], tile_seg, tile_heads, tile_pref;
   DevBuf<unsigned long long> keys[2];
 };
+
+// What the host knows about one sequence without asking the device (mirrors of device state that only host calls change, then its map, then what the device
+// holds for its sweep and last clouds).  Written only by aloam_create_stages and the events of capi_seq.hip (the table of events against fields).
+struct SeqHost {
+  int active = 1;                    // the mask in force (aloam_set_active), 0 / 1
+  int reg_active = 1;                // the mask of the last registration, while its odometry step is still to come (reg_pending)
+  int parity = 0, inited = 0;        // SeqMeta::parity, OdomState::inited
+  bool needs_odom = false;           // loaded by aloam_load_sequences and not yet through an odometry step: may not map
+  long long map_err_seen = 0;        // pool capacity events (MapSeq.err_steps) aloam_synchronize has already returned
+  bool frozen = false;               // aloam_set_map_frozen: localizes against its map in the mapping steps, does not extend it
+  bool scorable = false;             // last took part in a mapping step frozen, and its search grid has not been invalidated since
+  bool attached = false;             // mirror of d_at_attached (with the device mark d_at_stale: the next step cuts the window anew)
+  bool has_sweep = false;            // holds a registered sweep (since creation / reset / load): a place descriptor can be made
+  bool desc_valid = false;           // d_pl_desc[b] is that sweep's
+  bool grid_built = false;           // the grid set of its LAST clouds holds their grids: set by the step that made them the last ones (it built
+                                     // them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
+};
 }  // namespace aloam
 
 struct aloam_ctx {
@@ -100,16 +117,10 @@ struct aloam_ctx {
   DevBuf<int> d_nin;
   PinnedBuf<int> h_nin; int h_nin_slot = 0;         // pinned ring of kNinSlots x B ints (counts, masks, reset ids): an async H2D copy reads its slot later
   bool nin_used[kNinSlots] = {};
-  // per-sequence lifecycle (aloam_set_active / aloam_reset_sequences)
-  std::vector<int> active;                          // [B] the mask in force, 0 / 1
-  bool all_active = true;
-  std::vector<int> reg_active;                      // the mask of the last registration, while its odometry step is still to come (reg_pending)
+  std::vector<SeqHost> seq;                         // [B] per-sequence host state
+  bool all_active = true, any_frozen = false, any_attached = false;   // aggregates of seq[].active / frozen / attached, each recomputed by that field's event
   bool reg_pending = false;
   const int* reg_mask = nullptr;                    // what the last registration's kernels were given (nullptr = all); k_dense_cloud reuses it
-  std::vector<int> parity, inited;                  // host mirrors of SeqMeta::parity and OdomState::inited: both change only through host calls
-  std::vector<char> needs_odom;                     // [B] loaded by aloam_load_sequences and not yet through an odometry step: may not map
-  std::vector<char> frozen;                         // [B] aloam_set_map_frozen: localizes against its map in the mapping steps, does not extend it
-  bool any_frozen = false;
   DevBuf<int> d_mask_reg, d_mask_odo, d_mask_map, d_reset_ids;   // [B] each: masks as the launches of one stage see them, ids of a reset
   DevBuf<SeqMeta> d_meta;
   DevBuf<float4> d_slabs; int slab = 0;             // ring-ordered points, one slab per (sequence, ring): what k_front writes and the feature kernels read
@@ -131,14 +142,11 @@ struct aloam_ctx {
   DevBuf<int> d_grid_flags[2][2], d_grid_walk[2][2];
   int grid_H[2] = {4096, 16384};
   bool grid_overlap = false;         // environment ALOAM_GRID_OVERLAP (default on), read once at creation; off with use_graph / debug_sync
-  std::vector<char> grid_built;      // [B] the grid set of the sequence's LAST clouds holds their grids: set by the step that made them the last ones
-                                     // (it built them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
   DevBuf<EdgeRec> d_edges; DevBuf<PlaneRec> d_planes;
   DevBuf<float4> d_sel_sharp, d_sel_flat;
   // scan-to-map refinement (allocated by aloam_mapping_enable)
   bool map_on = false;
   long long map_err_reported = 0;    // voxel-scratch capacity events (vox counters[3]) aloam_synchronize has already returned
-  std::vector<long long> map_err_seen;   // per sequence: pool capacity events (MapSeq.err_steps) already returned
   float map_line_res = 0.4f, map_plane_res = 0.8f;
   int map_levels = 0, map_stack_tile_bound = 0, map_nsegs_max = 0;   // general voxel path over the incoming clouds: merge levels, tiles
   MapPool map;                       // the pool-sized state (map_alloc_pool)
@@ -175,7 +183,6 @@ struct aloam_ctx {
   DevBuf<char> d_ck_stage; size_t ck_stage_bytes = 0;               // load: records from pageable host memory
   int ck_save_n = 0; long long ck_load_bytes = 0;                   // the last save / load (algorithmic bytes)
   // map-pose hypotheses (aloam_score_map_corrections / aloam_apply_map_corrections)
-  std::vector<char> scorable;                                       // [B] last took part in a mapping step frozen, and its search grid has not been invalidated since
   DevBuf<int> d_rl_seqs, d_rl_bad;                                  // [B] listed ids; [1] choices found outside 0 .. K-1 by k_apply_corrections
   DevBuf<ScorePartial> d_rl_part; long long rl_part_cap = 0;        // [n][K][kScoreParts] per-workgroup partials
   DevBuf<aloam_map_correction> d_rl_cand; long long rl_cand_cap = 0;   // candidates handed in as pageable host memory
@@ -190,7 +197,6 @@ struct aloam_ctx {
   DevBuf<int> d_sp_seqs, d_sp_cnt, d_sp_chunk; DevBuf<long long> d_sp_off;   // the drain: listed ids, [2][B] counts, [2][B + 1] chunk / element offsets (tiles, points)
   // atlas (aloam_atlas_load / aloam_atlas_attach): one immutable tile store, shared by the attached sequences
   bool atlas_on = false;
-  std::vector<char> attached; bool any_attached = false;            // [B] host mirror of d_at_attached
   DevBuf<int> d_at_attached, d_at_stale;                            // [B] each; stale != 0: the next step cuts the window anew
   DevBuf<AtlasEntry> d_at_dir[2]; int at_dir_mask[2] = {0, 0};      // per class: directory absolute cube -> (first, count)
   DevBuf<float4> d_at_points[2];
@@ -200,7 +206,6 @@ struct aloam_ctx {
   bool places_on = false;
   int pl_capacity = 0, pl_count = 0;                                // entries the store holds / has; the count is host state (adds are stream-ordered)
   float pl_max_range = 80.f, pl_height = 2.f;
-  std::vector<char> pl_has_sweep, pl_desc_valid;                    // [B] holds a registered sweep (since creation / reset / load); d_pl_desc[b] is that sweep's
   DevBuf<PlaceDesc> d_pl_desc;                                      // [B]
   DevBuf<aloam_place> d_pl_store;                                   // [capacity]
   DevBuf<float> d_pl_unit; DevBuf<unsigned long long> d_pl_masks;   // [capacity][1200] unit-normalised columns, [capacity] non-zero columns
@@ -297,33 +302,49 @@ int grow_scratch(aloam_ctx* c, DevBuf<T>& p, N& have, N need) {
 // The row of sequence `seq` that a getter reads through `s` (cloud_desc): base[0 / parity / 1 - parity] + seq * stride; nullptr when this
 // context has no buffer for it (aloam_create_stages leaves some out).  Writable: the setters fill the context's own buffers through it.
 inline float4* cloud_row(const aloam_ctx* c, const ExportSrc& s, int seq) {
-  const int r = s.sel == kSelFixed ? 0 : s.sel == kSelCurrent ? c->parity[seq] : 1 - c->parity[seq];
+  const int r = s.sel == kSelFixed ? 0 : s.sel == kSelCurrent ? c->seq[seq].parity : 1 - c->seq[seq].parity;
   return s.base[r] ? const_cast<float4*>(s.base[r]) + (size_t)seq * s.stride : nullptr;
 }
 
 // aloam_capi.hip
 int stage_ints(aloam_ctx* c, const int* src, int n, int* dst);
-int stage_mask(aloam_ctx* c, DevBuf<int>& dst, const int** out);
 int check_seq(aloam_ctx* c, int seq);
 int require_stage(aloam_ctx* c, int stage);
 int check_ids(aloam_ctx* c, const int* ids, int n);
-int queue_reset(aloam_ctx* c, const int* seqs, int n);
 // capi_odometry.hip
 int ensure_dense(aloam_ctx* c);
 long long cloud_desc(const aloam_ctx* c, int id, ExportSrc* s);
 int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n);
 // capi_mapping.hip
-inline void clear_scorable(aloam_ctx* c, int seq) { c->scorable[seq] = 0; }   // the search grid of `seq` is no longer that of its stacks
 int grow_map_pool(aloam_ctx* c, long long want, bool clamp);
 // capi_atlas.hip
 void queue_map_spill(aloam_ctx* c, const int* mask);
 int spill_dropped_since(aloam_ctx* c, long long* fresh);
-int mark_window_stale(aloam_ctx* c, int seq);            // the map, frame or slot of `seq` was replaced: an attached sequence cuts its window anew
 int atlas_step_check(aloam_ctx* c);                      // ALOAM_E_STATE when an attached sequence that is active in this step is not frozen
 bool queue_atlas_window(aloam_ctx* c, const int* mask);  // k_atlas_window when an attached sequence takes part
-// capi_places.hip
-inline void place_sweep_registered(aloam_ctx* c, int seq) { c->pl_has_sweep[seq] = 1; c->pl_desc_valid[seq] = 0; }   // a new sweep: its descriptor is still to be made
-inline void place_sweep_dropped(aloam_ctx* c, int seq) { c->pl_has_sweep[seq] = 0; c->pl_desc_valid[seq] = 0; }       // reset or loaded: nothing to describe
+// capi_seq.hip: the one "does sequence b take part in this step", a stage's mask, and what happens to a sequence, each with its whole consequence
+inline bool takes_part(const aloam_ctx* c, int b) { return c->all_active || c->seq[b].active; }
+struct StageMask {
+  std::vector<int> bits;             // [B] SeqBits of every sequence in this step
+  const int* dev = nullptr;          // bits as the launches see them; nullptr: the stage runs unmasked (the kernels then load nothing)
+  bool any_active = false, any_solve = false, all_solve = true, any_grow = false;
+};
+int stage_mask(aloam_ctx* c, DevBuf<int>& dst, int (*extra_bits)(const SeqHost&), bool (*unmasked)(const aloam_ctx*, const StageMask&), StageMask* m);
+void on_active_mask_set(aloam_ctx* c, const int* active);
+void on_frozen_mask_set(aloam_ctx* c, const int* frozen);
+int on_slots_reset(aloam_ctx* c, const int* seqs, int n);
+void on_slot_loaded(aloam_ctx* c, int seq, bool inited, long long err_events);
+void on_sweep_registered(aloam_ctx* c);
+void on_odometry_advanced(aloam_ctx* c, const StageMask& m);
+void on_last_clouds_replaced(aloam_ctx* c, int seq);
+void on_system_inited_forced(aloam_ctx* c, int inited);
+int on_map_replaced(aloam_ctx* c, int seq);
+int on_map_pool_reallocated(aloam_ctx* c, MapPool&& fresh);
+void on_mapping_step_queued(aloam_ctx* c);
+int on_atlas_attached(aloam_ctx* c, const std::vector<int>& attached);
+void on_places_enabled(aloam_ctx* c);
+void on_descriptors_made(aloam_ctx* c, const int* seqs, int n);
+long long on_pool_events_reported(aloam_ctx* c, int seq, long long events);
 // capi_mapping.hip
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);
 // capi_records.hip

@@ -72,11 +72,7 @@ static int map_alloc_pool(aloam_ctx* c, int pool_points) {
     else HIP_TRY(c, hipMemsetAsync(n.pool[k].get(), 0, sizeof(float4) * B * pool, c->stream));
     HIP_TRY(c, hipMemsetAsync(n.grid_start[k].get(), 0, sizeof(int) * B * ((size_t)n.H + 1), c->stream));
   }
-  if (c->d_grid_sig) HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get(), 0, sizeof(MapGridSig) * B * 2, c->stream));   // the grids are not moved
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->map = std::move(n);
-  for (int b = 0; b < c->B; ++b) clear_scorable(c, b);
-  return ALOAM_OK;
+  return on_map_pool_reallocated(c, std::move(n));
 }
 
 // The reference's cubes are std::vectors: a map grows as long as the sensor travels (src/laserMapping.cpp:737-783).  Here a (sequence,
@@ -221,29 +217,18 @@ int aloam_mapping_step(aloam_ctx* c) {
   if (!c) return ALOAM_E_ARG;
   if (!c->map_on) { c->err = "aloam_mapping_step before aloam_mapping_enable"; return ALOAM_E_STATE; }
   for (int b = 0; b < c->B; ++b)
-    if (c->needs_odom[b] && (c->all_active || c->active[b])) {
+    if (c->seq[b].needs_odom && takes_part(c, b)) {
       c->err = "sequence " + std::to_string(b) + " was loaded (aloam_load_sequences) and has not had its odometry step yet: it may not map";
       return ALOAM_E_STATE;
     }
   if (const int rc = atlas_step_check(c)) return rc;
   // Per sequence: kSeqActive = takes part, kSeqMapGrow = takes part and extends its map (not frozen).  The kernels get no mask at all when
   // every sequence grows: the launches of a lock-step batch are those of a context without aloam_set_active / aloam_set_map_frozen.
-  const int* mask = nullptr;
-  bool any_active = c->all_active, any_grow = !c->any_frozen;
-  if (!c->all_active || c->any_frozen) {
-    std::vector<int> bits(c->B);
-    any_grow = false;
-    for (int b = 0; b < c->B; ++b) {
-      const bool on = c->all_active || c->active[b];
-      bits[b] = on ? (kSeqActive | (c->frozen[b] ? 0 : kSeqMapGrow)) : 0;
-      any_active |= on;
-      any_grow |= (bits[b] & kSeqMapGrow) != 0;
-    }
-    if (!c->d_mask_map && dmalloc(c, c->d_mask_map, c->B)) return ALOAM_E_HIP;
-    if (const int rc = stage_ints(c, bits.data(), c->B, c->d_mask_map.get())) return rc;
-    mask = c->d_mask_map.get();
-  }
-  const bool sizes_pools = any_grow || !any_active;       // every active sequence frozen: nothing is inserted, the pools are neither sized nor waited for
+  StageMask m;
+  if (const int rc = stage_mask(c, c->d_mask_map, [](const SeqHost& s) { return s.frozen ? 0 : (int)kSeqMapGrow; },
+                                [](const aloam_ctx* x, const StageMask&) { return x->all_active && !x->any_frozen; }, &m)) return rc;
+  const int* mask = m.dev;
+  const bool sizes_pools = m.any_grow || !m.any_active;       // every active sequence frozen: nothing is inserted, the pools are neither sized nor waited for
   // at most four steps queued ahead of the device: the occupancy report the pools are sized from is never older than that
   hipEvent_t done = c->map_step_done[c->map_steps & 3];
   if (sizes_pools && c->map_steps >= 4) HIP_TRY(c, hipEventSynchronize(done));
@@ -279,8 +264,7 @@ int aloam_mapping_step(aloam_ctx* c) {
     launch_map_report(a, (int)c->map_steps, c->stream); }
   HIP_TRY(c, hipEventRecord(done, c->stream));
   HIP_TRY(c, hipGetLastError());
-  for (int b = 0; b < c->B; ++b)                          // what aloam_score_map_corrections may read: the stacks and grid of a frozen step
-    if (c->all_active || c->active[b]) c->scorable[b] = c->frozen[b];
+  on_mapping_step_queued(c);
   return ALOAM_OK;
 }
 
@@ -302,9 +286,7 @@ int aloam_set_map(aloam_ctx* c, int seq, int cls, const int* cube_ids, const int
   if (total && !points_xyzw) return ALOAM_E_ARG;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (total > c->map.points && (rc = grow_map_pool(c, total, false))) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // another submap: its grids are built anew
-  clear_scorable(c, seq);
-  if ((rc = mark_window_stale(c, seq))) return rc;
+  if ((rc = on_map_replaced(c, seq))) return rc;
   HIP_TRY(c, hipMemcpy(c->d_cubes.get() + ((size_t)seq * 2 + cls) * kMapCubes, d.data(), sizeof(CubeDesc) * kMapCubes, hipMemcpyHostToDevice));
   if (total) HIP_TRY(c, hipMemcpy(c->map.pool[cls].get() + (size_t)seq * c->map.points, points_xyzw, sizeof(float4) * (size_t)total, hipMemcpyHostToDevice));
   if ((rc = edit_seq(c, c->d_mapseq.get() + seq, [&](MapSeq& ms) { ms.pool_used[cls] = (int)total; }))) return rc;
@@ -323,9 +305,7 @@ int aloam_set_map_frame(aloam_ctx* c, int seq, const int cen[3], const double q_
          for (int k = 0; k < 4; ++k) ms.q_wmap_wodom[k] = q_wmap_wodom[k];
          ms.frame_count = frame_count;
        }))) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));   // a new frame: the grids are built anew
-  clear_scorable(c, seq);
-  return mark_window_stale(c, seq);
+  return on_map_replaced(c, seq);
 }
 
 int aloam_set_map_frozen(aloam_ctx* c, const int* frozen) {
@@ -333,10 +313,7 @@ int aloam_set_map_frozen(aloam_ctx* c, const int* frozen) {
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_stage(c, ALOAM_STAGE_MAPPING)) return rc;
   if (!c->map_on) { c->err = "aloam_set_map_frozen before aloam_mapping_enable"; return ALOAM_E_STATE; }
-  std::vector<char> m(c->B, 0);
-  if (frozen) for (int b = 0; b < c->B; ++b) m[b] = frozen[b] != 0 ? 1 : 0;
-  c->any_frozen = std::find(m.begin(), m.end(), 1) != m.end();
-  c->frozen = std::move(m);
+  on_frozen_mask_set(c, frozen);
   return ALOAM_OK;
 }
 

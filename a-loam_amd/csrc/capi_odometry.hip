@@ -60,10 +60,13 @@ int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, con
   // A sequence that sits out keeps its dense cloud: made now from its slabs if the last registration's was never asked for (a no-op otherwise)
   if (!c->all_active && (rc = ensure_dense(c))) return rc;
   c->nin_max = 0;
-  for (int b = 0; b < c->B; ++b) if (c->all_active || c->active[b]) c->nin_max = std::max(c->nin_max, n_in[b]);
+  for (int b = 0; b < c->B; ++b) if (takes_part(c, b)) c->nin_max = std::max(c->nin_max, n_in[b]);
   if ((rc = stage_ints(c, n_in, c->B, c->d_nin.get()))) return rc;
-  if ((rc = stage_mask(c, c->d_mask_reg, &c->reg_mask))) return rc;
-  if (c->stages & ALOAM_STAGE_ODOMETRY) { c->reg_active = c->active; c->reg_pending = true; }
+  StageMask m;                                                               // nothing but who takes part; no mask when that is everyone
+  rc = stage_mask(c, c->d_mask_reg, [](const SeqHost&) { return 0; }, [](const aloam_ctx* x, const StageMask&) { return x->all_active; }, &m);
+  c->reg_mask = m.dev;
+  if (rc) return rc;
+  on_sweep_registered(c);
   c->debug_arrays = debug_arrays || c->sum_order != 0;      // the reference-order pass reads cloudLabel
   if (((++c->reg_epoch) & 0x7fffffffu) == 0) ++c->reg_epoch;                 // 31 bits of it tag the look-back granules; 0 = "never written"
   const RegArgs a = reg_args(c, d_scans, seq_stride, stride_bytes);
@@ -71,7 +74,6 @@ int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, con
   { ProfScope p(c, K_FRONT); launch_front(a, c->stream); }
   { ProfScope p(c, K_RING_STARTS); launch_ring_starts(a, c->stream); }
   c->dense_valid = false;
-  for (int b = 0; b < c->B; ++b) if (c->all_active || c->active[b]) place_sweep_registered(c, b);
   if (slot >= 0) { HIP_TRY(c, hipEventRecord(c->in_consumed[slot], c->stream)); c->in_used[slot] = true; }   // the raw sweep is not read after this
   { ProfScope p(c, K_RING_FEATURES); launch_ring_features(a, c->npad, 0.2f, c->stream);     // leaf 0.2 (src/scanRegistration.cpp:404)
     if (c->sum_order) launch_less_flat_reference_order(reg_args(c, d_scans, seq_stride, stride_bytes), c->npad, 0.2f, c->stream); }
@@ -229,20 +231,11 @@ int aloam_odometry_step(aloam_ctx* c) {
   if (!c->have_features) { c->err = "aloam_odometry_step before any features were registered / set"; return ALOAM_E_STATE; }
   // Per sequence: kSeqActive = takes part (swaps), kSeqSolve = takes part and is past its first frame (src/laserOdometry.cpp:267-271).  The
   // kernels get no mask at all when every sequence solves: the launches of a lock-step batch are those of a context without the feature.
-  std::vector<int> bits(c->B);
-  bool any_solve = false, all_solve = true;
-  for (int b = 0; b < c->B; ++b) {
-    const bool on = c->all_active || c->active[b];
-    bits[b] = on ? (kSeqActive | (c->inited[b] ? kSeqSolve : 0)) : 0;
-    any_solve |= (bits[b] & kSeqSolve) != 0;
-    all_solve &= (bits[b] & kSeqSolve) != 0;
-  }
-  const int* mask = nullptr;
-  if (!all_solve && (any_solve || !c->all_active)) {             // (a first frame of the whole batch needs no mask: k_advance swaps all)
-    if (!c->d_mask_odo && dmalloc(c, c->d_mask_odo, c->B)) return ALOAM_E_HIP;
-    if (const int rc = stage_ints(c, bits.data(), c->B, c->d_mask_odo.get())) return rc;
-    mask = c->d_mask_odo.get();
-  }
+  StageMask m;                                                   // (a first frame of the whole batch needs no mask either: k_advance swaps all)
+  if (const int rc = stage_mask(c, c->d_mask_odo, [](const SeqHost& s) { return s.inited ? (int)kSeqSolve : 0; },
+                                [](const aloam_ctx* x, const StageMask& k) { return k.all_solve || (!k.any_solve && x->all_active); }, &m)) return rc;
+  const int* mask = m.dev;
+  const bool any_solve = m.any_solve;
   // The kd-tree stand-in of a step (launch_build_grids) covers clouds that were complete before the step began, so it need not wait for the step
   // that searches it.  With grid_overlap every step builds, on the grid stream and beside its own association and solve, the grids of the sweep it
   // is about to make the last one (the "next" form, into the grid set of that cloud buffer); the step after it finds them built (grid_built) and
@@ -251,7 +244,7 @@ int aloam_odometry_step(aloam_ctx* c) {
   // sends the step through the serial "last" build first, which is also the whole schedule without grid_overlap.
   const bool overlap = c->grid_overlap;
   bool build_last = !overlap;
-  if (overlap) for (int b = 0; b < c->B; ++b) build_last |= (bits[b] & kSeqSolve) && !c->grid_built[b];
+  if (overlap) for (int b = 0; b < c->B; ++b) build_last |= (m.bits[b] & kSeqSolve) && !c->seq[b].grid_built;
   hipError_t join_err = hipSuccess;
   const int cus = c->gather_blocks / 8;                                           // (aloam_create: eight gather workgroups per CU)
   auto launch_all = [&]() {
@@ -311,8 +304,7 @@ int aloam_odometry_step(aloam_ctx* c) {
   }
   HIP_TRY(c, join_err);
   HIP_TRY(c, hipGetLastError());
-  for (int b = 0; b < c->B; ++b) if (bits[b] & kSeqActive) { c->parity[b] ^= 1; c->inited[b] = 1; c->needs_odom[b] = 0; c->grid_built[b] = overlap; }
-  c->reg_pending = false;
+  on_odometry_advanced(c, m);
   return ALOAM_OK;
 }
 
@@ -393,7 +385,7 @@ int aloam_set_last(aloam_ctx* c, int seq, const float* corner_last, int n_corner
   for (auto& x : in) if (!cloud_row(c, x.s, seq)) { c->err = "this context has no buffers for the last clouds (created for the registration stage only)"; return ALOAM_E_STATE; }
   c->inject_max = std::max(c->inject_max, std::max(n_corner, n_surf));   // what the next mapping step may add (never lowers the bound)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->grid_built[seq] = 0;                                                // other last clouds: the next step builds their grids before it searches
+  on_last_clouds_replaced(c, seq);
   for (auto& x : in) if (x.n) HIP_TRY(c, hipMemcpy(cloud_row(c, x.s, seq), x.pts, sizeof(float4) * x.n, hipMemcpyHostToDevice));
   return edit_seq(c, c->d_meta.get() + seq, [&](SeqMeta& m) { m.n_corner_last = n_corner; m.n_surf_last = n_surf; });
 }
@@ -411,7 +403,7 @@ int aloam_set_state(aloam_ctx* c, int seq, const double para_q[4], const double 
 int aloam_set_system_inited(aloam_ctx* c, int inited) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  std::fill(c->inited.begin(), c->inited.end(), inited != 0 ? 1 : 0);
+  on_system_inited_forced(c, inited != 0 ? 1 : 0);
   launch_set_inited(c->d_state.get(), c->B, inited != 0 ? 1 : 0, c->stream);
   HIP_TRY(c, hipGetLastError());
   return ALOAM_OK;
@@ -479,7 +471,7 @@ int aloam_get_last_cloud_order(aloam_ctx* c, int seq, int out[2]) {
   if (!c->d_grid_flags[0][0]) { c->err = "this context has no odometry stage"; return ALOAM_E_STATE; }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   // The step searched the grids of cloud buffer 1 - parity and flipped the parity afterwards: that set is the one of the buffer `parity` names now.
-  const int set = c->parity[seq];
+  const int set = c->seq[seq].parity;
   for (int k = 0; k < 2; ++k) {
     int f[4];
     HIP_TRY(c, hipMemcpy(f, c->d_grid_flags[set][k].get() + (size_t)seq * 4, sizeof(f), hipMemcpyDeviceToHost));

@@ -16,7 +16,7 @@ static int require_places(aloam_ctx* c) {
 static int check_listed(aloam_ctx* c, const int* seqs, int n) {
   if (const int rc = check_ids(c, seqs, n)) return rc;
   for (int i = 0; i < n; ++i)
-    if (!c->pl_has_sweep[seqs[i]]) {
+    if (!c->seq[seqs[i]].has_sweep) {
       c->err = "sequence " + std::to_string(seqs[i]) + " has registered no sweep since it was created, reset or loaded: nothing to describe";
       return ALOAM_E_STATE;
     }
@@ -27,7 +27,7 @@ static int check_listed(aloam_ctx* c, const int* seqs, int n) {
 static int ensure_descriptors(aloam_ctx* c, const int* seqs, int n) {
   std::vector<int> wanted(c->B, 0);
   bool any = false;
-  for (int i = 0; i < n; ++i) if (!c->pl_desc_valid[seqs[i]]) { wanted[seqs[i]] = 1; any = true; }
+  for (int i = 0; i < n; ++i) if (!c->seq[seqs[i]].desc_valid) { wanted[seqs[i]] = 1; any = true; }
   if (!any) return ALOAM_OK;
   if (const int rc = stage_ints(c, wanted.data(), c->B, c->d_pl_wanted.get())) return rc;
   PlaceDescArgs a{};
@@ -35,7 +35,7 @@ static int ensure_descriptors(aloam_ctx* c, const int* seqs, int n) {
   a.ring_scale = (float)kPlaceRings / c->pl_max_range; a.height = c->pl_height; a.desc = c->d_pl_desc.get();
   launch_place_descriptor(a, c->stream);
   HIP_TRY(c, hipGetLastError());
-  for (int i = 0; i < n; ++i) c->pl_desc_valid[seqs[i]] = 1;
+  on_descriptors_made(c, seqs, n);
   return ALOAM_OK;
 }
 
@@ -62,7 +62,7 @@ int aloam_places_enable(aloam_ctx* c, int capacity, float max_range, float senso
   HIP_TRY(c, dalloc(c->d_pl_seqs, B)); HIP_TRY(c, dalloc(c->d_pl_wanted, B)); HIP_TRY(c, dalloc(c->d_pl_lo, B)); HIP_TRY(c, dalloc(c->d_pl_hi, B));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->pl_capacity = capacity; c->pl_count = 0; c->pl_max_range = max_range; c->pl_height = sensor_height;
-  std::fill(c->pl_desc_valid.begin(), c->pl_desc_valid.end(), 0);
+  on_places_enabled(c);
   c->places_on = true;
   return ALOAM_OK;
 }

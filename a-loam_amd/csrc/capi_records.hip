@@ -324,7 +324,7 @@ int aloam_load_sequences(aloam_ctx* c, const int* slots, int n, const void* src,
   }
   s_off[n] = off[n]; s_chunk[n] = chunks;
   HIP_TRY(c, hipMemcpyAsync(c->d_ck_load.get(), h, info_at + sizeof(int) * kRecInfo * n, hipMemcpyHostToDevice, c->stream));
-  if (const int rc = queue_reset(c, slots, n)) return rc;
+  if (const int rc = on_slots_reset(c, slots, n)) return rc;
   CkptLoadArgs a{};
   a.src = base; a.off = reinterpret_cast<const long long*>(c->d_ck_load.get());
   a.chunk_off = reinterpret_cast<const int*>(c->d_ck_load.get() + chunk_at); a.info = reinterpret_cast<const int*>(c->d_ck_load.get() + info_at);
@@ -337,13 +337,9 @@ int aloam_load_sequences(aloam_ctx* c, const int* slots, int n, const void* src,
   }
   { ProfScope p(c, K_LOAD); launch_load_sequences(a, c->gather_blocks, c->stream); }
   HIP_TRY(c, hipGetLastError());
-  // host mirrors: parity 0 (the reset), systemInited from the header, capacity events already seen, no mapping before the next odometry step
   c->ck_load_bytes = off[n] - off[0];
   for (int i = 0; i < n; ++i) {
-    const int s = slots[i];
-    c->inited[s] = hdr[i].inited != 0;
-    c->map_err_seen[s] = hdr[i].err_events;
-    c->needs_odom[s] = (c->stages & ALOAM_STAGE_ODOMETRY) ? 1 : 0;
+    on_slot_loaded(c, slots[i], hdr[i].inited != 0, hdr[i].err_events);
     if (c->map_on) for (int k = 0; k < 2; ++k) c->h_map_report[1 + k] = std::max((int)c->h_map_report[1 + k], hdr[i].map_points[k]);
   }
   return ALOAM_OK;

@@ -41,7 +41,7 @@ int aloam_score_map_corrections(aloam_ctx* c, const int* seqs, int n, const aloa
   if (!c) return ALOAM_E_ARG;
   if (const int rc = check_call(c, seqs, n, K)) return rc;
   for (int i = 0; i < n; ++i)
-    if (!c->scorable[seqs[i]]) {
+    if (!c->seq[seqs[i]].scorable) {
       c->err = "sequence " + std::to_string(seqs[i]) + ": its last mapping step was not a frozen one, or its map, frame or pools were replaced since: nothing to score against";
       return ALOAM_E_STATE;
     }
