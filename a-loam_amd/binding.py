@@ -92,6 +92,26 @@ def map_corrections(q, t):
     return c
 
 
+class AloamRangeDecoder(C.Structure):
+    """aloam_range_decoder: how a 16-bit range image becomes points (a-loam_amd/range_input.py holds the definition)."""
+    _fields_ = [("rows", C.c_int), ("n_az", C.c_int), ("order", C.c_int), ("range_scale", C.c_float),
+                ("az_x", C.POINTER(C.c_float)), ("az_y", C.POINTER(C.c_float)), ("cos_el", C.POINTER(C.c_float)), ("sin_el", C.POINTER(C.c_float)),
+                ("range_off", C.POINTER(C.c_float)), ("z_off", C.POINTER(C.c_float)), ("az_off", C.POINTER(C.c_int)), ("ring_id", C.POINTER(C.c_int))]
+
+
+RANGE_COLUMN_MAJOR, RANGE_ROW_MAJOR = 0, 1
+
+
+def range_decoder_struct(dec):
+    """The C struct of a range_input.RangeDecoder (or anything with its fields); the second value keeps the arrays it points to alive."""
+    keep = {k: np.ascontiguousarray(getattr(dec, k), dtype=np.float32) for k in ("az_x", "az_y", "cos_el", "sin_el", "range_off", "z_off")}
+    keep.update({k: np.ascontiguousarray(getattr(dec, k), dtype=np.int32) for k in ("az_off", "ring_id")})
+    d = AloamRangeDecoder(int(dec.rows), int(dec.n_az), int(dec.order), float(dec.range_scale))
+    for k, a in keep.items():
+        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_float if a.dtype == np.float32 else C.c_int)))
+    return d, keep
+
+
 class AloamSeqRecordHeader(C.Structure):
     """The first 128 bytes of a sequence record (aloam_seq_record_header)."""
     _fields_ = [("magic", C.c_uint), ("version", C.c_uint), ("bytes", C.c_longlong), ("parts", C.c_int), ("n_scans", C.c_int),
@@ -160,6 +180,11 @@ def lib():
         L.aloam_input_consumed.argtypes = [vp]
         L.aloam_odometry_step.argtypes = [vp]
         L.aloam_process_device.argtypes = [vp, vp, C.c_longlong, ip, C.c_int]
+        L.aloam_set_range_decoder.argtypes = [vp, C.POINTER(AloamRangeDecoder)]
+        L.aloam_scan_register_range_device.argtypes = [vp, vp, C.c_longlong, ip]
+        L.aloam_scan_register_range_host.argtypes = [vp, vp, C.c_longlong, ip]
+        L.aloam_process_range_device.argtypes = [vp, vp, C.c_longlong, ip]
+        L.aloam_process_range_host.argtypes = [vp, vp, C.c_longlong, ip]
         L.aloam_cloud_size.argtypes = [vp, C.c_int, C.c_int]
         L.aloam_get_cloud.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
         L.aloam_get_pose.argtypes = [vp, C.c_int, vp, vp, vp, vp]
@@ -302,6 +327,41 @@ class Aloam:
     def scan_register_host(self, h_ptr, seq_stride_bytes, n_in, stride_bytes=16):
         nin = n_in if isinstance(n_in, C.Array) else (C.c_int * self.batch)(*[int(v) for v in n_in])
         self._check(lib().aloam_scan_register_host(self.h, C.c_void_p(h_ptr), seq_stride_bytes, nin, stride_bytes))
+
+    # ---- stage 1 from 16-bit range images (a-loam_amd/range_input.py) ---------------------------------------------------------------
+    def set_range_decoder(self, dec):
+        """dec: a range_input.RangeDecoder, or an AloamRangeDecoder struct as it is (the error tests hand in broken ones)."""
+        d = dec if isinstance(dec, AloamRangeDecoder) else range_decoder_struct(dec)[0]
+        self._check(lib().aloam_set_range_decoder(self.h, C.byref(d)))
+
+    def _ncols(self, n_cols):
+        return n_cols if isinstance(n_cols, C.Array) else (C.c_int * self.batch)(*[int(v) for v in n_cols])
+
+    def scan_register_range(self, blobs, n_cols, check=True):
+        """blobs: one uint16 array per sequence (range_input.pack_sweep), from pageable memory; waits for the input to be consumed."""
+        arrs = [np.ascontiguousarray(b, dtype=np.uint16).reshape(-1) for b in blobs]
+        assert len(arrs) == self.batch
+        stride = max(16, max(a.nbytes for a in arrs))
+        buf = np.zeros(self.batch * stride, np.uint8)
+        for b, a in enumerate(arrs):
+            buf[b * stride:b * stride + a.nbytes] = a.view(np.uint8)
+        self.scan_register_range_host(buf.ctypes.data, stride, n_cols)
+        self.input_consumed()
+        if check:
+            self.synchronize()
+
+    def scan_register_range_device(self, d_ptr, seq_stride_bytes, n_cols):
+        self._check(lib().aloam_scan_register_range_device(self.h, C.c_void_p(d_ptr), seq_stride_bytes, self._ncols(n_cols)))
+
+    def scan_register_range_host(self, h_ptr, seq_stride_bytes, n_cols):
+        self._check(lib().aloam_scan_register_range_host(self.h, C.c_void_p(h_ptr), seq_stride_bytes, self._ncols(n_cols)))
+
+    def process_range_device(self, d_ptr, seq_stride_bytes, n_cols):
+        self._check(lib().aloam_process_range_device(self.h, C.c_void_p(d_ptr), seq_stride_bytes, self._ncols(n_cols)))
+
+    def process_range_host(self, h_ptr, seq_stride_bytes, n_cols):
+        """One host-resident batch of range images (pinned for true asynchrony): batched H2D copy on the copy stream + stage 1 + stage 2."""
+        self._check(lib().aloam_process_range_host(self.h, C.c_void_p(h_ptr), seq_stride_bytes, self._ncols(n_cols)))
 
     def input_consumed(self):
         self._check(lib().aloam_input_consumed(self.h))

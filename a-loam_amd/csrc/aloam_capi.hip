@@ -332,9 +332,12 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
     for (int b = 0; b < c->B; ++b) {
       const double Nin = m[b].n_in, N = m[b].n_cloud, Fc = m[b].n_sharp, Lc = m[b].n_less_sharp, Fs = m[b].n_flat, Ls = m[b].n_less_flat;
       const double Lcl = m[b].n_corner_last, Lsl = m[b].n_surf_last;
+      // the raw sweep: 16-byte records, or a range image at 2 bytes per point + its azimuth header (the last registration's kind)
+      const bool ranges = !c->range_cols.empty();
+      const double in_pt = ranges ? 2 : 16, in_hdr = ranges ? 2.0 * ((c->range_cols[b] + 7) & ~7) : 0;
       switch (kernel) {
-        case K_FIND_ENDS: bytes += 2 * 256 * 16; break;
-        case K_FRONT: bytes += 16 * Nin + 16 * N + 16.0 * (c->R + 1) * ((Nin + kBlockPts - 1) / kBlockPts); break;   // k_front: the sweep in, the slabs out, two granules per ring and block
+        case K_FIND_ENDS: bytes += 2 * 256 * in_pt; break;
+        case K_FRONT: bytes += in_pt * Nin + in_hdr + 16 * N + 16.0 * (c->R + 1) * ((Nin + kBlockPts - 1) / kBlockPts); break;   // k_front: the sweep in, the slabs out, two granules per ring and block
         case K_RING_STARTS: bytes += 12.0 * c->R; break;                                                                  // k_ring_starts
         case K_DENSE_CLOUD: bytes += 32 * N; break;                                                                            // k_dense_cloud (on demand)
         case K_RING_FEATURES: bytes += 16 * N + (c->debug_arrays ? 5 * N : 0) + 16 * (Fc + Lc + Fs + Ls); break;   // ring-ordered cloud in, the four feature clouds out (+ curvature / labels for the parity entry points)

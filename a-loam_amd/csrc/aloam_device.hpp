@@ -90,6 +90,17 @@ struct RegArgs {
   const int* active;         // [B] SeqBits of this registration, nullptr = all sequences
 };
 
+// A sweep handed over as a 16-bit range image (aloam_range_decoder, include/aloam_mi355x.h): what k_find_ends_range / k_front_range get beside
+// RegArgs (RegArgs::in / seq_stride address the blobs; pt_stride is not used).  The tables are the context's device copies of the decoder.
+constexpr int kRangeRowTables = 6;     // per-row tables, kMaxRings entries each, in this order: cos_el, sin_el, range_off, z_off, az_off (int), (float)ring_id
+struct RangeArgs {
+  const int* n_cols;         // [B] columns of every sweep (the staged counts of this call)
+  const float2* az_xy;       // [n_az] {az_x, az_y}
+  const float* row_tab;      // [kRangeRowTables][kMaxRings]
+  int rows, n_az, row_major;
+  float range_scale;
+};
+
 struct OdomArgs {
   int B, cap, R;
   SeqMeta* meta;

@@ -2,7 +2,7 @@
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
 // setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
-// capi_places.hip (place recognition), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
+// capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -211,6 +211,12 @@ struct aloam_ctx {
   DevBuf<float> d_pl_unit; DevBuf<unsigned long long> d_pl_masks;   // [capacity][1200] unit-normalised columns, [capacity] non-zero columns
   DevBuf<int> d_pl_seqs, d_pl_wanted, d_pl_lo, d_pl_hi;             // [B] each: listed ids, descriptors to make, the ranges of a match
   DevBuf<int2> d_pl_pairs; long long pl_pairs_cap = 0;              // [n][longest range] per-entry results of a match
+  // range-image input (aloam_set_range_decoder, capi_range.hip): the decoder's scalars and the device copies of its tables
+  bool range_on = false;
+  int rd_rows = 0, rd_n_az = 0, rd_order = 0; float rd_scale = 0.f;
+  DevBuf<float2> d_rd_az;                                           // [n_az] {az_x, az_y}
+  DevBuf<float> d_rd_rows;                                          // [kRangeRowTables][kMaxRings]
+  std::vector<int> range_cols;                                      // columns per sequence of the last registration when it read range images, else empty (algorithmic bytes)
   int sum_order = 0;                 // ALOAM_SUM_INPUT_ORDER / ALOAM_SUM_REFERENCE_ORDER (aloam_set_voxel_sum_order)
   bool use_graph = false;            // batch <= ALOAM_GRAPH_MAX_BATCH (environment, default 0 = off), read once at creation
   bool have_features = false;
@@ -312,6 +318,11 @@ int check_seq(aloam_ctx* c, int seq);
 int require_stage(aloam_ctx* c, int stage);
 int check_ids(aloam_ctx* c, const int* ids, int n);
 // capi_odometry.hip
+// One registration of a checked batch: n_in = points per sequence; n_cols != nullptr: the sweeps are range images of that many columns (capi_range.hip).
+int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot = -1, bool debug_arrays = true,
+                    const int* n_cols = nullptr);
+// A host-resident batch into the next staging slab, on the copy stream: rows 0 .. B-2 with `row` bytes each, the last with `last`; the compute stream waits for it.
+int stage_batch(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, size_t row, size_t last, size_t d_seq_stride, int* slot, char** d_in);
 int ensure_dense(aloam_ctx* c);
 long long cloud_desc(const aloam_ctx* c, int id, ExportSrc* s);
 int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n);

@@ -53,15 +53,20 @@ int check_batch(aloam_ctx* c, const int* n_in, int stride_bytes) {
   return ALOAM_OK;
 }
 
+}  // namespace
+
+namespace aloam {
+
 // debug_arrays: also write cloudCurvature / cloudLabel (the per-point entry points aloam_get_curvature / aloam_get_labels);
 // the throughput entries (aloam_process_device / aloam_process_host) leave those 5 bytes per point out.  The batch has passed check_batch.
-int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot = -1, bool debug_arrays = true) {
+int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot, bool debug_arrays, const int* n_cols) {
   int rc = ALOAM_OK;
   // A sequence that sits out keeps its dense cloud: made now from its slabs if the last registration's was never asked for (a no-op otherwise)
   if (!c->all_active && (rc = ensure_dense(c))) return rc;
   c->nin_max = 0;
   for (int b = 0; b < c->B; ++b) if (takes_part(c, b)) c->nin_max = std::max(c->nin_max, n_in[b]);
-  if ((rc = stage_ints(c, n_in, c->B, c->d_nin.get()))) return rc;
+  if ((rc = stage_ints(c, n_cols ? n_cols : n_in, c->B, c->d_nin.get()))) return rc;   // what the first kernel reads: points, or columns of a range image
+  if (n_cols) c->range_cols.assign(n_cols, n_cols + c->B); else c->range_cols.clear();
   StageMask m;                                                               // nothing but who takes part; no mask when that is everyone
   rc = stage_mask(c, c->d_mask_reg, [](const SeqHost&) { return 0; }, [](const aloam_ctx* x, const StageMask&) { return x->all_active; }, &m);
   c->reg_mask = m.dev;
@@ -70,8 +75,14 @@ int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, con
   c->debug_arrays = debug_arrays || c->sum_order != 0;      // the reference-order pass reads cloudLabel
   if (((++c->reg_epoch) & 0x7fffffffu) == 0) ++c->reg_epoch;                 // 31 bits of it tag the look-back granules; 0 = "never written"
   const RegArgs a = reg_args(c, d_scans, seq_stride, stride_bytes);
-  { ProfScope p(c, K_FIND_ENDS); launch_find_ends(a, c->d_nin.get(), c->stream); }
-  { ProfScope p(c, K_FRONT); launch_front(a, c->stream); }
+  if (n_cols) {
+    const RangeArgs d{c->d_nin.get(), c->d_rd_az.get(), c->d_rd_rows.get(), c->rd_rows, c->rd_n_az, c->rd_order == ALOAM_RANGE_ROW_MAJOR ? 1 : 0, c->rd_scale};
+    { ProfScope p(c, K_FIND_ENDS); launch_find_ends_range(a, d, c->stream); }
+    { ProfScope p(c, K_FRONT); launch_front_range(a, d, c->stream); }
+  } else {
+    { ProfScope p(c, K_FIND_ENDS); launch_find_ends(a, c->d_nin.get(), c->stream); }
+    { ProfScope p(c, K_FRONT); launch_front(a, c->stream); }
+  }
   { ProfScope p(c, K_RING_STARTS); launch_ring_starts(a, c->stream); }
   c->dense_valid = false;
   if (slot >= 0) { HIP_TRY(c, hipEventRecord(c->in_consumed[slot], c->stream)); c->in_used[slot] = true; }   // the raw sweep is not read after this
@@ -81,10 +92,6 @@ int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, con
   c->have_features = true;
   return ALOAM_OK;
 }
-
-}  // namespace
-
-namespace aloam {
 
 // The dense ring-by-ring cloud (laserCloud of src/scanRegistration.cpp:246-252) is made from the slabs when a consumer of the FULL cloud asks for it.
 int ensure_dense(aloam_ctx* c) {
@@ -140,17 +147,6 @@ int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n) {
   return ALOAM_OK;
 }
 
-}  // namespace aloam
-
-extern "C" {
-
-int aloam_scan_register_device(aloam_ctx* c, const void* d_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
-  DeviceScope device_scope(c);
-  if (!c || !d_scans || !n_in) return ALOAM_E_ARG;
-  if (const int rc = check_batch(c, n_in, stride_bytes)) return rc;
-  return register_launch(c, d_scans, seq_stride_bytes, n_in, stride_bytes);
-}
-
 // Next device staging slab for a host-resident batch: waits (host side) until the kernels that read the slab two calls ago
 // are done with it, grows it if needed (the old slab is released first: its contents are not needed).
 static int acquire_slab(aloam_ctx* c, size_t need, int* slot_out) {
@@ -160,6 +156,35 @@ static int acquire_slab(aloam_ctx* c, size_t need, int* slot_out) {
   if (const int rc = grow_scratch(c, c->d_in[s], c->d_in_bytes[s], need)) return rc;
   *slot_out = s;
   return ALOAM_OK;
+}
+
+int stage_batch(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, size_t row, size_t last, size_t d_seq_stride, int* slot_out, char** d_in_out) {
+  if (seq_stride_bytes < 0) { c->err = "bad stride"; return ALOAM_E_ARG; }
+  if (c->B > 1 && (size_t)seq_stride_bytes < row) { c->err = "seq_stride_bytes smaller than a scan"; return ALOAM_E_ARG; }
+  int slot = 0;
+  if (const int rc = acquire_slab(c, d_seq_stride * c->B, &slot)) return rc;
+  char* d_in = c->d_in[slot].get();
+  if (row > 0) {
+    // rows 0 .. B-2 as one strided copy of the batch-wide maximum (every row but the last is followed by the next one, so the
+    // extra bytes are readable); the last row with its own length, so that a buffer that ends with the last sweep is never over-read
+    if (c->B > 1) HIP_TRY(c, hipMemcpy2DAsync(d_in, d_seq_stride, h_scans, (size_t)seq_stride_bytes, row, (size_t)c->B - 1, hipMemcpyHostToDevice, c->copy_stream));
+    if (last > 0) HIP_TRY(c, hipMemcpyAsync(d_in + (size_t)(c->B - 1) * d_seq_stride, (const char*)h_scans + (size_t)(c->B - 1) * (size_t)seq_stride_bytes, last, hipMemcpyHostToDevice, c->copy_stream));
+  }
+  HIP_TRY(c, hipEventRecord(c->in_copied[slot], c->copy_stream));
+  HIP_TRY(c, hipStreamWaitEvent(c->stream, c->in_copied[slot], 0));
+  *slot_out = slot; *d_in_out = d_in;
+  return ALOAM_OK;
+}
+
+}  // namespace aloam
+
+extern "C" {
+
+int aloam_scan_register_device(aloam_ctx* c, const void* d_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
+  DeviceScope device_scope(c);
+  if (!c || !d_scans || !n_in) return ALOAM_E_ARG;
+  if (const int rc = check_batch(c, n_in, stride_bytes)) return rc;
+  return register_launch(c, d_scans, seq_stride_bytes, n_in, stride_bytes);
 }
 
 int aloam_scan_register(aloam_ctx* c, const void* const* scans, const int* n_in, int stride_bytes) {
@@ -186,22 +211,10 @@ static int stage_and_register(aloam_ctx* c, const void* h_scans, long long seq_s
   if (!c || !h_scans || !n_in) return ALOAM_E_ARG;
   int rc = check_batch(c, n_in, stride_bytes);
   if (rc) return rc;
-  if (seq_stride_bytes < 0) { c->err = "bad stride"; return ALOAM_E_ARG; }
-  const size_t row = (size_t)*std::max_element(n_in, n_in + c->B) * stride_bytes;
-  if (c->B > 1 && (size_t)seq_stride_bytes < row) { c->err = "seq_stride_bytes smaller than a scan"; return ALOAM_E_ARG; }
   const size_t d_seq_stride = (size_t)c->cap * stride_bytes;
   int slot = 0;
-  if ((rc = acquire_slab(c, d_seq_stride * c->B, &slot))) return rc;
-  char* d_in = c->d_in[slot].get();
-  if (row > 0) {
-    // rows 0 .. B-2 as one strided copy of the batch-wide maximum (every row but the last is followed by the next one, so the
-    // extra bytes are readable); the last row with its own length, so that a buffer that ends with the last sweep is never over-read
-    if (c->B > 1) HIP_TRY(c, hipMemcpy2DAsync(d_in, d_seq_stride, h_scans, (size_t)seq_stride_bytes, row, (size_t)c->B - 1, hipMemcpyHostToDevice, c->copy_stream));
-    const size_t last = (size_t)n_in[c->B - 1] * stride_bytes;
-    if (last > 0) HIP_TRY(c, hipMemcpyAsync(d_in + (size_t)(c->B - 1) * d_seq_stride, (const char*)h_scans + (size_t)(c->B - 1) * (size_t)seq_stride_bytes, last, hipMemcpyHostToDevice, c->copy_stream));
-  }
-  HIP_TRY(c, hipEventRecord(c->in_copied[slot], c->copy_stream));
-  HIP_TRY(c, hipStreamWaitEvent(c->stream, c->in_copied[slot], 0));
+  char* d_in = nullptr;
+  if ((rc = stage_batch(c, h_scans, seq_stride_bytes, (size_t)*std::max_element(n_in, n_in + c->B) * stride_bytes, (size_t)n_in[c->B - 1] * stride_bytes, d_seq_stride, &slot, &d_in))) return rc;
   return register_launch(c, d_in, (long long)d_seq_stride, n_in, stride_bytes, slot, debug_arrays);
 }
 

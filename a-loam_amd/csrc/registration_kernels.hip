@@ -5,6 +5,7 @@
 //   k_find_ends       :136-153   first / last kept point, startOri / endOri
 //   k_front           :85-112,156-241  the front end in one pass: NaN + range filter, ring id, azimuth, halfPassed, relTime -> intensity and
 //                                the STABLE per-ring compaction into one slab per ring (decoupled look-back over the blocks of a sweep)
+//   k_find_ends_range, k_front_range   the same two bodies over a sweep handed in as a 16-bit range image (RangeLoader)
 //   k_ring_starts     :246-252   ring lengths -> start of every ring in the reference's dense numbering, cloud size
 //   k_dense_cloud     :246-252   the dense ring-by-ring cloud from the slabs, only when a consumer of the full cloud asks
 //   k_ring_features   :256-407   one workgroup per (sweep, ring): 11-tap curvature from alternating 266-point LDS
@@ -23,11 +24,69 @@
 namespace aloam {
 
 // -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __restrict__ n_in) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (seq_idle(a.active, b)) return;                                         // a sequence that sits out: its n_in row is never read
-  const int n = n_in[b];
-  const char* in = a.in + (long long)b * a.seq_stride;
+// How the two kernels that read the raw sweep get point i of it: 16- / 12-byte float records (load_point), or the 16-bit range image of
+// aloam_range_decoder (RangeLoader below).  Everything behind the load is shared: find_ends_body, front_body.
+struct RecordLoader {
+  static constexpr bool kKeepPoint = true;                                    // front_body holds the point in registers from its load to its store
+  const char* in; int stride;
+  __device__ __forceinline__ float4 operator()(int i) const { return load_point(in, i, stride); }
+};
+
+// Point i of a range-image sweep, the definition of include/aloam_mi355x.h operation by operation (f32, every operation rounded on its own under
+// -ffp-contract=off; no trigonometry).  Loads: the range is ONE 2-byte load per point, consecutive lanes = consecutive points, so a wave-wide load is
+// 128 contiguous bytes; the azimuth code of the column likewise 2 bytes (column-major with 64 rows: one address per wave; row-major: consecutive);
+// {az_x, az_y} is one 8-byte gather from a table that lives in L2 (<= 512 kB); the per-row tables sit in LDS as [table][row] - consecutive rows fall
+// into consecutive banks, one row for the whole wave is a broadcast.
+// i -> (column, row) divides by a divisor known only at run time (rows, or in row-major order this sweep's n_cols): magic = floor((2^32 - 1) / d), made
+// once per workgroup; q = mulhi(i, magic) is floor(i / d) or one below it for every i < 2^32 (i / d - i * magic / 2^32 = i * (2^32 - magic * d) / (d * 2^32)
+// with 1 <= 2^32 - magic * d <= d, so the difference is below 1), and one compare of the remainder against d settles which: exact, no division per point.
+#ifndef ALOAM_RANGE_KEEP_POINT
+#define ALOAM_RANGE_KEEP_POINT 0                                              // 1: an A/B build (tools/build_variant.sh) that holds the point as k_front does
+#endif
+struct RangeLoader {
+  // front_body decodes the point a second time for its store instead of holding x, y, z of four points across the look-back: twelve registers less, which
+  // is what brings k_front_range to eight waves per SIMD with nothing spilled (k_front: 64 registers with six spilled).  The second decode reads what the
+  // first one left in the caches: 2 + 2 + 8 bytes and the LDS tables.
+  static constexpr bool kKeepPoint = ALOAM_RANGE_KEEP_POINT;
+  const unsigned short* az; const unsigned short* range;
+  const float2* az_xy; const float* tab;                                      // tab: the LDS copy of RangeArgs::row_tab
+  unsigned div, magic; int n_az; bool row_major; float scale;
+  __device__ __forceinline__ float4 operator()(int i) const {
+#ifdef ALOAM_RANGE_PHASES   // debug builds only: python tools/isa_phases.py registration_kernels k_front_range -DALOAM_RANGE_PHASES counts the decode (all its inlined copies)
+    asm volatile("; ##PHASE decode");
+#endif
+    const unsigned code = range[i];
+    unsigned q = __umulhi((unsigned)i, magic), r = (unsigned)i - q * div;
+    if (r >= div) { r -= div; ++q; }
+    const int row = (int)(row_major ? q : r), col = (int)(row_major ? r : q);
+    const int azc = az[col];
+    const bool hit = code != 0u && azc < n_az;                                // no return, or an azimuth code off the table
+    int ac = azc + reinterpret_cast<const int*>(tab)[4 * kMaxRings + row];    // |az_off| < n_az: one wrap either way
+    ac = ac < 0 ? ac + n_az : ac;
+    ac = ac >= n_az ? ac - n_az : ac;
+    const float2 cs = az_xy[hit ? ac : 0];                                    // (a code off the table must not become an address)
+    const float rho = (float)code * scale + tab[2 * kMaxRings + row];
+    const float rxy = rho * tab[0 * kMaxRings + row];
+    const float nan = __builtin_nanf("");
+#ifdef ALOAM_RANGE_PHASES
+    asm volatile("; ##PHASE body");
+#endif
+    return make_float4(hit ? rxy * cs.x : nan, hit ? rxy * cs.y : nan, hit ? rho * tab[1 * kMaxRings + row] + tab[3 * kMaxRings + row] : nan, tab[5 * kMaxRings + row]);
+  }
+};
+// The loader of sweep b; `tab` is filled by the whole workgroup (ends with a barrier).
+__device__ __forceinline__ RangeLoader range_loader(const RegArgs& a, const RangeArgs& d, int b, float* tab) {
+  for (int q = threadIdx.x; q < kRangeRowTables * kMaxRings; q += blockDim.x) tab[q] = d.row_tab[q];
+  __syncthreads();
+  const int n_cols = d.n_cols[b];
+  const unsigned short* blob = reinterpret_cast<const unsigned short*>(a.in + (long long)b * a.seq_stride);
+  const unsigned div = (unsigned)(d.row_major ? n_cols : d.rows);
+  return RangeLoader{blob, blob + ((n_cols + 7) & ~7), d.az_xy, tab, div, div ? 0xffffffffu / div : 0u, d.n_az, d.row_major != 0, d.range_scale};
+}
+
+template <class Loader>
+__device__ __forceinline__ void find_ends_body(const RegArgs& a, const int b, const int n, const Loader& load) {
+  const int tid = threadIdx.x;
   __shared__ int s_first, s_last;
   if (tid == 0) { s_first = 0x7fffffff; s_last = -1; }
   __syncthreads();
@@ -37,7 +96,7 @@ __global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __rest
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int i = base + k * 1024 + tid;
-      if (i < n && point_kept(load_point(in, i, a.pt_stride), a.min_range)) { atomicMin(&s_first, i); any = true; }
+      if (i < n && point_kept(load(i), a.min_range)) { atomicMin(&s_first, i); any = true; }
     }
     if (__syncthreads_or(any)) break;
   }
@@ -46,7 +105,7 @@ __global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __rest
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int i = n - 1 - (base + k * 1024 + tid);
-      if (i >= 0 && point_kept(load_point(in, i, a.pt_stride), a.min_range)) { atomicMax(&s_last, i); any = true; }
+      if (i >= 0 && point_kept(load(i), a.min_range)) { atomicMax(&s_last, i); any = true; }
     }
     if (__syncthreads_or(any)) break;
   }
@@ -64,8 +123,8 @@ __global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __rest
     if (s_last < 0) {
       m.err = kErrEmpty;
     } else {
-      const float4 p0 = load_point(in, s_first, a.pt_stride);
-      const float4 p1 = load_point(in, s_last, a.pt_stride);
+      const float4 p0 = load(s_first);
+      const float4 p1 = load(s_last);
       const float startOri = -atan2f_port(p0.y, p0.x);                                  // :141
       float endOri = (float)((double)(-atan2f_port(p1.y, p1.x)) + 2 * M_PI);             // :142-144
       if ((double)(endOri - startOri) > 3 * M_PI) endOri = (float)((double)endOri - 2 * M_PI);      // :146-149
@@ -76,6 +135,11 @@ __global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __rest
     if (n > a.cap) m.err |= kErrPointCap;
     a.meta[b] = m;
   }
+}
+__global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __restrict__ n_in) {
+  const int b = blockIdx.x;
+  if (seq_idle(a.active, b)) return;                                         // a sequence that sits out: its n_in row is never read
+  find_ends_body(a, b, n_in[b], RecordLoader{a.in + (long long)b * a.seq_stride, a.pt_stride});
 }
 
 // Ring id from the elevation angle in degrees, exactly the expressions of reference src/scanRegistration.cpp:169-205; -1 = rejected.
@@ -164,7 +228,8 @@ __device__ __forceinline__ int front_lookback(unsigned long long* slot0, int blk
 
 // Measured at batch 1024 (A/B on one box): 1.13 ms (1.15 without the eight-waves hint, which costs six spilled registers); block-major launch order
 // 1.59 ms (the look-back chains); with the waits compiled out 1.07 ms: the look-back costs 0.06 ms.  Before: k_classify 0.89 + k_ring_offsets 0.02 + k_scatter 0.76.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_front(RegArgs a) {
+template <bool FIELD_RING, class MakeLoader>
+__device__ __forceinline__ void front_body(const RegArgs& a, const MakeLoader& make_loader) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   __shared__ int s_cnt[16][kMaxRings];        // [round * 4 + wave][ring]: points of that ring in that wave's round -> offsets inside the ring's slab
   __shared__ int s_half, s_ticket;
@@ -176,7 +241,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
   const SeqMeta m = a.meta[b];
   const int n = m.n_in < a.cap ? m.n_in : a.cap;
   if (blk * kBlockPts >= n) return;            // (every later ticket of the sweep returns here too: nobody waits for this block)
-  const char* in = a.in + (long long)b * a.seq_stride;
+  const auto load = make_loader(b);
   const float startOri = m.start_ori, endOri = m.end_ori;
   int ring[4], rank[4];
   float4 p[4];
@@ -189,11 +254,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     p[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     ori[k] = 0.f;
     if (i < n) {
-      const float4 q = load_point(in, i, a.pt_stride);
+      const float4 q = load(i);
       if (point_kept(q, a.min_range)) {
-        ring[k] = ring_of(q, a.R, a.ring_from_field);
+        ring[k] = ring_of(q, a.R, FIELD_RING ? 1 : a.ring_from_field);
         if (ring[k] >= 0) {
-          p[k] = q;
+          if constexpr (decltype(load)::kKeepPoint) p[k] = q;
           ori[k] = -atan2f_port(q.y, q.x);                                                  // :208
           float o1 = ori[k];                                                                // branch taken while !halfPassed
           if ((double)o1 < (double)startOri - M_PI / 2) o1 = (float)((double)o1 + 2 * M_PI);          // :211-214
@@ -251,10 +316,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     }
     const float relTime = (o - startOri) / (endOri - startOri);                               // :238
     const float inten = (float)((double)ring[k] + 0.1 * (double)relTime);                     // :239, scanPeriod 0.1
-    if (pos < a.slab) slabs[(long long)ring[k] * a.slab + pos] = make_float4(p[k].x, p[k].y, p[k].z, inten);   // (a ring longer than its slab: kErrRingCap, k_ring_starts)
+    float4 pk = p[k];
+    if constexpr (!decltype(load)::kKeepPoint) pk = load(i);
+    if (pos < a.slab) slabs[(long long)ring[k] * a.slab + pos] = make_float4(pk.x, pk.y, pk.z, inten);   // (a ring longer than its slab: kErrRingCap, k_ring_starts)
   }
 }
-
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_front(RegArgs a) {
+  front_body<false>(a, [&](int b) { return RecordLoader{a.in + (long long)b * a.seq_stride, a.pt_stride}; });
+}
 // After the pass: ring lengths = the inclusive prefixes of the sweep's last block; scanStartInd-like dense starts (ringstart, :246-252 in the
 // reference's dense numbering), the cloud size, the halfPassed index; the block tickets of the next launch.  One wave per sweep.
 __global__ __launch_bounds__(64) void k_ring_starts(RegArgs a) {
@@ -980,6 +1049,22 @@ __global__ __launch_bounds__(64) void k_cloud_sizes(RegArgs a) {
   if (lane == 0) { a.meta[b].n_sharp = n0; a.meta[b].n_less_sharp = n1; a.meta[b].n_flat = n2; a.meta[b].n_less_flat = n3; a.ring_ticket[b] = 0; }   // tickets for the next launch
 }
 
+// ---- range-image input (kept behind the other kernels: their code does not move) --------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_find_ends_range(RegArgs a, RangeArgs d) {
+  const int b = blockIdx.x;
+  __shared__ float s_tab[kRangeRowTables * kMaxRings];
+  if (seq_idle(a.active, b)) return;
+  find_ends_body(a, b, d.n_cols[b] * d.rows, range_loader(a, d, b, s_tab));
+}
+
+// The same pass over a range image: the ring is the row's ring_id (carried in w, the ring_from_field rule), so ring_of's polynomial and its f64
+// fallback are not in this kernel at all, and the sweep is read at 2 bytes per point.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_front_range(RegArgs a, RangeArgs d) {
+  __shared__ float s_tab[kRangeRowTables * kMaxRings];
+  if (seq_idle(a.active, blockIdx.x)) return;  // (front_body asks again: before its ticket, and before this kernel's barrier)
+  front_body<true>(a, [&](int b) { return range_loader(a, d, b, s_tab); });
+}
+
 // -------------------------------------------------------------------------------------------------------
 size_t ring_features_lds_bytes(int npad) {
   const int maxn = npad + 11;
@@ -990,6 +1075,8 @@ size_t ring_features_lds_bytes(int npad) {
 
 void launch_find_ends(const RegArgs& a, const int* d_nin, hipStream_t s) { hipLaunchKernelGGL(k_find_ends, dim3(a.B), dim3(1024), 0, s, a, d_nin); }
 void launch_front(const RegArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_front, dim3(a.B, a.NB), dim3(256), 0, s, a); }   // sweep-major, see k_front   // sweep-major, see k_front
+void launch_find_ends_range(const RegArgs& a, const RangeArgs& d, hipStream_t s) { hipLaunchKernelGGL(k_find_ends_range, dim3(a.B), dim3(1024), 0, s, a, d); }
+void launch_front_range(const RegArgs& a, const RangeArgs& d, hipStream_t s) { hipLaunchKernelGGL(k_front_range, dim3(a.B, a.NB), dim3(256), 0, s, a, d); }
 void launch_ring_starts(const RegArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_ring_starts, dim3(a.B), dim3(64), 0, s, a); }
 void launch_dense_cloud(const RegArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_dense_cloud, dim3(a.R, a.B), dim3(256), 0, s, a); }
 void launch_ring_features(const RegArgs& a, int npad, float leaf, hipStream_t s) {

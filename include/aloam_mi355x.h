@@ -125,6 +125,56 @@ int aloam_process_device(aloam_ctx* ctx, const void* d_scans, long long seq_stri
 
 int aloam_process_host(aloam_ctx* ctx, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes);   /* same from a host buffer (see aloam_scan_register_host) */
 
+/* ---- stage 1 from 16-bit range images ----------------------------------------------------------------------------------------
+ * A spinning LiDAR produces a 16-bit range per laser and firing and a 16-bit azimuth per firing; a driver inflates that to 12 - 16 bytes per point
+ * before laserCloudHandler sees it (reference src/scanRegistration.cpp:127-133).  These entries take the sensor's own numbers, 2 bytes per point, and
+ * decode them in the front-end kernels: a sixth to an eighth of the PCIe bytes of the host-fed path.
+ *
+ * aloam_range_decoder describes the sensor: set once per context (the tables are copied to the device; the call waits for the stream).
+ *
+ * A sweep of n_cols columns is one blob per sequence:
+ *     uint16 az[(n_cols + 7) & ~7]      azimuth code of every column (the padding makes the ranges start 16-byte aligned)
+ *     uint16 range[n_cols * rows]       in the decoder's order
+ * Point i of the sweep, every operation in f32 and rounded on its own:
+ *     (col, row) = COLUMN_MAJOR: (i / rows, i % rows);  ROW_MAJOR: (i % n_cols, i / n_cols)
+ *     code = range[i];   a = (az[col] + az_off[row]) mod n_az                       (into 0 .. n_az-1)
+ *     rho  = (float)code * range_scale + range_off[row]
+ *     rxy  = rho * cos_el[row]
+ *     x = rxy * az_x[a];   y = rxy * az_y[a];   z = rho * sin_el[row] + z_off[row];   w = (float)ring_id[row]
+ * code == 0 (no return) or az[col] >= n_az gives (NaN, NaN, NaN): the NaN filter removes it, as removeNaNFromPointCloud would
+ * (src/scanRegistration.cpp:136).  The decoded sweep, no-return cells included and in storage order, IS the input of laserCloudHandler: everything
+ * downstream evaluates the reference's expressions on that f32 point, and the ring is (int)w under the ring_from_field rule (outside 0 .. n_scans-1:
+ * rejected; such a point still counts for the first / last kept point).  The reference's elevation formulas (:166-205) are not evaluated and
+ * aloam_config.ring_from_field plays no part.  There is no trigonometry on the device: the caller's az_x / az_y fix the axis convention. */
+enum { ALOAM_RANGE_COLUMN_MAJOR = 0,   /* firing order: point i = column i / rows, row i % rows                       */
+       ALOAM_RANGE_ROW_MAJOR = 1 };    /* ring-major (KITTI-like): point i = row i / n_cols, column i % n_cols        */
+typedef struct aloam_range_decoder {
+  int rows;                /* lasers per column, 1 .. 128                                                                        */
+  int n_az;                /* azimuth codes per turn, 1 .. 65536 (Velodyne: 36000)                                               */
+  int order;               /* ALOAM_RANGE_COLUMN_MAJOR / ALOAM_RANGE_ROW_MAJOR                                                   */
+  float range_scale;       /* metres per range code                                                                              */
+  const float* az_x;       /* [n_az] cosine of the azimuth of every code, in the caller's axis convention                        */
+  const float* az_y;       /* [n_az] sine                                                                                        */
+  const float* cos_el;     /* [rows] cosine of every laser's elevation                                                           */
+  const float* sin_el;     /* [rows] sine                                                                                        */
+  const float* range_off;  /* [rows] metres added to the scaled range                                                            */
+  const float* z_off;      /* [rows] metres added to z (vertical offset of the laser)                                            */
+  const int* az_off;       /* [rows] azimuth codes added to the column's, |az_off| < n_az: the per-laser rotational correction   */
+  const int* ring_id;      /* [rows] the reference's scanID of every laser, 0 .. n_scans-1, or -1: the row is rejected (how a caller
+                              reproduces the scanID > 50 cut of src/scanRegistration.cpp:198 on HDL-64)                          */
+} aloam_range_decoder;
+/* ALOAM_E_ARG on any bad field (aloam_last_error names it), nothing is changed then.  May be called again with another decoder. */
+int aloam_set_range_decoder(aloam_ctx* ctx, const aloam_range_decoder* decoder);
+/* The four entries of stage 1 / the throughput path for range images: sequence b's blob at base + b * seq_stride_bytes holds n_cols[b] columns.
+ * n_cols[b] * rows > max_points: ALOAM_E_CAPACITY; a negative count: ALOAM_E_ARG; before aloam_set_range_decoder: ALOAM_E_STATE - each before
+ * anything is queued.  Device blobs must be 2-byte aligned with an even seq_stride_bytes.  The host forms go through the same two staging slabs, copy
+ * stream and events as aloam_scan_register_host (aloam_input_consumed works unchanged; rows 0 .. batch-2 are copied with the batch-wide largest blob
+ * length), and a context may alternate between float records and range images from one sweep to the next. */
+int aloam_scan_register_range_device(aloam_ctx* ctx, const void* d_sweeps, long long seq_stride_bytes, const int* n_cols);
+int aloam_scan_register_range_host(aloam_ctx* ctx, const void* h_sweeps, long long seq_stride_bytes, const int* n_cols);
+int aloam_process_range_device(aloam_ctx* ctx, const void* d_sweeps, long long seq_stride_bytes, const int* n_cols);   /* + aloam_odometry_step */
+int aloam_process_range_host(aloam_ctx* ctx, const void* h_sweeps, long long seq_stride_bytes, const int* n_cols);     /* + aloam_odometry_step */
+
 /* ---- stage 3: scan-to-map refinement, body of process() (reference src/laserMapping.cpp:231-893), no frame dropping ---- */
 /* Replaces the node's globals (cube arrays laserCloudCornerArray / SurfArray[4851], q_wmap_wodom, t_wmap_wodom, `parameters`,
  * laserCloudCen*; src/laserMapping.cpp:72-116) and reads the launch parameters mapping_line_resolution / mapping_plane_resolution

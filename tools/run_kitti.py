@@ -24,6 +24,11 @@ metres of travel, in the same file; `--prior-atlas a.npz --global-relocalize` th
 against the stored places (aloam_places_match), the pose and yaw of the best one become the first guess (a-loam_amd/places.py
 guess_from_match), one frozen step is taken from it, relocalize() searches its default grid around it, and the run continues.
 
+`--range-input` hands every sweep over as a 16-bit range image instead of float records (aloam_set_range_decoder, aloam_scan_register_range_host): the
+.bin sweep is put back on the grid of an HDL-64 with --range-columns columns (a-loam_amd/range_input.py encode_sweep: nearest ray, range quantised
+to 2 mm) - what a driver would hand over had it kept the sensor's own numbers.  Meant for the --selftest drive, whose sensor is known; recorded KITTI
+sweeps are motion-compensated and no longer sit on a grid.
+
 `--seqs 00 05 07 ... --batch N` runs several sequences at once by continuous batching (schedule() below): every one of the N slots of one
 context runs one sequence; when it ends, the slot is reset in place (aloam_reset_sequences) and takes the next one, and slots with nothing
 left sit the step out (aloam_set_active).  `--slice K` time-slices more sequences than slots (schedule_sliced()): after K frames a sequence
@@ -236,6 +241,9 @@ def main():
                     "pose) every this many metres of travel, in the same file; 0 stores none")
     ap.add_argument("--global-relocalize", action="store_true", help="with --prior-atlas, instead of --initial-pose: match the first sweep against the places "
                     "stored in the atlas file, start from the best one's pose and yaw, then search relocalize()'s default grid around it")
+    ap.add_argument("--range-input", action="store_true", help="hand the sweeps over as 16-bit range images (encoded from the .bin points on the grid of an "
+                    "HDL-64 with --range-columns columns) through the range entry points")
+    ap.add_argument("--range-columns", type=int, default=1024, help="with --range-input: columns of the sensor grid (the --selftest drive has 1024)")
     args = ap.parse_args()
     if args.global_relocalize and not args.prior_atlas:
         ap.error("--global-relocalize needs --prior-atlas")
@@ -275,6 +283,12 @@ def main():
     gpu = binding.Aloam(n_scans=64, min_range=5.0, batch=batch, max_points=140000, distortion=args.distortion)
     if args.reference_order:
         gpu.set_voxel_sum_order(True)
+    rin = None
+    if args.range_input:                               # the sensor of the drive, and its decoder
+        rin = importlib.import_module("a-loam_amd.range_input")
+        range_model = importlib.import_module("a-loam_amd.synthetic").sensor_model("HDL-64", columns=args.range_columns)
+        range_dec = rin.decoder_from_model(range_model)
+        gpu.set_range_decoder(range_dec)
     if args.mapping:
         gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)          # where the map starts: the pools double as it grows (src/laserMapping.cpp:737-783 push_back)
     os.makedirs(args.out, exist_ok=True)
@@ -319,7 +333,11 @@ def main():
         scans = [idle] * batch
         for slot, (i, k) in frames.items():
             scans[slot] = read_lidar(os.path.join(args.dataset, "velodyne", "sequences", seqs[i], "velodyne", f"{k:06d}.bin"))
-        gpu.scan_register(scans)
+        if rin:
+            blobs = [rin.encode_sweep(x, range_model, range_dec)[0] if len(x) else np.zeros(0, np.uint16) for x in scans]
+            gpu.scan_register_range(blobs, [args.range_columns if len(x) else 0 for x in scans])
+        else:
+            gpu.scan_register(scans)
         gpu.odometry_step()
         if stored is not None and guess is not None:   # the first sweep: its best stored place is the first guess
             guess = global_guess(gpu, stored)
