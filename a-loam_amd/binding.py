@@ -46,6 +46,25 @@ class AloamPoseRecord(C.Structure):
                 ("inited", C.c_int), ("map_frames", C.c_int), ("pad", C.c_int * 2)]
 
 
+class AloamPoseInformation(C.Structure):
+    """The information matrix of one solve (aloam_pose_information, 1048 bytes); a-loam_amd/information.py holds the definition."""
+    _fields_ = [("info", C.c_double * 36), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36),
+                ("trans_info", C.c_double * 9), ("trans_eigenvalues", C.c_double * 3), ("trans_eigenvectors", C.c_double * 9),
+                ("rot_info", C.c_double * 9), ("rot_eigenvalues", C.c_double * 3), ("rot_eigenvectors", C.c_double * 9),
+                ("gradient", C.c_double * 6), ("cost", C.c_double), ("n_line", C.c_int), ("n_plane", C.c_int), ("rows", C.c_int),
+                ("status", C.c_int), ("frame", C.c_int), ("pad", C.c_int * 3)]
+
+
+INFO_ODOMETRY, INFO_MAPPING = 0, 1
+INFO_OK, INFO_NONE, INFO_NO_FACTORS, INFO_SINGULAR = 0, 1, 2, 3
+POSE_INFORMATION_DTYPE = np.dtype([
+    ("info", np.float64, (6, 6)), ("eigenvalues", np.float64, 6), ("eigenvectors", np.float64, (6, 6)),
+    ("trans_info", np.float64, (3, 3)), ("trans_eigenvalues", np.float64, 3), ("trans_eigenvectors", np.float64, (3, 3)),
+    ("rot_info", np.float64, (3, 3)), ("rot_eigenvalues", np.float64, 3), ("rot_eigenvectors", np.float64, (3, 3)),
+    ("gradient", np.float64, 6), ("cost", np.float64), ("n_line", np.int32), ("n_plane", np.int32), ("rows", np.int32),
+    ("status", np.int32), ("frame", np.int32), ("pad", np.int32, 3)])
+
+
 class AloamMapCorrection(C.Structure):
     """One candidate map <- odometry correction (aloam_map_correction, 64 bytes)."""
     _fields_ = [("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3), ("pad", C.c_double)]
@@ -232,6 +251,8 @@ def lib():
         L.aloam_get_map_cloud.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
         L.aloam_export_poses.argtypes = [vp, vp]
         L.aloam_export_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
+        L.aloam_export_pose_information.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+        L.aloam_get_map_factors.argtypes = [vp, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -733,6 +754,31 @@ class Aloam:
         them), segment (i, b) at [offsets[i * batch + b], offsets[i * batch + b + 1]); offsets_ptr receives len(ids) * batch + 1 int64."""
         a = (C.c_int * max(1, len(ids)))(*[int(v) for v in ids])
         self._check(lib().aloam_export_clouds(self.h, a, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None, int(cap_points), C.c_void_p(offsets_ptr)))
+
+    def export_pose_information_into(self, which, seqs, dst_ptr):
+        """Queue one aloam_pose_information per listed sequence (INFO_ODOMETRY / INFO_MAPPING) into dst_ptr: device memory of this
+        context's device, or pinned host memory."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_export_pose_information(self.h, int(which), _p(ids) if len(ids) else None, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def export_pose_information(self, which, seqs, pinned=True):
+        """The records of `seqs` after a synchronise: a structured array [len(seqs)] of POSE_INFORMATION_DTYPE (information.py says what a
+        caller does with one); with pinned=False the destination is device memory, copied back afterwards."""
+        import torch
+        n = len(seqs)
+        buf = torch.zeros(max(1, n) * POSE_INFORMATION_DTYPE.itemsize, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.export_pose_information_into(which, seqs, buf.data_ptr())
+        self.synchronize()
+        return buf.cpu().numpy()[:n * POSE_INFORMATION_DTYPE.itemsize].view(POSE_INFORMATION_DTYPE).copy()
+
+    def map_factors(self, seq=0):
+        """The factor records the last mapping solve of `seq` read: (lines [n, 9] cp, a, b; planes [m, 7] cp, n, d), float64, in the solver's order."""
+        nl, npl = C.c_int(0), C.c_int(0)
+        self._check(lib().aloam_get_map_factors(self.h, seq, None, 0, C.byref(nl), None, 0, C.byref(npl)))
+        lines, planes = np.zeros((nl.value, 9)), np.zeros((npl.value, 7))
+        self._check(lib().aloam_get_map_factors(self.h, seq, _p(lines) if nl.value else None, nl.value, C.byref(nl),
+                                                _p(planes) if npl.value else None, npl.value, C.byref(npl)))
+        return lines, planes
 
     def export_segment(self, points, offsets, ids, which, seq):
         """The points of cloud `which` of sequence `seq` in an export's destination (a torch tensor or numpy array of float32, viewed as

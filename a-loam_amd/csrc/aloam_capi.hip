@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "capi_internal.hpp"
+#include "information_device.hpp"
 
 namespace aloam {
 
@@ -372,6 +373,19 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
     if (c->map_on && kernel == K_SCORE) {
       bytes = 64.0 * c->rl_last_K + 32.0 * c->rl_last_seqs.size() * c->rl_last_K;
       for (const int b : c->rl_last_seqs) bytes += 16.0 * (ms[b].n_stack[0] + ms[b].n_stack[1]) + 16.0 * (ms[b].from_total[0] + ms[b].from_total[1]) + 8.0 * c->map.H;
+    }
+    // the last aloam_export_pose_information: the valid records of the listed sequences that had a solve, read once, and one record written per id
+    if (kernel == K_POSE_INFO) {
+      bytes = (double)sizeof(aloam_pose_information) * c->info_last_list.size();
+      std::vector<OdomState> os(c->info_last_which == ALOAM_INFO_ODOMETRY && !c->info_last_list.empty() ? c->B : 0);
+      if (!os.empty()) HIP_TRY(c, hipMemcpy(os.data(), c->d_state.get(), sizeof(OdomState) * c->B, hipMemcpyDeviceToHost));
+      const int o = c->cfg.outer_iterations < 2 ? 0 : 1;
+      for (const int code : c->info_last_list) {
+        if (!(code & kInfoSolvedBit)) continue;
+        const int b = code & kInfoSeqMask;
+        if (c->info_last_which == ALOAM_INFO_ODOMETRY) bytes += (double)sizeof(EdgeRec) * os[b].corner_corr[o] + (double)sizeof(PlaneRec) * os[b].plane_corr[o];
+        else if (c->map_on) bytes += (double)sizeof(MapEdgeRec) * ms[b].factor_num[1][0] + (double)sizeof(MapNormRec) * ms[b].factor_num[1][1];
+      }
     }
     if (kernel == K_APPLY) bytes = c->rl_apply_n * (4.0 + 4.0 + 64.0 + 56.0);   // id, choice, candidate in, correction out
     *algorithmic_bytes = bytes;

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,11 +28,11 @@ using namespace aloam;
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "save_sequences",
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "save_sequences",
                                     "load_sequences", "score_corrections", "apply_corrections"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
@@ -89,6 +89,8 @@ struct SeqHost {
   bool attached = false;             // mirror of d_at_attached (with the device mark d_at_stale: the next step cuts the window anew)
   bool has_sweep = false;            // holds a registered sweep (since creation / reset / load): a place descriptor can be made
   bool desc_valid = false;           // d_pl_desc[b] is that sweep's
+  bool info_odom = false, info_map = false;   // the records and the pose of its last odometry / mapping solve are still in place
+                                     // (aloam_export_pose_information; else ALOAM_INFO_NONE).  Host state only: not part of a sequence record
   bool grid_built = false;           // the grid set of its LAST clouds holds their grids: set by the step that made them the last ones (it built
                                      // them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
 };
@@ -189,6 +191,9 @@ struct aloam_ctx {
   long long rl_bad_reported = 0;                                    // of d_rl_bad, already returned by aloam_synchronize
   std::vector<int> rl_last_seqs; int rl_last_K = 0;                 // the last scoring call: its listed sequences and K (algorithmic bytes)
   int rl_apply_n = 0;
+  // pose information (aloam_export_pose_information)
+  DevBuf<int> d_info_list;                                          // [B] listed ids with their "solved" bit
+  std::vector<int> info_last_list; int info_last_which = 0;         // the last call (algorithmic bytes)
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -326,6 +331,9 @@ int stage_batch(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, s
 int ensure_dense(aloam_ctx* c);
 long long cloud_desc(const aloam_ctx* c, int id, ExportSrc* s);
 int find_cloud(aloam_ctx* c, int seq, int id, const float4** ptr, int* n);
+// capi_odometry.hip / capi_mapping.hip: the kernel arguments of a stage as the context stands (the caller sets `active`)
+OdomArgs odom_args(aloam_ctx* c);
+MapArgs map_args(aloam_ctx* c);
 // capi_mapping.hip
 int grow_map_pool(aloam_ctx* c, long long want, bool clamp);
 // capi_atlas.hip
@@ -348,6 +356,8 @@ void on_slot_loaded(aloam_ctx* c, int seq, bool inited, long long err_events);
 void on_sweep_registered(aloam_ctx* c);
 void on_odometry_advanced(aloam_ctx* c, const StageMask& m);
 void on_last_clouds_replaced(aloam_ctx* c, int seq);
+void on_odometry_inputs_replaced(aloam_ctx* c, int seq);
+void on_map_corrections_applied(aloam_ctx* c, const int* seqs, int n);
 void on_system_inited_forced(aloam_ctx* c, int inited);
 int on_map_replaced(aloam_ctx* c, int seq);
 int on_map_pool_reallocated(aloam_ctx* c, MapPool&& fresh);

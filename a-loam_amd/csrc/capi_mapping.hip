@@ -6,7 +6,8 @@
 #include "capi_internal.hpp"
 
 // ---- stage 3: scan-to-map refinement --------------------------------------------------------------------------------
-static MapArgs map_args(aloam_ctx* c) {
+namespace aloam {
+MapArgs map_args(aloam_ctx* c) {
   MapArgs a{};
   a.B = c->B; a.cap = c->cap; a.R = c->R;
   a.meta = c->d_meta.get(); a.odom = c->d_state.get(); a.seq = c->d_mapseq.get();
@@ -30,7 +31,6 @@ static MapArgs map_args(aloam_ctx* c) {
   a.rec_tiles = c->d_rec_tiles.get(); a.rec_tiles_per_seq = c->rec_tiles_per_seq; a.rec_tiles_corner = c->rec_tiles_corner;
   return a;
 }
-namespace aloam {
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels) {
   VoxArgs v{};
   v.segs = c->d_segs.get(); v.n_segs = n_segs; v.tile_seg = c->map.tile_seg.get(); v.tile_heads = c->map.tile_heads.get(); v.tile_pref = c->map.tile_pref.get();

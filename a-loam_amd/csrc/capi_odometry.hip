@@ -21,6 +21,10 @@ RegArgs reg_args(aloam_ctx* c, const void* d_scans, long long seq_stride, int pt
   return a;
 }
 
+}  // namespace
+
+namespace aloam {
+
 OdomArgs odom_args(aloam_ctx* c) {
   OdomArgs a{};
   a.B = c->B; a.cap = c->cap; a.R = c->R;
@@ -40,6 +44,10 @@ OdomArgs odom_args(aloam_ctx* c) {
   a.distortion = c->cfg.distortion != 0;
   return a;
 }
+
+}  // namespace aloam
+
+namespace {
 
 // A batch handed to scan registration, checked before anything of it is queued.
 int check_batch(aloam_ctx* c, const int* n_in, int stride_bytes) {
@@ -386,6 +394,7 @@ int aloam_set_features(aloam_ctx* c, int seq, const float* sharp, int n_sharp, c
   for (auto& x : in) if (x.n) HIP_TRY(c, hipMemcpy(cloud_row(c, x.s, seq), x.pts, sizeof(float4) * x.n, hipMemcpyHostToDevice));
   if ((rc = edit_seq(c, c->d_meta.get() + seq, [&](SeqMeta& m) { m.n_sharp = n_sharp; m.n_less_sharp = n_less_sharp; m.n_flat = n_flat; m.n_less_flat = n_less_flat; m.err = 0; }))) return rc;
   c->have_features = true;
+  on_odometry_inputs_replaced(c, seq);
   return ALOAM_OK;
 }
 
@@ -407,6 +416,7 @@ int aloam_set_state(aloam_ctx* c, int seq, const double para_q[4], const double 
   DeviceScope device_scope(c);
   int rc = check_seq(c, seq);
   if (rc) return rc;
+  on_odometry_inputs_replaced(c, seq);
   return edit_seq(c, c->d_state.get() + seq, [&](OdomState& s) {
     for (int k = 0; k < 4; ++k) { s.para_q[k] = para_q[k]; s.q_w[k] = q_w[k]; }
     for (int k = 0; k < 3; ++k) { s.para_t[k] = para_t[k]; s.t_w[k] = t_w[k]; }

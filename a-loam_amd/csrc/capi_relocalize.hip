@@ -89,6 +89,7 @@ int aloam_apply_map_corrections(aloam_ctx* c, const int* seqs, int n, const aloa
   { ProfScope p(c, K_APPLY); launch_apply_corrections(a, c->stream); }
   HIP_TRY(c, hipGetLastError());
   c->rl_apply_n = n;
+  on_map_corrections_applied(c, seqs, n);
   return ALOAM_OK;
 }
 

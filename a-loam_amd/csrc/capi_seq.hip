@@ -54,6 +54,7 @@ int on_slots_reset(aloam_ctx* c, const int* seqs, int n) {
   for (int i = 0; i < n; ++i) {
     SeqHost& s = c->seq[seqs[i]];
     s.parity = 0; s.inited = 0; s.grid_built = false; s.needs_odom = false; s.map_err_seen = 0; s.scorable = false; s.has_sweep = false; s.desc_valid = false;
+    s.info_odom = false; s.info_map = false;
   }
   for (int i = 0; i < n; ++i) if (const int rc = mark_window_stale(c, seqs[i])) return rc;
   return ALOAM_OK;
@@ -71,7 +72,7 @@ void on_sweep_registered(aloam_ctx* c) {
   for (int b = 0; b < c->B; ++b) {
     SeqHost& s = c->seq[b];
     if (odo) s.reg_active = s.active;
-    if (takes_part(c, b)) { s.has_sweep = true; s.desc_valid = false; }
+    if (takes_part(c, b)) { s.has_sweep = true; s.desc_valid = false; s.info_odom = false; }   // (the feature counts its records are read through are the new sweep's)
   }
   if (odo) c->reg_pending = true;
 }
@@ -80,17 +81,21 @@ void on_sweep_registered(aloam_ctx* c) {
 void on_odometry_advanced(aloam_ctx* c, const StageMask& m) {
   for (int b = 0; b < c->B; ++b) {
     SeqHost& s = c->seq[b];
-    if (m.bits[b] & kSeqActive) { s.parity ^= 1; s.inited = 1; s.needs_odom = false; s.grid_built = c->grid_overlap; }
+    if (m.bits[b] & kSeqActive) {
+      s.parity ^= 1; s.inited = 1; s.needs_odom = false; s.grid_built = c->grid_overlap;
+      s.info_odom = (m.bits[b] & kSeqSolve) && c->cfg.outer_iterations > 0;   // a first frame solves nothing
+    }
   }
   c->reg_pending = false;
 }
 
-void on_last_clouds_replaced(aloam_ctx* c, int seq) { c->seq[seq].grid_built = false; }   // aloam_set_last: the next step builds their grids before it searches
+void on_last_clouds_replaced(aloam_ctx* c, int seq) { c->seq[seq].grid_built = false; c->seq[seq].info_odom = false; }   // aloam_set_last: the next step builds their grids before it searches
+void on_odometry_inputs_replaced(aloam_ctx* c, int seq) { c->seq[seq].info_odom = false; }   // aloam_set_state / aloam_set_features: the pose or the feature counts of its last solve are gone
 
 // aloam_set_map / aloam_set_map_frame: another submap or frame, so its grids are built anew, nothing to score against, an attached window is cut anew.
 int on_map_replaced(aloam_ctx* c, int seq) {
   HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seq * 2, 0, sizeof(MapGridSig) * 2, c->stream));
-  c->seq[seq].scorable = false;
+  c->seq[seq].scorable = false; c->seq[seq].info_map = false;
   return mark_window_stale(c, seq);
 }
 
@@ -104,8 +109,10 @@ int on_map_pool_reallocated(aloam_ctx* c, MapPool&& fresh) {
 }
 
 void on_mapping_step_queued(aloam_ctx* c) {   // aloam_score_map_corrections may read the stacks and the grid that a frozen step leaves
-  for (int b = 0; b < c->B; ++b) if (takes_part(c, b)) c->seq[b].scorable = c->seq[b].frozen;
+  for (int b = 0; b < c->B; ++b) if (takes_part(c, b)) { c->seq[b].scorable = c->seq[b].frozen; c->seq[b].info_map = true; }
 }
+void on_map_corrections_applied(aloam_ctx* c, const int* seqs, int n) { for (int i = 0; i < n; ++i) c->seq[seqs[i]].info_map = false; }   // the pose of its last solve is in a frame that is gone
+
 
 // aloam_atlas_attach has staged the mask: a newly attached sequence cuts its window in its next step and has nothing to score against.
 int on_atlas_attached(aloam_ctx* c, const std::vector<int>& attached) {

@@ -2,6 +2,8 @@
 #pragma once
 #include "aloam_device.hpp"
 
+struct aloam_pose_information;
+
 namespace aloam {
 
 constexpr int kMapW = 21, kMapH = 21, kMapD = 11, kMapCubes = kMapW * kMapH * kMapD;   // reference src/laserMapping.cpp:75-80
@@ -130,6 +132,8 @@ int prepare_map_grid(int H);
 void launch_map_grid(const MapArgs& a, hipStream_t s);
 void launch_map_associate(const MapArgs& a, int iter, hipStream_t s);
 void launch_map_solve(const MapArgs& a, int iter, bool last, hipStream_t s);
+// list[n]: sequence | kInfoSolvedBit (information_device.hpp); dst[n] as the device reaches it
+void launch_pose_information_map(const MapArgs& a, const int* list, int n, aloam_pose_information* dst, hipStream_t s);
 void launch_map_insert(const MapArgs& a, float4* staging, hipStream_t s);   // staging: 2 pools per sequence
 void launch_map_register(const MapArgs& a, hipStream_t s);   // reads the slabs when a.slabs is set, the dense cloud otherwise
 void launch_map_report(const MapArgs& a, int step, hipStream_t s);

@@ -2,6 +2,8 @@
 #pragma once
 #include "aloam_device.hpp"
 
+struct aloam_pose_information;
+
 namespace aloam {
 size_t build_grids_lds_bytes(int H, int R);
 int prepare_build_grids(int H_surf);
@@ -10,5 +12,7 @@ void launch_transform_queries(const OdomArgs& a, hipStream_t s);
 void launch_associate(const OdomArgs& a, bool plane, hipStream_t s);
 void launch_solve(const OdomArgs& a, hipStream_t s);
 void launch_advance(const OdomArgs& a, hipStream_t s);             // the swap of every active sequence (a.active bit kSeqActive)
+// list[n]: sequence | kInfoSolvedBit (information_device.hpp); dst[n] as the device reaches it
+void launch_pose_information_odom(const OdomArgs& a, const int* list, int n, aloam_pose_information* dst, hipStream_t s);
 void launch_set_inited(OdomState* state, int B, int inited, hipStream_t s);
 }  // namespace aloam

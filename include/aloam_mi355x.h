@@ -586,6 +586,71 @@ typedef struct aloam_seq_record_header {     /* first 128 bytes of a record     
 int aloam_save_sequences(aloam_ctx* ctx, const int* seqs, int n, void* dst, long long cap_bytes, long long* dst_offsets);
 int aloam_load_sequences(aloam_ctx* ctx, const int* slots, int n, const void* src, const long long* src_offsets);
 
+/* ---- pose information: how well the geometry constrained the pose a solve returned ---------------------------------------------------
+ * The 6 x 6 information matrix (J^T J of the robustified residuals) of the last odometry or mapping solve of each listed sequence, at the
+ * pose that solve left, with its eigen-decomposition and the two 3 x 3 marginals.  A pose with thousands of factors and a small cost can
+ * still be unconstrained along one direction (a corridor, a tunnel, an open field): the smallest eigenvalue of trans_info against the next
+ * one says so, and its eigenvector says which way.  The matrix reports what the solver saw, not the truth.
+ *
+ * Definition, operation by operation (a-loam_amd/information.py restates it in numpy):
+ *   1. Factor set.  The factor records the last solve of the sequence read: odometry - the correspondences of the last outer iteration
+ *      (aloam_get_correspondences); mapping - the line and plane-norm factors of the second iteration (aloam_get_map_factors).
+ *   2. Pose.  The one that solve left: odometry q_last_curr / t_last_curr (para_q / para_t), mapping q_w_curr / t_w_curr.  After a solve
+ *      that ended as FAILURE this is the restored entry pose.
+ *   3. Rows.  Per line factor the three residuals r = (lp - a) x (lp - b) / |a - b|, per plane factor the one residual r = n . (lp - j)
+ *      (odometry, n = normalize((j - l) x (j - m))) or r = n . lp + d (mapping), with lp = q cp + t, or with aloam_config.distortion = 1 (odometry)
+ *      lp = slerp(identity, q, s) cp + s t, s = the interpolation ratio of the query point (its intensity's fractional part / 0.1).
+ *   4. Weights.  Every residual block is scaled by sqrt(rho'(|r|^2)) of HuberLoss(0.1), as in the solver: rho' = 1 for |r|^2 <= 0.01, else
+ *      0.1 / |r|.  cost = 1/2 sum rho(|r|^2).  No Jacobi (column) scaling.
+ *   5. Tangent and units.  The solver's tangent is Ceres' EigenQuaternionParameterization::Plus, q' = (sin|d| d/|d|, cos|d|) * q: a LEFT
+ *      perturbation by the rotation vector theta = 2 d, expressed in the target frame (odometry: the last sweep's frame; mapping: the map
+ *      frame), followed by t' = t + dt in the same frame.  With H_d = sum w J_d^T J_d and g_d = sum w J_d^T r in that tangent,
+ *      info = S H_d S and gradient = S g_d, S = diag(1/2, 1/2, 1/2, 1, 1, 1): radians and metres, order (theta_x, theta_y, theta_z, t_x, t_y, t_z).
+ *   6. Eigenpairs.  Cyclic Jacobi in f64 with a fixed rotation order (0,1), (0,2) .. (4,5), sweeps until sum |a_pq| <= 1e-17 sum |a_pp|:
+ *      a function of the matrix alone.  Ascending eigenvalues; column k of `eigenvectors` (row-major) belongs to eigenvalues[k]; the
+ *      component of largest magnitude of every eigenvector is positive, the lowest index deciding a tie.
+ *   7. Marginals.  trans_info = H_tt - H_tr H_rr^-1 H_rt and rot_info = H_rr - H_rt H_tt^-1 H_tr (Schur complements: the information about
+ *      one half when the other is unknown), through a 3 x 3 Cholesky factorisation of the block that is inverted; a block counts as
+ *      positive definite when every pivot exceeds 1e-12 times its diagonal entry.  Their eigenpairs as in 6.
+ * Covariance.  Not computed on the device: cov = sigma^2 V diag(1 / lambda) V^T with sigma^2 = 2 cost / (rows - 6), V / lambda the
+ * eigenpairs of `info` (a-loam_amd/information.py covariance(); INTEGRATION.md for nav_msgs/Odometry, whose order is translation first).
+ *
+ * status: ALOAM_INFO_NONE - no solve of that kind has run for this sequence since the context was created or since the last of these that
+ *   touched it: aloam_reset_sequences, aloam_load_sequences (both kinds); aloam_set_state, aloam_set_features, aloam_set_last (odometry:
+ *   they replace the pose, the feature counts or the clouds its records belong to); aloam_set_map, aloam_set_map_frame,
+ *   aloam_apply_map_corrections (mapping: the pose of its solve is in a map or frame that is gone).  For the odometry kind also a
+ *   registration of a new sweep that the odometry step has not consumed yet (the records are read through the feature counts of the sweep
+ *   they were made from, as aloam_get_correspondences reads them), and a first frame, which solves nothing.  Everything but status and
+ *   frame is zero.
+ *   ALOAM_INFO_NO_FACTORS - the solve ran with no residual block (mapping: the gate of src/laserMapping.cpp:554 was false); everything but
+ *   status and frame is zero.  ALOAM_INFO_SINGULAR - info, its eigenpairs, gradient, cost and counts are valid, but a block needed for a
+ *   Schur complement is not positive definite: that marginal and its eigenpairs are zero.
+ * A sequence that sat out the last step reports exactly the bits it reported before that step.
+ *
+ * Call semantics, as aloam_export_poses: queued on the context's stream, no host synchronisation, nothing read back; it writes the state at
+ * that point of the stream.  dst[i] belongs to seqs[i]; its bits do not depend on n, on i or on the other sequences listed.  dst is device
+ * memory of the context's device or pinned host memory, 8-byte aligned, classified before anything is queued: pageable, another device's,
+ * managed or NULL with n > 0 -> ALOAM_E_ARG.  Out-of-range or repeated ids, n outside 0 .. batch, an unknown `which` -> ALOAM_E_ARG.
+ * ALOAM_INFO_MAPPING before aloam_mapping_enable, or a kind whose stage the context was created without -> ALOAM_E_STATE.  n = 0 is legal
+ * and queues nothing.  `seqs` is read during the call only.  The flags behind ALOAM_INFO_NONE are host state of the context, not part of
+ * a sequence record (ALOAM_SEQ_RECORD_VERSION is unchanged). */
+enum { ALOAM_INFO_ODOMETRY = 0, ALOAM_INFO_MAPPING = 1 };
+enum { ALOAM_INFO_OK = 0, ALOAM_INFO_NONE = 1, ALOAM_INFO_NO_FACTORS = 2, ALOAM_INFO_SINGULAR = 3 };
+typedef struct aloam_pose_information {       /* one per listed sequence; 1048 bytes                                                    */
+  double info[36];                            /* 6 x 6, row-major, symmetric; order (theta_x, theta_y, theta_z, t_x, t_y, t_z)          */
+  double eigenvalues[6];                      /* ascending                                                                              */
+  double eigenvectors[36];                    /* row-major, column k belongs to eigenvalues[k]                                          */
+  double trans_info[9], trans_eigenvalues[3], trans_eigenvectors[9];   /* H_tt - H_tr H_rr^-1 H_rt                                      */
+  double rot_info[9], rot_eigenvalues[3], rot_eigenvectors[9];         /* H_rr - H_rt H_tt^-1 H_tr                                      */
+  double gradient[6];                         /* J^T r, same units                                                                      */
+  double cost;                                /* 1/2 sum rho(|r|^2) at that pose                                                        */
+  int n_line, n_plane, rows;                  /* residual blocks per class; rows = 3 n_line + n_plane                                   */
+  int status;                                 /* ALOAM_INFO_OK ..                                                                       */
+  int frame;                                  /* mapping: frameCount after that step; odometry: -1                                      */
+  int pad[3];
+} aloam_pose_information;
+int aloam_export_pose_information(aloam_ctx* ctx, int which, const int* seqs, int n, aloam_pose_information* dst /* [n] */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */
@@ -596,6 +661,10 @@ int aloam_get_labels(aloam_ctx* ctx, int seq, int* out, int cap);               
  * index of the query feature each belongs to (src/laserOdometry.cpp:365-381,460-479). */
 int aloam_get_correspondences(aloam_ctx* ctx, int seq, float* edges, int cap_edges, int* n_edges, int* edge_query,
                               float* planes, int cap_planes, int* n_planes, int* plane_query);
+/* factor records the last mapping solve of `seq` read (second iteration), in the dense order the solver visits them (tile after tile of
+ * 256 stack points, stack order inside a tile): lines 9 doubles (cp, a, b), planes 7 doubles (cp, n, d) (src/laserMapping.cpp:618,683).
+ * Counts of zero when the gate (:554) was false.  Synchronises. */
+int aloam_get_map_factors(aloam_ctx* ctx, int seq, double* lines, int cap_lines, int* n_lines, double* planes, int cap_planes, int* n_planes);
 
 /* How the ring ids of the clouds the last aloam_odometry_step searched (laserCloudCornerLast, laserCloudSurfLast of that step) are ordered, as
  * found when their kd-tree stand-ins were built (src/laserOdometry.cpp:567-568): 0 = int(intensity) never decreases with the index; 1 = it decreases, but never by more than 2 below an earlier

@@ -244,6 +244,9 @@ def main():
     ap.add_argument("--range-input", action="store_true", help="hand the sweeps over as 16-bit range images (encoded from the .bin points on the grid of an "
                     "HDL-64 with --range-columns columns) through the range entry points")
     ap.add_argument("--range-columns", type=int, default=1024, help="with --range-input: columns of the sensor grid (the --selftest drive has 1024)")
+    ap.add_argument("--pose-information", action="store_true", help="after every step, also export the information matrix of each slot's odometry solve (and, "
+                    "with --mapping, of its mapping solve): <seq>_info_odom.npy / <seq>_info_map.npy beside the poses, one record of "
+                    "binding.POSE_INFORMATION_DTYPE per sweep (a-loam_amd/information.py: covariance(), degeneracy())")
     args = ap.parse_args()
     if args.global_relocalize and not args.prior_atlas:
         ap.error("--global-relocalize needs --prior-atlas")
@@ -296,6 +299,9 @@ def main():
     rec_buf = torch.empty(batch * ctypes.sizeof(binding.AloamPoseRecord), dtype=torch.uint8, pin_memory=True)   # the poses of a step, written by the device
     recs = (binding.AloamPoseRecord * batch).from_address(rec_buf.data_ptr())
     odo, mapped = [[] for _ in seqs], [[] for _ in seqs]
+    info_kinds = ([("odom", binding.INFO_ODOMETRY)] + ([("map", binding.INFO_MAPPING)] if args.mapping else [])) if args.pose_information else []
+    info_buf = {name: torch.zeros(batch * binding.POSE_INFORMATION_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True) for name, _ in info_kinds}
+    info_rows = {name: [[] for _ in seqs] for name, _ in info_kinds}
     spill = None                                       # --save-atlas: the pinned destinations of the drain that follows every mapping step
     if args.save_atlas:
         atlas = importlib.import_module("a-loam_amd.atlas")
@@ -354,6 +360,8 @@ def main():
                   f"with {int(b['corner_factors']) + int(b['surf_factors'])} factors")
             guess = None
         gpu.export_poses(rec_buf.data_ptr())           # odometry and mapped poses of every slot in one call
+        for name, which in info_kinds:                 # --pose-information: one more stream-ordered call per kind, every slot listed
+            gpu.export_pose_information_into(which, range(batch), info_buf[name].data_ptr())
         try:
             gpu.synchronize()
         except binding.AloamError as e:
@@ -366,6 +374,8 @@ def main():
             odo[i].append([times[i][k], *r.t_w, *r.q_w])
             if args.mapping:
                 mapped[i].append([times[i][k], *r.map_t_w, *r.map_q_w])
+            for name, _ in info_kinds:
+                info_rows[name][i].append(info_buf[name].numpy().view(binding.POSE_INFORMATION_DTYPE)[slot].copy())
         if spill and int(spill["off"][1]):             # (the rows hold at most what the destinations hold: a drain is always written)
             nt, npts = int(spill["off"][1]), int(spill["off"][3])
             spill["log"].add(spill["tiles"].numpy()[:nt * 32].view(atlas.TILE_DTYPE), spill["points"].numpy()[:npts])
@@ -392,6 +402,13 @@ def main():
         np.savetxt(os.path.join(args.out, f"{seq}_odometry.txt"), np.array(odo[i]), fmt="%.9e")
         if mapped[i]:
             np.savetxt(os.path.join(args.out, f"{seq}_{mapped_name}.txt"), np.array(mapped[i]), fmt="%.9e")
+        for name, _ in info_kinds:
+            rows = np.array(info_rows[name][i], dtype=binding.POSE_INFORMATION_DTYPE)
+            np.save(os.path.join(args.out, f"{seq}_info_{name}.npy"), rows)
+            ok = rows[rows["status"] == binding.INFO_OK]
+            if args.selftest and len(ok):
+                ratio = ok["trans_eigenvalues"][:, 0] / ok["trans_eigenvalues"][:, 1]
+                print(f"{seq} pose information ({name}): {len(ok)} of {len(rows)} sweeps with a matrix, translation lambda0 / lambda1 in [{ratio.min():.3f}, {ratio.max():.3f}]")
         gt_path = os.path.join(args.dataset, "results", seq + ".txt")
         if os.path.exists(gt_path):
             Rg, tg = read_gt(gt_path)
