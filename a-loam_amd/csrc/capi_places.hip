@@ -23,6 +23,11 @@ static int check_listed(aloam_ctx* c, const int* seqs, int n) {
   return ALOAM_OK;
 }
 
+// The positive cells a load accepts: inside this range the f32 square of a cell and the sum of 20 of them are normal numbers, so a column
+// with a non-zero cell has a positive finite norm (place_column_norm) and counts as non-zero, as the header says.  Below it the squares
+// underflow and the column would lose its mask bit; above it the norm is inf and the column would count with cosine 0.
+static constexpr float kPlaceCellMin = 0x1p-62f, kPlaceCellMax = 0x1p60f;
+
 // k_place_descriptor for the listed sequences whose current sweep has none yet: at most once per registered sweep.
 static int ensure_descriptors(aloam_ctx* c, const int* seqs, int n) {
   std::vector<int> wanted(c->B, 0);
@@ -163,7 +168,10 @@ int aloam_places_load(aloam_ctx* c, const aloam_place* src, int count) {
   for (int i = 0; i < count; ++i) {
     const float* cells = &h[i].cells[0][0];
     for (int k = 0; k < kPlaceCells; ++k)
-      if (!std::isfinite(cells[k]) || cells[k] < 0.f) { c->err = "place record " + std::to_string(i) + ": a cell is negative or not finite"; return ALOAM_E_ARG; }
+      if (!std::isfinite(cells[k]) || cells[k] < 0.f || (cells[k] > 0.f && (cells[k] < kPlaceCellMin || cells[k] > kPlaceCellMax))) {
+        c->err = "place record " + std::to_string(i) + ": a cell is negative, not finite, or positive outside [2^-62, 2^60]";
+        return ALOAM_E_ARG;
+      }
   }
   aloam_place* at = c->d_pl_store.get() + c->pl_count;
   // (pageable memory: the runtime stages the copy and has read the source when the call returns)

@@ -504,7 +504,9 @@ int aloam_atlas_info(aloam_ctx* ctx, long long out[12]);
  *
  * aloam_places_export / aloam_places_load: entries [first, first + count) to dst (device or pinned), and count records appended from src
  * (device, pinned, or pageable through one staged copy); both stream-ordered.  A load validates every record before anything changes
- * (cells finite and non-negative, else ALOAM_E_ARG; records in device memory are read back once for that).  aloam_places_clear empties the
+ * (cells finite and non-negative, and the positive ones inside [2^-62, 2^60] (2.2e-19 .. 1.2e18; the cells are heights in metres), else
+ * ALOAM_E_ARG; records in device memory are read back once for that).  Inside that range the f32 squares of a column's cells and their sum
+ * are normal numbers: a column is non-zero for the match exactly when one of its cells is.  aloam_places_clear empties the
  * store in stream order.  aloam_places_info: out = count, capacity, max_range bits, sensor_height bits (IEEE-754).
  *
  * The store is not part of a sequence record (ALOAM_SEQ_RECORD_VERSION, MapSeq and aloam_pose_record are unchanged);

@@ -180,6 +180,12 @@ def test_add_then_match_needs_no_synchronise_and_a_loaded_store_matches_alike(bi
     with pytest.raises(binding.AloamError) as e:
         gpu.places_load(bad)
     assert e.value.code == binding.E_ARG and gpu.places_info()["count"] == 2 * N
+    # so is a positive cell outside [2^-62, 2^60]: the f32 norm of its column would underflow to 0 or overflow to inf
+    for cell in (1e-25, 1e20):
+        bad["cells"][1, 3, 4] = cell
+        with pytest.raises(binding.AloamError) as e:
+            gpu.places_load(bad)
+        assert e.value.code == binding.E_ARG and gpu.places_info()["count"] == 2 * N
     gpu.close()
 
 
