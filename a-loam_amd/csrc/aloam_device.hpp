@@ -267,6 +267,31 @@ __device__ __forceinline__ int wave_scan_i32(int v) {
   return v;
 }
 
+// Exclusive prefix over the NT threads of a workgroup (Hillis-Steele in LDS, NT entries); *total = the sum of all.
+template <typename T, int NT>
+__device__ __forceinline__ T block_exclusive_scan(T v, T* lds, T* total) {
+  const int tid = threadIdx.x;
+  lds[tid] = v;
+  __syncthreads();
+  for (int d = 1; d < NT; d <<= 1) {
+    const T add = tid >= d ? lds[tid - d] : T(0);
+    __syncthreads();
+    lds[tid] += add;
+    __syncthreads();
+  }
+  const T incl = lds[tid];
+  *total = lds[NT - 1];
+  __syncthreads();                                       // the caller may reuse lds
+  return incl - v;
+}
+
+// Wave-wide f32 minimum / maximum of a 3-axis bounding box (the voxel filters' getMinMax3D): shfl_down ladder, the result is in lane 0.
+// How the waves of a workgroup are combined is the caller's (LDS partials, ordered-int atomics).
+__device__ __forceinline__ void wave_box_reduce(float (&mn)[3], float (&mx)[3]) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    for (int d = 32; d > 0; d >>= 1) { mn[q] = fminf(mn[q], __shfl_down(mn[q], d, 64)); mx[q] = fmaxf(mx[q], __shfl_down(mx[q], d, 64)); }
+}
 
 // LDS bitonic sort of n 32- or 64-bit keys, ascending, 256 threads.  The network is the all-ascending form (a "flip" stage
 // i <-> block_end - i opens every merge, half-cleaners follow), so the slots n .. pow2ceil(n)-1 can stay imaginary +inf:

@@ -47,24 +47,6 @@ struct ExportArgs {
 // ---- device helpers of the export, shared with the sequence records (checkpoint_kernels.hip) ---------------------------------------
 __device__ __forceinline__ int ceil_chunks(int n) { return (n + kExportChunk - 1) / kExportChunk; }
 
-// Exclusive prefix over the NT threads of a workgroup (Hillis-Steele in LDS); *total = the sum of all.
-template <typename T, int NT>
-__device__ T block_exclusive_scan(T v, T* lds, T* total) {
-  const int tid = threadIdx.x;
-  lds[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < NT; d <<= 1) {
-    const T add = tid >= d ? lds[tid - d] : T(0);
-    __syncthreads();
-    lds[tid] += add;
-    __syncthreads();
-  }
-  const T incl = lds[tid];
-  *total = lds[NT - 1];
-  __syncthreads();                                       // the caller may reuse lds
-  return incl - v;
-}
-
 // n points from s to d: tiles of 8 x 256 points with the 8 loads of a thread in flight before its stores (named registers: a local array
 // indexed in an unrolled loop was left in scratch memory), the rest point by point.  Consecutive lanes take consecutive points.
 __device__ __forceinline__ void copy_points(float4* d, const float4* s, int n) {

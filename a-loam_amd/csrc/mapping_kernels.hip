@@ -25,6 +25,7 @@
 #include "mapping_solve_device.hpp"
 #include "map_search_device.hpp"
 #include "map_window_device.hpp"
+#include "voxel_device.hpp"
 
 namespace aloam {
 
@@ -96,17 +97,10 @@ __global__ __launch_bounds__(256) void k_map_compact_plan(MapArgs a) {
   if (mode == 0) { if (tid == 0) *flag = 0; return; }                       // really full (k_map_reserve reports that)
   int local = 0;
   for (int k = 0; k < PER; ++k) { const int c = tid * PER + k; if (c < kMapCubes) { const int ad = add[c]; local += compact_cap(T[c].cnt + (ad > 0 ? ad : 0), mode); } }
-  s_part[tid] = local;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int x = tid >= d ? s_part[tid - d] : 0;
-    __syncthreads();
-    s_part[tid] += x;
-    __syncthreads();
-  }
-  int run = s_part[tid] - local;
+  int total;
+  int run = block_exclusive_scan<int, 256>(local, s_part, &total);
   for (int k = 0; k < PER; ++k) { const int c = tid * PER + k; if (c < kMapCubes) { const int ad = add[c]; newoff[c] = run; run += compact_cap(T[c].cnt + (ad > 0 ? ad : 0), mode); } }
-  if (tid == 0) { *flag = mode; ms.pool_used[cls] = s_part[255]; ms.compactions += 1; }
+  if (tid == 0) { *flag = mode; ms.pool_used[cls] = total; ms.compactions += 1; }
 }
 
 template <int PHASE>   // 0: cubes -> staging at their new offsets; 1: staging -> pool, descriptors updated
@@ -298,22 +292,11 @@ __global__ __launch_bounds__(1024) void k_vox_setup(VoxArgs v) {
   long long kk = 0;
   int tt = 0;
   for (int s = s0; s < s1; ++s) { const int n = v.segs[s].n; kk += n; tt += (n + kVoxTile - 1) / kVoxTile; }
-  s_keys[tid] = kk;
-  s_tiles[tid] = tt;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const long long ak = tid >= d ? s_keys[tid - d] : 0;
-    const int at = tid >= d ? s_tiles[tid - d] : 0;
-    __syncthreads();
-    s_keys[tid] += ak;
-    s_tiles[tid] += at;
-    __syncthreads();
-  }
-  const long long total_keys = s_keys[1023];
-  const int total_tiles = s_tiles[1023];
+  long long total_keys;
+  int total_tiles;
+  long long ko = block_exclusive_scan<long long, 1024>(kk, s_keys, &total_keys);   // two scans, one after the other: this kernel only works when a
+  int to = block_exclusive_scan<int, 1024>(tt, s_tiles, &total_tiles);             // segment was left to the general path, once per filter call
   const bool bad = total_keys > v.key_cap || total_tiles > v.tile_cap;
-  long long ko = s_keys[tid] - kk;
-  int to = s_tiles[tid] - tt;
   for (int s = s0; s < s1; ++s) {
     VoxSeg& sg = v.segs[s];
     if (bad || sg.n > (kVoxTile << v.levels)) {                              // skipped, reported through counters[1]
@@ -347,74 +330,68 @@ __global__ __launch_bounds__(1024) void k_vox_setup(VoxArgs v) {
   }
 }
 
+// Entry gt of the tile work list: tile t of segment s (a copy of its descriptor).
+struct VoxTile { int s; VoxSeg sg; int t; };
+__device__ __forceinline__ VoxTile vox_tile(const VoxArgs& v, int gt) {
+  VoxTile w;
+  w.s = v.tile_seg[gt];
+  w.sg = v.segs[w.s];
+  w.t = gt - w.sg.tile0;
+  return w;
+}
+
 __global__ __launch_bounds__(256) void k_vox_bbox(VoxArgs v) {
   const int tid = threadIdx.x, lane = tid & 63;
-  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list
-  const int s = v.tile_seg[gt];
-  const VoxSeg sg = v.segs[s];
-  const int t = gt - sg.tile0;
-  float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-  for (int e = tid; e < kVoxTile; e += 256) {
-    const int i = t * kVoxTile + e;
-    if (i < sg.n) {
-      const float4 p = sg.in[i];
-      mn[0] = fminf(mn[0], p.x); mx[0] = fmaxf(mx[0], p.x);
-      mn[1] = fminf(mn[1], p.y); mx[1] = fmaxf(mx[1], p.y);
-      mn[2] = fminf(mn[2], p.z); mx[2] = fmaxf(mx[2], p.z);
+  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list (k_vox_setup)
+    const auto [s, sg, t] = vox_tile(v, gt);
+    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+    for (int e = tid; e < kVoxTile; e += 256) {
+      const int i = t * kVoxTile + e;
+      if (i < sg.n) {
+        const float4 p = sg.in[i];
+        mn[0] = fminf(mn[0], p.x); mx[0] = fmaxf(mx[0], p.x);
+        mn[1] = fminf(mn[1], p.y); mx[1] = fmaxf(mx[1], p.y);
+        mn[2] = fminf(mn[2], p.z); mx[2] = fmaxf(mx[2], p.z);
+      }
     }
-  }
+    wave_box_reduce(mn, mx);
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    for (int d = 32; d > 0; d >>= 1) { mn[q] = fminf(mn[q], __shfl_down(mn[q], d, 64)); mx[q] = fmaxf(mx[q], __shfl_down(mx[q], d, 64)); }
-    if (lane == 0) { atomicMin(&v.bbox[s * 6 + q], f2o(mn[q])); atomicMax(&v.bbox[s * 6 + 3 + q], f2o(mx[q])); }
-  }
+    for (int q = 0; q < 3; ++q)
+      if (lane == 0) { atomicMin(&v.bbox[s * 6 + q], f2o(mn[q])); atomicMax(&v.bbox[s * 6 + 3 + q], f2o(mx[q])); }
   }
 }
 
 // (voxel index, point index) keys of one tile, sorted in LDS.
 __global__ __launch_bounds__(256) void k_vox_keys_sort(VoxArgs v) {
   const int tid = threadIdx.x;
-  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list
-  const int s = v.tile_seg[gt];
-  const VoxSeg sg = v.segs[s];
-  const int t = gt - sg.tile0;
-  __shared__ unsigned long long keys[kVoxTile];
-  const float inv = 1.0f / sg.leaf;
-  float gmn[3], gmx[3], fminb[3];
-  int divb[3];
+  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list (k_vox_setup)
+    const auto [s, sg, t] = vox_tile(v, gt);
+    __shared__ unsigned long long keys[kVoxTile];
+    const float inv = voxel::inverse_leaf(sg.leaf);
+    float gmn[3], gmx[3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) { gmn[q] = o2f(v.bbox[s * 6 + q]); gmx[q] = o2f(v.bbox[s * 6 + 3 + q]); }
-  const long long dx = (long long)((gmx[0] - gmn[0]) * inv) + 1, dy = (long long)((gmx[1] - gmn[1]) * inv) + 1, dz = (long long)((gmx[2] - gmn[2]) * inv) + 1;
-  const bool overflow = dx * dy * dz > 2147483647ll;                      // PCL then returns the input unfiltered
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int minb = (int)floorf(gmn[q] * inv);
-    divb[q] = (int)floorf(gmx[q] * inv) - minb + 1;
-    fminb[q] = (float)minb;
-  }
-  for (int e = tid; e < kVoxTile; e += 256) {
-    const int i = t * kVoxTile + e;
-    unsigned long long key = ~0ull;
-    if (i < sg.n) {
-      unsigned vi;
-      if (overflow) vi = (unsigned)i;
-      else {
-        const float4 p = sg.in[i];
-        const int i0 = (int)(floorf(p.x * inv) - fminb[0]);
-        const int i1 = (int)(floorf(p.y * inv) - fminb[1]);
-        const int i2 = (int)(floorf(p.z * inv) - fminb[2]);
-        vi = (unsigned)(i0 + i1 * divb[0] + i2 * divb[0] * divb[1]);
+    for (int q = 0; q < 3; ++q) { gmn[q] = o2f(v.bbox[s * 6 + q]); gmx[q] = o2f(v.bbox[s * 6 + 3 + q]); }
+    const voxel::Box box = voxel::make_box(gmn, gmx, inv);
+    for (int e = tid; e < kVoxTile; e += 256) {
+      const int i = t * kVoxTile + e;
+      unsigned long long key = ~0ull;
+      if (i < sg.n) {
+        unsigned vi;
+        if (box.unfiltered) vi = (unsigned)i;                                  // every point its own cell: the input comes back, in order
+        else {
+          const float4 p = sg.in[i];
+          vi = voxel::cell_index(box, p.x, p.y, p.z, inv);
+        }
+        key = ((unsigned long long)vi << 32) | (unsigned)i;
       }
-      key = ((unsigned long long)vi << 32) | (unsigned)i;
+      keys[e] = key;
     }
-    keys[e] = key;
-  }
-  __syncthreads();
-  const int in_tile = min(kVoxTile, sg.n - t * kVoxTile);
-  bitonic_sort_u64(keys, in_tile, tid);
-  unsigned long long* dst = v.keys[0] + sg.key_off;
-  for (int e = tid; e < kVoxTile; e += 256) { const int i = t * kVoxTile + e; if (i < sg.n) dst[i] = keys[e]; }
-  __syncthreads();
+    __syncthreads();
+    const int in_tile = min(kVoxTile, sg.n - t * kVoxTile);
+    bitonic_sort_u64(keys, in_tile, tid);
+    unsigned long long* dst = v.keys[0] + sg.key_off;
+    for (int e = tid; e < kVoxTile; e += 256) { const int i = t * kVoxTile + e; if (i < sg.n) dst[i] = keys[e]; }
+    __syncthreads();
   }
 }
 
@@ -423,72 +400,70 @@ __global__ __launch_bounds__(256) void k_vox_keys_sort(VoxArgs v) {
 __global__ __launch_bounds__(256) void k_vox_merge(VoxArgs v, int level) {
   const int tid = threadIdx.x;
   if (level > v.counters[2]) return;                                       // no segment of this call is that large (k_vox_setup)
-  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list
-  const VoxSeg sg = v.segs[v.tile_seg[gt]];
-  const int t = gt - sg.tile0;
-  // a segment of ntiles tiles is sorted after ceil(log2(ntiles)) levels; after that it only has to end up in the buffer the
-  // later stages read (keys[levels & 1]): at most one copy, then nothing
-  int need = 0;
-  while ((1 << need) < sg.ntiles) ++need;
-  if (level > need || (level == need && ((v.levels - need) & 1) == 0)) continue;
-  const unsigned long long* src = v.keys[level & 1] + sg.key_off;
-  unsigned long long* dst = v.keys[(level & 1) ^ 1] + sg.key_off;
-  const int run = kVoxTile << level;
-  constexpr int PER = kVoxTile / 256;
-  // all keys of a tile belong to the same run, so they search the same sibling range with the same number of steps: the
-  // PER searches of a thread are advanced in lock-step, PER independent loads in flight per step
-  const int p_first = t * kVoxTile;
-  const int r = p_first / run, sb = (r ^ 1) * run;
-  const bool has_sib = sb < sg.n;
-  const int s_end = has_sib ? min(sg.n, sb + run) : sb;
-  unsigned long long key[PER];
-  int lo[PER], hi[PER];
+  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list (k_vox_setup)
+    const auto [s, sg, t] = vox_tile(v, gt);
+    // a segment of ntiles tiles is sorted after ceil(log2(ntiles)) levels; after that it only has to end up in the buffer the
+    // later stages read (keys[levels & 1]): at most one copy, then nothing
+    int need = 0;
+    while ((1 << need) < sg.ntiles) ++need;
+    if (level > need || (level == need && ((v.levels - need) & 1) == 0)) continue;
+    const unsigned long long* src = v.keys[level & 1] + sg.key_off;
+    unsigned long long* dst = v.keys[(level & 1) ^ 1] + sg.key_off;
+    const int run = kVoxTile << level;
+    constexpr int PER = kVoxTile / 256;
+    // all keys of a tile belong to the same run, so they search the same sibling range with the same number of steps: the
+    // PER searches of a thread are advanced in lock-step, PER independent loads in flight per step
+    const int p_first = t * kVoxTile;
+    const int r = p_first / run, sb = (r ^ 1) * run;
+    const bool has_sib = sb < sg.n;
+    const int s_end = has_sib ? min(sg.n, sb + run) : sb;
+    unsigned long long key[PER];
+    int lo[PER], hi[PER];
 #pragma unroll
-  for (int u = 0; u < PER; ++u) {
-    const int p = p_first + tid + u * 256;
-    key[u] = p < sg.n ? src[p] : ~0ull;
-    lo[u] = sb; hi[u] = s_end;
-  }
-  if (has_sib) {
-    for (int len = s_end - sb; len > 0; len >>= 1) {                    // ceil(log2(len + 1)) steps
-      unsigned long long probe[PER];
+    for (int u = 0; u < PER; ++u) {
+      const int p = p_first + tid + u * 256;
+      key[u] = p < sg.n ? src[p] : ~0ull;
+      lo[u] = sb; hi[u] = s_end;
+    }
+    if (has_sib) {
+      for (int len = s_end - sb; len > 0; len >>= 1) {                    // ceil(log2(len + 1)) steps
+        unsigned long long probe[PER];
 #pragma unroll
-      for (int u = 0; u < PER; ++u) { const int mid = (lo[u] + hi[u]) >> 1; probe[u] = lo[u] < hi[u] ? src[mid] : 0ull; }
+        for (int u = 0; u < PER; ++u) { const int mid = (lo[u] + hi[u]) >> 1; probe[u] = lo[u] < hi[u] ? src[mid] : 0ull; }
 #pragma unroll
-      for (int u = 0; u < PER; ++u) {
-        if (lo[u] < hi[u]) { const int mid = (lo[u] + hi[u]) >> 1; if (probe[u] < key[u]) lo[u] = mid + 1; else hi[u] = mid; }
+        for (int u = 0; u < PER; ++u) {
+          if (lo[u] < hi[u]) { const int mid = (lo[u] + hi[u]) >> 1; if (probe[u] < key[u]) lo[u] = mid + 1; else hi[u] = mid; }
+        }
       }
     }
-  }
 #pragma unroll
-  for (int u = 0; u < PER; ++u) {
-    const int p = p_first + tid + u * 256;
-    if (p >= sg.n) continue;
-    const int dest = has_sib ? (r >> 1) * 2 * run + (p - r * run) + (lo[u] - sb) : p;
-    dst[dest] = key[u];
-  }
+    for (int u = 0; u < PER; ++u) {
+      const int p = p_first + tid + u * 256;
+      if (p >= sg.n) continue;
+      const int dest = has_sib ? (r >> 1) * 2 * run + (p - r * run) + (lo[u] - sb) : p;
+      dst[dest] = key[u];
+    }
   }
 }
 
 __global__ __launch_bounds__(256) void k_vox_heads(VoxArgs v) {
   const int tid = threadIdx.x;
-  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list
-  const VoxSeg sg = v.segs[v.tile_seg[gt]];
-  const int t = gt - sg.tile0;
-  const unsigned long long* K = v.keys[v.levels & 1] + sg.key_off;
-  int heads = 0;
-  for (int e = tid; e < kVoxTile; e += 256) {
-    const int p = t * kVoxTile + e;
-    if (p < sg.n && (p == 0 || (unsigned)(K[p - 1] >> 32) != (unsigned)(K[p] >> 32))) ++heads;
-  }
-  __shared__ int s_sum;
-  if (tid == 0) s_sum = 0;
-  __syncthreads();
-  for (int d = 32; d > 0; d >>= 1) heads += __shfl_down(heads, d, 64);
-  if ((tid & 63) == 0) atomicAdd(&s_sum, heads);
-  __syncthreads();
-  if (tid == 0) v.tile_heads[gt] = s_sum;
-  __syncthreads();
+  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list (k_vox_setup)
+    const auto [s, sg, t] = vox_tile(v, gt);
+    const unsigned long long* K = v.keys[v.levels & 1] + sg.key_off;
+    int heads = 0;
+    for (int e = tid; e < kVoxTile; e += 256) {
+      const int p = t * kVoxTile + e;
+      if (p < sg.n && (p == 0 || (unsigned)(K[p - 1] >> 32) != (unsigned)(K[p] >> 32))) ++heads;
+    }
+    __shared__ int s_sum;
+    if (tid == 0) s_sum = 0;
+    __syncthreads();
+    for (int d = 32; d > 0; d >>= 1) heads += __shfl_down(heads, d, 64);
+    if ((tid & 63) == 0) atomicAdd(&s_sum, heads);
+    __syncthreads();
+    if (tid == 0) v.tile_heads[gt] = s_sum;
+    __syncthreads();
   }
 }
 
@@ -502,17 +477,11 @@ __global__ __launch_bounds__(1024) void k_vox_scan(VoxArgs v) {
   const int t0 = tid * per, t1 = min(n, t0 + per);
   int local = 0;
   for (int t = t0; t < t1; ++t) local += v.tile_heads[t];
-  s_part[tid] = local;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int x = tid >= d ? s_part[tid - d] : 0;
-    __syncthreads();
-    s_part[tid] += x;
-    __syncthreads();
-  }
-  int run = s_part[tid] - local;
+  int sum;
+  int run = block_exclusive_scan<int, 1024>(local, s_part, &sum);
+  const int total = sum;                                                     // (read before the fence below: `sum` itself would be kept in scratch across it)
   for (int t = t0; t < t1; ++t) { v.tile_pref[t] = run; run += v.tile_heads[t]; }
-  if (tid == 1023 || t1 == n) v.tile_pref[n] = s_part[1023];
+  if (tid == 1023 || t1 == n) v.tile_pref[n] = total;
   __threadfence();
   __syncthreads();
   for (int s = tid; s < v.n_segs; s += 1024) {
@@ -522,7 +491,7 @@ __global__ __launch_bounds__(1024) void k_vox_scan(VoxArgs v) {
       int hi = 0;                                                           // prefix at the end of the segment's last tile
       const int last = sg.tile0 + sg.ntiles;
       // tile_pref of other threads' ranges is visible after the barrier (same workgroup, global memory)
-      hi = (last >= n) ? s_part[1023] : ((volatile int*)v.tile_pref)[last];
+      hi = (last >= n) ? total : ((volatile int*)v.tile_pref)[last];
       m = hi - ((volatile int*)v.tile_pref)[sg.tile0];
     }
     if (sg.out_count && !sg.final_count) *sg.out_count = m;
@@ -533,72 +502,59 @@ __global__ __launch_bounds__(1024) void k_vox_scan(VoxArgs v) {
 // centroids: the head of every voxel run sums its members in key order (= input order) and writes output number `rank`
 __global__ __launch_bounds__(256) void k_vox_emit(VoxArgs v) {
   const int tid = threadIdx.x;
-  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list
-  const VoxSeg sg = v.segs[v.tile_seg[gt]];
-  const int t = gt - sg.tile0;
-  const unsigned long long* K = v.keys[v.levels & 1] + sg.key_off;
-  constexpr int PER = kVoxTile / 256;
-  __shared__ int s_scan[256];
-  __shared__ float4 s_pts[kVoxTile];                                         // the tile's points in key order
-  __shared__ unsigned s_vi[kVoxTile];                                         // and their voxel indices
-  // stage the tile: every thread fetches its own members (independent loads); the serial per-voxel sums then run out of LDS
-  for (int e = tid; e < kVoxTile; e += 256) {
-    const int p = t * kVoxTile + e;
-    if (p < sg.n) { const unsigned long long k = K[p]; s_vi[e] = (unsigned)(k >> 32); s_pts[e] = sg.in[(unsigned)k]; }
-  }
-  __syncthreads();
-  const int e0 = tid * PER, p0 = t * kVoxTile + e0;
-  const int in_tile = min(kVoxTile, sg.n - t * kVoxTile);
-  int heads = 0;
-  unsigned flags = 0;
-#pragma unroll
-  for (int e = 0; e < PER; ++e) {
-    const int q = e0 + e;
-    if (q < in_tile && (q == 0 ? (p0 + e == 0 || (unsigned)(K[p0 + e - 1] >> 32) != s_vi[q]) : s_vi[q - 1] != s_vi[q])) { ++heads; flags |= 1u << e; }
-  }
-  s_scan[tid] = heads;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int x = tid >= d ? s_scan[tid - d] : 0;
-    __syncthreads();
-    s_scan[tid] += x;
-    __syncthreads();
-  }
-  int rank = v.tile_pref[gt] - v.tile_pref[sg.tile0] + s_scan[tid] - heads;
-#pragma unroll 1
-  for (int e = 0; e < PER; ++e) {
-    if (!(flags & (1u << e))) continue;
-    const int q0 = e0 + e;
-    const unsigned vi = s_vi[q0];
-    float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-    int cnt = 0;
-    int q = q0;
-    for (; q < in_tile && s_vi[q] == vi; ++q) { const float4 pt = s_pts[q]; sx += pt.x; sy += pt.y; sz += pt.z; si += pt.w; ++cnt; }
-    if (q == in_tile) {                                                       // the voxel continues in the next tile(s): finish from global memory
-      for (int p = t * kVoxTile + q; p < sg.n; ++p) {
-        const unsigned long long kq = K[p];
-        if ((unsigned)(kq >> 32) != vi) break;
-        const float4 pt = sg.in[(unsigned)kq];
-        sx += pt.x; sy += pt.y; sz += pt.z; si += pt.w;
-        ++cnt;
-      }
+  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list (k_vox_setup)
+    const auto [s, sg, t] = vox_tile(v, gt);
+    const unsigned long long* K = v.keys[v.levels & 1] + sg.key_off;
+    constexpr int PER = kVoxTile / 256;
+    __shared__ int s_scan[256];
+    __shared__ float4 s_pts[kVoxTile];                                         // the tile's points in key order
+    __shared__ unsigned s_vi[kVoxTile];                                         // and their voxel indices
+    // stage the tile: every thread fetches its own members (independent loads); the serial per-voxel sums then run out of LDS
+    for (int e = tid; e < kVoxTile; e += 256) {
+      const int p = t * kVoxTile + e;
+      if (p < sg.n) { const unsigned long long k = K[p]; s_vi[e] = (unsigned)(k >> 32); s_pts[e] = sg.in[(unsigned)k]; }
     }
-    const float fc = (float)cnt;
-    sg.out[rank++] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
-  }
-  __syncthreads();
+    __syncthreads();
+    const int e0 = tid * PER, p0 = t * kVoxTile + e0;
+    const int in_tile = min(kVoxTile, sg.n - t * kVoxTile);
+    int heads = 0;
+    unsigned flags = 0;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      const int q = e0 + e;
+      if (q < in_tile && (q == 0 ? (p0 + e == 0 || (unsigned)(K[p0 + e - 1] >> 32) != s_vi[q]) : s_vi[q - 1] != s_vi[q])) { ++heads; flags |= 1u << e; }
+    }
+    int tile_heads;
+    int rank = v.tile_pref[gt] - v.tile_pref[sg.tile0] + block_exclusive_scan<int, 256>(heads, s_scan, &tile_heads);
+#pragma unroll 1
+    for (int e = 0; e < PER; ++e) {
+      if (!(flags & (1u << e))) continue;
+      const int q0 = e0 + e;
+      const unsigned vi = s_vi[q0];
+      voxel::Centroid c;
+      int q = q0;
+      for (; q < in_tile && s_vi[q] == vi; ++q) c.add(s_pts[q]);
+      if (q == in_tile) {                                                       // the voxel continues in the next tile(s): finish from global memory
+        for (int p = t * kVoxTile + q; p < sg.n; ++p) {
+          const unsigned long long kq = K[p];
+          if ((unsigned)(kq >> 32) != vi) break;
+          c.add(sg.in[(unsigned)kq]);
+        }
+      }
+      sg.out[rank++] = c.get();
+    }
+    __syncthreads();
   }
 }
 
 // in-place re-filter of a map cube: copy the centroids from the scratch area back over the cube's segment
 __global__ __launch_bounds__(256) void k_vox_copyback(VoxArgs v) {
   const int tid = threadIdx.x;
-  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list
-  const VoxSeg sg = v.segs[v.tile_seg[gt]];
-  if (!sg.final_out) continue;
-  const int t = gt - sg.tile0;
-  const int m = v.tile_pref[min(sg.tile0 + sg.ntiles, v.counters[0])] - v.tile_pref[sg.tile0];
-  for (int e = tid; e < kVoxTile; e += 256) { const int i = t * kVoxTile + e; if (i < m) sg.final_out[i] = sg.out[i]; }
+  for (int gt = blockIdx.x; gt < v.counters[0]; gt += gridDim.x) {   // grid-stride over the tile work list (k_vox_setup)
+    const auto [s, sg, t] = vox_tile(v, gt);
+    if (!sg.final_out) continue;
+    const int m = v.tile_pref[min(sg.tile0 + sg.ntiles, v.counters[0])] - v.tile_pref[sg.tile0];
+    for (int e = tid; e < kVoxTile; e += 256) { const int i = t * kVoxTile + e; if (i < m) sg.final_out[i] = sg.out[i]; }
   }
 }
 
@@ -722,7 +678,7 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
     const VoxSeg sg = v.segs[s];
     const int n = sg.n;
     const float4* in = sg.in;
-    const float inv = 1.0f / sg.leaf;
+    const float inv = voxel::inverse_leaf(sg.leaf);
     const int chunk = ((n + NW - 1) / NW + 63) & ~63;                        // every wave owns a contiguous, 64-aligned stretch of the segment
     const int w0 = wave * chunk, w1 = min(n, w0 + chunk);
     // ---- pass 1: bounding box, run heads ------------------------------------------------------------------------------------
@@ -730,7 +686,7 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
     int heads = 0;
     bool big = false;
     float cfx = 0.f, cfy = 0.f, cfz = 0.f;                                   // cell of the point in front of this row (lane 0's predecessor)
-    if (w0 < w1 && w0 > 0) { const float4 p = in[w0 - 1]; cfx = floorf(p.x * inv); cfy = floorf(p.y * inv); cfz = floorf(p.z * inv); }
+    if (w0 < w1 && w0 > 0) { const float4 p = in[w0 - 1]; cfx = voxel::cell_coord(p.x, inv); cfy = voxel::cell_coord(p.y, inv); cfz = voxel::cell_coord(p.z, inv); }
     for (int base = w0; base < w1; base += 64 * U) {
       float4 p[U];
 #pragma unroll
@@ -740,18 +696,18 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
         const int rb = base + u * 64, i = rb + lane;
         if (rb >= w1) break;                                                 // uniform
         const bool act = i < w1;
-        const float fx = floorf(p[u].x * inv), fy = floorf(p[u].y * inv), fz = floorf(p[u].z * inv);
+        const float fx = voxel::cell_coord(p[u].x, inv), fy = voxel::cell_coord(p[u].y, inv), fz = voxel::cell_coord(p[u].z, inv);
         if (act) {
           mn[0] = fminf(mn[0], p[u].x); mx[0] = fmaxf(mx[0], p[u].x);
           mn[1] = fminf(mn[1], p[u].y); mx[1] = fmaxf(mx[1], p[u].y);
           mn[2] = fminf(mn[2], p[u].z); mx[2] = fmaxf(mx[2], p[u].z);
-          if (!(fabsf(fx) < 8388608.f && fabsf(fy) < 8388608.f && fabsf(fz) < 8388608.f)) big = true;
+          if (!voxel::cell_exact(fx, fy, fz)) big = true;
         }
         // predecessor's cell: wave_shr:1 on the DPP network, lane 0 keeps `old` = the carried cell
         const float px = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(cfx), __float_as_int(fx), 0x138, 0xF, 0xF, false));
         const float py = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(cfy), __float_as_int(fy), 0x138, 0xF, 0xF, false));
         const float pz = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(cfz), __float_as_int(fz), 0x138, 0xF, 0xF, false));
-        const bool head = act && (i == 0 || fx != px || fy != py || fz != pz);
+        const bool head = act && (i == 0 || voxel::cell_differs(fx, fy, fz, px, py, pz));
         const unsigned long long hm = __ballot(head), am = __ballot(act), cm = am & ~hm;
         heads += __popcll(hm);
         if (lane == 0) cont[rb >> 5] = (unsigned)cm;
@@ -759,11 +715,10 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
         cfx = __shfl(fx, 63, 64); cfy = __shfl(fy, 63, 64); cfz = __shfl(fz, 63, 64);
       }
     }
+    wave_box_reduce(mn, mx);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      for (int d = 32; d > 0; d >>= 1) { mn[q] = fminf(mn[q], __shfl_down(mn[q], d, 64)); mx[q] = fmaxf(mx[q], __shfl_down(mx[q], d, 64)); }
+    for (int q = 0; q < 3; ++q)
       if (lane == 0) { s_f[q * NW + wave] = mn[q]; s_f[(3 + q) * NW + wave] = mx[q]; }
-    }
     const bool anybig = __ballot(big) != 0ull;
     if (lane == 0) { s_i[wave] = heads; s_i[16 + wave] = anybig ? 1 : 0; }
     __syncthreads();
@@ -784,20 +739,12 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
       continue;
     }
     float4* const stage = sg.out;                                            // final place (stacks) or the staging range (in-place cube filter)
-    const long long dx = (long long)((gmx[0] - gmn[0]) * inv) + 1, dy = (long long)((gmx[1] - gmn[1]) * inv) + 1, dz = (long long)((gmx[2] - gmn[2]) * inv) + 1;
+    const voxel::Box box = voxel::make_box(gmn, gmx, inv);
     int n_vox = 0;
-    if (dx * dy * dz > 2147483647ll) {                                       // PCL's overflow guard: the input comes back unfiltered
+    if (box.unfiltered) {                                                    // PCL's overflow guard: the input comes back unfiltered
       n_vox = n;
       if (!sg.final_out) for (int i = tid; i < n; i += NT) stage[i] = in[i];
     } else {
-      int divb[3];
-      float fminb[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int minb = (int)floorf(gmn[q] * inv);
-        divb[q] = (int)floorf(gmx[q] * inv) - minb + 1;
-        fminb[q] = (float)minb;
-      }
       // ---- pass 2: one (voxel index, first point) key per run, in input order ------------------------------------------------
       for (int base = w0; base < w1; base += 64 * U) {
         float4 p[U];
@@ -810,9 +757,8 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
           const bool head = i < w1 && !((cont[i >> 5] >> (i & 31)) & 1u);
           const unsigned long long hm = __ballot(head);
           if (head) {
-            const int i0 = (int)(floorf(p[u].x * inv) - fminb[0]), i1 = (int)(floorf(p[u].y * inv) - fminb[1]), i2 = (int)(floorf(p[u].z * inv) - fminb[2]);
             const int r = rank + __popcll(hm & lt);
-            khi[r] = (unsigned)(i0 + i1 * divb[0] + i2 * divb[0] * divb[1]);
+            khi[r] = voxel::cell_index(box, p[u].x, p[u].y, p[u].z, inv);
             klo[r] = (unsigned short)i;
           }
           rank += __popcll(hm);
@@ -820,7 +766,7 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
       }
       __syncthreads();
       {
-        const long long cells = (long long)divb[0] * divb[1] * divb[2];      // every voxel index is below this (<= 2^31 - 1)
+        const long long cells = voxel::box_cells(box.divb);                  // every voxel index is below this (<= 2^31 - 1)
         const int key_bits = cells > 1 ? 64 - __clzll(cells - 1) : 1;
         radix_sort_pairs<NT, CAPR>(khi, klo, cntw, s_i + 32, n_runs, key_bits, tid);
       }
@@ -855,8 +801,7 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
         const int vrank = __popcll(__ballot(h) & lt);                        // (the ballot again instead of 20 registers carried across the scan)
         if (!h) continue;
         const unsigned vi = khi[p];
-        float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-        int cnt = 0;
+        voxel::Centroid c;
         // the members in order: runs q = p, p + 1, ... of this voxel, the points of a run while the continuation bit is set.  Up to
         // eight member indices are collected from LDS first, their loads issued together, then added in order: one memory round trip
         // per eight members instead of one per run.
@@ -877,16 +822,14 @@ __global__ __launch_bounds__(NT) void k_vox_lds(VoxArgs v, int which) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) pt[k] = in[idx[k]];
 #pragma unroll
-          for (int k = 0; k < 8; ++k) if (k < m) { sx += pt[k].x; sy += pt[k].y; sz += pt[k].z; si += pt[k].w; }
-          cnt += m;
+          for (int k = 0; k < 8; ++k) if (k < m) c.add(pt[k]);
         }
-        const float fc = (float)cnt;
-        stage[s_tab[it * NW + wave] + vrank] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
+        stage[s_tab[it * NW + wave] + vrank] = c.get();
       }
     }
     if (sg.final_out) {                                                      // in-place filter: back over the cube once every member has been read
       __syncthreads();
-      if (stage != sg.final_out && !(dx * dy * dz > 2147483647ll)) for (int i = tid; i < n_vox; i += NT) sg.final_out[i] = stage[i];
+      if (stage != sg.final_out && !box.unfiltered) for (int i = tid; i < n_vox; i += NT) sg.final_out[i] = stage[i];
     }
     if (tid == 0) {
       if (sg.final_count) *sg.final_count = n_vox; else if (sg.out_count) *sg.out_count = n_vox;
@@ -947,15 +890,8 @@ __global__ __launch_bounds__(1024) void k_mapgrid_build(MapArgs a) {
   const int per = H / 1024;
   int local = 0;
   for (int k = 0; k < per; ++k) local += cnt[tid * per + k];
-  part[tid] = local;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int x = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += x;
-    __syncthreads();
-  }
-  int run = part[tid] - local;
+  int total;
+  int run = block_exclusive_scan<int, 1024>(local, part, &total);
   for (int k = 0; k < per; ++k) { const int c = cnt[tid * per + k]; cnt[tid * per + k] = run; start[tid * per + k] = run; run += c; }
   if (tid == 1023) start[H] = run;
   __syncthreads();

@@ -373,15 +373,8 @@ __device__ __forceinline__ void build_grids(const OdomArgs& a) {
     const int per = g.H / 1024;
     int local = 0;
     for (int k = 0; k < per; ++k) local += cnt[tid * per + k];
-    part[tid] = local;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-      const int v = tid >= d ? part[tid - d] : 0;
-      __syncthreads();
-      part[tid] += v;
-      __syncthreads();
-    }
-    int run = part[tid] - local;
+    int total;
+    int run = block_exclusive_scan<int, 1024>(local, part, &total);
     for (int k = 0; k < per; ++k) { const int c = cnt[tid * per + k]; cnt[tid * per + k] = run; start[tid * per + k] = run; run += c; }
     if (tid == 1023) start[g.H] = run;
     __syncthreads();

@@ -10,6 +10,7 @@
 #include "aloam_stdsort.hpp"
 #include "mapping_kernels.hpp"
 #include "registration_kernels.hpp"
+#include "voxel_device.hpp"
 
 namespace aloam {
 
@@ -128,7 +129,7 @@ __device__ void sort_reference_order(Entry* E, int n, int* fpos, int* lpos, int*
 template <class PointFn>
 __device__ int voxel_grid_reference_order(PointFn&& point, int n, float leaf, Entry* E, float4* out, float* s_f, int* s_i, int* s_work, int work_max, int* s_chunk, int chunk_max, int* fpos, int* lpos, bool* unfiltered) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float inv = 1.0f / leaf;                            // inverse_leaf_size_
+  const float inv = voxel::inverse_leaf(leaf);              // inverse_leaf_size_
   float mn[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f}, mx[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
   for (int i = tid; i < n; i += kLitThreads) {              // getMinMax3D
     const float4 p = point(i);
@@ -138,17 +139,12 @@ __device__ int voxel_grid_reference_order(PointFn&& point, int n, float leaf, En
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) { mn[k] = block_min(mn[k], s_f, tid); mx[k] = -block_min(-mx[k], s_f, tid); }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  *unfiltered = dx * dy * dz > 2147483647ll;                // PCL warns and copies its input
+  const voxel::Box box = voxel::make_box(mn, mx, inv);
+  *unfiltered = box.unfiltered;                             // PCL warns and copies its input
   if (*unfiltered) return n;
-  int minb[3], divb[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { minb[k] = (int)floorf(mn[k] * inv); divb[k] = (int)floorf(mx[k] * inv) - minb[k] + 1; }
-  const int mul1 = divb[0], mul2 = divb[0] * divb[1];
   for (int i = tid; i < n; i += kLitThreads) {              // the index vector, in input order
     const float4 p = point(i);
-    const int i0 = (int)(floorf(p.x * inv) - (float)minb[0]), i1 = (int)(floorf(p.y * inv) - (float)minb[1]), i2 = (int)(floorf(p.z * inv) - (float)minb[2]);
-    E[i] = Entry{(unsigned)(i0 + i1 * mul1 + i2 * mul2), (unsigned)i};
+    E[i] = Entry{voxel::cell_index(box, p.x, p.y, p.z, inv), (unsigned)i};
   }
   __syncthreads();
   sort_reference_order(E, n, fpos, lpos, s_work, work_max, s_chunk, chunk_max, s_i);   // std::sort(index_vector.begin(), index_vector.end(), std::less<cloud_point_index_idx>())
@@ -165,15 +161,9 @@ __device__ int voxel_grid_reference_order(PointFn&& point, int n, float leaf, En
     const int total = s_i[0] + s_i[1] + s_i[2] + s_i[3];
     if (head) {
       const unsigned cell = E[p].idx;
-      float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-      int cnt = 0;
-      for (int q = p; q < n && E[q].idx == cell; ++q) {
-        const float4 pt = point((int)E[q].pt);
-        sx += pt.x; sy += pt.y; sz += pt.z; si += pt.w;
-        ++cnt;
-      }
-      const float fc = (float)cnt;
-      out[rank] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
+      voxel::Centroid c;
+      for (int q = p; q < n && E[q].idx == cell; ++q) c.add(point((int)E[q].pt));
+      out[rank] = c.get();
     }
     base += total;
     __syncthreads();
@@ -277,7 +267,8 @@ __global__ __launch_bounds__(kLitThreads) void k_less_flat_reference_order(RegAr
   bool unf;
   float4* out = row_of(a.less_flat, a.meta[b].parity, b, a.cap) + off;
   const int n_vox = voxel_grid_reference_order([&](int i) { return cloud[member[i]]; }, n_mem, leaf, E, out, s_f, s_i, s_work, kRingWorkMax, s_chunk, kRingChunkMax, fpos, lpos, &unf);
-  if (tid == 0 && (unf || n_vox != expect)) atomicOr(&a.meta[b].err, kErrInternal);
+  // (a box PCL does not filter is no error: nothing is written, n_vox is the number of members, and k_ring_features has already put them there one per cell, in order)
+  if (tid == 0 && n_vox != expect) atomicOr(&a.meta[b].err, kErrInternal);
 }
 
 void launch_less_flat_reference_order(const RegArgs& a, int npad, float leaf, hipStream_t s) {

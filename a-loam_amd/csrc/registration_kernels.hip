@@ -20,6 +20,7 @@
 // All of it is HBM/latency-bound integer + f32 work: coalesced 16-B loads, LDS staging, wave64 ballots; no MFMA.
 #include "aloam_device.hpp"
 #include "registration_kernels.hpp"
+#include "voxel_device.hpp"
 
 namespace aloam {
 
@@ -659,8 +660,7 @@ __device__ __forceinline__ int voxel_runs_tail(unsigned char* smem, unsigned cha
     if (!((vmask >> it) & 1u)) continue;
     const int p = it * 256 + tid;
     const unsigned vi = (unsigned)(rkeys[p] >> SHIFT);
-    float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-    int cnt = 0;
+    voxel::Centroid c;
     for (int q = p; q < n_runs; ++q) {                                       // the runs of this voxel, in element order
       const K kq = rkeys[q];
       if ((unsigned)(kq >> SHIFT) != vi) break;
@@ -673,18 +673,17 @@ __device__ __forceinline__ int voxel_runs_tail(unsigned char* smem, unsigned cha
         const float4 p0 = cloud[e + 5], p1 = cloud[e + 6], p2 = cloud[e + 7], p3 = cloud[e + 8];
         const bool c1 = e + 1 < L && (flags[e + 6] & 4), c2 = e + 2 < L && (flags[e + 7] & 4), c3 = e + 3 < L && (flags[e + 8] & 4);
         more = e + 4 < L && (flags[e + 9] & 4);                               // the run stops at the next head or non-member
-        sx += p0.x; sy += p0.y; sz += p0.z; si += p0.w; ++cnt;
+        c.add(p0);
         if (!c1) break;
-        sx += p1.x; sy += p1.y; sz += p1.z; si += p1.w; ++cnt;
+        c.add(p1);
         if (!c2) break;
-        sx += p2.x; sy += p2.y; sz += p2.z; si += p2.w; ++cnt;
+        c.add(p2);
         if (!c3) break;
-        sx += p3.x; sy += p3.y; sz += p3.z; si += p3.w; ++cnt;
+        c.add(p3);
         e += 4;
       } while (more);
     }
-    const float fc = (float)cnt;
-    out[vrank[it]] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
+    out[vrank[it]] = c.get();
   }
   ALOAM_PHASE("after_centroids");   // centroids
   return n_vox;
@@ -746,14 +745,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
   constexpr int kSlots = kSharpPerSector + kLessSharpPerSector + kFlatPerSector;
   short* s_pick = reinterpret_cast<short*>(s_misc + 48);      // s_misc: [0] scratch, [1..6] pick counts, [8..13] spill marks, [16..], [24..], [32..] sector offsets
 
-  // 0.2 m voxel cell of every point, packed 11 + 11 + 10 bits (+-204 m, +-102 m in z), written while the point is in the
+  // 0.2 m voxel cell of every point, packed 11 + 11 + 10 bits (voxel::pack_cell: +-204 m, +-102 m in z), written while the point is in the
   // curvature tile: the voxel filter of the less-flat points then needs no second and third pass over the ring in global memory
   // (its bounding box in cells and the voxel indices are integer work on this array).  A point outside that range (s_misc[44])
   // or a box of more than 2^31 cells sends the ring down the float path, which is pcl::VoxelGrid's arithmetic as written.
   constexpr int CELLS_OFF = (4 * MAXN + 15) & ~15;
   static_assert(CELLS_OFF + 4 * MAXN <= A_BYTES, "the packed cells sit behind the curvature array in region A");
   unsigned* cells = reinterpret_cast<unsigned*>(smem + CELLS_OFF);
-  const float inv = 1.0f / leaf;
+  const float inv = voxel::inverse_leaf(leaf);
   // "the step s -> s + 1 is longer than the 0.05 threshold" as ONE BIT per step (bit s + 64 of gapw; steps that do not exist, s < 0
   // and s >= n - 1, read 1): a wave ballots the 64 steps it has just computed, and the reach of the neighbour suppression around a
   // point is two count-trailing-zeros on a 10-bit window of this array instead of up to ten dependent LDS byte reads.
@@ -806,9 +805,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
       }
       const f2 cxy = q0 * inv;
       const float fx = floorf(cxy.x), fy = floorf(cxy.y), fz = floorf(z0 * inv);
-      const bool okc = fabsf(fx) < 1024.f && fabsf(fy) < 1024.f && fabsf(fz) < 512.f;
+      const bool okc = voxel::cell_packable(fx, fy, fz);
       if (!okc) s_misc[44] = 1;
-      cells[i] = okc ? (unsigned)((int)fx + 1024) | ((unsigned)((int)fy + 1024) << 11) | ((unsigned)((int)fz + 512) << 22) : 0u;
+      cells[i] = okc ? voxel::pack_cell(fx, fy, fz) : 0u;
     }
     {
       const unsigned long long gb = __ballot(gapf);                            // steps it * 256 + wave * 64 .. + 63
@@ -915,15 +914,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
   bool voxels_done = false;
   int (*s_redi)[4] = reinterpret_cast<int (*)[4]>(s_red);
   if (s_misc[44] == 0) {
-    // integer path: min_b = floor(min * inv) = min of floor(p * inv) (floor is monotone), likewise max_b; PCL's own overflow
-    // guard multiplies int((max - min) * inv) + 1 <= div_b + 1 per axis, so a product of (div_b + 1) below 2^31 settles it
+    // integer path on the packed cells: the box from the cell minima / maxima, decided or not by voxel::make_packed_box
     int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
     for (int e = tid; e < L; e += 256) {
       const int i = e + 5;
       if (label_is_member(flags[i])) {
-        const unsigned c = cells[i];
-        const int cx = (int)(c & 2047u), cy = (int)((c >> 11) & 2047u), cz = (int)(c >> 22);
-        mn[0] = min(mn[0], cx); mx[0] = max(mx[0], cx); mn[1] = min(mn[1], cy); mx[1] = max(mx[1], cy); mn[2] = min(mn[2], cz); mx[2] = max(mx[2], cz);
+        int c[3];
+        voxel::unpack_cell(cells[i], c);
+        mn[0] = min(mn[0], c[0]); mx[0] = max(mx[0], c[0]); mn[1] = min(mn[1], c[1]); mx[1] = max(mx[1], c[1]); mn[2] = min(mn[2], c[2]); mx[2] = max(mx[2], c[2]);
       }
     }
 #pragma unroll
@@ -933,23 +931,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
       if (lane == 0) { s_redi[q][wave] = mn[q]; s_redi[3 + q][wave] = mx[q]; }
     }
     __syncthreads();
-    int minc[3], divc[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      minc[q] = min(min(s_redi[q][0], s_redi[q][1]), min(s_redi[q][2], s_redi[q][3]));
-      divc[q] = max(max(s_redi[3 + q][0], s_redi[3 + q][1]), max(s_redi[3 + q][2], s_redi[3 + q][3])) - minc[q] + 1;
+      mn[q] = min(min(s_redi[q][0], s_redi[q][1]), min(s_redi[q][2], s_redi[q][3]));
+      mx[q] = max(max(s_redi[3 + q][0], s_redi[3 + q][1]), max(s_redi[3 + q][2], s_redi[3 + q][3]));
     }
     __syncthreads();                                                         // s_red may be needed by the float path below
-    if (divc[0] > 0 && (long long)(divc[0] + 1) * (divc[1] + 1) * (divc[2] + 1) <= 2147483647ll) {
-      cells_in_box = (long long)divc[0] * divc[1] * divc[2];
+    voxel::PackedBox box;
+    if (voxel::make_packed_box(mn, mx, box)) {
+      cells_in_box = voxel::box_cells(box.divc);
       for (int e = tid; e < L; e += 256) {
         const int i = e + 5;
         unsigned vi = 0xffffffffu;                                            // not a member (corner-labelled)
-        if (label_is_member(flags[i])) {
-          const unsigned c = cells[i];
-          const int i0 = (int)(c & 2047u) - minc[0], i1 = (int)((c >> 11) & 2047u) - minc[1], i2 = (int)(c >> 22) - minc[2];
-          vi = (unsigned)(i0 + i1 * divc[0] + i2 * divc[0] * divc[1]);
-        }
+        if (label_is_member(flags[i])) vi = voxel::packed_cell_index(box, cells[i]);
         vis[e] = vi;
       }
       voxels_done = true;
@@ -966,28 +960,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
         mn[2] = fminf(mn[2], p.z); mx[2] = fmaxf(mx[2], p.z);
       }
     }
+    wave_box_reduce(mn, mx);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      for (int d = 32; d > 0; d >>= 1) { mn[q] = fminf(mn[q], __shfl_down(mn[q], d, 64)); mx[q] = fmaxf(mx[q], __shfl_down(mx[q], d, 64)); }
+    for (int q = 0; q < 3; ++q)
       if (lane == 0) { s_red[q][wave] = mn[q]; s_red[3 + q][wave] = mx[q]; }
-    }
     __syncthreads();
-    int minb[3], divb[3];
-    float fminb[3], gmn[3], gmx[3];
+    float gmn[3], gmx[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       gmn[q] = fminf(fminf(s_red[q][0], s_red[q][1]), fminf(s_red[q][2], s_red[q][3]));
       gmx[q] = fmaxf(fmaxf(s_red[3 + q][0], s_red[3 + q][1]), fmaxf(s_red[3 + q][2], s_red[3 + q][3]));
     }
-    const long long dx = (long long)((gmx[0] - gmn[0]) * inv) + 1, dy = (long long)((gmx[1] - gmn[1]) * inv) + 1, dz = (long long)((gmx[2] - gmn[2]) * inv) + 1;
-    overflow = dx * dy * dz > 2147483647ll;   // PCL returns the input unfiltered in this case
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      minb[q] = (int)floorf(gmn[q] * inv);
-      divb[q] = (int)floorf(gmx[q] * inv) - minb[q] + 1;
-      fminb[q] = (float)minb[q];
-    }
-    cells_in_box = (long long)divb[0] * divb[1] * divb[2];
+    const voxel::Box box = voxel::make_box(gmn, gmx, inv);
+    overflow = box.unfiltered;                  // PCL returns the input unfiltered in this case
+    cells_in_box = voxel::box_cells(box.divb);
     for (int e = tid; e < L; e += 256) {
       const int i = e + 5;
       unsigned vi = 0xffffffffu;                                              // not a member (corner-labelled)
@@ -995,10 +981,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPAD <= 204
         if (overflow) vi = (unsigned)e;         // every point its own cell -> output = input, in order
         else {
           const float4 p = cloud[i];
-          const int i0 = (int)(floorf(p.x * inv) - fminb[0]);
-          const int i1 = (int)(floorf(p.y * inv) - fminb[1]);
-          const int i2 = (int)(floorf(p.z * inv) - fminb[2]);
-          vi = (unsigned)(i0 + i1 * divb[0] + i2 * divb[0] * divb[1]);
+          vi = voxel::cell_index(box, p.x, p.y, p.z, inv);
         }
       }
       vis[e] = vi;

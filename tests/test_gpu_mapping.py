@@ -279,18 +279,22 @@ def test_capacity_errors_of_unsynchronised_steps_are_not_lost(binding):
     gpu.close()
 
 
-@pytest.mark.parametrize("case", ["many_runs", "far_point", "voxel_overflow", "big_segment"])
+@pytest.mark.parametrize("case", ["many_runs", "far_point", "voxel_overflow", "big_segment", "far_point-reference_order", "voxel_overflow-reference_order"])
 def test_voxel_filter_segments_the_lds_kernel_hands_to_the_general_path(O, binding, case):
     """k_vox_lds takes a segment only when its runs fit the LDS, its coordinates keep floor(p / leaf) an exact f32 integer below 2^23
     and it has at most 65535 points; everything else must come out of the tile-sort / rank-merge path of round 2 — unchanged results:
     the down-sampled incoming clouds (laserCloudCornerStack / SurfStack, reference src/laserMapping.cpp:542-550) and the re-filtered
-    cubes (:788-801) bit for bit against the oracle, solver off."""
+    cubes (:788-801) bit for bit against the oracle, solver off.  The far point and the overflowing box also in the reference's summation
+    order (k_vox_reference_order against the oracle in its literal order): that kernel's box, guard and unfiltered return."""
+    case, _, order = case.partition("-")
     rng = np.random.default_rng(17)
     cap = 90000
-    orc = O.Oracle(16, 0.3, lm_max_iterations=0)
+    orc = O.Oracle(16, 0.3, lm_max_iterations=0, canonical_order=not order)
     orc.map_config(0.4, 0.8)
     gpu = binding.Aloam(n_scans=16, min_range=0.3, batch=1, max_points=cap, lm_max_iterations=0)
     gpu.mapping_enable(0.4, 0.8, pool_points=262144)
+    if order:
+        gpu.set_voxel_sum_order(True)
     corner = rng.uniform(-30, 30, (1500, 4)).astype(np.float32); corner[:, 3] = np.sort(rng.integers(0, 16, 1500))
     if case == "many_runs":            # 30 000 scattered points: every point its own run, more than the 24 576 the LDS holds
         surf = rng.uniform(-60, 60, (30000, 4)).astype(np.float32); surf[:, 2] *= 0.05

@@ -311,6 +311,34 @@ def test_single_long_ring_uses_large_lds_class(O, binding):
     gpu.close()
 
 
+@pytest.mark.parametrize("reference_order", [False, True])
+@pytest.mark.parametrize("far", [250.0, 3.0e5])
+def test_ring_with_far_points_takes_the_float_voxel_path(O, binding, far, reference_order):
+    """The less-flat filter of k_ring_features works on packed 0.2 m cells while every point of the ring lies within +-1024 (z: +-512) cells.  One ring of
+    1200 points with points 300..499 at 250 m: a point outside the packed range sends the ring down the float path (pcl::VoxelGrid's arithmetic on the
+    points themselves), far points among the less-flat members.  The same points at 3e5 m: the ring's box exceeds 2^31 cells and the filter returns the
+    members unfiltered.  Features bit-equal to the oracle, in both summation orders."""
+    rng = np.random.default_rng(0)
+    ang = np.linspace(np.pi, -np.pi, 1200, endpoint=False)
+    rad = 10 + 3 * np.sign(np.sin(6 * ang)) + rng.normal(size=1200) * 0.02
+    rad[300:500] = far
+    ring = np.stack([rad * np.cos(ang), rad * np.sin(ang), np.tan(np.deg2rad(1.0)) * rad, np.zeros_like(ang)], 1).astype(np.float32)
+    orc = O.Oracle(16, 0.3, canonical_order=not reference_order)
+    fo = orc.scan_register(ring)
+    gpu = binding.Aloam(n_scans=16, min_range=0.3, max_points=4096)
+    if reference_order:
+        gpu.set_voxel_sum_order(True)
+    gpu.scan_register(ring)
+    _assert_features_equal(fo, gpu.features(), ("far ring", far, reference_order))
+    n_far = int((np.linalg.norm(fo["less_flat"][:, :3].astype(np.float64), axis=1) > 100.0).sum())
+    print("less-flat points:", len(fo["less_flat"]), "beyond 100 m:", n_far)
+    if far == 250.0:
+        assert len(fo["less_flat"]) > 100 and n_far > 100
+    else:
+        assert len(fo["less_flat"]) > 1000
+    gpu.close()
+
+
 @pytest.mark.parametrize("path", sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.npz")) if not os.path.basename(p).startswith("ref")))
 def test_gpu_reproduces_committed_goldens(binding, path):
     g = np.load(path)

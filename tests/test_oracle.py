@@ -464,3 +464,17 @@ def test_std_sort_order_restatement_matches_libstdcxx():
     assert r.returncode == 0, r.stdout + r.stderr
     r = subprocess.run([os.path.join(host, "build", "test_stdsort_port")], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.startswith("aloam_stdsort == std::sort"), r.stdout[-2000:]
+
+
+def test_voxel_cell_arithmetic_restatement_matches_the_pcl_stand_in():
+    """a-loam_amd/csrc/voxel_device.hpp (pcl::VoxelGrid's box, overflow guard, cell index and centroid as the four device filters share them) compiled for
+    the host: a filter assembled from the header alone against pcl::VoxelGrid::filter of oracle/ref_shim, count and every float bit for bit, on 3000 seeded
+    clouds (metres to +-3e5 m, points on cell borders, single cells); the packed-cell box and index of k_ring_features against the float ones wherever the
+    integer guard decides; "cell differs from predecessor" against "index differs" wherever floor(p / leaf) is exact.  The program itself fails unless
+    enough clouds were unfiltered, decided by the integer path and placed on borders."""
+    import subprocess
+    host = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
+    r = subprocess.run(["make", "-C", host, "build/test_voxel_port"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([os.path.join(host, "build", "test_voxel_port")], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("voxel_device == pcl::VoxelGrid"), r.stdout[-2000:]
