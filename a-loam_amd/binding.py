@@ -65,6 +65,41 @@ POSE_INFORMATION_DTYPE = np.dtype([
     ("status", np.int32), ("frame", np.int32), ("pad", np.int32, 3)])
 
 
+class AloamGraphNode(C.Structure):
+    """One keyframe of a pose graph (aloam_graph_node, 128 bytes); a-loam_amd/posegraph.py holds the definitions of this section."""
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("q_opt", C.c_double * 4), ("t_opt", C.c_double * 3), ("frame", C.c_int),
+                ("pad", C.c_int * 3)]
+
+
+class AloamGraphEdge(C.Structure):
+    """One edge (aloam_graph_edge, 240 bytes): i = -1 is an anchor; info is the upper triangle, row-major."""
+    _fields_ = [("seq", C.c_int), ("i", C.c_int), ("j", C.c_int), ("flags", C.c_int), ("q", C.c_double * 4), ("t", C.c_double * 3),
+                ("info", C.c_double * 21)]
+
+
+class AloamGraphOptions(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("pcg_max_iterations", C.c_int), ("function_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("pcg_tolerance", C.c_double), ("huber_delta", C.c_double)]
+
+
+class AloamGraphResult(C.Structure):
+    """The outcome of one sequence's solve (aloam_graph_result, 64 bytes)."""
+    _fields_ = [("status", C.c_int), ("termination", C.c_int), ("lm_iterations", C.c_int), ("accepted_steps", C.c_int),
+                ("pcg_iterations", C.c_int), ("nodes", C.c_int), ("edges", C.c_int), ("pad", C.c_int), ("initial_cost", C.c_double),
+                ("final_cost", C.c_double), ("gradient_max", C.c_double), ("reserved", C.c_double)]
+
+
+GRAPH_EDGE_ROBUST = 1
+GRAPH_OK, GRAPH_NO_EDGES, GRAPH_FAILED = 0, 1, 2
+GRAPH_NODE_DTYPE = np.dtype([("q", np.float64, 4), ("t", np.float64, 3), ("q_opt", np.float64, 4), ("t_opt", np.float64, 3),
+                             ("frame", np.int32), ("pad", np.int32, 3)])
+GRAPH_EDGE_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("flags", np.int32), ("q", np.float64, 4),
+                             ("t", np.float64, 3), ("info", np.float64, 21)])
+GRAPH_RESULT_DTYPE = np.dtype([("status", np.int32), ("termination", np.int32), ("lm_iterations", np.int32), ("accepted_steps", np.int32),
+                               ("pcg_iterations", np.int32), ("nodes", np.int32), ("edges", np.int32), ("pad", np.int32),
+                               ("initial_cost", np.float64), ("final_cost", np.float64), ("gradient_max", np.float64), ("reserved", np.float64)])
+
+
 class AloamMapCorrection(C.Structure):
     """One candidate map <- odometry correction (aloam_map_correction, 64 bytes)."""
     _fields_ = [("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3), ("pad", C.c_double)]
@@ -253,6 +288,15 @@ def lib():
         L.aloam_export_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_export_pose_information.argtypes = [vp, C.c_int, vp, C.c_int, vp]
         L.aloam_get_map_factors.argtypes = [vp, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
+        L.aloam_graph_default_options.argtypes = [C.POINTER(AloamGraphOptions)]; L.aloam_graph_default_options.restype = None
+        L.aloam_graph_enable.argtypes = [vp, C.c_int, C.c_int]
+        L.aloam_graph_add_nodes.argtypes = [vp, vp, C.c_int, vp]
+        L.aloam_graph_add_edges.argtypes = [vp, vp, C.c_int]
+        L.aloam_graph_export.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+        L.aloam_graph_export_edges.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+        L.aloam_graph_clear.argtypes = [vp, vp, C.c_int]
+        L.aloam_graph_info.argtypes = [vp, C.c_int, vp]
+        L.aloam_graph_optimize.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphOptions), vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -621,6 +665,75 @@ class Aloam:
         v = np.zeros(4, np.int32)
         self._check(lib().aloam_places_info(self.h, _p(v)))
         return {"count": int(v[0]), "capacity": int(v[1]), "max_range": float(v[2:3].view(np.float32)[0]), "sensor_height": float(v[3:4].view(np.float32)[0])}
+
+    # ---- pose graphs (stream-ordered; a-loam_amd/posegraph.py holds the definitions) -------------------------------------------------------
+    def graph_enable(self, max_nodes, max_edges):
+        """One pose graph per sequence: rows of max_nodes nodes and max_edges edges (odometry edges included)."""
+        self._check(lib().aloam_graph_enable(self.h, int(max_nodes), int(max_edges)))
+
+    def graph_add_nodes(self, seqs, odom_info):
+        """Enter the pose each listed sequence holds at this point of the stream as its next node; odom_info: one 6 x 6 information (or its
+        21-element upper triangle) for all, or one per sequence, for the odometry edge to the node before.  Returns the new nodes' indices."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        info = np.asarray(odom_info, dtype=np.float64)
+        if info.shape[-2:] == (6, 6):
+            info = info[..., np.triu_indices(6)[0], np.triu_indices(6)[1]]
+        info = np.ascontiguousarray(np.broadcast_to(info, (len(ids), 21)))
+        index = [self.graph_info(int(b))["nodes"] for b in ids]
+        self._check(lib().aloam_graph_add_nodes(self.h, _p(ids) if len(ids) else None, len(ids), _p(info) if len(ids) else None))
+        return index
+
+    def graph_add_edges(self, edges):
+        """edges: a structured array of GRAPH_EDGE_DTYPE (posegraph.make_edges builds one)."""
+        e = np.ascontiguousarray(edges, dtype=GRAPH_EDGE_DTYPE)
+        self._check(lib().aloam_graph_add_edges(self.h, _p(e) if len(e) else None, len(e)))
+
+    def graph_options(self, **kw):
+        o = AloamGraphOptions()
+        lib().aloam_graph_default_options(C.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def graph_optimize_into(self, seqs, dst_ptr, options=None):
+        """Queue the solve of the listed sequences' graphs; dst_ptr receives one aloam_graph_result each (device or pinned memory)."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_graph_optimize(self.h, _p(ids) if len(ids) else None, len(ids), C.byref(options) if options is not None else None,
+                                               C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def graph_optimize(self, seqs, pinned=True, **options):
+        """Solve and wait: a structured array [len(seqs)] of GRAPH_RESULT_DTYPE.  Keyword arguments are fields of aloam_graph_options."""
+        import torch
+        n = len(seqs)
+        buf = torch.zeros(max(1, n) * 64, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_optimize_into(seqs, buf.data_ptr(), self.graph_options(**options))
+        self.synchronize()
+        return buf.cpu().numpy()[:n * 64].view(GRAPH_RESULT_DTYPE).copy()
+
+    def graph_export_into(self, seq, first, count, dst_ptr, edges=False):
+        f = lib().aloam_graph_export_edges if edges else lib().aloam_graph_export
+        self._check(f(self.h, int(seq), int(first), int(count), C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def graph_export(self, seq=0, first=0, count=None, edges=False, pinned=True):
+        """Nodes (or edges) [first, first + count) of one sequence after a synchronise, as a structured array."""
+        import torch
+        dt = GRAPH_EDGE_DTYPE if edges else GRAPH_NODE_DTYPE
+        if count is None:
+            count = self.graph_info(seq)["edges" if edges else "nodes"] - first
+        buf = torch.zeros(max(1, count) * dt.itemsize, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_export_into(seq, first, count, buf.data_ptr(), edges)
+        self.synchronize()
+        return buf.cpu().numpy()[:count * dt.itemsize].view(dt).copy()
+
+    def graph_clear(self, seqs):
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_graph_clear(self.h, _p(ids) if len(ids) else None, len(ids)))
+
+    def graph_info(self, seq=0):
+        v = np.zeros(4, np.int32)
+        self._check(lib().aloam_graph_info(self.h, int(seq), _p(v)))
+        return {"nodes": int(v[0]), "edges": int(v[1]), "max_nodes": int(v[2]), "max_edges": int(v[3])}
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

@@ -387,6 +387,8 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
         else if (c->map_on) bytes += (double)sizeof(MapEdgeRec) * ms[b].factor_num[1][0] + (double)sizeof(MapNormRec) * ms[b].factor_num[1][1];
       }
     }
+    // the last aloam_graph_optimize: nodes and edges read once, the estimates and one result written (the iterations run out of L2)
+    if (kernel == K_POSE_GRAPH) bytes = (double)(sizeof(aloam_graph_node) + 56) * c->pg_last_nodes + (double)sizeof(aloam_graph_edge) * c->pg_last_edges;
     if (kernel == K_APPLY) bytes = c->rl_apply_n * (4.0 + 4.0 + 64.0 + 56.0);   // id, choice, candidate in, correction out
     *algorithmic_bytes = bytes;
   }

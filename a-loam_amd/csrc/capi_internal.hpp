@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "places_kernels.hpp"
+#include "posegraph_kernels.hpp"
 #include "registration_kernels.hpp"
 #include "relocalize_kernels.hpp"
 
@@ -28,15 +29,16 @@ using namespace aloam;
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "save_sequences",
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "pose_graph", "save_sequences",
                                     "load_sequences", "score_corrections", "apply_corrections"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
 constexpr int kNinSlots = 8;
+constexpr int kGraphStageSlots = 4;
 
 // Owners of everything the context allocates: released by their destructors when the context is deleted, so a failed
 // allocation or copy half way through leaks nothing.
@@ -91,6 +93,8 @@ struct SeqHost {
   bool desc_valid = false;           // d_pl_desc[b] is that sweep's
   bool info_odom = false, info_map = false;   // the records and the pose of its last odometry / mapping solve are still in place
                                      // (aloam_export_pose_information; else ALOAM_INFO_NONE).  Host state only: not part of a sequence record
+  int graph_nodes = 0, graph_edges = 0;   // its pose graph (aloam_graph_*): what its rows of the store hold.  Host state only, and not the sequence's
+                                     // but the slot's: reset and load leave it, aloam_graph_clear empties it
   bool grid_built = false;           // the grid set of its LAST clouds holds their grids: set by the step that made them the last ones (it built
                                      // them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
 };
@@ -101,6 +105,7 @@ struct aloam_ctx {
   Stream stream, copy_stream;
   Stream grid_stream;                // the build of the next step's search grids runs here, beside the association and the solve (aloam_odometry_step)
   Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
+  Event pg_stage_done[kGraphStageSlots];   // pose graphs: the copy that read a slot of h_pg_stage has run
   Event grid_fork, grids_done;       // main stream -> grid stream at the start of a step, grid stream -> main stream before k_advance
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
   // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
@@ -194,6 +199,18 @@ struct aloam_ctx {
   // pose information (aloam_export_pose_information)
   DevBuf<int> d_info_list;                                          // [B] listed ids with their "solved" bit
   std::vector<int> info_last_list; int info_last_which = 0;         // the last call (algorithmic bytes)
+  // pose graphs (aloam_graph_enable): one row of nodes and one of edges per sequence; the counts are SeqHost fields
+  bool graph_on = false;
+  int pg_max_nodes = 0, pg_max_edges = 0;
+  DevBuf<aloam_graph_node> d_pg_nodes;                              // [B][max_nodes]
+  DevBuf<aloam_graph_edge> d_pg_edges;                              // [B][max_edges]
+  DevBuf<GraphAddItem> d_pg_add;                                    // [B] the nodes of one aloam_graph_add_nodes
+  DevBuf<GraphSolveItem> d_pg_items;                                // [B] the listed sequences of one aloam_graph_optimize
+  PinnedBuf<char> h_pg_stage; size_t pg_stage_bytes = 0;            // pinned ring of kGraphStageSlots x pg_stage_bytes: the items of one add / optimize,
+  int pg_stage_slot = 0; bool pg_stage_used[kGraphStageSlots] = {}; //   read later by an async H2D copy (as h_nin)
+  DevBuf<double> d_pg_f64; long long pg_f64_cap = 0;                // the solve's scratch rows, grown on first use
+  DevBuf<int> d_pg_i32; long long pg_i32_cap = 0;
+  long long pg_last_nodes = 0, pg_last_edges = 0;                   // the last solve (algorithmic bytes)
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -365,6 +382,9 @@ void on_mapping_step_queued(aloam_ctx* c);
 int on_atlas_attached(aloam_ctx* c, const std::vector<int>& attached);
 void on_places_enabled(aloam_ctx* c);
 void on_descriptors_made(aloam_ctx* c, const int* seqs, int n);
+void on_graph_nodes_added(aloam_ctx* c, const int* seqs, int n);
+void on_graph_edges_added(aloam_ctx* c, int seq, int count);
+void on_graph_cleared(aloam_ctx* c, const int* seqs, int n);
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events);
 // capi_mapping.hip
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);

@@ -126,6 +126,12 @@ int on_atlas_attached(aloam_ctx* c, const std::vector<int>& attached) {
 void on_system_inited_forced(aloam_ctx* c, int inited) { for (SeqHost& s : c->seq) s.inited = inited; }   // aloam_set_system_inited, beside its launch
 void on_places_enabled(aloam_ctx* c) { for (SeqHost& s : c->seq) s.desc_valid = false; }                    // d_pl_desc is new: it holds nobody's descriptor
 void on_descriptors_made(aloam_ctx* c, const int* seqs, int n) { for (int i = 0; i < n; ++i) c->seq[seqs[i]].desc_valid = true; }
+// The pose graph of a slot (capi_posegraph.hip): its counts change here and nowhere else.  A node past the first brings its odometry edge.
+void on_graph_nodes_added(aloam_ctx* c, const int* seqs, int n) {
+  for (int i = 0; i < n; ++i) { SeqHost& s = c->seq[seqs[i]]; if (s.graph_nodes > 0) ++s.graph_edges; ++s.graph_nodes; }
+}
+void on_graph_edges_added(aloam_ctx* c, int seq, int count) { c->seq[seq].graph_edges += count; }
+void on_graph_cleared(aloam_ctx* c, const int* seqs, int n) { for (int i = 0; i < n; ++i) { c->seq[seqs[i]].graph_nodes = 0; c->seq[seqs[i]].graph_edges = 0; } }
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events) {   // aloam_synchronize has read a sequence's pool capacity events: how many are new
   const long long fresh = events > c->seq[seq].map_err_seen ? events - c->seq[seq].map_err_seen : 0;
   c->seq[seq].map_err_seen = events;

@@ -1,0 +1,393 @@
+"""Pose graphs over keyframes: the numpy model of aloam_graph_* (include/aloam_mi355x.h, "pose graphs").
+
+A pose X = (q, t) maps a point of the node's frame into the frame the graph lives in: x' = q x q* + t, q = (x, y, z, w).
+
+    compose(Xa, Xb)      = (q_a q_b, q_a t_b + t_a)
+    relative_pose(Xi, Xj) = X_i^-1 o X_j
+    edge (i, j, Z, Omega): E = Z^-1 o X_i^-1 o X_j  (X_i = identity for an anchor, i = -1); q_E negated when its w < 0;
+                           r = (2 q_E.xyz, t_E),  s = r^T Omega r
+    cost = 1/2 sum rho(s);  rho(s) = s, or for robust edges Ceres' HuberLoss(delta): s <= delta^2 ? s : 2 delta sqrt(s) - delta^2
+    node 0 is fixed; the tangent of node k is a LEFT perturbation q' = exp(theta / 2) q, t' = t + dt, order (theta, t).
+
+Everything here is float64 numpy on the host: the definition the device is tested against, a dense Levenberg-Marquardt reference
+(optimize), the chain-preconditioned conjugate gradients of the device restated (chain_pcg), the two lines of algebra that turn a
+relocalized pose into an edge, and the fixture generator of the tests (drifted_laps).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+EDGE_ROBUST = 1
+NODE_DTYPE = np.dtype([("q", np.float64, 4), ("t", np.float64, 3), ("q_opt", np.float64, 4), ("t_opt", np.float64, 3),
+                       ("frame", np.int32), ("pad", np.int32, 3)])
+EDGE_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("flags", np.int32), ("q", np.float64, 4), ("t", np.float64, 3),
+                       ("info", np.float64, 21)])
+_IU = np.triu_indices(6)
+
+
+# ---- quaternions and poses (batched over leading axes) -----------------------------------------------------------------------------
+def qmul(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    ax, ay, az, aw = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bx, by, bz, bw = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz], -1)
+
+
+def qconj(q):
+    q = np.asarray(q, np.float64)
+    return q * np.array([-1.0, -1.0, -1.0, 1.0])
+
+
+def qrot(q, v):
+    """q v q* as Eigen evaluates it: uv = 2 u x v; v + w uv + u x uv."""
+    q, v = np.asarray(q, np.float64), np.asarray(v, np.float64)
+    u = q[..., :3]
+    uv = np.cross(u, v)
+    uv = uv + uv
+    return v + q[..., 3:4] * uv + np.cross(u, uv)
+
+
+def rotmat(q):
+    return np.stack([qrot(q, e) for e in np.eye(3)], -1)
+
+
+def qexp(theta):
+    """exp(theta / 2): the unit quaternion of the rotation vector theta."""
+    theta = np.asarray(theta, np.float64)
+    n = np.linalg.norm(theta, axis=-1, keepdims=True)
+    h = 0.5 * n
+    k = np.where(n > 0, np.sin(h) / np.where(n > 0, n, 1.0), 0.5)
+    return np.concatenate([k * theta, np.cos(h)], -1)
+
+
+def compose(qa, ta, qb, tb):
+    return qmul(qa, qb), qrot(qa, tb) + np.asarray(ta, np.float64)
+
+
+def inverse(q, t):
+    qi = qconj(q)
+    return qi, -qrot(qi, t)
+
+
+def relative_pose(qi, ti, qj, tj):
+    """X_i^-1 o X_j: node j in the frame of node i, operation by operation as the device forms an odometry edge."""
+    qc = qconj(qi)
+    return qmul(qc, qj), qrot(qc, np.asarray(tj, np.float64) - np.asarray(ti, np.float64))
+
+
+def info_full(info21):
+    a = np.asarray(info21, np.float64)
+    m = np.zeros(a.shape[:-1] + (6, 6))
+    m[..., _IU[0], _IU[1]] = a
+    m[..., _IU[1], _IU[0]] = a
+    return m
+
+
+def info_upper(m):
+    return np.asarray(m, np.float64)[..., _IU[0], _IU[1]]
+
+
+def make_edges(seq, i, j, q, t, info, robust=False):
+    """A structured array of EDGE_DTYPE; info is [n, 6, 6] / [6, 6] (full) or [n, 21] / [21] (upper triangle)."""
+    i = np.atleast_1d(np.asarray(i, np.int32))
+    e = np.zeros(len(i), EDGE_DTYPE)
+    info = np.asarray(info, np.float64)
+    if info.shape[-1] == 6:
+        info = info_upper(info)
+    e["seq"], e["i"], e["j"], e["q"], e["t"], e["info"] = seq, i, j, q, t, info
+    e["flags"] = np.where(np.broadcast_to(robust, i.shape), EDGE_ROBUST, 0)
+    return e
+
+
+# ---- the problem ---------------------------------------------------------------------------------------------------------------------
+def _edge_frames(q, t, edges):
+    i, j = edges["i"], edges["j"]
+    anchor = i < 0
+    qi = np.where(anchor[:, None], np.array([0.0, 0.0, 0.0, 1.0]), q[np.maximum(i, 0)])
+    ti = np.where(anchor[:, None], 0.0, t[np.maximum(i, 0)])
+    return qi, ti, q[j], t[j], anchor
+
+
+def residual(q, t, edges):
+    """r [E, 6] = (2 q_E.xyz, t_E) with E = Z^-1 o X_i^-1 o X_j."""
+    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    qi, ti, qj, tj, _ = _edge_frames(q, t, edges)
+    qd, td = relative_pose(qi, ti, qj, tj)
+    qz = qconj(edges["q"])
+    qe, te = qmul(qz, qd), qrot(qz, td - edges["t"])
+    qe = np.where(qe[:, 3:4] < 0, -qe, qe)
+    return np.concatenate([2.0 * qe[:, :3], te], 1)
+
+
+def _rho(s, robust, delta):
+    big = robust & (s > delta * delta)
+    rs = np.sqrt(np.where(big, s, 1.0))
+    rho0 = np.where(big, 2.0 * delta * rs - delta * delta, s)
+    rho1 = np.where(big, np.maximum(2.2250738585072014e-308, delta / rs), 1.0)
+    return rho0, rho1
+
+
+def cost(q, t, edges, huber_delta=1.0):
+    r = residual(q, t, edges)
+    s = np.einsum("ea,eab,eb->e", r, info_full(edges["info"]), r)
+    return 0.5 * float(np.sum(_rho(s, (edges["flags"] & EDGE_ROBUST) != 0, huber_delta)[0]))
+
+
+def _skew(v):
+    z = np.zeros(v.shape[:-1])
+    return np.stack([np.stack([z, -v[..., 2], v[..., 1]], -1), np.stack([v[..., 2], z, -v[..., 0]], -1), np.stack([-v[..., 1], v[..., 0], z], -1)], -2)
+
+
+def linearize(q, t, edges, huber_delta=1.0):
+    """r [E, 6], w [E] (rho'), J_i and J_j [E, 6, 6] in the left tangent of the two nodes (J_i of an anchor is zero), rho [E]."""
+    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    qi, ti, qj, tj, anchor = _edge_frames(q, t, edges)
+    qa = qmul(qconj(edges["q"]), qconj(qi))            # A = Z^-1 o X_i^-1 (rotation part)
+    RA = rotmat(qa)
+    qe = qmul(qa, qj)
+    r0 = residual(q, t, edges)
+    qe = np.where(qe[:, 3:4] < 0, -qe, qe)
+    B = (qe[:, 3, None, None] * np.eye(3) - _skew(qe[:, :3])) @ RA        # d(2 q_E.xyz) / d theta_j
+    E = len(edges)
+    Jj = np.zeros((E, 6, 6)); Ji = np.zeros((E, 6, 6))
+    Jj[:, :3, :3] = B; Jj[:, 3:, 3:] = RA
+    Ji[:, :3, :3] = -B; Ji[:, 3:, 3:] = -RA; Ji[:, 3:, :3] = RA @ _skew(tj - ti)
+    Ji[anchor] = 0.0
+    s = np.einsum("ea,eab,eb->e", r0, info_full(edges["info"]), r0)
+    rho0, rho1 = _rho(s, (edges["flags"] & EDGE_ROBUST) != 0, huber_delta)
+    return r0, rho1, Ji, Jj, rho0
+
+
+def gradient(q, t, edges, huber_delta=1.0):
+    """d cost / d (theta_k, t_k) [N, 6]; the row of the fixed node 0 is zero."""
+    r, w, Ji, Jj, _ = linearize(q, t, edges, huber_delta)
+    Om = info_full(edges["info"])
+    wr = w[:, None] * np.einsum("eab,eb->ea", Om, r)
+    g = np.zeros((len(q), 6))
+    np.add.at(g, edges["j"], np.einsum("eab,ea->eb", Jj, wr))
+    m = edges["i"] >= 0
+    np.add.at(g, edges["i"][m], np.einsum("eab,ea->eb", Ji[m], wr[m]))
+    g[0] = 0.0
+    return g
+
+
+def normal_equations(q, t, edges, huber_delta=1.0):
+    """Dense Gauss-Newton H [6 (N - 1), 6 (N - 1)] and g over the nodes 1 .. N - 1, and the cost."""
+    r, w, Ji, Jj, rho0 = linearize(q, t, edges, huber_delta)
+    N = len(q)
+    Om = info_full(edges["info"]) * w[:, None, None]
+    H = np.zeros((N, 6, N, 6)); g = np.zeros((N, 6))
+    for e in range(len(edges)):
+        i, j = int(edges["i"][e]), int(edges["j"][e])
+        Tj = Om[e] @ Jj[e]
+        H[j, :, j, :] += Jj[e].T @ Tj
+        g[j] += Tj.T @ r[e]
+        if i >= 0:
+            Ti = Om[e] @ Ji[e]
+            H[i, :, i, :] += Ji[e].T @ Ti
+            g[i] += Ti.T @ r[e]
+            Hij = Ji[e].T @ Tj
+            H[i, :, j, :] += Hij
+            H[j, :, i, :] += Hij.T
+    n = 6 * (N - 1)
+    return H[1:, :, 1:, :].reshape(n, n), g[1:].reshape(n), 0.5 * float(rho0.sum())
+
+
+def retract(q, t, delta):
+    """The left perturbation delta [N, 6] applied to every node."""
+    return qmul(qexp(delta[:, :3]), q), t + delta[:, 3:]
+
+
+DEFAULT_OPTIONS = dict(max_iterations=20, function_tolerance=1e-10, gradient_tolerance=1e-10, pcg_tolerance=1e-8, pcg_max_iterations=200,
+                       huber_delta=1.0)
+TERMINATION = {0: "max_iterations", 2: "function_tolerance", 3: "gradient_tolerance", 5: "failure", 6: "min_radius"}
+
+
+def optimize(q, t, edges, max_iterations=20, function_tolerance=1e-10, gradient_tolerance=1e-10, huber_delta=1.0, solve=None, **_):
+    """Levenberg-Marquardt with the trust-region rules of the device (lm_device.hpp's, without Jacobi scaling and without the parameter
+    tolerance) and a dense solve of every step.  `solve(H, D, g, q, t)` replaces the dense solve (chain_pcg's hook).
+    Returns q, t and a dict with the fields of aloam_graph_result."""
+    q, t = np.array(q, np.float64), np.array(t, np.float64)
+    N = len(q)
+    res = dict(status=1, termination=0, lm_iterations=0, accepted_steps=0, pcg_iterations=0, nodes=N, edges=len(edges), initial_cost=0.0,
+               final_cost=0.0, gradient_max=0.0)
+    if N < 2 or len(edges) == 0:
+        return q, t, res
+    H, g, c = normal_equations(q, t, edges, huber_delta)
+    res.update(status=0, initial_cost=c)
+    q0, t0 = q.copy(), t.copy()
+    radius, decrease, diag, reuse, invalid, it = 1e4, 2.0, None, False, 0, 0
+    gmax = float(np.abs(g).max())
+    term = 0
+    while True:
+        if not (np.isfinite(c) and np.isfinite(gmax)): term = 5; break      # a non-finite cost, gradient or block: failure
+        if it >= max_iterations: term = 0; break
+        if gmax <= gradient_tolerance: term = 3; break
+        if radius <= 1e-32: term = 6; break
+        it += 1
+        if not reuse:
+            diag = np.clip(np.diag(H), 1e-6, 1e32)
+        D = diag / radius
+        reuse = True
+        try:
+            if solve is None:
+                y = np.linalg.solve(H + np.diag(D), g)
+            else:
+                y, k = solve(H, D, g)
+                res["pcg_iterations"] += k
+            ok = bool(np.all(np.isfinite(y)))
+        except np.linalg.LinAlgError:
+            ok = False
+        model_change = float(y @ g - 0.5 * y @ (H @ y)) if ok else 0.0
+        if not ok or not model_change > 0.0:
+            invalid += 1
+            if invalid >= 5: term = 5; break
+            radius /= decrease; decrease *= 2.0
+            continue
+        invalid = 0
+        d = np.zeros((N, 6)); d[1:] = -y.reshape(N - 1, 6)
+        qc, tc = retract(q, t, d)
+        cc = cost(qc, tc, edges, huber_delta)
+        if abs(c - cc) <= function_tolerance * c: term = 2; break
+        rel = (c - cc) / model_change
+        if rel > 1e-3:
+            q, t = qc, tc
+            H, g, c = normal_equations(q, t, edges, huber_delta)
+            res["accepted_steps"] += 1
+            gmax = float(np.abs(g).max())
+            c3 = 2.0 * rel - 1.0
+            radius = min(1e16, radius / max(1.0 / 3.0, 1.0 - c3 ** 3))
+            decrease, reuse = 2.0, False
+        else:
+            radius /= decrease; decrease *= 2.0
+    if term == 5 or not c <= res["initial_cost"]:
+        q, t, c = q0, t0, res["initial_cost"]
+        if term != 5: res["status"] = 2
+    if term == 5: res["status"] = 2
+    res.update(termination=term, lm_iterations=it, final_cost=c, gradient_max=gmax)
+    return q, t, res
+
+
+# ---- the device's linear solver, restated -------------------------------------------------------------------------------------------
+def _chain_mask(n_blocks):
+    """Block-tridiagonal pattern over n_blocks 6 x 6 blocks."""
+    k = np.arange(n_blocks)
+    return np.kron(np.abs(k[:, None] - k[None, :]) <= 1, np.ones((6, 6), bool))
+
+
+def pcg(A, b, apply_minv, tol=1e-8, max_iterations=200):
+    """Preconditioned conjugate gradients from x = 0; stops when sqrt(r^T M^-1 r) <= tol * its first value.  Returns x, iterations."""
+    x = np.zeros_like(b); r = b.copy()
+    z = apply_minv(r); p = z.copy()
+    rz = float(r @ z); rz0 = rz
+    k = 0
+    if not rz0 > 0.0:
+        return x, 0
+    while k < max_iterations:
+        Ap = A @ p
+        alpha = rz / float(p @ Ap)
+        x += alpha * p; r -= alpha * Ap
+        k += 1
+        z = apply_minv(r)
+        rz_new = float(r @ z)
+        if not rz_new > tol * tol * rz0:
+            break
+        p = z + (rz_new / rz) * p
+        rz = rz_new
+    return x, k
+
+
+def chain_solver(tol=1e-8, max_iterations=200):
+    """solve(H, D, g) for optimize(): PCG on H + diag(D) preconditioned with its block-tridiagonal part (the chain)."""
+    def solve(H, D, g):
+        from scipy.linalg import cholesky_banded, cho_solve_banded
+        A = H + np.diag(D)
+        n = len(g)
+        band = np.zeros((12, n))                        # upper form: band[11 + i - j, j] = M[i, j]; the chain lies inside bandwidth 11
+        M = np.where(_chain_mask(n // 6), A, 0.0)
+        for u in range(12):
+            band[11 - u, u:] = np.diagonal(M, u)
+        cb = cholesky_banded(band)
+        return pcg(A, g, lambda r: cho_solve_banded((cb, False), r), tol, max_iterations)
+    return solve
+
+
+def jacobi_solver(tol=1e-8, max_iterations=100000):
+    """The same with the 6 x 6 diagonal blocks alone (block-Jacobi): what the chain preconditioner is measured against."""
+    def solve(H, D, g):
+        A = H + np.diag(D)
+        n = len(g) // 6
+        inv = np.stack([np.linalg.inv(A[6 * k:6 * k + 6, 6 * k:6 * k + 6]) for k in range(n)])
+        return pcg(A, g, lambda r: np.einsum("kab,kb->ka", inv, r.reshape(n, 6)).reshape(-1), tol, max_iterations)
+    return solve
+
+
+def chain_pcg(q, t, edges, **options):
+    """optimize() with every step solved by the chain-preconditioned PCG; the result's pcg_iterations is the yardstick of the device's."""
+    o = dict(DEFAULT_OPTIONS); o.update(options)
+    return optimize(q, t, edges, solve=chain_solver(o["pcg_tolerance"], o["pcg_max_iterations"]), **o)
+
+
+# ---- edges from a localization -------------------------------------------------------------------------------------------------------
+def anchor_from_localization(j, q_map, t_map, info, seq=0, robust=False):
+    """Node j was localized at (q_map, t_map) in the fixed world (atlas) frame with information `info`: the anchor edge (-1, j)."""
+    return make_edges(seq, -1, j, np.asarray(q_map, np.float64)[None], np.asarray(t_map, np.float64)[None], np.asarray(info)[None], robust)
+
+
+def loop_from_localization(i, q_place, t_place, j, q_reloc, t_reloc, info, seq=0, robust=False):
+    """The sweep of node j was relocalized at (q_reloc, t_reloc) in the frame in which the stored place of node i has the pose
+    (q_place, t_place): the loop edge (i, j) with Z = X_place^-1 o X_reloc."""
+    qz, tz = relative_pose(q_place, t_place, q_reloc, t_reloc)
+    return make_edges(seq, i, j, qz[None], tz[None], np.asarray(info)[None], robust)
+
+
+# ---- fixtures ------------------------------------------------------------------------------------------------------------------------
+def drifted_laps(seed, nodes, loops, radius=10.0, per_lap=None, sigma_theta=5e-3, sigma_t=5e-2, yaw_bias=1.5e-3, noise=1.0):
+    """Ground-truth laps of a circle (with a slow climb), odometry edges with seeded noise and a yaw bias, `loops` loop edges between
+    laps; noise = 0 makes every edge exact.  Returns dict(q_true, t_true, q, t (the drifted chain: node 0 true, then X[k] = X[k - 1] o Z_k), odom (edges (k - 1, k)),
+    loop (edges), info (the 6 x 6 information every edge carries))."""
+    rng = np.random.default_rng(seed)
+    per_lap = per_lap or max(8, nodes // 3)
+    k = np.arange(nodes)
+    ang = 2.0 * np.pi * k / per_lap
+    t_true = np.stack([radius * np.cos(ang), radius * np.sin(ang), 0.002 * k], 1)
+    yaw = ang + 0.5 * np.pi
+    q_true = np.stack([0.02 * np.sin(ang), 0.02 * np.cos(ang), np.sin(0.5 * yaw), np.cos(0.5 * yaw)], 1)
+    q_true /= np.linalg.norm(q_true, axis=1, keepdims=True)
+    info = np.diag([1.0 / sigma_theta ** 2] * 3 + [1.0 / sigma_t ** 2] * 3)
+
+    def noisy(qz, tz, n):
+        dth = noise * sigma_theta * rng.standard_normal((n, 3))
+        return qmul(qz, qexp(dth)), tz + noise * sigma_t * rng.standard_normal((n, 3))
+
+    qz, tz = relative_pose(q_true[:-1], t_true[:-1], q_true[1:], t_true[1:])
+    qz, tz = noisy(qz, tz, nodes - 1)
+    qz = qmul(qz, qexp(np.tile([0.0, 0.0, noise * yaw_bias], (nodes - 1, 1))))
+    odom = make_edges(0, k[:-1], k[1:], qz, tz, info)
+    q, t = [q_true[0]], [t_true[0]]
+    for e in range(nodes - 1):
+        a, b = compose(q[-1], t[-1], qz[e], tz[e])
+        q.append(a); t.append(b)
+    q, t = np.array(q), np.array(t)
+    # loop edges: node j against the node one or more laps earlier at the same place
+    js = np.linspace(per_lap + 1, nodes - 1, loops).astype(int) if loops else np.zeros(0, int)
+    is_ = js - per_lap * (js // per_lap)
+    is_ = np.where(is_ == js, js - per_lap, is_)
+    ql, tl = relative_pose(q_true[is_], t_true[is_], q_true[js], t_true[js])
+    if loops:
+        ql, tl = noisy(ql, tl, loops)
+    loop = make_edges(0, is_, js, ql.reshape(-1, 4), tl.reshape(-1, 3), info)
+    return dict(q_true=q_true, t_true=t_true, q=q, t=t, odom=odom, loop=loop, info=info)
+
+
+def ate(t, t_true):
+    """Absolute trajectory error: the RMS distance of the positions (both trajectories share node 0; no alignment)."""
+    return float(np.sqrt(np.mean(np.sum((np.asarray(t) - np.asarray(t_true)) ** 2, 1))))
+
+
+def pose_difference(qa, ta, qb, tb):
+    """The largest of |t_a - t_b| and 2 |q_a -+ q_b| over all nodes and components (radians and metres)."""
+    qa, qb = np.asarray(qa), np.asarray(qb)
+    sgn = np.where(np.sum(qa * qb, 1, keepdims=True) < 0, -1.0, 1.0)
+    return float(max(np.abs(np.asarray(ta) - np.asarray(tb)).max(), 2.0 * np.abs(qa - sgn * qb).max()))

@@ -653,6 +653,91 @@ typedef struct aloam_pose_information {       /* one per listed sequence; 1048 b
 } aloam_pose_information;
 int aloam_export_pose_information(aloam_ctx* ctx, int which, const int* seqs, int n, aloam_pose_information* dst /* [n] */);
 
+/* ---- pose graphs: keyframes, odometry / loop / anchor edges, and a batched solve --------------------------------------------------------
+ * One graph per sequence, kept on the device: nodes are poses entered from the sequence's own state, edges are relative poses between two
+ * nodes (odometry, loop closures) or absolute poses of one node (anchors: a localization in an atlas).  aloam_graph_optimize runs
+ * Levenberg-Marquardt over the graphs of the listed sequences, one workgroup each.  Beside the reference (A-LOAM has no back end) and
+ * opt-in: a context that never calls aloam_graph_enable launches what it launched before.  a-loam_amd/posegraph.py restates every
+ * operation in numpy; DESIGN.md §7k.
+ *
+ * Poses.  X = (q, t), q = (x, y, z, w): x' = q x q* + t.  Xa o Xb = (q_a q_b, q_a t_b + t_a); X^-1 = (q*, -(q* t)).
+ * Problem.  For an edge (i, j, Z, Omega): E = Z^-1 o X_i^-1 o X_j, evaluated as q_d = q_i* q_j, t_d = q_i* (t_j - t_i), q_E = q_Z* q_d,
+ *   t_E = q_Z* (t_d - t_Z); X_i is the identity for an anchor (i = -1).  q_E is negated when its w < 0.  r = (2 q_E.xyz, t_E), s = r^T Omega r.
+ *   cost = 1/2 sum rho(s): rho(s) = s for plain edges; for edges flagged ALOAM_GRAPH_EDGE_ROBUST it is Ceres' HuberLoss(huber_delta),
+ *   s <= delta^2 ? s : 2 delta sqrt(s) - delta^2, applied as the solvers apply it (rows scaled by sqrt(rho'), rho' = delta / sqrt(s)).
+ *   Node 0 is held fixed.  The tangent of a node is a LEFT perturbation, q' = exp(theta / 2) q, t' = t + dt, order (theta, t): the order and
+ *   the units (radians, metres) of aloam_pose_information.info, so the upper triangle of such a record can be copied into an edge.
+ *
+ * aloam_graph_enable(ctx, max_nodes, max_edges): once per context; every sequence gets a row of max_nodes nodes and max_edges edges (the
+ *   odometry edges count).  1 <= max_nodes <= 2^20, 1 <= max_edges <= 2^22, else ALOAM_E_ARG; a second call: ALOAM_E_STATE.  Needs
+ *   ALOAM_STAGE_ODOMETRY.  Every other call of this section returns ALOAM_E_STATE before it, and queues nothing on any error.
+ * aloam_graph_add_nodes: one node per listed sequence (distinct, in range), stream-ordered, no host synchronisation.  The pose is read on
+ *   the device at that point of the stream, as aloam_places_add reads it: q_w_curr / t_w_curr and frameCount with mapping enabled, else
+ *   the odometry's q_w / t_w and -1.  Node k > 0 also gets the odometry edge (k - 1, k) with Z = X[k-1]^-1 o X[k] of the entered poses and
+ *   the information odom_info[i] (upper triangle, 21 doubles; required; finite and positive definite, else ALOAM_E_ARG), and the estimate
+ *   X_opt[k-1] o Z; node 0's estimate is its entered pose.  The counts are host state: the new node's index is aloam_graph_info's count
+ *   before the call.  A row without room for the node or its edge: ALOAM_E_CAPACITY.
+ * aloam_graph_add_edges: `edges` in host memory (pinned or pageable), read during the call.  Everything is validated before anything is
+ *   queued: seq in range; -1 <= i < nodes, 0 <= j < nodes, i != j; q finite and within 1e-6 of unit norm (stored normalised); t finite;
+ *   info finite and positive definite (a host Cholesky succeeds); flags 0 or ALOAM_GRAPH_EDGE_ROBUST: else ALOAM_E_ARG.  No room:
+ *   ALOAM_E_CAPACITY.  Edges are appended to their sequence's row in the order given.  (Stream-ordered on the device; the copy out of
+ *   pageable memory may wait on the host for the stream, unlike aloam_graph_add_nodes and aloam_graph_optimize.)
+ * aloam_graph_export / aloam_graph_export_edges: nodes / edges [first, first + count) of one sequence, stream-ordered, into device memory
+ *   of the context's device or pinned host memory, 8-byte aligned (pageable, managed, another device's, NULL with count > 0: ALOAM_E_ARG).
+ * aloam_graph_clear: the listed sequences' graphs become empty (counts are host state; later adds overwrite in stream order).
+ * aloam_graph_info: out = {nodes, edges, max_nodes, max_edges} of one sequence.
+ * The graph is NOT part of a sequence record: aloam_reset_sequences, aloam_save_sequences and aloam_load_sequences leave it alone, like the
+ *   map spill.  The caller clears a slot's graph before the slot starts another drive.
+ *
+ * aloam_graph_optimize: stream-ordered; dst[i] belongs to seqs[i], in device or pinned memory like the exports; its bits and the exported
+ *   nodes do not depend on n, on i or on the other sequences listed.  opt = NULL: the defaults.  Options (the algorithm's parameters):
+ *   max_iterations >= 0, pcg_max_iterations >= 1, the tolerances >= 0 and finite, huber_delta > 0, else ALOAM_E_ARG.
+ *   status: ALOAM_GRAPH_OK; ALOAM_GRAPH_NO_EDGES - fewer than two nodes or no edge, nothing done; ALOAM_GRAPH_FAILED - the solve ended as a
+ *   failure or above its initial cost: the estimates are as they were.  The estimates (q_opt, t_opt) are written back only when the final
+ *   cost is not above the initial one.  termination: 0 max_iterations, 2 function_tolerance (|cost change| <= tol * cost), 3
+ *   gradient_tolerance (max-norm of the gradient in the tangent above), 5 failure (five unusable steps in a row, or a non-finite
+ *   evaluation), 6 minimum trust-region radius.  The loop is the trust-region Levenberg-Marquardt of the odometry and mapping solvers
+ *   (initial radius 1e4, diagonal clamp [1e-6, 1e32], acceptance above 1e-3 relative decrease); each step is solved by conjugate
+ *   gradients preconditioned with the block-tridiagonal chain, to pcg_tolerance relative in the preconditioned norm.  No host
+ *   synchronisation.  A node's incident edges are ordered by one lane, d^2 / 2 moves for d of them: meant for up to a few hundred
+ *   edges on one node. */
+enum { ALOAM_GRAPH_EDGE_ROBUST = 1 };
+enum { ALOAM_GRAPH_OK = 0, ALOAM_GRAPH_NO_EDGES = 1, ALOAM_GRAPH_FAILED = 2 };
+typedef struct aloam_graph_node {             /* 128 bytes                                                                              */
+  double q[4], t[3];                          /* the pose as entered, in the sequence's own (drifting) frame; never changed             */
+  double q_opt[4], t_opt[3];                  /* the current estimate                                                                   */
+  int frame;                                  /* frameCount when it was entered (mapping), else -1                                      */
+  int pad[3];
+} aloam_graph_node;
+typedef struct aloam_graph_edge {             /* 240 bytes                                                                              */
+  int seq, i, j, flags;                       /* i = -1: the fixed world frame (an anchor of node j)                                    */
+  double q[4], t[3];                          /* Z: the measured pose of node j in the frame of node i                                  */
+  double info[21];                            /* upper triangle, row-major, of the 6 x 6 information, order (theta_x .. t_z)            */
+} aloam_graph_edge;
+typedef struct aloam_graph_options {          /* 40 bytes                                                                               */
+  int max_iterations;                         /* 20                                                                                     */
+  int pcg_max_iterations;                     /* 200                                                                                    */
+  double function_tolerance;                  /* 1e-10, relative cost change                                                            */
+  double gradient_tolerance;                  /* 1e-10, max-norm                                                                        */
+  double pcg_tolerance;                       /* 1e-8, relative in the preconditioned norm                                              */
+  double huber_delta;                         /* 1.0: s is a squared Mahalanobis distance, so delta is in standard deviations           */
+} aloam_graph_options;
+typedef struct aloam_graph_result {           /* 64 bytes                                                                               */
+  int status, termination;
+  int lm_iterations, accepted_steps, pcg_iterations;
+  int nodes, edges, pad;
+  double initial_cost, final_cost, gradient_max, reserved;
+} aloam_graph_result;
+void aloam_graph_default_options(aloam_graph_options* opt);
+int aloam_graph_enable(aloam_ctx* ctx, int max_nodes, int max_edges);
+int aloam_graph_add_nodes(aloam_ctx* ctx, const int* seqs, int n, const double* odom_info /* [n][21] */);
+int aloam_graph_add_edges(aloam_ctx* ctx, const aloam_graph_edge* edges, int n);
+int aloam_graph_export(aloam_ctx* ctx, int seq, int first, int count, aloam_graph_node* dst);
+int aloam_graph_export_edges(aloam_ctx* ctx, int seq, int first, int count, aloam_graph_edge* dst);
+int aloam_graph_clear(aloam_ctx* ctx, const int* seqs, int n);
+int aloam_graph_info(aloam_ctx* ctx, int seq, int out[4]);
+int aloam_graph_optimize(aloam_ctx* ctx, const int* seqs, int n, const aloam_graph_options* opt, aloam_graph_result* dst /* [n] */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */
