@@ -1,5 +1,6 @@
 """Map tiles on the host (numpy only): the record that the map spill produces (aloam_map_tile), a log that collects drained spills, files,
-and a model of the window arithmetic - which cubes a shift empties, and the window cut out of a set of tiles at any centre.
+a model of the window arithmetic - which cubes a shift empties, and the window cut out of a set of tiles at any centre - and the model
+of the map assembled from keyframe clouds at the poses of a pose graph (tiles_from_keyframes, aloam_graph_export_map).
 
 A tile is one 50 m cube of one class with ABSOLUTE cube coordinates: window index (i, j, k) minus the window centre (cenW, cenH, cenD),
 which is int((t + 25) / 50), minus one when t + 25 < 0, of the coordinates of its points (reference src/laserMapping.cpp:312-321).  The
@@ -132,6 +133,71 @@ def load_atlas_places(path):
 def load_atlas(path):
     with np.load(path) as z:
         return np.asarray(z["tiles"], TILE_DTYPE), np.asarray(z["points"], np.float32).reshape(-1, 4)
+
+
+# ---- the map of a pose graph: keyframe clouds at the graph's poses (aloam_graph_export_map) --------------------------------
+CUBE_MIN, CUBE_MAX = -512, 511                          # absolute cubes an atlas holds per axis
+
+
+def associate_to_map(points, q, t):
+    """pointAssociateToMap as the device evaluates it (map_search_device.hpp, lm_device.hpp quat_rotate): q = (x, y, z, w), every product,
+    sum and difference a separately rounded f64 operation in this order, each component stored to f32, the intensity kept."""
+    p = np.asarray(points, np.float32).reshape(-1, 4)
+    q0, q1, q2, q3 = (np.float64(v) for v in q)
+    t0, t1, t2 = (np.float64(v) for v in t)
+    vx, vy, vz = (p[:, k].astype(np.float64) for k in range(3))
+    ux, uy, uz = q1 * vz - q2 * vy, q2 * vx - q0 * vz, q0 * vy - q1 * vx
+    ux, uy, uz = ux + ux, uy + uy, uz + uz
+    ox = vx + q3 * ux + (q1 * uz - q2 * uy)
+    oy = vy + q3 * uy + (q2 * ux - q0 * uz)
+    oz = vz + q3 * uz + (q0 * uy - q1 * ux)
+    out = np.empty_like(p)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = (ox + t0).astype(np.float32), (oy + t1).astype(np.float32), (oz + t2).astype(np.float32), p[:, 3]
+    return out
+
+
+def cube_coord(v):
+    """int((v + 25) / 50), minus one when v + 25 < 0, of f32 coordinates widened to f64 (cube_coord with centre 0): -75 lands in -2."""
+    s = np.asarray(v, np.float32).astype(np.float64) + 25.0
+    return np.trunc(s / 50.0).astype(np.int64) - (s < 0)
+
+
+def tiles_from_keyframes(q, t, clouds, leaves, voxel_filter, stats=None):
+    """The map of keyframes k = 0 .. K-1 with poses (q[k], t[k]) and sensor-frame clouds clouds[k] = (corner, surf): every point through
+    associate_to_map, into the cube of its coordinates; the members of a (cube, class) - node order, then point order inside the node - are
+    filtered once with voxel_filter(points, leaves[class]) (the caller's input-order pcl::VoxelGrid), always, also with one contributor.
+    Returns (tiles, points): corner tiles, then surf tiles, each ascending in (cube[0], cube[1], cube[2]), frame 0.  Points whose cube
+    lies outside -512 .. 511 on some axis are left out.  stats (a dict) receives tiles, points, raw_points (per class) and outside."""
+    members = ({}, {})
+    outside = 0
+    for k, cl in enumerate(clouds):
+        for cls in (0, 1):
+            w = associate_to_map(cl[cls], q[k], t[k])
+            if not len(w):
+                continue
+            cube = np.stack([cube_coord(w[:, a]) for a in range(3)], 1)
+            ok = np.all((cube >= CUBE_MIN) & (cube <= CUBE_MAX), 1)
+            outside += int(np.count_nonzero(~ok))
+            for key in sorted(set(map(tuple, cube[ok].tolist()))):
+                members[cls].setdefault(key, []).append(w[ok & np.all(cube == np.array(key), 1)])
+    tiles, pts, first = [], [], 0
+    st = {"tiles": [0, 0], "points": [0, 0], "raw_points": [0, 0], "outside": outside}
+    for cls in (0, 1):
+        for key in sorted(members[cls]):
+            raw = np.concatenate(members[cls][key])
+            p = np.asarray(voxel_filter(raw, leaves[cls]), np.float32).reshape(-1, 4)
+            tl = np.zeros((), TILE_DTYPE)
+            tl["cube"] = key
+            tl["feature_class"], tl["count"], tl["frame"], tl["first_point"] = cls, len(p), 0, first
+            tiles.append(tl)
+            pts.append(p)
+            first += len(p)
+            st["tiles"][cls] += 1
+            st["points"][cls] += len(p)
+            st["raw_points"][cls] += len(raw)
+    if stats is not None:
+        stats.update(st)
+    return (np.array(tiles, TILE_DTYPE) if tiles else np.zeros(0, TILE_DTYPE)), (np.concatenate(pts) if pts else np.zeros((0, 4), np.float32))
 
 
 # ---- a set of tiles as a map of any extent ---------------------------------------------------------------------------------------------

@@ -89,6 +89,20 @@ class AloamGraphResult(C.Structure):
                 ("final_cost", C.c_double), ("gradient_max", C.c_double), ("reserved", C.c_double)]
 
 
+class AloamGraphMapRequest(C.Structure):
+    """Nodes [first, first + count) of one sequence at the entered or the optimised poses (aloam_graph_map_request, 16 bytes)."""
+    _fields_ = [("seq", C.c_int), ("first", C.c_int), ("count", C.c_int), ("pose", C.c_int)]
+
+
+class AloamGraphMapStats(C.Structure):
+    """What aloam_graph_export_map made of one request (aloam_graph_map_stats, 32 bytes)."""
+    _fields_ = [("tiles", C.c_int * 2), ("points", C.c_int * 2), ("raw_points", C.c_int * 2), ("outside", C.c_int), ("written", C.c_int)]
+
+
+GRAPH_POSE_ENTERED, GRAPH_POSE_OPTIMIZED = 0, 1
+GRAPH_MAP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32)])
+GRAPH_MAP_STATS_DTYPE = np.dtype([("tiles", np.int32, 2), ("points", np.int32, 2), ("raw_points", np.int32, 2), ("outside", np.int32),
+                                  ("written", np.int32)])
 GRAPH_EDGE_ROBUST = 1
 GRAPH_OK, GRAPH_NO_EDGES, GRAPH_FAILED = 0, 1, 2
 GRAPH_NODE_DTYPE = np.dtype([("q", np.float64, 4), ("t", np.float64, 3), ("q_opt", np.float64, 4), ("t_opt", np.float64, 3),
@@ -297,6 +311,10 @@ def lib():
         L.aloam_graph_clear.argtypes = [vp, vp, C.c_int]
         L.aloam_graph_info.argtypes = [vp, C.c_int, vp]
         L.aloam_graph_optimize.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphOptions), vp]
+        L.aloam_graph_keyframes_enable.argtypes = [vp, C.c_int, C.c_int]
+        L.aloam_graph_export_keyframes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp]
+        L.aloam_graph_keyframe_info.argtypes = [vp, C.c_int, vp]
+        L.aloam_graph_export_map.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -734,6 +752,72 @@ class Aloam:
         v = np.zeros(4, np.int32)
         self._check(lib().aloam_graph_info(self.h, int(seq), _p(v)))
         return {"nodes": int(v[0]), "edges": int(v[1]), "max_nodes": int(v[2]), "max_edges": int(v[3])}
+
+    # ---- keyframe clouds and the map at the graph's poses (atlas.tiles_from_keyframes holds the definition) --------------------------------
+    def graph_keyframes_enable(self, max_corner_points, max_surf_points):
+        """Keep every new node's stacks (sensor frame) on the device: per sequence a row of that many corner / surf points."""
+        self._check(lib().aloam_graph_keyframes_enable(self.h, int(max_corner_points), int(max_surf_points)))
+
+    def graph_export_keyframes_into(self, seq, first, count, feature_class, points_ptr, cap_points, offsets_ptr):
+        self._check(lib().aloam_graph_export_keyframes(self.h, int(seq), int(first), int(count), int(feature_class), C.c_void_p(points_ptr) if points_ptr else None,
+                                                       int(cap_points), C.c_void_p(offsets_ptr) if offsets_ptr else None))
+
+    def graph_export_keyframes(self, seq=0, first=0, count=None, feature_class=0, pinned=True):
+        """The clouds of nodes [first, first + count) of one class: a size query, one allocation, the export and a synchronise.  Returns
+        (points float32 [n, 4], offsets int64 [count + 1])."""
+        import torch
+        if count is None:
+            count = self.graph_info(seq)["nodes"] - first
+        off = torch.zeros(count + 1, dtype=torch.int64, pin_memory=True)
+        self.graph_export_keyframes_into(seq, first, count, feature_class, 0, 0, off.data_ptr())
+        self.synchronize()
+        n = int(off[count])
+        pts = torch.zeros((max(1, n), 4), dtype=torch.float32, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_export_keyframes_into(seq, first, count, feature_class, pts.data_ptr(), n, off.data_ptr())
+        self.synchronize()
+        return pts.cpu().numpy()[:n].copy(), off.numpy().copy()
+
+    def graph_keyframe_info(self, seq=0):
+        v = np.zeros(8, np.int64)
+        self._check(lib().aloam_graph_keyframe_info(self.h, int(seq), _p(v)))
+        return {"points": v[0:2].tolist(), "capacity": v[2:4].tolist(), "dropped_nodes": int(v[4]), "dropped_points": int(v[5])}
+
+    @staticmethod
+    def graph_map_requests(requests):
+        """[(seq, first, count, pose), ...] -> structured array of GRAPH_MAP_REQUEST_DTYPE."""
+        r = np.zeros(len(requests), GRAPH_MAP_REQUEST_DTYPE)
+        for i, q in enumerate(requests):
+            r[i] = tuple(int(v) for v in q)
+        return r
+
+    def graph_export_map_into(self, requests, tiles_ptr, cap_tiles, points_ptr, cap_points, offsets_ptr, stats_ptr=0):
+        """Queue the map of each request (synchronises the stream once on the way): tiles_ptr receives up to cap_tiles aloam_map_tile
+        records, points_ptr up to cap_points float4 points, offsets_ptr 2 * (len(requests) + 1) int64, stats_ptr (0 = not wanted) one
+        aloam_graph_map_stats per request - device memory or pinned host memory; 0 pointers with caps of 0 = the size query."""
+        r = requests if isinstance(requests, np.ndarray) else self.graph_map_requests(requests)
+        r = np.ascontiguousarray(r, dtype=GRAPH_MAP_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_export_map(self.h, _p(r) if len(r) else None, len(r), C.c_void_p(tiles_ptr) if tiles_ptr else None, int(cap_tiles),
+                                                 C.c_void_p(points_ptr) if points_ptr else None, int(cap_points),
+                                                 C.c_void_p(offsets_ptr) if offsets_ptr else None, C.c_void_p(stats_ptr) if stats_ptr else None))
+
+    def graph_export_map(self, requests, pinned=True):
+        """The maps of `requests` ((seq, first, count, pose) each): a size query, pinned destinations (device memory with pinned=False), then
+        the call and a synchronise.  Returns (tiles, points, offsets, stats): MAP_TILE_DTYPE [t], float32 [p, 4], int64 [2, n + 1] and
+        GRAPH_MAP_STATS_DTYPE [n]."""
+        import torch
+        n = len(requests)
+        off = torch.zeros(2 * (n + 1), dtype=torch.int64, pin_memory=True)
+        self.graph_export_map_into(requests, 0, 0, 0, 0, off.data_ptr())
+        self.synchronize()
+        nt, npts = int(off[n]), int(off[2 * n + 1])
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, **where)
+        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **where)
+        stats = torch.zeros(max(1, n) * 32, dtype=torch.uint8, pin_memory=True)
+        self.graph_export_map_into(requests, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), stats.data_ptr())
+        self.synchronize()
+        return (tiles.cpu().numpy()[:nt * 32].view(MAP_TILE_DTYPE).copy(), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy(),
+                stats.numpy()[:n * 32].view(GRAPH_MAP_STATS_DTYPE).copy())
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

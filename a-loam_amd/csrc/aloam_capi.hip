@@ -258,6 +258,12 @@ int aloam_synchronize(aloam_ctx* c) {
       c->err = "map spill full: " + std::to_string(fresh_spill) + " tile(s) dropped since the last aloam_synchronize (drain more often or raise max_tiles / max_points)";
       return ALOAM_E_CAPACITY;
     }
+    long long fresh_kf = 0;                               // nodes k_keyframe_capture kept without clouds: reported once, like the dropped tiles
+    if (const int rc = keyframes_dropped_since(c, &fresh_kf)) return rc;
+    if (fresh_kf > 0) {
+      c->err = "keyframe store full: " + std::to_string(fresh_kf) + " node(s) kept without clouds since the last aloam_synchronize (raise max_corner_points / max_surf_points)";
+      return ALOAM_E_CAPACITY;
+    }
     if (c->d_rl_bad) {                                    // choices k_apply_corrections found outside 0 .. K-1: reported once, like the capacity events
       int bad = 0;
       HIP_TRY(c, hipMemcpy(&bad, c->d_rl_bad.get(), sizeof(bad), hipMemcpyDeviceToHost));
@@ -389,6 +395,13 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
     }
     // the last aloam_graph_optimize: nodes and edges read once, the estimates and one result written (the iterations run out of L2)
     if (kernel == K_POSE_GRAPH) bytes = (double)(sizeof(aloam_graph_node) + 56) * c->pg_last_nodes + (double)sizeof(aloam_graph_edge) * c->pg_last_edges;
+    // the last aloam_graph_export_map: 16 B read + 16 B written per raw point (transform), the slot written and read and the point read and
+    // written again (grouping, 40 B), 16 B per emitted point and 32 B per tile
+    if (kernel == K_GRAPH_MAP && c->gm_last_segs >= 0) {
+      long long emitted = 0;
+      HIP_TRY(c, hipMemcpy(&emitted, c->d_gm_point_off.get() + c->gm_last_segs, sizeof(emitted), hipMemcpyDeviceToHost));
+      bytes = 72.0 * c->gm_last_raw + 16.0 * emitted + 32.0 * c->gm_last_segs;
+    }
     if (kernel == K_APPLY) bytes = c->rl_apply_n * (4.0 + 4.0 + 64.0 + 56.0);   // id, choice, candidate in, correction out
     *algorithmic_bytes = bytes;
   }

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "atlas_kernels.hpp"
 #include "checkpoint_kernels.hpp"
 #include "export_kernels.hpp"
+#include "graphmap_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "places_kernels.hpp"
@@ -29,11 +30,11 @@ using namespace aloam;
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_GRAPH_MAP, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "pose_graph", "save_sequences",
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "pose_graph", "graph_map", "save_sequences",
                                     "load_sequences", "score_corrections", "apply_corrections"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
@@ -95,6 +96,7 @@ struct SeqHost {
                                      // (aloam_export_pose_information; else ALOAM_INFO_NONE).  Host state only: not part of a sequence record
   int graph_nodes = 0, graph_edges = 0;   // its pose graph (aloam_graph_*): what its rows of the store hold.  Host state only, and not the sequence's
                                      // but the slot's: reset and load leave it, aloam_graph_clear empties it
+  bool has_stacks = false;           // took part in a mapping step since creation / reset / load: its stacks can be kept as a keyframe's clouds
   bool grid_built = false;           // the grid set of its LAST clouds holds their grids: set by the step that made them the last ones (it built
                                      // them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
 };
@@ -211,6 +213,28 @@ struct aloam_ctx {
   DevBuf<double> d_pg_f64; long long pg_f64_cap = 0;                // the solve's scratch rows, grown on first use
   DevBuf<int> d_pg_i32; long long pg_i32_cap = 0;
   long long pg_last_nodes = 0, pg_last_edges = 0;                   // the last solve (algorithmic bytes)
+  // keyframe clouds of the pose graphs (aloam_graph_keyframes_enable): per sequence and class a row of sensor-frame points, per node a descriptor
+  bool kf_on = false;
+  int kf_cap[2] = {0, 0};                                           // points per sequence: corner, surf
+  DevBuf<float4> d_kf_points[2];                                    // [B][kf_cap[cls]]
+  DevBuf<KfDesc> d_kf_desc;                                         // [B][pg_max_nodes]
+  DevBuf<int> d_kf_counters;                                        // [B][kKfInts]
+  long long kf_dropped_reported = 0;                                // nodes kept without clouds aloam_synchronize has already returned
+  // the map at the graph's poses (aloam_graph_export_map): scratch grown on first use, used in stream order
+  DevBuf<float4> d_gm_world, d_gm_grouped; long long gm_points_cap = 0;   // transformed points as laid out for the bounds; grouped by (request, class, cube)
+  DevBuf<int> d_gm_slot; long long gm_slot_cap = 0;                 // directory slot of every transformed point
+  DevBuf<unsigned long long> d_gm_dir_key; long long gm_dir_key_cap = 0;   // the directory of (request, class, cube, piece): keys, counts / cursors, bases
+  DevBuf<int> d_gm_dir_count; long long gm_dir_count_cap = 0;
+  DevBuf<long long> d_gm_dir_base; long long gm_dir_base_cap = 0;
+  DevBuf<GmRequest> d_gm_req; long long gm_req_cap = 0;
+  DevBuf<GmRequestOut> d_gm_req_out; long long gm_req_out_cap = 0;
+  DevBuf<int> d_gm_ints; long long gm_ints_cap = 0;                 // first piece per (request, class), points outside per request, the overflow flag
+  DevBuf<AtlasMergeJob> d_gm_jobs; long long gm_jobs_cap = 0;       // one per (request, class, cube), with its filtered size and point offset
+  DevBuf<GmSegInfo> d_gm_seg; long long gm_seg_info_cap = 0;
+  DevBuf<int> d_gm_counts; long long gm_counts_cap = 0;
+  DevBuf<long long> d_gm_point_off; long long gm_point_off_cap = 0;
+  long long gm_dir_hint = 0;                                        // the directory size an earlier call had to grow to
+  long long gm_last_raw = 0; int gm_last_segs = -1;                 // the last call that succeeded (algorithmic bytes); -1 while its scratch is not valid
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -358,6 +382,11 @@ void queue_map_spill(aloam_ctx* c, const int* mask);
 int spill_dropped_since(aloam_ctx* c, long long* fresh);
 int atlas_step_check(aloam_ctx* c);                      // ALOAM_E_STATE when an attached sequence that is active in this step is not frozen
 bool queue_atlas_window(aloam_ctx* c, const int* mask);  // k_atlas_window when an attached sequence takes part
+// capi_graphmap.hip
+int keyframe_add_check(aloam_ctx* c, const int* seqs, int n);        // ALOAM_E_STATE when a listed sequence holds no stacks (store enabled)
+void queue_keyframe_capture(aloam_ctx* c, int n);                    // k_keyframe_capture behind k_graph_add_nodes, for the items in d_pg_add
+int queue_keyframe_rewind(aloam_ctx* c, const int* seqs, int n);     // aloam_graph_clear: the listed cursors back to 0, in stream order
+int keyframes_dropped_since(aloam_ctx* c, long long* fresh);
 // capi_seq.hip: the one "does sequence b take part in this step", a stage's mask, and what happens to a sequence, each with its whole consequence
 inline bool takes_part(const aloam_ctx* c, int b) { return c->all_active || c->seq[b].active; }
 struct StageMask {

@@ -108,6 +108,7 @@ int aloam_graph_add_nodes(aloam_ctx* c, const int* seqs, int n, const double* od
       return ALOAM_E_CAPACITY;
     }
   }
+  if (const int rc = keyframe_add_check(c, seqs, n)) return rc;
   if (n == 0) return ALOAM_OK;
   GraphAddItem* items = nullptr;
   int slot = 0;
@@ -122,6 +123,7 @@ int aloam_graph_add_nodes(aloam_ctx* c, const int* seqs, int n, const double* od
   a.n = n; a.items = c->d_pg_add.get(); a.odom = c->d_state.get(); a.mapseq = c->map_on ? c->d_mapseq.get() : nullptr;
   a.nodes = c->d_pg_nodes.get(); a.edges = c->d_pg_edges.get(); a.max_nodes = c->pg_max_nodes; a.max_edges = c->pg_max_edges;
   launch_graph_add_nodes(a, c->stream);
+  queue_keyframe_capture(c, n);        // the stacks of the listed sequences become the new nodes' clouds (aloam_graph_keyframes_enable)
   HIP_TRY(c, hipGetLastError());
   on_graph_nodes_added(c, seqs, n);
   return ALOAM_OK;
@@ -192,7 +194,7 @@ int aloam_graph_clear(aloam_ctx* c, const int* seqs, int n) {
   if (const int rc = require_graph(c)) return rc;
   if (const int rc = check_ids(c, seqs, n)) return rc;
   on_graph_cleared(c, seqs, n);       // later adds overwrite the rows in stream order; nothing on the device depends on the counts
-  return ALOAM_OK;
+  return queue_keyframe_rewind(c, seqs, n);
 }
 
 int aloam_graph_info(aloam_ctx* c, int seq, int out[4]) {

@@ -54,7 +54,7 @@ int on_slots_reset(aloam_ctx* c, const int* seqs, int n) {
   for (int i = 0; i < n; ++i) {
     SeqHost& s = c->seq[seqs[i]];
     s.parity = 0; s.inited = 0; s.grid_built = false; s.needs_odom = false; s.map_err_seen = 0; s.scorable = false; s.has_sweep = false; s.desc_valid = false;
-    s.info_odom = false; s.info_map = false;
+    s.info_odom = false; s.info_map = false; s.has_stacks = false;
   }
   for (int i = 0; i < n; ++i) if (const int rc = mark_window_stale(c, seqs[i])) return rc;
   return ALOAM_OK;
@@ -109,7 +109,7 @@ int on_map_pool_reallocated(aloam_ctx* c, MapPool&& fresh) {
 }
 
 void on_mapping_step_queued(aloam_ctx* c) {   // aloam_score_map_corrections may read the stacks and the grid that a frozen step leaves
-  for (int b = 0; b < c->B; ++b) if (takes_part(c, b)) { c->seq[b].scorable = c->seq[b].frozen; c->seq[b].info_map = true; }
+  for (int b = 0; b < c->B; ++b) if (takes_part(c, b)) { c->seq[b].scorable = c->seq[b].frozen; c->seq[b].info_map = true; c->seq[b].has_stacks = true; }
 }
 void on_map_corrections_applied(aloam_ctx* c, const int* seqs, int n) { for (int i = 0; i < n; ++i) c->seq[seqs[i]].info_map = false; }   // the pose of its last solve is in a frame that is gone
 

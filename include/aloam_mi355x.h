@@ -738,6 +738,76 @@ int aloam_graph_clear(aloam_ctx* ctx, const int* seqs, int n);
 int aloam_graph_info(aloam_ctx* ctx, int seq, int out[4]);
 int aloam_graph_optimize(aloam_ctx* ctx, const int* seqs, int n, const aloam_graph_options* opt, aloam_graph_result* dst /* [n] */);
 
+/* ---- keyframe clouds and the map at the graph's poses ---------------------------------------------------------------------------------
+ * aloam_graph_optimize moves the poses of a graph's nodes; this section lets the map follow.  Every node keeps its own clouds on the device
+ * in the sensor frame, and map tiles (aloam_map_tile, the format aloam_export_map_spill writes and aloam_atlas_load reads) are assembled
+ * from them at whichever poses the graph holds now.  Opt-in and beside the reference: a context that never calls
+ * aloam_graph_keyframes_enable launches exactly what it launched before.  a-loam_amd/atlas.py (tiles_from_keyframes) restates the
+ * definition in numpy; DESIGN.md §7l.
+ *
+ * aloam_graph_keyframes_enable(ctx, max_corner_points, max_surf_points): once per context, after aloam_graph_enable and
+ *   aloam_mapping_enable and while every sequence's graph is empty, else ALOAM_E_STATE.  Allocates, per sequence and class, a row of that
+ *   many 16-byte points, per node a descriptor (first, count) per class, per sequence and class an append cursor on the device.  Sizes in
+ *   1 .. 2^26, else ALOAM_E_ARG; nothing stays allocated behind a refusal.  Every other call of this section is ALOAM_E_STATE before it.
+ *   From then on aloam_graph_add_nodes queues one more kernel behind its own: for every listed sequence the sequence's
+ *   laserCloudCornerStack / laserCloudSurfStack (ALOAM_MAP_CORNER_STACK / ALOAM_MAP_SURF_STACK) as they are at that point of the stream
+ *   become the new node's clouds.  They are in the sensor frame: associate-to-map of them with the node's pose is where the mapping step
+ *   put them.
+ *   - A node's clouds are kept whole or not at all.  A node whose corner or surf cloud does not fit what is left of its rows is kept
+ *     without clouds (counts of 0) and counted; the next aloam_synchronize returns ALOAM_E_CAPACITY once, "keyframe store full".
+ *   - A listed sequence that has not been active in a mapping step since the context was created or the slot was last reset or loaded
+ *     (a host flag, like the one of aloam_score_map_corrections): aloam_graph_add_nodes returns ALOAM_E_STATE and queues nothing.
+ *   - aloam_graph_clear also rewinds the listed sequences' cursors, in stream order.  aloam_reset_sequences, aloam_save_sequences and
+ *     aloam_load_sequences leave the store alone, like the graph; it is not part of a sequence record.
+ * aloam_graph_export_keyframes: the clouds of nodes [first, first + count) of one sequence and class, packed in node order.  Stream-
+ *   ordered; destinations are classified like those of aloam_export_clouds (device memory of the context's device or pinned host memory).
+ *   dst_offsets[0 .. count] is always written (node first + j at [dst_offsets[j], dst_offsets[j + 1])); the points are written only when
+ *   the range ends inside cap_points; a cap of 0 is the size query (points_dst may then be NULL).
+ * aloam_graph_keyframe_info (synchronises): out = points held (corner, surf), capacities (corner, surf), nodes kept without clouds so far,
+ *   their points, and two reserved zeros.
+ *
+ * aloam_graph_export_map: for each of the n requests (host memory, read during the call), the map made of the nodes
+ *   [first, first + count) of sequence seq at their entered poses (q, t) or their estimates (q_opt, t_opt):
+ *   - every point p of every node k becomes w = associate-to-map(p, X_k): rotation and translation in f64, each component stored to f32,
+ *     the intensity kept (the operations of the mapping step, in that order);
+ *   - the cube of w is int((v + 25) / 50), minus one when v + 25 < 0, of (double)w.x, w.y, w.z (the definition under "map tiles"; -75
+ *     exactly lands in cube -2); points whose cube lies outside -512 .. 511 on some axis are left out and counted in `outside`;
+ *   - the members of a (cube, class) are its points in node order, then point order inside the node;
+ *   - they are filtered once with that class's pcl::VoxelGrid leaf (mapping_line_resolution / mapping_plane_resolution), always the
+ *     input-order sum, as in aloam_atlas_load, and always applied, even when one node contributes: a rotated cloud is not on its own grid;
+ *   - corner tiles come first, then surf tiles, each ascending in (cube[0], cube[1], cube[2]); frame is 0; first_point indexes points_dst.
+ *   dst_offsets[0 .. n] holds the tile offsets and dst_offsets[n + 1 .. 2 n + 1] the point offsets, always written; a request's tiles and
+ *   points are written only when BOTH of its ranges end inside cap_tiles / cap_points, nothing is ever written past a cap, and caps of 0
+ *   are the size query, as in aloam_export_map_spill.  stats_dst (NULL = not wanted) receives one record per request.  The bits written
+ *   for a request do not depend on n, on its position in the list or on the other requests; a sequence may be listed more than once.
+ *   Checked before anything is queued, ALOAM_E_ARG: seq in range; 0 <= first, 0 <= count, first + count <= the sequence's nodes; pose 0 or
+ *   1; n <= 32768; the destinations like those of the exports (stats_dst too).
+ *   It SYNCHRONISES the context's stream once, after the transform pass: the counts per (cube, class) are read back, and from them the
+ *   host lays out the cubes and plans the rounds of the voxel filter as aloam_atlas_load does.  Keyframe points never pass through host
+ *   memory; everything behind that point is stream-ordered (wait with aloam_synchronize before reading the destinations).  Meant to be
+ *   called once per loop closure, not once per sweep.  A (cube, class) with more raw points than a map pool row grows the map pools first;
+ *   at the pool limit it is ALOAM_E_CAPACITY and nothing is written.  The counts are kept per (cube, piece of 4096 points) in a
+ *   directory sized for a dozen cubes per sweep; a call whose points scatter over more cubes than it holds runs its first pass again with
+ *   the directory doubled (one more synchronisation each time; the size is kept for later calls), and one that needs more than 2^22
+ *   entries is ALOAM_E_CAPACITY with nothing written: export fewer nodes per call. */
+enum { ALOAM_GRAPH_POSE_ENTERED = 0, ALOAM_GRAPH_POSE_OPTIMIZED = 1 };
+typedef struct aloam_graph_map_request {      /* 16 bytes: nodes [first, first + count) of sequence seq                                 */
+  int seq, first, count, pose;                /* pose: ALOAM_GRAPH_POSE_ENTERED (q, t) or ALOAM_GRAPH_POSE_OPTIMIZED (q_opt, t_opt)     */
+} aloam_graph_map_request;
+typedef struct aloam_graph_map_stats {        /* 32 bytes                                                                               */
+  int tiles[2], points[2];                    /* of the request: corner, surf                                                           */
+  int raw_points[2];                          /* keyframe points that went into its cubes                                               */
+  int outside;                                /* points whose cube lies outside -512 .. 511 on some axis: left out                      */
+  int written;                                /* 1 when the request's tiles and points were written                                     */
+} aloam_graph_map_stats;
+int aloam_graph_keyframes_enable(aloam_ctx* ctx, int max_corner_points, int max_surf_points);
+int aloam_graph_export_keyframes(aloam_ctx* ctx, int seq, int first, int count, int feature_class, float* points_dst_xyzw, long long cap_points,
+                                 long long* dst_offsets /* [count + 1] */);
+int aloam_graph_keyframe_info(aloam_ctx* ctx, int seq, long long out[8]);
+int aloam_graph_export_map(aloam_ctx* ctx, const aloam_graph_map_request* req, int n, aloam_map_tile* tiles_dst, long long cap_tiles,
+                           float* points_dst_xyzw, long long cap_points, long long* dst_offsets /* [2][n + 1] */,
+                           aloam_graph_map_stats* stats_dst /* [n] or NULL */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

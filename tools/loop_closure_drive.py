@@ -1,0 +1,182 @@
+"""tools/loop_closure_drive.py — a loop closure inside one drive, with nothing but calls the project already has ("A loop
+edge inside a drive").
+
+    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6]
+
+A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
+node with its clouds) and a place every few metres.  At the last keyframe:
+  1. aloam_places_match of slot 0's sweep against the places older than --gap keyframes;
+  2. aloam_graph_export_map of the nodes around the matched keyframe, at the optimised poses, into device memory; aloam_atlas_load of it;
+  3. the spare slot 1 - reset, attached to the atlas, frozen - is fed the same sweep, its map frame set from the match
+     (places.guess_from_match), then relocalize() and frozen steps;
+  4. posegraph.loop_from_localization with the information of slot 1's last mapping solve; aloam_graph_add_edges; aloam_graph_optimize;
+  5. aloam_graph_export_map of all nodes at the entered and at the optimised poses.
+Printed against ground truth: the loop edge's error, ATE before and after the solve, tiles and points of the two maps.  One JSON object; a
+step that fails is named with what was known by then.
+"""
+from __future__ import annotations
+
+import argparse
+import importlib
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def quat_of(R):
+    """(x, y, z, w) of a rotation matrix."""
+    R = np.asarray(R, np.float64)
+    w = math.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2
+    if w > 1e-6:
+        return np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w])
+    i = int(np.argmax(np.diag(R)))
+    j, k = (i + 1) % 3, (i + 2) % 3
+    s = math.sqrt(max(1e-30, 1.0 + R[i, i] - R[j, j] - R[k, k])) * 2
+    q = np.zeros(4)
+    q[i], q[j], q[k], q[3] = s / 4, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s, (R[k, j] - R[j, k]) / s
+    return q
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--radius", type=float, default=12.0, help="metres, of the circle driven (synthetic.trajectory)")
+    ap.add_argument("--step", type=float, default=0.5, help="metres per sweep")
+    ap.add_argument("--laps", type=float, default=1.25)
+    ap.add_argument("--keyframe-spacing", type=float, default=2.0, help="metres between keyframes (and places)")
+    ap.add_argument("--gap", type=int, default=20, help="a place must be this many keyframes old to be matched")
+    ap.add_argument("--neighbours", type=int, default=6, help="keyframes either side of the matched one that make the local atlas")
+    ap.add_argument("--frozen-steps", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=3)
+    args = ap.parse_args()
+
+    import torch
+    binding = importlib.import_module("a-loam_amd.binding")
+    syn = importlib.import_module("a-loam_amd.synthetic")
+    pg = importlib.import_module("a-loam_amd.posegraph")
+    places = importlib.import_module("a-loam_amd.places")
+    reloc = importlib.import_module("a-loam_amd.relocalize")
+
+    frames = int(round(args.laps * 2 * math.pi * args.radius / args.step))
+    every = max(1, int(round(args.keyframe_spacing / args.step)))
+    model = syn.sensor_model("VLP-16")
+    world = syn.make_world(args.seed, track_radius=args.radius)
+    R, t = syn.trajectory(frames, step=args.step, radius=args.radius, seed=args.seed)
+    gen = torch.Generator().manual_seed(77 + args.seed)
+    scans = [syn.render_scan(world, model, R[k], t[k], 0.01, gen).numpy() for k in range(frames)]
+    nan_row = np.full((1, 4), np.nan, np.float32)
+    # ground truth in the frame of sweep 0 (where the drive's own frame starts)
+    R, t = R.numpy(), t.numpy()
+    q_true = np.array([quat_of(R[0].T @ R[k]) for k in range(frames)])
+    t_true = np.array([R[0].T @ (t[k] - t[0]) for k in range(frames)])
+
+    n_key = (frames + every - 1) // every
+    gpu = binding.Aloam(n_scans=16, min_range=model.min_range, batch=2, max_points=max(len(s) for s in scans) + 64)
+    gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)
+    gpu.graph_enable(n_key + 4, n_key + 8)
+    gpu.graph_keyframes_enable(n_key * 2048, n_key * 16384)
+    gpu.places_enable(n_key + 4, max_range=40.0, sensor_height=syn.SENSOR_HEIGHT)
+    info = np.diag([1.0 / 5e-3 ** 2] * 3 + [1.0 / 5e-2 ** 2] * 3)
+    out = {"frames": frames, "keyframes": 0, "radius": args.radius, "step": args.step}
+    key_frames = []
+    stage = "drive"
+    try:
+        for k in range(frames):
+            gpu.set_active([1, 0])
+            gpu.scan_register([scans[k], nan_row], check=False)
+            gpu.odometry_step()
+            gpu.mapping_step()
+            if k % every == 0 or k == frames - 1:
+                gpu.graph_add_nodes([0], info)
+                gpu.places_add([0])
+                key_frames.append(k)
+        gpu.synchronize()
+        out["keyframes"] = len(key_frames)
+        j = len(key_frames) - 1
+        nodes = gpu.graph_export(0)
+        truth_q, truth_t = q_true[key_frames], t_true[key_frames]
+        out["ate_before"] = pg.ate(nodes["t_opt"], truth_t)
+
+        stage = "places_match"
+        m = gpu.places_match([0], [(0, max(1, j - args.gap))])[0, 0]
+        i = int(m["entry"])
+        out["match"] = {"entry": i, "shift": int(m["shift"]), "distance": float(m["distance"]), "truth_distance_m": float(np.linalg.norm(truth_t[i] - truth_t[j]))}
+        if i < 0:
+            raise RuntimeError("no stored place matches the last sweep")
+
+        stage = "graph_export_map (local)"
+        lo, hi = max(0, i - args.neighbours), min(j - args.gap, i + args.neighbours + 1)
+        req = [(0, lo, hi - lo, binding.GRAPH_POSE_OPTIMIZED)]
+        off = torch.zeros(4, dtype=torch.int64, pin_memory=True)
+        gpu.graph_export_map_into(req, 0, 0, 0, 0, off.data_ptr())
+        gpu.synchronize()
+        nt, npts = int(off[1]), int(off[3])
+        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, device="cuda")
+        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, device="cuda")
+        gpu.graph_export_map_into(req, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr())
+        out["local_atlas"] = {"nodes": [lo, hi], "tiles": nt, "points": npts}
+
+        stage = "atlas_load"
+        gpu.atlas_load(tiles[:nt * 32], pts[:npts])
+
+        stage = "spare slot"
+        gpu.reset_sequences([1])
+        gpu.set_active([0, 1])
+        gpu.scan_register([nan_row, scans[key_frames[j]]], check=False)
+        gpu.odometry_step()
+        odom = gpu.pose(1)
+        gq, gt = places.guess_from_match(nodes["q_opt"][i], nodes["t_opt"][i], int(m["shift"]), odom["q_w"], odom["t_w"])
+        gpu.set_map_frozen([0, 1])
+        gpu.atlas_attach([0, 1])
+        gpu.set_map_frame((10, 10, 5), gq, gt, 0, seq=1)
+        gpu.mapping_step()
+        stage = "relocalize"
+        r = reloc.relocalize(gpu, [1])
+        out["relocalize"] = {"best_node": r[1]["nodes"][r[1]["best"]].tolist()}
+        stage = "frozen steps"
+        for _ in range(args.frozen_steps):
+            gpu.mapping_step()
+        gpu.synchronize()
+        mp = gpu.map_pose(1)
+        pi = gpu.export_pose_information(binding.INFO_MAPPING, [1])[0]
+        out["localization"] = {"status": int(pi["status"]), "n_line": int(pi["n_line"]), "n_plane": int(pi["n_plane"]),
+                               "error_m": float(np.linalg.norm(mp["t_w"] - truth_t[j])), "drive_error_m": float(np.linalg.norm(nodes["t_opt"][j] - truth_t[j]))}
+        gpu.atlas_attach(None)
+        gpu.set_map_frozen(None)
+        gpu.set_active([1, 0])
+        if pi["status"] != binding.INFO_OK:
+            raise RuntimeError("the frozen steps of the spare slot ended without a usable solve")
+
+        stage = "loop edge"
+        edge = pg.loop_from_localization(i, nodes["q_opt"][i], nodes["t_opt"][i], j, mp["q_w"], mp["t_w"], pi["info"])
+        qz, tz = pg.relative_pose(truth_q[i], truth_t[i], truth_q[j], truth_t[j])
+        dq = pg.qmul(pg.qconj(qz), edge["q"][0])
+        out["loop_edge"] = {"i": i, "j": j, "translation_error_m": float(np.linalg.norm(edge["t"][0] - tz)),
+                            "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dq[:3])))))}
+        stage = "graph_optimize"
+        gpu.graph_add_edges(edge)
+        res = gpu.graph_optimize([0])[0]
+        after = gpu.graph_export(0)
+        out["solve"] = {"status": int(res["status"]), "lm_iterations": int(res["lm_iterations"]), "initial_cost": float(res["initial_cost"]), "final_cost": float(res["final_cost"])}
+        out["ate_after"] = pg.ate(after["t_opt"], truth_t)
+
+        stage = "graph_export_map (all)"
+        for name, pose in (("entered", binding.GRAPH_POSE_ENTERED), ("optimised", binding.GRAPH_POSE_OPTIMIZED)):
+            tl, pp, _, st = gpu.graph_export_map([(0, 0, len(key_frames), pose)], pinned=False)
+            out["map_" + name] = {"tiles": len(tl), "points": len(pp), "raw_points": st[0]["raw_points"].tolist()}
+        stage = "done"
+    except Exception as e:  # noqa: BLE001 - the tool reports how far the chain got
+        out["failed_at"] = stage
+        out["error"] = str(e)
+    out["stage"] = stage
+    print(json.dumps(out))
+    gpu.close()
+
+
+if __name__ == "__main__":
+    main()
