@@ -204,10 +204,12 @@ DEFAULT_OPTIONS = dict(max_iterations=20, function_tolerance=1e-10, gradient_tol
 TERMINATION = {0: "max_iterations", 2: "function_tolerance", 3: "gradient_tolerance", 5: "failure", 6: "min_radius"}
 
 
-def optimize(q, t, edges, max_iterations=20, function_tolerance=1e-10, gradient_tolerance=1e-10, huber_delta=1.0, solve=None, **_):
+def optimize(q, t, edges, max_iterations=20, function_tolerance=1e-10, gradient_tolerance=1e-10, huber_delta=1.0, solve=None, trace=None, **_):
     """Levenberg-Marquardt with the trust-region rules of the device (lm_device.hpp's, without Jacobi scaling and without the parameter
-    tolerance) and a dense solve of every step.  `solve(H, D, g, q, t)` replaces the dense solve (chain_pcg's hook).
-    Returns q, t and a dict with the fields of aloam_graph_result."""
+    tolerance) and a dense solve of every step.  `solve(H, D, g)` replaces the dense solve (chain_pcg's hook).
+    `trace`, a list, receives one dict per iteration: rel, model_change, the radius the step was solved with, the cost before and of the
+    candidate, and the decision ("accepted", "rejected", "invalid", "function_tolerance").  Returns q, t and a dict with the fields of
+    aloam_graph_result."""
     q, t = np.array(q, np.float64), np.array(t, np.float64)
     N = len(q)
     res = dict(status=1, termination=0, lm_iterations=0, accepted_steps=0, pcg_iterations=0, nodes=N, edges=len(edges), initial_cost=0.0,
@@ -240,6 +242,8 @@ def optimize(q, t, edges, max_iterations=20, function_tolerance=1e-10, gradient_
         except np.linalg.LinAlgError:
             ok = False
         model_change = float(y @ g - 0.5 * y @ (H @ y)) if ok else 0.0
+        step = dict(rel=np.nan, model_change=model_change, radius=radius, cost=c, candidate_cost=np.nan, decision="invalid")
+        if trace is not None: trace.append(step)
         if not ok or not model_change > 0.0:
             invalid += 1
             if invalid >= 5: term = 5; break
@@ -249,8 +253,10 @@ def optimize(q, t, edges, max_iterations=20, function_tolerance=1e-10, gradient_
         d = np.zeros((N, 6)); d[1:] = -y.reshape(N - 1, 6)
         qc, tc = retract(q, t, d)
         cc = cost(qc, tc, edges, huber_delta)
+        step.update(candidate_cost=cc, decision="function_tolerance")
         if abs(c - cc) <= function_tolerance * c: term = 2; break
         rel = (c - cc) / model_change
+        step.update(rel=rel, decision="accepted" if rel > 1e-3 else "rejected")
         if rel > 1e-3:
             q, t = qc, tc
             H, g, c = normal_equations(q, t, edges, huber_delta)

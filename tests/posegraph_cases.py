@@ -1,5 +1,6 @@
-"""What the pose-graph tests share: the solver options they run with, eps_ref, and the helpers that enter a graph into a context through
-aloam_set_state and read it back."""
+"""What the pose-graph tests share: the solver options they run with, eps_ref, the helpers that enter a graph into a context through
+aloam_set_state and read it back, and (second half) the cases with dense information and truncated solves that the model's tests, the host
+emulation and the GPU tests all run, with the assertions the last two share."""
 import functools
 import importlib
 import os
@@ -39,13 +40,14 @@ IDENT_Q, ZERO_T = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3)
 
 def enter(gpu, graphs, info):
     """graphs: {seq: (q [n, 4], t [n, 3])}.  Node k of every sequence is entered with one aloam_graph_add_nodes after its pose was
-    injected as the odometry's q_w / t_w."""
+    injected as the odometry's q_w / t_w.  info: one 6 x 6 information for every odometry edge, or {seq: [n - 1, 21]}, one per edge
+    (k - 1, k)."""
     longest = max(len(q) for q, _ in graphs.values())
     for k in range(longest):
         listed = [b for b, (q, _) in graphs.items() if k < len(q)]
         for b in listed:
             gpu.set_state(IDENT_Q, ZERO_T, graphs[b][0][k], graphs[b][1][k], seq=b)
-        gpu.graph_add_nodes(listed, info)
+        gpu.graph_add_nodes(listed, np.stack([info[b][max(k, 1) - 1] for b in listed]) if isinstance(info, dict) else info)
 
 
 def with_seq(edges, seq):
@@ -94,6 +96,286 @@ def scipy_optimize(q0, t0, edges):
     sol = least_squares(fun, np.zeros(6 * (N - 1)), jac=jac, method="trf", ftol=1e-15, xtol=1e-15, gtol=1e-15, max_nfev=400)
     (q, t), _ = unpack(sol.x)
     return q, t, sol
+
+
+
+# ---- dense information and truncated solves (test_posegraph_model.py, test_posegraph_emulation.py, test_gpu_posegraph_steps.py) --------
+# The cases below exist because one Levenberg-Marquardt iteration taken far from the minimum is decided by H, where the comparison at the
+# minimum only sees the gradient; and because an information matrix diag(a, a, a, b, b, b) forgives a wrong rotation, a transposed block
+# and a dropped rotation-translation coupling.  A layer (the host emulation, the device) solves a case and hands what it solved and what
+# it got to the check_* functions here, so both layers assert the same things.
+STEP_OPTIONS = dict(OPTIONS, pcg_tolerance=1e-13)
+CONDS, DELTAS, STEPS = (1e2, 1e6), (0.3, 1.0, 3.0), (1, 2, 3)
+SIGMA = np.array([5e-3] * 3 + [5e-2] * 3)
+
+
+def dense_edges(rng, q_true, t_true, i, j, cond, scale=1.0, seq=0):
+    """Edges (i, j) (i = -1: anchors) measured on the ground truth, each with a dense covariance of its own: Sigma = L L^T,
+    L = diag(SIGMA) (Q diag(s) Q^T), Q random orthogonal, s log-uniform in [cond^-1/2, 1] with both ends present.  The measurement is
+    Z = X_i^-1 o X_j o (exp(xi_theta), xi_t) with xi = scale L z, z ~ N(0, I): to first order r = -xi, so the information Sigma^-1
+    (symmetrised) is the noise's own when scale = 1."""
+    i, j = np.atleast_1d(np.asarray(i, np.int32)), np.atleast_1d(np.asarray(j, np.int32))
+    n = len(i)
+    L = np.zeros((n, 6, 6))
+    for e in range(n):
+        Q, _ = np.linalg.qr(rng.standard_normal((6, 6)))
+        u = rng.uniform(size=6)
+        u[0], u[1] = 0.0, 1.0                              # both ends of the range (Q is random: which axis gets which does not matter)
+        L[e] = SIGMA[:, None] * ((Q * cond ** (-0.5 * u)) @ Q.T)
+    xi = np.broadcast_to(scale, (n,))[:, None] * np.einsum("eab,eb->ea", L, rng.standard_normal((n, 6)))
+    info = np.linalg.inv(L @ L.transpose(0, 2, 1))
+    info = 0.5 * (info + info.transpose(0, 2, 1))
+    anchor = (i < 0)[:, None]
+    qz, tz = pg.relative_pose(np.where(anchor, IDENT_Q, q_true[np.maximum(i, 0)]), np.where(anchor, 0.0, t_true[np.maximum(i, 0)]), q_true[j], t_true[j])
+    qz, tz = pg.compose(qz, tz, pg.qexp(xi[:, :3]), xi[:, 3:])
+    return pg.make_edges(seq, i, j, qz, tz, info)
+
+
+def chain_from(q0, t0, odom):
+    """Node 0, then X[k] = X[k - 1] o Z_k, as drifted_laps builds its chain."""
+    q, t = [np.asarray(q0, np.float64)], [np.asarray(t0, np.float64)]
+    for e in odom:
+        a, b = pg.compose(q[-1], t[-1], e["q"], e["t"])
+        q.append(a); t.append(b)
+    return np.array(q), np.array(t)
+
+
+def dense_laps(seed, nodes, loops, cond):
+    """drifted_laps' ground truth (noise = 0) with dense_edges' odometry and loop edges, and the chain rebuilt from the noisy odometry.
+    Returns drifted_laps' dict without `info` (every edge carries its own)."""
+    d = pg.drifted_laps(seed, nodes, loops, noise=0.0)
+    rng = np.random.default_rng([seed, nodes, loops])
+    k = np.arange(nodes)
+    odom = dense_edges(rng, d["q_true"], d["t_true"], k[:-1], k[1:], cond)
+    loop = dense_edges(rng, d["q_true"], d["t_true"], d["loop"]["i"], d["loop"]["j"], cond)
+    q, t = chain_from(d["q_true"][0], d["t_true"][0], odom)
+    return dict(q_true=d["q_true"], t_true=d["t_true"], q=q, t=t, odom=odom, loop=loop)
+
+
+def edge_s(q, t, edges):
+    r = pg.residual(q, t, edges)
+    return np.einsum("ea,eab,eb->e", r, pg.info_full(edges["info"]), r)
+
+
+@functools.lru_cache(maxsize=None)
+def step_case(cond, seed=3):
+    """The 40-node graph of the linearisation and truncated-solve tests: dense_laps(seed, 40, 3, cond) (loops (1, 14), (0, 26), (0, 39):
+    two reach the fixed node), a loop edge with i > j, one between the neighbours k and k - 1 (the chain block's untransposed branch),
+    anchors on nodes 0, 1 and 17.  Flagged robust: the first loop edge, the two added loops and the anchors, whose noise is scaled so that at
+    the start s lies on both sides of delta^2 for delta = 0.3 and for delta = 3 (checked here).  Returns dict(q, t, odom, extra, ...)."""
+    d = dense_laps(seed, 40, 3, cond)
+    rng = np.random.default_rng([seed, 40, 77])
+    truth = d["q_true"], d["t_true"]
+    extra = np.concatenate([d["loop"], dense_edges(rng, *truth, [33], [6], cond), dense_edges(rng, *truth, [21], [20], cond),
+                            dense_edges(rng, *truth, [-1, -1, -1], [0, 1, 17], cond, scale=[0.05, 0.4, 1.0])])
+    extra["flags"][[0, 3, 4, 5, 6, 7]] = pg.EDGE_ROBUST
+    s = edge_s(d["q"], d["t"], extra)[extra["flags"] != 0]
+    for delta in (0.3, 3.0):
+        assert (s > delta ** 2).any() and (s <= delta ** 2).any(), (cond, seed, delta, s)
+    return dict(d, extra=extra, edges=np.concatenate([d["odom"], extra]), max_nodes=40, max_edges=64)
+
+
+@functools.lru_cache(maxsize=None)
+def rejected_case():
+    """drifted_laps(4, 40, 2) with the second loop edge's rotation off by 2.5 rad about z: the first three steps are rejected (rel -9.6,
+    -8.1, -3.1), the fourth is accepted."""
+    d = pg.drifted_laps(4, 40, 2)
+    extra = d["loop"].copy()
+    extra["q"][1] = pg.qmul(extra["q"][1], pg.qexp(np.array([0.0, 0.0, 2.5])))
+    return dict(d, extra=extra, edges=np.concatenate([d["odom"], extra]), max_nodes=40, max_edges=64)
+
+
+@functools.lru_cache(maxsize=None)
+def failing_case():
+    """drifted_laps(4, 40, 2), and the same with one more loop edge whose t = (1e200, 0, 0): finite, so it is accepted, and with the
+    isotropic information of drifted_laps its s = sum a r^2 overflows to +infinity (a dense information would give inf - inf)."""
+    d = pg.drifted_laps(4, 40, 2)
+    healthy = dict(d, extra=d["loop"], edges=np.concatenate([d["odom"], d["loop"]]), max_nodes=40, max_edges=64)
+    bad = d["loop"][1:2].copy()
+    bad["t"] = [1e200, 0.0, 0.0]
+    return healthy, dict(healthy, extra=np.concatenate([d["loop"], bad]), edges=np.concatenate([healthy["edges"], bad]))
+
+
+REJECTED_STEPS, REJECTED_ACCEPTED = (1, 2, 3, 4, 5, 6), [0, 0, 0, 1, 2, 3]
+
+
+@functools.lru_cache(maxsize=None)
+def hub_case():
+    """515 nodes (three passes of 256 threads) with drifted_laps' edges, and node 7 joined to 300 other nodes by loop edges in alternating
+    orientation (an incidence list longer than a workgroup): exact relative poses of the ground truth plus drifted_laps' noise."""
+    d = pg.drifted_laps(6, 515, 2)
+    rng = np.random.default_rng(12)
+    others = np.arange(20, 320)
+    qz, tz = pg.relative_pose(d["q_true"][7], d["t_true"][7], d["q_true"][others], d["t_true"][others])
+    qz, tz = pg.qmul(qz, pg.qexp(5e-3 * rng.standard_normal((300, 3)))), tz + 5e-2 * rng.standard_normal((300, 3))
+    hub = pg.make_edges(0, np.full(300, 7), others, qz, tz, d["info"])
+    hub[::2] = pg.make_edges(0, others[::2], np.full(150, 7), *pg.inverse(qz[::2], tz[::2]), d["info"])
+    extra = np.concatenate([d["loop"], hub])
+    return dict(d, extra=extra, edges=np.concatenate([d["odom"], extra]), max_nodes=515, max_edges=816)
+
+
+FAR_Q, FAR_T = pg.qexp(np.array([0.3, -1.1, 2.0])), np.array([4.1e5, -5.3e6, 312.0])
+
+
+def moved(case, qg=FAR_Q, tg=FAR_T):
+    """The case composed on the left with G: every node G o X, every anchor's measurement G o Z; relative measurements are unchanged."""
+    q, t = pg.compose(qg, tg, case["q"], case["t"])
+    extra = case["extra"].copy()
+    a = extra["i"] < 0
+    extra["q"][a], extra["t"][a] = pg.compose(qg, tg, extra["q"][a], extra["t"][a])
+    return dict(case, q=q, t=t, extra=extra, edges=np.concatenate([case["odom"], extra]))
+
+
+def odom_info(case):
+    return case["odom"]["info"] if "info" not in case else np.tile(pg.info_upper(case["info"]), (len(case["odom"]), 1))
+
+
+# ---- the longdouble restatement of cost and gradient: what eps_lin is measured against ------------------------------------------------
+def linear_longdouble(q, t, edges, huber_delta):
+    """cost and gradient [N, 6] (row 0 zero) of posegraph.cost / posegraph.gradient, every operation in np.longdouble."""
+    F = np.longdouble
+    assert np.finfo(F).nmant >= 63
+    q, t, zq, zt, delta = np.asarray(q, F), np.asarray(t, F), edges["q"].astype(F), edges["t"].astype(F), F(huber_delta)
+
+    def mul(a, b):
+        ax, ay, az, aw = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+        bx, by, bz, bw = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+        return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                         aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz], -1)
+
+    def conj(a):
+        return a * np.array([-1, -1, -1, 1], F)
+
+    def rot(a, v):
+        u = a[..., :3]
+        uv = 2 * np.cross(u, v)
+        return v + a[..., 3:4] * uv + np.cross(u, uv)
+
+    def skew(v):
+        z = np.zeros(v.shape[:-1], F)
+        return np.stack([np.stack([z, -v[..., 2], v[..., 1]], -1), np.stack([v[..., 2], z, -v[..., 0]], -1), np.stack([-v[..., 1], v[..., 0], z], -1)], -2)
+
+    i, j = edges["i"], edges["j"]
+    anchor = i < 0
+    qi = np.where(anchor[:, None], np.array([0, 0, 0, 1], F), q[np.maximum(i, 0)])
+    ti = np.where(anchor[:, None], F(0), t[np.maximum(i, 0)])
+    qj, tj = q[j], t[j]
+    qa = mul(conj(zq), conj(qi))
+    qe = mul(qa, qj)
+    qe = np.where(qe[:, 3:4] < 0, -qe, qe)
+    r = np.concatenate([2 * qe[:, :3], rot(conj(zq), rot(conj(qi), tj - ti) - zt)], 1)
+    Om = pg.info_full(edges["info"]).astype(F)
+    Or = (Om * r[:, None, :]).sum(-1)
+    s = (r * Or).sum(-1)
+    big = ((edges["flags"] & pg.EDGE_ROBUST) != 0) & (s > delta * delta)
+    rs = np.sqrt(np.where(big, s, F(1)))
+    rho0, rho1 = np.where(big, 2 * delta * rs - delta * delta, s), np.where(big, delta / rs, F(1))
+    RA = np.stack([rot(qa, np.broadcast_to(e, (len(edges), 3))) for e in np.eye(3, dtype=F)], -1)
+    B = ((qe[:, 3, None, None] * np.eye(3, dtype=F) - skew(qe[:, :3]))[:, :, :, None] * RA[:, None, :, :]).sum(2)
+    S = (RA[:, :, :, None] * skew(tj - ti)[:, None, :, :]).sum(2)
+    wr = rho1[:, None] * Or
+    gj = np.concatenate([(B * wr[:, :3, None]).sum(1), (RA * wr[:, 3:, None]).sum(1)], 1)               # J_j^T (w Omega r)
+    gi = np.concatenate([-(B * wr[:, :3, None]).sum(1) + (S * wr[:, 3:, None]).sum(1), -(RA * wr[:, 3:, None]).sum(1)], 1)
+    g = np.zeros((len(q), 6), F)
+    np.add.at(g, j, gj)
+    np.add.at(g, i[~anchor], gi[~anchor])
+    g[0] = 0
+    return rho0.sum() / 2, g
+
+
+def linear_deviation(q, t, edges, huber_delta, cost, gradient_max):
+    """(relative deviation of `cost`, of `gradient_max`) from the longdouble restatement."""
+    c, g = linear_longdouble(q, t, edges, huber_delta)
+    gm = np.abs(g).max()
+    return float(abs(cost - c) / c), float(abs(gradient_max - gm) / gm)
+
+
+def eps_lin(problems):
+    """The f64 model's largest relative deviation from the longdouble restatement, cost or gradient, over `problems` ([(q, t, edges)]) and
+    DELTAS: measured in the run, the yardstick of test (a)."""
+    worst = 0.0
+    for q, t, edges in problems:
+        for delta in DELTAS:
+            worst = max(worst, *linear_deviation(q, t, edges, delta, pg.cost(q, t, edges, delta), np.abs(pg.gradient(q, t, edges, delta)).max()))
+    return worst
+
+
+# ---- truncated solves of the model ---------------------------------------------------------------------------------------------------
+def chain_solver_dense(tol, max_iterations):
+    """posegraph.chain_solver with the preconditioner applied by a dense LU solve of the chain instead of the banded Cholesky: the second
+    statement of a PCG that is cut short, where the dense solve of the whole step is no yardstick."""
+    def solve(H, D, g):
+        from scipy.linalg import lu_factor, lu_solve
+        A = H + np.diag(D)
+        lu = lu_factor(np.where(pg._chain_mask(len(g) // 6), A, 0.0))
+        return pg.pcg(A, g, lambda r: lu_solve(lu, r), tol, max_iterations)
+    return solve
+
+
+_MODEL = {}
+
+
+def model_pair(q0, t0, edges, **options):
+    """The model's two solves of one truncated problem: `first` is the dense solve of every step (with pcg_max_iterations below the default,
+    where PCG is cut short: chain_solver_dense), `chain` is chain_pcg.  Each is (q, t, result, trace); eps = their pose_difference."""
+    key = (np.asarray(q0).tobytes(), np.asarray(t0).tobytes(), edges.tobytes(), tuple(sorted(options.items())))
+    if key not in _MODEL:
+        capped = options["pcg_max_iterations"] < OPTIONS["pcg_max_iterations"]
+        tr1, tr2 = [], []
+        first = pg.optimize(q0, t0, edges, trace=tr1, solve=chain_solver_dense(options["pcg_tolerance"], options["pcg_max_iterations"]) if capped else None, **options)
+        chain = pg.chain_pcg(q0, t0, edges, trace=tr2, **options)
+        _MODEL[key] = dict(first=first + (tr1,), chain=chain + (tr2,), eps=pg.pose_difference(first[0], first[1], chain[0], chain[1]))
+    return _MODEL[key]
+
+
+def eps_step(problems, deltas, steps, **options):
+    """The largest eps of model_pair over a family: `problems` x deltas x steps (max_iterations)."""
+    o = dict(STEP_OPTIONS, **options)
+    return max(model_pair(q, t, e, **dict(o, huber_delta=d, max_iterations=k))["eps"] for q, t, e in problems for d in deltas for k in steps)
+
+
+def decisions(trace):
+    return [s["decision"] for s in trace]
+
+
+# ---- what a layer's result is held to ------------------------------------------------------------------------------------------------
+def bits_equal(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def check_linearisation(what, nodes0, edges, res, out, delta, eps):
+    """(a): max_iterations = 0.  `res` has the fields of aloam_graph_result, `out` the nodes afterwards, eps = eps_lin of the family."""
+    dc, dg = linear_deviation(nodes0["q_opt"], nodes0["t_opt"], edges, delta, res["initial_cost"], res["gradient_max"])
+    print(f"{what}: cost {float(res['initial_cost']):.6g} deviates {dc:.3e}, gradient_max {float(res['gradient_max']):.6g} deviates {dg:.3e} from the longdouble "
+          f"restatement (eps_lin {eps:.3e}, tolerance {8 * eps:.3e})")
+    assert (res["status"], res["termination"], res["lm_iterations"], res["accepted_steps"], res["pcg_iterations"]) == (0, 0, 0, 0, 0)
+    assert bits_equal(out, nodes0)
+    assert res["final_cost"] == res["initial_cost"]
+    assert dc <= 8 * eps and dg <= 8 * eps
+    return max(dc, dg)
+
+
+def check_truncated(what, nodes0, edges, res, out, eps, **options):
+    """(b) - (e): after options['max_iterations'] iterations the layer's estimates are the model's to 8 eps, eps = eps_step of the family,
+    and its counters are the model's.  Where the model accepted nothing the nodes are bit for bit the start."""
+    pair = model_pair(nodes0["q_opt"], nodes0["t_opt"], edges, **options)
+    capped = options["pcg_max_iterations"] < OPTIONS["pcg_max_iterations"]
+    q, t, m, trace = pair["chain" if capped else "first"]
+    dev = pg.pose_difference(out["q_opt"], out["t_opt"], q, t)
+    print(f"{what}: against the model after {options['max_iterations']} iterations {dev:.3e} (the model's two solvers {pair['eps']:.3e}, family eps_step {eps:.3e}, "
+          f"tolerance {8 * eps:.3e}); decisions {decisions(trace)}; LM {int(res['lm_iterations'])} accepted {int(res['accepted_steps'])} PCG {int(res['pcg_iterations'])} "
+          f"(chain_pcg {pair['chain'][2]['pcg_iterations']}) termination {int(res['termination'])}")
+    assert res["status"] == 0 and res["termination"] == m["termination"] == 0
+    assert res["lm_iterations"] == options["max_iterations"] == m["lm_iterations"]
+    assert res["accepted_steps"] == m["accepted_steps"] == pair["chain"][2]["accepted_steps"]
+    assert all(bits_equal(out[f], nodes0[f]) for f in ("q", "t", "frame"))
+    if m["accepted_steps"] == 0:
+        assert bits_equal(out, nodes0)
+    else:
+        assert dev <= 8 * eps
+    if capped:
+        assert res["pcg_iterations"] == pair["chain"][2]["pcg_iterations"] == options["max_iterations"] * options["pcg_max_iterations"]
+    return dev
 
 
 if __name__ == "__main__":          # records scipy's solution of the GPU tests' graph

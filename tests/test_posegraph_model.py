@@ -24,12 +24,17 @@ def test_the_residual_is_zero_on_a_consistent_graph():
     assert np.abs(pg.residual(d["q"], d["t"], d["odom"])).max() <= 1e-12
 
 
-@pytest.mark.parametrize("robust", [False, True])
+@pytest.mark.parametrize("robust", [False, True, pytest.param(0.3, id="dense-0.3"), pytest.param(3.0, id="dense-3.0")])
 def test_gradient_against_central_differences(robust):
+    """The two isotropic cases, and the dense one: step_case(1e4) - every edge with a dense information of its own at condition 1e4 (1e6 with
+    the radian / metre scaling), anchors on nodes 0, 1 and 17, flagged edges on both sides of delta^2 at either delta."""
     d = pg.drifted_laps(2, 14, 2)
     edges = np.concatenate([d["odom"], d["loop"], pg.anchor_from_localization(9, d["q_true"][9], d["t_true"][9], d["info"])])
     delta = 1.0
-    if robust:
+    if robust not in (False, True):
+        d, delta = pc.step_case(1e4), robust
+        edges = d["edges"]
+    elif robust:
         edges["flags"][-3:] = pg.EDGE_ROBUST
         delta = 0.5
         s = np.einsum("ea,eab,eb->e", *(lambda r: (r, pg.info_full(edges["info"]), r))(pg.residual(d["q"], d["t"], edges)))
@@ -43,6 +48,92 @@ def test_gradient_against_central_differences(robust):
     err = np.abs(g - num).max() / np.abs(g).max()
     print(f"gradient against central differences: relative {err:.3e}")
     assert (g[0] == 0).all() and err <= 1e-7            # h^2 truncation plus eps / h of the cost's rounding
+
+
+@pytest.mark.parametrize("delta", [0.3, 3.0])
+def test_normal_equations_against_central_differences_of_the_residual(delta):
+    """H of normal_equations without linearize: J by central differences of residual() per edge and node, rho' from s, and
+    H_num = sum rho' J^T Omega J assembled here.  The bound: an entry of J is good to dJ = h^2 / 6 D3 + 4 eps |t| / h, with the residual's
+    third derivative D3 and |t| at most 20 (a rotation acting on t_j - t_i, at most the circle's diameter): 3e-10 + 2e-9 at h = 1e-5.  An
+    entry of H collects 36 products dJ Omega J twice, so against max |H| >= max |Omega| the error is at most 72 dJ max |J| =
+    72 * 2.3e-9 * 20 = 3.3e-6 if every term aligned.  A dropped block or a transposed one is an error of order one."""
+    c = pc.step_case(1e4)
+    q, t, edges = c["q"], c["t"], c["edges"]
+    N, E, h = len(q), len(edges), 1e-5
+    H, _, _ = pg.normal_equations(q, t, edges, delta)
+    Om = pg.info_full(edges["info"])
+    s = pc.edge_s(q, t, edges)
+    big = (edges["flags"] != 0) & (s > delta ** 2)
+    w = np.where(big, delta / np.sqrt(s), 1.0)
+    J = np.zeros((E, 6, N, 6))
+    for k in range(1, N):
+        touched = (edges["i"] == k) | (edges["j"] == k)
+        for a in range(6):
+            dd = np.zeros((N, 6)); dd[k, a] = h
+            J[touched, :, k, a] = (pg.residual(*pg.retract(q, t, dd), edges[touched]) - pg.residual(*pg.retract(q, t, -dd), edges[touched])) / (2 * h)
+    Jm = J[:, :, 1:, :].reshape(E, 6, 6 * (N - 1))
+    Hn = np.einsum("e,eax,eab,eby->xy", w, Jm, Om, Jm, optimize=True)
+    err = np.abs(H - Hn).max() / np.abs(H).max()
+    print(f"H against sum rho' J^T Omega J with J by central differences, delta {delta}: relative {err:.3e} (bound 3.3e-6); {int(big.sum())} edges on Huber's linear part")
+    assert big.any() and ((edges["flags"] != 0) & ~big).any()
+    assert np.abs(H - H.T).max() <= 1e-12 * np.abs(H).max()
+    assert err <= 3.3e-6
+
+
+def truncated_cases():
+    """Every truncated solve of test_gpu_posegraph_steps.py / test_posegraph_emulation.py at its largest k: (name, case, options)."""
+    out = [(f"steps cond {c:g} delta {d}", pc.step_case(c), dict(pc.STEP_OPTIONS, huber_delta=d, max_iterations=max(pc.STEPS))) for c in pc.CONDS for d in pc.DELTAS]
+    out.append(("rejected", pc.rejected_case(), dict(pc.STEP_OPTIONS, max_iterations=max(pc.REJECTED_STEPS))))
+    out.append(("one PCG iteration", pc.step_case(pc.CONDS[0]), dict(pc.STEP_OPTIONS, max_iterations=2, pcg_max_iterations=1)))
+    out.append(("hub 515", pc.hub_case(), dict(pc.STEP_OPTIONS, max_iterations=2)))
+    return out
+
+
+@pytest.mark.parametrize("index", range(9))
+def test_the_truncated_cases_decide_far_from_the_thresholds(index):
+    """What the truncated comparisons rest on: both of the model's solvers take the same decisions, every rel is at least 0.05 away from the
+    acceptance threshold 1e-3 (so that a layer with another rounding decides alike), and no iteration ends on the function tolerance.  A
+    solve stopped after k iterations is the first k of these."""
+    cases = truncated_cases()
+    assert len(cases) == 9
+    name, case, options = cases[index]
+    pair = pc.model_pair(case["q"], case["t"], case["edges"], **options)
+    first, chain = pair["first"][3], pair["chain"][3]
+    print(f"{name}: " + ", ".join(f"{a['decision']} rel {a['rel']:.3f} | {b['rel']:.3f} radius {a['radius']:.3g}" for a, b in zip(first, chain)) + f"; eps {pair['eps']:.3e}")
+    assert len(first) == len(chain) == options["max_iterations"] == pair["first"][2]["lm_iterations"]
+    assert pc.decisions(first) == pc.decisions(chain) and set(pc.decisions(first)) <= {"accepted", "rejected"}
+    assert all(abs(s["rel"] - 1e-3) >= 0.05 for s in first + chain)
+    assert all(abs(a["radius"] - b["radius"]) <= 1e-6 * a["radius"] for a, b in zip(first, chain))
+    assert pair["first"][2]["termination"] == pair["chain"][2]["termination"] == 0
+    if name == "rejected":
+        assert np.cumsum([d == "accepted" for d in pc.decisions(first)]).tolist() == pc.REJECTED_ACCEPTED
+
+
+def test_the_trace_changes_nothing():
+    d = pg.drifted_laps(2, 30, 2)
+    edges = np.concatenate([d["odom"], d["loop"]])
+    trace = []
+    a, b = pg.optimize(d["q"], d["t"], edges, **OPTIONS), pg.optimize(d["q"], d["t"], edges, trace=trace, **OPTIONS)
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[2] == b[2]
+    assert len(trace) == a[2]["lm_iterations"] and sum(s["decision"] == "accepted" for s in trace) == a[2]["accepted_steps"]
+
+
+def test_the_step_cases_carry_what_they_claim():
+    for cond in pc.CONDS + (1e4,):
+        c = pc.step_case(cond)
+        e, s = c["extra"], pc.edge_s(c["q"], c["t"], c["extra"])
+        flagged = e["flags"] != 0
+        for delta in (0.3, 3.0):
+            assert (s[flagged] > delta ** 2).any() and (s[flagged] <= delta ** 2).any()
+        loops = e[e["i"] >= 0]
+        assert (loops["i"] < loops["j"]).any() and (loops["i"] > loops["j"]).any() and (loops["i"] == loops["j"] + 1).any()
+        assert sorted(e["j"][e["i"] < 0]) == [0, 1, 17]
+        ev = np.linalg.eigvalsh(pg.info_full(c["edges"]["info"]) * np.outer(pc.SIGMA, pc.SIGMA))
+        assert np.allclose(ev[:, -1] / ev[:, 0], cond, rtol=1e-6)                # the condition asked for, with both ends present
+        assert np.abs(pg.info_full(c["edges"]["info"])[:, :3, 3:]).min() > 0      # rotation and translation are coupled on every edge
+        assert np.abs(pg.residual(c["q"], c["t"], c["odom"])).max() <= 1e-12      # the chain is the odometry's
+    h = pc.hub_case()
+    assert len(h["q"]) == 515 and (np.r_[h["edges"]["i"], h["edges"]["j"]] == 7).sum() == 302
 
 
 def test_optimize_against_scipy(small):
