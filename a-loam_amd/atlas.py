@@ -200,6 +200,28 @@ def tiles_from_keyframes(q, t, clouds, leaves, voxel_filter, stats=None):
     return (np.array(tiles, TILE_DTYPE) if tiles else np.zeros(0, TILE_DTYPE)), (np.concatenate(pts) if pts else np.zeros((0, 4), np.float32))
 
 
+def window_centre(t_w_curr):
+    """The window centre that puts the sensor's cube at the middle of the window: (10, 10, 5) - cube of the f64 position."""
+    s = np.asarray(t_w_curr, np.float64) + 25.0
+    cube = np.trunc(s / 50.0).astype(np.int64) - (s < 0)
+    return tuple(int(v) for v in np.array([10, 10, 5]) - cube)
+
+
+def window_from_keyframes(q, t, clouds, leaves, voxel_filter, cen, stats=None):
+    """The window aloam_graph_apply builds: Atlas(*tiles_from_keyframes(...)).cut(cen), [{window index: points}] * 2.  stats (a dict)
+    receives tiles_from_keyframes' figures plus cubes and points of the window (per class) and outside_window, the filtered points of the
+    tiles that the window leaves out."""
+    st = {}
+    atlas = Atlas(*tiles_from_keyframes(q, t, clouds, leaves, voxel_filter, st))
+    cut = atlas.cut(cen)
+    if stats is not None:
+        stats.update(st)
+        stats["cubes"] = [len(c) for c in cut]
+        stats["window_points"] = [sum(len(p) for p in c.values()) for c in cut]
+        stats["outside_window"] = sum(st["points"]) - sum(stats["window_points"])
+    return cut
+
+
 # ---- a set of tiles as a map of any extent ---------------------------------------------------------------------------------------------
 class Atlas:
     """Tiles keyed by (absolute cube, class).  Several tiles of one key (a cube that left the window, was re-entered and left again) are

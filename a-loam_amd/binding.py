@@ -99,6 +99,22 @@ class AloamGraphMapStats(C.Structure):
     _fields_ = [("tiles", C.c_int * 2), ("points", C.c_int * 2), ("raw_points", C.c_int * 2), ("outside", C.c_int), ("written", C.c_int)]
 
 
+class AloamGraphApplyRequest(C.Structure):
+    """The map of nodes [first, first + count) of one sequence carried into its live state (aloam_graph_apply_request, 16 bytes)."""
+    _fields_ = [("seq", C.c_int), ("first", C.c_int), ("count", C.c_int), ("flags", C.c_int)]
+
+
+class AloamGraphApplyResult(C.Structure):
+    """What aloam_graph_apply did to one sequence (aloam_graph_apply_result, 104 bytes)."""
+    _fields_ = [("status", C.c_int), ("nodes", C.c_int), ("cen", C.c_int * 3), ("cubes", C.c_int * 2), ("points", C.c_int * 2),
+                ("raw_points", C.c_int * 2), ("outside_window", C.c_int), ("q_corr", C.c_double * 4), ("t_corr", C.c_double * 3)]
+
+
+GRAPH_APPLY_POSE, GRAPH_APPLY_MAP = 1, 2
+GRAPH_APPLIED, GRAPH_APPLY_NO_NODES, GRAPH_APPLY_NO_ROOM = 0, 1, 2
+GRAPH_APPLY_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("first", np.int32), ("count", np.int32), ("flags", np.int32)])
+GRAPH_APPLY_RESULT_DTYPE = np.dtype([("status", np.int32), ("nodes", np.int32), ("cen", np.int32, 3), ("cubes", np.int32, 2), ("points", np.int32, 2),
+                                     ("raw_points", np.int32, 2), ("outside_window", np.int32), ("q_corr", np.float64, 4), ("t_corr", np.float64, 3)])
 GRAPH_POSE_ENTERED, GRAPH_POSE_OPTIMIZED = 0, 1
 GRAPH_MAP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32)])
 GRAPH_MAP_STATS_DTYPE = np.dtype([("tiles", np.int32, 2), ("points", np.int32, 2), ("raw_points", np.int32, 2), ("outside", np.int32),
@@ -315,6 +331,7 @@ def lib():
         L.aloam_graph_export_keyframes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_keyframe_info.argtypes = [vp, C.c_int, vp]
         L.aloam_graph_export_map.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp, vp]
+        L.aloam_graph_apply.argtypes = [vp, vp, C.c_int, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -818,6 +835,31 @@ class Aloam:
         self.synchronize()
         return (tiles.cpu().numpy()[:nt * 32].view(MAP_TILE_DTYPE).copy(), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy(),
                 stats.numpy()[:n * 32].view(GRAPH_MAP_STATS_DTYPE).copy())
+
+    # ---- a solved graph carried into the live state (posegraph.apply_correction, atlas.window_from_keyframes hold the definition) ------------
+    @staticmethod
+    def graph_apply_requests(requests):
+        """[(seq, first, count, flags), ...] -> structured array of GRAPH_APPLY_REQUEST_DTYPE."""
+        r = np.zeros(len(requests), GRAPH_APPLY_REQUEST_DTYPE)
+        for i, q in enumerate(requests):
+            r[i] = tuple(int(v) for v in q)
+        return r
+
+    def graph_apply_into(self, requests, dst_ptr):
+        """Queue the correction of each request's sequence (with GRAPH_APPLY_MAP the stream is synchronised on the way): dst_ptr receives one
+        aloam_graph_apply_result per request, device memory or pinned host memory."""
+        r = requests if isinstance(requests, np.ndarray) else self.graph_apply_requests(requests)
+        r = np.ascontiguousarray(r, dtype=GRAPH_APPLY_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_apply(self.h, _p(r) if len(r) else None, len(r), C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def graph_apply(self, requests, pinned=True):
+        """Apply and wait: a structured array [len(requests)] of GRAPH_APPLY_RESULT_DTYPE."""
+        import torch
+        n, size = len(requests), GRAPH_APPLY_RESULT_DTYPE.itemsize
+        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_apply_into(requests, buf.data_ptr())
+        self.synchronize()
+        return buf.cpu().numpy()[:n * size].view(GRAPH_APPLY_RESULT_DTYPE).copy()
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

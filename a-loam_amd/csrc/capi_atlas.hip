@@ -59,7 +59,7 @@ bool queue_atlas_window(aloam_ctx* c, const int* mask) {
 
 // The largest number of points any 21 x 21 x 11 box of cubes holds: sliding sums over the occupied bounding box (exact), or, when that box
 // has more than 2^24 cells, the class total (an upper bound).  *exact says which.
-static long long largest_window(const std::vector<int>& keys, const std::vector<int>& counts, const int lo[3], const int hi[3], bool* exact) {
+long long aloam::largest_window(const std::vector<int>& keys, const std::vector<int>& counts, const int lo[3], const int hi[3], bool* exact) {
   long long total = 0;
   for (int n : counts) total += n;
   const long long d[3] = {hi[0] - lo[0] + 1LL, hi[1] - lo[1] + 1LL, hi[2] - lo[2] + 1LL};

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "atlas_kernels.hpp"
 #include "checkpoint_kernels.hpp"
 #include "export_kernels.hpp"
+#include "graphapply_kernels.hpp"
 #include "graphmap_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -235,6 +236,9 @@ struct aloam_ctx {
   DevBuf<long long> d_gm_point_off; long long gm_point_off_cap = 0;
   long long gm_dir_hint = 0;                                        // the directory size an earlier call had to grow to
   long long gm_last_raw = 0; int gm_last_segs = -1;                 // the last call that succeeded (algorithmic bytes); -1 while its scratch is not valid
+  // a solved graph carried into the live state (aloam_graph_apply): scratch grown on first use, used in stream order
+  DevBuf<GaItem> d_ga_items; long long ga_items_cap = 0;            // the listed sequences of one call
+  DevBuf<long long> d_ga_off; long long ga_off_cap = 0;             // the offsets the map pass writes for its requests
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -382,6 +386,8 @@ void queue_map_spill(aloam_ctx* c, const int* mask);
 int spill_dropped_since(aloam_ctx* c, long long* fresh);
 int atlas_step_check(aloam_ctx* c);                      // ALOAM_E_STATE when an attached sequence that is active in this step is not frozen
 bool queue_atlas_window(aloam_ctx* c, const int* mask);  // k_atlas_window when an attached sequence takes part
+// The largest number of points any 21 x 21 x 11 box of cubes holds (keys: atlas_key of every cube, lo / hi: their bounding box); *exact = false: the class total instead
+long long largest_window(const std::vector<int>& keys, const std::vector<int>& counts, const int lo[3], const int hi[3], bool* exact);
 // capi_graphmap.hip
 int keyframe_add_check(aloam_ctx* c, const int* seqs, int n);        // ALOAM_E_STATE when a listed sequence holds no stacks (store enabled)
 void queue_keyframe_capture(aloam_ctx* c, int n);                    // k_keyframe_capture behind k_graph_add_nodes, for the items in d_pg_add
@@ -414,6 +420,7 @@ void on_descriptors_made(aloam_ctx* c, const int* seqs, int n);
 void on_graph_nodes_added(aloam_ctx* c, const int* seqs, int n);
 void on_graph_edges_added(aloam_ctx* c, int seq, int count);
 void on_graph_cleared(aloam_ctx* c, const int* seqs, int n);
+int on_graph_applied(aloam_ctx* c, const int* seqs, int n);
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events);
 // capi_mapping.hip
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);

@@ -132,6 +132,16 @@ void on_graph_nodes_added(aloam_ctx* c, const int* seqs, int n) {
 }
 void on_graph_edges_added(aloam_ctx* c, int seq, int count) { c->seq[seq].graph_edges += count; }
 void on_graph_cleared(aloam_ctx* c, const int* seqs, int n) { for (int i = 0; i < n; ++i) { c->seq[seqs[i]].graph_nodes = 0; c->seq[seqs[i]].graph_edges = 0; } }
+// aloam_graph_apply has been queued for the listed sequences: another frame and, with its map rebuilt, another submap, so their grids are built
+// anew, there is nothing to score against and the pose of their last mapping solve is gone.  The graph's counts stay, and so does has_stacks:
+// the stacks are in the sensor frame.
+int on_graph_applied(aloam_ctx* c, const int* seqs, int n) {
+  for (int i = 0; i < n; ++i) {
+    HIP_TRY(c, hipMemsetAsync(c->d_grid_sig.get() + (size_t)seqs[i] * 2, 0, sizeof(MapGridSig) * 2, c->stream));
+    c->seq[seqs[i]].scorable = false; c->seq[seqs[i]].info_map = false;
+  }
+  return ALOAM_OK;
+}
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events) {   // aloam_synchronize has read a sequence's pool capacity events: how many are new
   const long long fresh = events > c->seq[seq].map_err_seen ? events - c->seq[seq].map_err_seen : 0;
   c->seq[seq].map_err_seen = events;

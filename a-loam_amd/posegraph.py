@@ -387,6 +387,21 @@ def drifted_laps(seed, nodes, loops, radius=10.0, per_lap=None, sigma_theta=5e-3
     return dict(q_true=q_true, t_true=t_true, q=q, t=t, odom=odom, loop=loop, info=info)
 
 
+def apply_correction(q, t, q_opt, t_opt, live):
+    """aloam_graph_apply restated: the correction D of a solved graph, the live poses moved by it and the rebase of the nodes.
+
+    q, t, q_opt, t_opt: the K >= 1 nodes as exported before the call; live: [(q, t), ...] poses of the live state (q_wmap_wodom / t_wmap_wodom,
+    q_w_curr / t_w_curr).  D comes from the last node: q_D = normalise(q_opt conj(q)), t_D = t_opt - q_D t, every operation a separately
+    rounded f64 operation in the order of the device.  Returns ((q_D, t_D), [D o X for X in live], (q, t) after the rebase = bit copies of
+    (q_opt, t_opt))."""
+    q, t, q_opt, t_opt = (np.asarray(v, np.float64) for v in (q, t, q_opt, t_opt))
+    qd = qmul(q_opt[-1], qconj(q[-1]))
+    qd = qd / np.sqrt(qd[0] * qd[0] + qd[1] * qd[1] + qd[2] * qd[2] + qd[3] * qd[3])
+    td = t_opt[-1] - qrot(qd, t[-1])
+    moved = [(qmul(qd, np.asarray(ql, np.float64)), qrot(qd, np.asarray(tl, np.float64)) + td) for ql, tl in live]
+    return (qd, td), moved, (q_opt.copy(), t_opt.copy())
+
+
 def ate(t, t_true):
     """Absolute trajectory error: the RMS distance of the positions (both trajectories share node 0; no alignment)."""
     return float(np.sqrt(np.mean(np.sum((np.asarray(t) - np.asarray(t_true)) ** 2, 1))))

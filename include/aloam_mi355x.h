@@ -704,7 +704,7 @@ int aloam_export_pose_information(aloam_ctx* ctx, int which, const int* seqs, in
 enum { ALOAM_GRAPH_EDGE_ROBUST = 1 };
 enum { ALOAM_GRAPH_OK = 0, ALOAM_GRAPH_NO_EDGES = 1, ALOAM_GRAPH_FAILED = 2 };
 typedef struct aloam_graph_node {             /* 128 bytes                                                                              */
-  double q[4], t[3];                          /* the pose as entered, in the sequence's own (drifting) frame; never changed             */
+  double q[4], t[3];                          /* the pose as entered, in the sequence's own (drifting) frame; changed only by aloam_graph_apply */
   double q_opt[4], t_opt[3];                  /* the current estimate                                                                   */
   int frame;                                  /* frameCount when it was entered (mapping), else -1                                      */
   int pad[3];
@@ -807,6 +807,60 @@ int aloam_graph_keyframe_info(aloam_ctx* ctx, int seq, long long out[8]);
 int aloam_graph_export_map(aloam_ctx* ctx, const aloam_graph_map_request* req, int n, aloam_map_tile* tiles_dst, long long cap_tiles,
                            float* points_dst_xyzw, long long cap_points, long long* dst_offsets /* [2][n + 1] */,
                            aloam_graph_map_stats* stats_dst /* [n] or NULL */);
+
+/* ---- a solved graph carried into the live state ----------------------------------------------------------------------------------------
+ * aloam_graph_optimize and aloam_graph_export_map end in exports; aloam_graph_apply closes the loop in the sequence itself, so that the
+ * next aloam_mapping_step registers against the corrected geometry and the next node is entered in the corrected frame.  Opt-in and
+ * beside the reference: a context that never calls it launches exactly what it launched before.  a-loam_amd/posegraph.py
+ * (apply_correction) and a-loam_amd/atlas.py (window_from_keyframes) restate the definition in numpy; DESIGN.md §7m.
+ *
+ * For each of the n requests (host memory, read during the call) whose sequence holds K >= 1 nodes, everything is read on the device at
+ * that point of the stream (aloam_graph_optimize, aloam_graph_apply, aloam_mapping_step need no synchronise from the caller in between),
+ * every operation a separately rounded f64 operation:
+ *   - the correction comes from the LAST node K - 1, whatever first and count are: q_D = normalise(q_opt conj(q)), t_D = t_opt - q_D t;
+ *   - q_wmap_wodom := q_D q_wmap_wodom, t_wmap_wodom := q_D t_wmap_wodom + t_D, and q_w_curr / t_w_curr (aloam_get_map_pose) the same way;
+ *     the odometry state and frameCount are not touched;
+ *   - every node of the sequence is rebased: (q, t) := (q_opt, t_opt), bit copies; q_opt, t_opt and every edge stay.  The live frame has
+ *     become the optimised one, and aloam_graph_add_nodes forms the next odometry edge from the entered poses;
+ *   - with ALOAM_GRAPH_APPLY_MAP the sequence's 2 x 4851 cubes are replaced by the map of nodes [first, first + count) at (q_opt, t_opt),
+ *     exactly as aloam_graph_export_map defines it, cut at the new window centre cen' = (10, 10, 5) - cube(t_w_curr'): the tile of
+ *     absolute cube c lands at window index c + cen'; tiles outside the window are left out and their filtered points counted in
+ *     outside_window.  The cubes are packed from the start of the pool row in ascending window index, as aloam_set_map would write that
+ *     cut.  The rebuilt map holds KEYFRAMES ONLY: the points of sweeps between keyframes are gone.  The old window is not spilled
+ *     (aloam_map_spill_enable): its cubes are in the old frame.
+ * All or nothing per sequence: a window that does not fit its pool row leaves pose, nodes and map as they were (status
+ *   ALOAM_GRAPH_APPLY_NO_ROOM).  The call grows the map pools first, to the largest 21 x 21 x 11 box of cubes of any listed map (filtered
+ *   points per class; where the sensor will be is known on the device only), so that this is a second line only; at the pool limit the call returns ALOAM_E_CAPACITY with nothing
+ *   changed.  K = 0: status ALOAM_GRAPH_APPLY_NO_NODES, nothing changed.
+ * Checked before anything is queued, nothing changes on a refusal.  ALOAM_E_STATE: before aloam_graph_enable or aloam_mapping_enable;
+ *   ALOAM_GRAPH_APPLY_MAP before aloam_graph_keyframes_enable; a listed sequence frozen (aloam_set_map_frozen) or attached
+ *   (aloam_atlas_attach): its map is not its own.  ALOAM_E_ARG: seq out of range or listed twice; first, count outside the sequence's
+ *   nodes; flags other than ALOAM_GRAPH_APPLY_POSE or ALOAM_GRAPH_APPLY_POSE | ALOAM_GRAPH_APPLY_MAP; dst not device memory of the
+ *   context's device or pinned host memory (classified like the exports).  n = 0 is ALOAM_OK.
+ * With ALOAM_GRAPH_APPLY_POSE alone on every request the call is stream-ordered with no host synchronisation.  With
+ *   ALOAM_GRAPH_APPLY_MAP it SYNCHRONISES the context's stream where aloam_graph_export_map does (its transform, group and filter passes
+ *   run into internal scratch) and once more behind the filter, to size the pools from the filtered counts.  Keyframe points never pass
+ *   through host memory.  Meant to be called once per loop closure.
+ * Afterwards the sequence's submap grids are built anew, aloam_score_map_corrections is ALOAM_E_STATE until its next frozen step and the
+ *   pose information of its last mapping solve is gone (ALOAM_INFO_NONE).  The stored places (aloam_places_*) keep their old-frame poses:
+ *   after an apply a place's pose is to be taken from its node.
+ * dst[i] belongs to req[i]; its bits, and everything written for a sequence, do not depend on n, on the position in the list or on the
+ *   other requests. */
+enum { ALOAM_GRAPH_APPLY_POSE = 1, ALOAM_GRAPH_APPLY_MAP = 2 };
+enum { ALOAM_GRAPH_APPLIED = 0, ALOAM_GRAPH_APPLY_NO_NODES = 1, ALOAM_GRAPH_APPLY_NO_ROOM = 2 };
+typedef struct aloam_graph_apply_request {    /* 16 bytes: the map is made of nodes [first, first + count) of sequence seq              */
+  int seq, first, count, flags;               /* flags: ALOAM_GRAPH_APPLY_POSE, or ALOAM_GRAPH_APPLY_POSE | ALOAM_GRAPH_APPLY_MAP       */
+} aloam_graph_apply_request;
+typedef struct aloam_graph_apply_result {     /* 104 bytes                                                                              */
+  int status;                                 /* ALOAM_GRAPH_APPLIED, ALOAM_GRAPH_APPLY_NO_NODES or ALOAM_GRAPH_APPLY_NO_ROOM           */
+  int nodes;                                  /* K: the nodes the sequence held, all rebased                                            */
+  int cen[3];                                 /* the window centre afterwards (NO_ROOM: the one that did not fit)                       */
+  int cubes[2], points[2];                    /* with MAP: non-empty cubes and points of the new window, corner / surf; else 0          */
+  int raw_points[2];                          /* with MAP: keyframe points that went into the map of the listed nodes                   */
+  int outside_window;                         /* with MAP: filtered points of tiles that lie outside the window                         */
+  double q_corr[4], t_corr[3];                /* D (identity rotation for NO_NODES)                                                     */
+} aloam_graph_apply_result;
+int aloam_graph_apply(aloam_ctx* ctx, const aloam_graph_apply_request* req, int n, aloam_graph_apply_result* dst /* [n] */);
 
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host

@@ -1,7 +1,7 @@
 """tools/loop_closure_drive.py — a loop closure inside one drive, with nothing but calls the project already has ("A loop
 edge inside a drive").
 
-    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6]
+    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -13,6 +13,10 @@ node with its clouds) and a place every few metres.  At the last keyframe:
   5. aloam_graph_export_map of all nodes at the entered and at the optimised poses.
 Printed against ground truth: the loop edge's error, ATE before and after the solve, tiles and points of the two maps.  One JSON object; a
 step that fails is named with what was known by then.
+
+With --apply the whole chain runs twice, and both runs drive on for another quarter lap behind the solve: one after aloam_graph_apply of
+all nodes (pose and map), one without it.  Reported for each, without judging them: the ATE of the live map pose over the continued sweeps,
+and the residual of the ground-truth loop edge between the last keyframe and the keyframe it revisits, at the graph's entered poses.
 """
 from __future__ import annotations
 
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--neighbours", type=int, default=6, help="keyframes either side of the matched one that make the local atlas")
     ap.add_argument("--frozen-steps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
     args = ap.parse_args()
 
     import torch
@@ -63,19 +68,29 @@ def main():
     reloc = importlib.import_module("a-loam_amd.relocalize")
 
     frames = int(round(args.laps * 2 * math.pi * args.radius / args.step))
+    more = int(round(0.25 * 2 * math.pi * args.radius / args.step)) if args.apply else 0   # the continued drive
     every = max(1, int(round(args.keyframe_spacing / args.step)))
     model = syn.sensor_model("VLP-16")
     world = syn.make_world(args.seed, track_radius=args.radius)
-    R, t = syn.trajectory(frames, step=args.step, radius=args.radius, seed=args.seed)
+    R, t = syn.trajectory(frames + more, step=args.step, radius=args.radius, seed=args.seed)
     gen = torch.Generator().manual_seed(77 + args.seed)
-    scans = [syn.render_scan(world, model, R[k], t[k], 0.01, gen).numpy() for k in range(frames)]
-    nan_row = np.full((1, 4), np.nan, np.float32)
+    scans = [syn.render_scan(world, model, R[k], t[k], 0.01, gen).numpy() for k in range(frames + more)]
     # ground truth in the frame of sweep 0 (where the drive's own frame starts)
     R, t = R.numpy(), t.numpy()
-    q_true = np.array([quat_of(R[0].T @ R[k]) for k in range(frames)])
-    t_true = np.array([R[0].T @ (t[k] - t[0]) for k in range(frames)])
+    q_true = np.array([quat_of(R[0].T @ R[k]) for k in range(frames + more)])
+    t_true = np.array([R[0].T @ (t[k] - t[0]) for k in range(frames + more)])
+    mods = (torch, binding, pg, places, reloc, syn, model)
+    if not args.apply:
+        print(json.dumps(drive(args, mods, scans, q_true, t_true, frames, 0, every, False)))
+        return
+    runs = {name: drive(args, mods, scans, q_true, t_true, frames, more, every, apply) for name, apply in (("applied", True), ("not_applied", False))}
+    print(json.dumps(runs))
 
-    n_key = (frames + every - 1) // every
+
+def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
+    torch, binding, pg, places, reloc, syn, model = mods
+    nan_row = np.full((1, 4), np.nan, np.float32)
+    n_key = (frames + more + every - 1) // every + 1
     gpu = binding.Aloam(n_scans=16, min_range=model.min_range, batch=2, max_points=max(len(s) for s in scans) + 64)
     gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)
     gpu.graph_enable(n_key + 4, n_key + 8)
@@ -169,13 +184,38 @@ def main():
         for name, pose in (("entered", binding.GRAPH_POSE_ENTERED), ("optimised", binding.GRAPH_POSE_OPTIMIZED)):
             tl, pp, _, st = gpu.graph_export_map([(0, 0, len(key_frames), pose)], pinned=False)
             out["map_" + name] = {"tiles": len(tl), "points": len(pp), "raw_points": st[0]["raw_points"].tolist()}
+        if more:
+            stage = "graph_apply"
+            if apply:
+                r = gpu.graph_apply([(0, 0, len(key_frames), binding.GRAPH_APPLY_POSE | binding.GRAPH_APPLY_MAP)])[0]
+                out["apply"] = {"status": int(r["status"]), "cen": r["cen"].tolist(), "cubes": r["cubes"].tolist(), "points": r["points"].tolist(),
+                                "outside_window": int(r["outside_window"]), "t_corr": r["t_corr"].tolist()}
+            stage = "continued drive"
+            live = []
+            for k in range(frames, frames + more):
+                gpu.scan_register([scans[k], nan_row], check=False)
+                gpu.odometry_step()
+                gpu.mapping_step()
+                if k % every == 0 or k == frames + more - 1:
+                    gpu.graph_add_nodes([0], info)
+                    key_frames.append(k)
+                live.append(gpu.map_pose(0)["t_w"].copy())
+            out["continued"] = {"sweeps": more, "ate_live_pose": pg.ate(np.array(live), t_true[frames:frames + more])}
+            # the keyframe the last one revisits: the nearest in ground truth among those at least --gap keyframes older
+            now = gpu.graph_export(0)
+            j2 = len(key_frames) - 1
+            older = np.arange(0, max(1, j2 - args.gap))
+            i2 = int(older[np.argmin(np.linalg.norm(t_true[np.array(key_frames)[older]] - t_true[key_frames[j2]], axis=1))])
+            qz, tz = pg.relative_pose(q_true[key_frames[i2]], t_true[key_frames[i2]], q_true[key_frames[j2]], t_true[key_frames[j2]])
+            res2 = pg.residual(now["q"], now["t"], pg.make_edges(0, i2, j2, qz[None], tz[None], info[None]))[0]
+            out["revisit"] = {"i": i2, "j": j2, "rotation_residual_rad": float(np.linalg.norm(res2[:3])), "translation_residual_m": float(np.linalg.norm(res2[3:]))}
         stage = "done"
     except Exception as e:  # noqa: BLE001 - the tool reports how far the chain got
         out["failed_at"] = stage
         out["error"] = str(e)
     out["stage"] = stage
-    print(json.dumps(out))
     gpu.close()
+    return out
 
 
 if __name__ == "__main__":
