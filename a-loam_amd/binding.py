@@ -110,6 +110,30 @@ class AloamGraphApplyResult(C.Structure):
                 ("raw_points", C.c_int * 2), ("outside_window", C.c_int), ("q_corr", C.c_double * 4), ("t_corr", C.c_double * 3)]
 
 
+class AloamGraphLoopRequest(C.Structure):
+    """Node j registered against nodes [first, first + count) in the frame of node i (aloam_graph_loop_request, 96 bytes)."""
+    _fields_ = [("seq", C.c_int), ("i", C.c_int), ("j", C.c_int), ("first", C.c_int), ("count", C.c_int), ("pose", C.c_int), ("pad", C.c_int * 2),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("reserved", C.c_double)]
+
+
+class AloamGraphLoopOptions(C.Structure):
+    _fields_ = [("outer_iterations", C.c_int), ("lm_max_iterations", C.c_int)]
+
+
+class AloamGraphLoopResult(C.Structure):
+    """The measured loop edge of one request (aloam_graph_loop_result, 448 bytes); a-loam_amd/loopreg.py holds the definitions."""
+    _fields_ = [("status", C.c_int), ("n_line", C.c_int), ("n_plane", C.c_int), ("lm_iterations", C.c_int), ("lm_termination", C.c_int), ("pad", C.c_int),
+                ("target_points", C.c_int * 2), ("target_raw", C.c_int * 2), ("source_points", C.c_int * 2), ("cost", C.c_double),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("info", C.c_double * 21), ("info_left", C.c_double * 21)]
+
+
+LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
+GRAPH_LOOP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32),
+                                     ("pad", np.int32, 2), ("q", np.float64, 4), ("t", np.float64, 3), ("reserved", np.float64)])
+GRAPH_LOOP_RESULT_DTYPE = np.dtype([("status", np.int32), ("n_line", np.int32), ("n_plane", np.int32), ("lm_iterations", np.int32),
+                                    ("lm_termination", np.int32), ("pad", np.int32), ("target_points", np.int32, 2), ("target_raw", np.int32, 2),
+                                    ("source_points", np.int32, 2), ("cost", np.float64), ("q", np.float64, 4), ("t", np.float64, 3),
+                                    ("info", np.float64, 21), ("info_left", np.float64, 21)])
 GRAPH_APPLY_POSE, GRAPH_APPLY_MAP = 1, 2
 GRAPH_APPLIED, GRAPH_APPLY_NO_NODES, GRAPH_APPLY_NO_ROOM = 0, 1, 2
 GRAPH_APPLY_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("first", np.int32), ("count", np.int32), ("flags", np.int32)])
@@ -332,6 +356,10 @@ def lib():
         L.aloam_graph_keyframe_info.argtypes = [vp, C.c_int, vp]
         L.aloam_graph_export_map.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp, vp]
         L.aloam_graph_apply.argtypes = [vp, vp, C.c_int, vp]
+        L.aloam_graph_loop_default_options.argtypes = [C.POINTER(AloamGraphLoopOptions)]; L.aloam_graph_loop_default_options.restype = None
+        L.aloam_graph_loops_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        L.aloam_graph_register_loops.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopOptions), vp]
+        L.aloam_graph_loop_export_target.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -860,6 +888,58 @@ class Aloam:
         self.graph_apply_into(requests, buf.data_ptr())
         self.synchronize()
         return buf.cpu().numpy()[:n * size].view(GRAPH_APPLY_RESULT_DTYPE).copy()
+
+    # ---- loop edges measured on the device (a-loam_amd/loopreg.py holds the definition) -----------------------------------------------------
+    def graph_loops_enable(self, max_requests, max_target_corner_points, max_target_surf_points):
+        """The scratch of max_requests registrations whose raw targets hold up to that many corner / surf points."""
+        self._check(lib().aloam_graph_loops_enable(self.h, int(max_requests), int(max_target_corner_points), int(max_target_surf_points)))
+
+    @staticmethod
+    def graph_loop_requests(requests):
+        """[(seq, i, j, first, count, pose, q_guess, t_guess), ...] -> structured array of GRAPH_LOOP_REQUEST_DTYPE."""
+        r = np.zeros(len(requests), GRAPH_LOOP_REQUEST_DTYPE)
+        for k, (seq, i, j, first, count, pose, q, t) in enumerate(requests):
+            r[k]["seq"], r[k]["i"], r[k]["j"], r[k]["first"], r[k]["count"], r[k]["pose"] = int(seq), int(i), int(j), int(first), int(count), int(pose)
+            r[k]["q"], r[k]["t"] = np.asarray(q, np.float64), np.asarray(t, np.float64)
+        return r
+
+    def graph_loop_options(self, **kw):
+        o = AloamGraphLoopOptions()
+        lib().aloam_graph_loop_default_options(C.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def graph_register_loops_into(self, requests, dst_ptr, options=None):
+        """Queue the registration of each request (no host synchronisation): dst_ptr receives one aloam_graph_loop_result per request, device
+        memory or pinned host memory."""
+        r = requests if isinstance(requests, np.ndarray) else self.graph_loop_requests(requests)
+        r = np.ascontiguousarray(r, dtype=GRAPH_LOOP_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_register_loops(self.h, _p(r) if len(r) else None, len(r), C.byref(options) if options is not None else None,
+                                                     C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def graph_register_loops(self, requests, pinned=True, **options):
+        """Register and wait: a structured array [len(requests)] of GRAPH_LOOP_RESULT_DTYPE.  Keyword arguments are fields of
+        aloam_graph_loop_options."""
+        import torch
+        n, size = len(requests), GRAPH_LOOP_RESULT_DTYPE.itemsize
+        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_register_loops_into(requests, buf.data_ptr(), self.graph_loop_options(**options))
+        self.synchronize()
+        return buf.cpu().numpy()[:n * size].view(GRAPH_LOOP_RESULT_DTYPE).copy()
+
+    def graph_loop_target(self, slot=0, feature_class=0):
+        """The filtered target of a scratch slot as the last graph_register_loops left it (parity tests): float32 [n, 4]."""
+        import torch
+        cnt = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        self._check(lib().aloam_graph_loop_export_target(self.h, int(slot), int(feature_class), None, 0, C.c_void_p(cnt.data_ptr())))
+        self.synchronize()
+        n = int(cnt[0])
+        pts = torch.zeros((max(1, n), 4), dtype=torch.float32, pin_memory=True)
+        self._check(lib().aloam_graph_loop_export_target(self.h, int(slot), int(feature_class), C.c_void_p(pts.data_ptr()), n, C.c_void_p(cnt.data_ptr())))
+        self.synchronize()
+        return pts.numpy()[:n].copy()
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include "export_kernels.hpp"
 #include "graphapply_kernels.hpp"
 #include "graphmap_kernels.hpp"
+#include "loopreg_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "places_kernels.hpp"
@@ -31,11 +32,11 @@ using namespace aloam;
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_GRAPH_MAP, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_GRAPH_MAP, K_LOOP_REGISTER, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "pose_graph", "graph_map", "save_sequences",
+                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "pose_graph", "graph_map", "loop_register", "save_sequences",
                                     "load_sequences", "score_corrections", "apply_corrections"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
@@ -109,6 +110,7 @@ struct aloam_ctx {
   Stream grid_stream;                // the build of the next step's search grids runs here, beside the association and the solve (aloam_odometry_step)
   Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
   Event pg_stage_done[kGraphStageSlots];   // pose graphs: the copy that read a slot of h_pg_stage has run
+  Event lr_stage_done[kLoopStageSlots];    // loop registration: the copy that read a slot of h_lr_stage has run
   Event grid_fork, grids_done;       // main stream -> grid stream at the start of a step, grid stream -> main stream before k_advance
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
   // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
@@ -239,6 +241,21 @@ struct aloam_ctx {
   // a solved graph carried into the live state (aloam_graph_apply): scratch grown on first use, used in stream order
   DevBuf<GaItem> d_ga_items; long long ga_items_cap = 0;            // the listed sequences of one call
   DevBuf<long long> d_ga_off; long long ga_off_cap = 0;             // the offsets the map pass writes for its requests
+  // loop edges (aloam_graph_loops_enable): the scratch of lr_slots registrations, used in stream order; the slots are the "sequences" of a
+  // scratch MapArgs (loopreg_kernels.hpp), so every per-sequence array of the mapping step has a per-slot twin here
+  bool lr_on = false;
+  int lr_slots = 0, lr_H = 0, lr_tile_bound = 0, lr_tile_cap = 0, lr_levels = 0;
+  long long lr_cap[2] = {0, 0}, lr_key_cap = 0;                     // raw target points per slot: corner, surf; keys of the general voxel path
+  DevBuf<aloam_graph_loop_request> d_lr_req;                        // [slots] the round's requests
+  PinnedBuf<aloam_graph_loop_request> h_lr_stage;                   // pinned ring of kLoopStageSlots x slots requests
+  int lr_stage_slot = 0; bool lr_stage_used[kLoopStageSlots] = {};
+  DevBuf<float4> d_lr_raw[2], d_lr_target[2], d_lr_sorted[2], d_lr_stack[2], d_lr_knn, d_lr_voxtmp;
+  DevBuf<int> d_lr_start[2], d_lr_plan, d_lr_rec_tiles, d_lr_list, d_lr_vox_counters, d_lr_vox_lists, d_lr_bbox, d_lr_tile_seg, d_lr_tile_heads, d_lr_tile_pref;
+  DevBuf<unsigned long long> d_lr_keys[2];
+  DevBuf<MapSeq> d_lr_seq;
+  DevBuf<MapEdgeRec> d_lr_edges; DevBuf<MapNormRec> d_lr_norms;
+  DevBuf<VoxSeg> d_lr_segs;
+  DevBuf<aloam_pose_information> d_lr_info;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;

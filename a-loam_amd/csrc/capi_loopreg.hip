@@ -1,0 +1,204 @@
+// a-loam_amd/csrc/capi_loopreg.hip — host side of the loop edges measured on the device (aloam_graph_loops_enable /
+// aloam_graph_register_loops / aloam_graph_loop_export_target).  A request runs in a scratch slot; the slots are the
+// "sequences" of a scratch MapArgs, so association, fit, solve and information are the launches of the mapping step over other buffers.
+// Everything is checked before anything is queued; nothing synchronises the host (a slot of the pinned request ring is waited for only when
+// kLoopStageSlots later rounds have been queued behind it).
+#include <algorithm>
+#include <cmath>
+
+#include "capi_internal.hpp"
+#include "information_device.hpp"
+
+static int require_loops(aloam_ctx* c) {
+  if (!c->lr_on) { c->err = "loop registration is not enabled (aloam_graph_loops_enable)"; return ALOAM_E_STATE; }
+  return ALOAM_OK;
+}
+
+// The scratch MapArgs of `n` slots: what launch_map_associate, launch_map_solve and launch_pose_information_map index by "sequence".
+static MapArgs loop_map_args(aloam_ctx* c, int n, int lm_max_iterations) {
+  MapArgs a{};
+  a.B = n; a.cap = c->cap; a.R = c->R;
+  a.seq = c->d_lr_seq.get();
+  a.line_res = c->map_line_res; a.plane_res = c->map_plane_res;
+  a.pool_cap = (int)std::max(c->lr_cap[0], c->lr_cap[1]);
+  for (int k = 0; k < 2; ++k) { a.stack[k] = c->d_lr_stack[k].get(); a.grid_sorted[k] = c->d_lr_sorted[k].get(); a.grid_start[k] = c->d_lr_start[k].get(); }
+  a.grid_H = c->lr_H;
+  a.knn = c->d_lr_knn.get(); a.edges = c->d_lr_edges.get(); a.norms = c->d_lr_norms.get();
+  a.lm_max_iterations = lm_max_iterations;
+  a.rec_tiles = c->d_lr_rec_tiles.get(); a.rec_tiles_per_seq = c->rec_tiles_per_seq; a.rec_tiles_corner = c->rec_tiles_corner;
+  a.active = nullptr;
+  return a;
+}
+
+// The feature's own voxel-filter scratch (the mapping step's is in use by the live sequences' steps in the same stream).
+static VoxArgs loop_vox_args(aloam_ctx* c, int n_segs) {
+  VoxArgs v{};
+  v.segs = c->d_lr_segs.get(); v.n_segs = n_segs; v.tile_seg = c->d_lr_tile_seg.get(); v.tile_heads = c->d_lr_tile_heads.get(); v.tile_pref = c->d_lr_tile_pref.get();
+  v.counters = c->d_lr_vox_counters.get(); v.keys[0] = c->d_lr_keys[0].get(); v.keys[1] = c->d_lr_keys[1].get(); v.tmp = c->d_lr_voxtmp.get();
+  v.bbox = c->d_lr_bbox.get(); v.tile_cap = c->lr_tile_cap; v.key_cap = c->lr_key_cap; v.levels = c->lr_levels; v.lists = c->d_lr_vox_lists.get();
+  return v;
+}
+
+static void loops_release(aloam_ctx* c) {
+  c->d_lr_req.reset(); c->h_lr_stage.reset(); c->d_lr_knn.reset(); c->d_lr_voxtmp.reset(); c->d_lr_plan.reset(); c->d_lr_rec_tiles.reset(); c->d_lr_list.reset();
+  c->d_lr_vox_counters.reset(); c->d_lr_vox_lists.reset(); c->d_lr_bbox.reset(); c->d_lr_tile_seg.reset(); c->d_lr_tile_heads.reset(); c->d_lr_tile_pref.reset();
+  c->d_lr_seq.reset(); c->d_lr_edges.reset(); c->d_lr_norms.reset(); c->d_lr_segs.reset(); c->d_lr_info.reset();
+  for (int k = 0; k < 2; ++k) { c->d_lr_raw[k].reset(); c->d_lr_target[k].reset(); c->d_lr_sorted[k].reset(); c->d_lr_stack[k].reset(); c->d_lr_start[k].reset(); c->d_lr_keys[k].reset(); }
+}
+
+extern "C" {
+
+void aloam_graph_loop_default_options(aloam_graph_loop_options* opt) {
+  if (!opt) return;
+  opt->outer_iterations = 2; opt->lm_max_iterations = 4;
+}
+
+int aloam_graph_loops_enable(aloam_ctx* c, int max_requests, int max_target_corner_points, int max_target_surf_points) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (!c->kf_on) { c->err = "aloam_graph_loops_enable before aloam_graph_keyframes_enable"; return ALOAM_E_STATE; }
+  if (c->lr_on) { c->err = "loop registration already enabled"; return ALOAM_E_STATE; }
+  if (max_requests < 1 || max_requests > kLoopMaxRequests || max_target_corner_points < 1 || max_target_corner_points > kLoopTargetMax || max_target_surf_points < 1 ||
+      max_target_surf_points > kLoopTargetMax) {
+    c->err = "bad loop registration sizes (1 <= max_requests <= 32768, 1 <= max_target_corner_points, max_target_surf_points <= 2^24)";
+    return ALOAM_E_ARG;
+  }
+  const size_t S = (size_t)max_requests, cap = c->cap, rowc = (size_t)c->R * kLessSharpPerRing, T = kVoxTile;
+  const size_t tc[2] = {(size_t)max_target_corner_points, (size_t)max_target_surf_points}, pool = std::max(tc[0], tc[1]);
+  int H = 4096, levels = 0;
+  while (H < (int)(pool / 16) && H < kMapGridMaxH) H <<= 1;
+  while ((T << levels) < pool) ++levels;
+  // the general path of the voxel filter takes whatever the single-workgroup filters pass on (more runs than their tables hold): sized for all of it
+  const size_t key_cap = S * (tc[0] + tc[1]), tile_cap = S * ((tc[0] + T - 1) / T + (tc[1] + T - 1) / T);
+  if (tile_cap > 0x7fffffffu) { c->err = "loop registration scratch: more voxel-filter tiles than an int counts"; return ALOAM_E_ARG; }
+  bool ok = true;
+  const char* cause = "device allocation failed";
+  auto grab = [&](auto& p, size_t count) { if (ok && dalloc(p, count) != hipSuccess) { ok = false; (void)hipGetLastError(); } };
+  for (int k = 0; k < 2; ++k) {
+    grab(c->d_lr_raw[k], S * tc[k]); grab(c->d_lr_target[k], S * tc[k]); grab(c->d_lr_sorted[k], S * pool); grab(c->d_lr_start[k], S * ((size_t)H + 1));
+    grab(c->d_lr_stack[k], S * (k == 0 ? rowc : cap)); grab(c->d_lr_keys[k], key_cap);
+  }
+  grab(c->d_lr_voxtmp, key_cap); grab(c->d_lr_tile_seg, tile_cap); grab(c->d_lr_tile_heads, tile_cap); grab(c->d_lr_tile_pref, tile_cap + 1);
+  grab(c->d_lr_req, S); grab(c->d_lr_knn, S * cap * 4); grab(c->d_lr_edges, S * rowc); grab(c->d_lr_norms, S * cap);
+  grab(c->d_lr_rec_tiles, S * (size_t)c->rec_tiles_per_seq); grab(c->d_lr_seq, S); grab(c->d_lr_plan, S * kLoopPlanInts); grab(c->d_lr_list, S);
+  grab(c->d_lr_segs, 2 * S); grab(c->d_lr_vox_lists, 3 * 2 * S); grab(c->d_lr_vox_counters, 8); grab(c->d_lr_bbox, 2 * S * 6); grab(c->d_lr_info, S);
+  aloam_graph_loop_request* ring = nullptr;
+  if (ok && hipHostMalloc((void**)&ring, sizeof(aloam_graph_loop_request) * S * kLoopStageSlots, hipHostMallocDefault) != hipSuccess) { ok = false; cause = "pinned request ring: allocation failed"; }
+  c->h_lr_stage.reset(ring);
+  for (Event& e : c->lr_stage_done)
+    if (ok && !e.h && hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess) { ok = false; cause = "event creation failed"; }
+  if (ok && prepare_loop_grid(H) != 0) { ok = false; cause = "k_loop_grid: dynamic LDS size rejected"; }
+  if (ok) {
+    // every slot counts as solved for k_pose_information_map: a slot whose gate is false holds no record and comes back without factors
+    std::vector<int> list(S);
+    for (size_t s = 0; s < S; ++s) list[s] = (int)s | kInfoSolvedBit;
+    ok = hipMemcpyAsync(c->d_lr_list.get(), list.data(), sizeof(int) * S, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+         hipMemsetAsync(c->d_lr_vox_counters.get(), 0, 8 * sizeof(int), c->stream) == hipSuccess &&
+         hipMemsetAsync(c->d_lr_seq.get(), 0, sizeof(MapSeq) * S, c->stream) == hipSuccess &&
+         hipMemsetAsync(c->d_lr_plan.get(), 0, sizeof(int) * S * kLoopPlanInts, c->stream) == hipSuccess &&
+         hipStreamSynchronize(c->stream) == hipSuccess;                          // (list is a local)
+    if (!ok) cause = "initialising the scratch failed";
+  }
+  if (!ok) {                           // nothing stays allocated behind a refusal
+    (void)hipGetLastError();
+    loops_release(c);
+    c->err = "loop registration scratch of " + std::to_string(max_requests) + " slots: " + cause;
+    return ALOAM_E_HIP;
+  }
+  c->lr_slots = max_requests; c->lr_H = H; c->lr_levels = levels; c->lr_cap[0] = (long long)tc[0]; c->lr_cap[1] = (long long)tc[1];
+  c->lr_key_cap = (long long)key_cap; c->lr_tile_cap = (int)tile_cap; c->lr_tile_bound = (int)std::max<size_t>(tile_cap, 1);
+  c->lr_stage_slot = 0;
+  c->lr_on = true;
+  return ALOAM_OK;
+}
+
+int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (const int rc = require_loops(c)) return rc;
+  // ---- everything is checked before anything is queued
+  if (n < 0 || (n > 0 && !req)) { c->err = "bad request list"; return ALOAM_E_ARG; }
+  aloam_graph_loop_options o;
+  aloam_graph_loop_default_options(&o);
+  if (opt) o = *opt;
+  if (o.outer_iterations < 1 || o.lm_max_iterations < 0) { c->err = "need outer_iterations >= 1 and lm_max_iterations >= 0"; return ALOAM_E_ARG; }
+  if (n == 0) return ALOAM_OK;
+  {
+    void* dev = nullptr;
+    const CallerMem m = classify_pointer(c, req, &dev);
+    if (m != kMemPageable && m != kMemPinned) { c->err = "req must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
+  }
+  void* d_dst = nullptr;
+  if (const int rc = export_target(c, dst, 8, "dst", &d_dst)) return rc;
+  std::vector<aloam_graph_loop_request> checked(req, req + n);
+  for (int r = 0; r < n; ++r) {
+    aloam_graph_loop_request& q = checked[r];
+    auto fail = [&](const char* what) { c->err = "request " + std::to_string(r) + ": " + what; return ALOAM_E_ARG; };
+    if (q.seq < 0 || q.seq >= c->B) return fail("seq out of range");
+    const long long nodes = c->seq[q.seq].graph_nodes;
+    if (q.first < 0 || q.count < 1 || q.first + (long long)q.count > nodes) return fail("need count >= 1 and [first, first + count) inside what the sequence's graph holds");
+    if (q.i < q.first || q.i >= q.first + (long long)q.count) return fail("node i must be one of the target nodes (first <= i < first + count)");
+    if (q.j < 0 || q.j >= nodes || (q.j >= q.first && q.j < q.first + (long long)q.count)) return fail("node j must be a node outside [first, first + count)");
+    if (q.pose != ALOAM_GRAPH_POSE_ENTERED && q.pose != ALOAM_GRAPH_POSE_OPTIMIZED) return fail("pose must be ALOAM_GRAPH_POSE_ENTERED or ALOAM_GRAPH_POSE_OPTIMIZED");
+    double nn = 0.0;
+    for (int a = 0; a < 4; ++a) { if (!std::isfinite(q.q[a])) return fail("the guess q is not finite"); nn += q.q[a] * q.q[a]; }
+    nn = std::sqrt(nn);
+    if (!(std::fabs(nn - 1.0) <= 1e-6)) return fail("the guess q is not within 1e-6 of unit norm");
+    for (int a = 0; a < 4; ++a) q.q[a] /= nn;
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(q.t[a])) return fail("the guess t is not finite");
+    q.pad[0] = 0; q.pad[1] = 0; q.reserved = 0.0;
+  }
+  // ---- rounds of at most lr_slots requests over the same scratch, in stream order
+  ProfScope prof(c, K_LOOP_REGISTER);
+  for (int r0 = 0; r0 < n; r0 += c->lr_slots) {
+    const int m = std::min(c->lr_slots, n - r0);
+    const int ns = c->lr_stage_slot;
+    c->lr_stage_slot = (ns + 1) % kLoopStageSlots;
+    if (c->lr_stage_used[ns]) HIP_TRY(c, hipEventSynchronize(c->lr_stage_done[ns]));
+    aloam_graph_loop_request* slot = c->h_lr_stage.get() + (size_t)ns * c->lr_slots;
+    std::copy(checked.begin() + r0, checked.begin() + r0 + m, slot);
+    HIP_TRY(c, hipMemcpyAsync(c->d_lr_req.get(), slot, sizeof(aloam_graph_loop_request) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->lr_stage_done[ns], c->stream));
+    c->lr_stage_used[ns] = true;
+    LoopArgs a{};
+    a.n = m; a.req = c->d_lr_req.get();
+    a.kf.points[0] = c->d_kf_points[0].get(); a.kf.points[1] = c->d_kf_points[1].get(); a.kf.desc = c->d_kf_desc.get(); a.kf.counters = c->d_kf_counters.get();
+    a.kf.cap[0] = c->kf_cap[0]; a.kf.cap[1] = c->kf_cap[1]; a.kf.max_nodes = c->pg_max_nodes;
+    a.nodes = c->d_pg_nodes.get(); a.max_nodes = c->pg_max_nodes;
+    a.map = loop_map_args(c, m, o.lm_max_iterations);
+    for (int k = 0; k < 2; ++k) { a.raw[k] = c->d_lr_raw[k].get(); a.raw_cap[k] = c->lr_cap[k]; a.target[k] = c->d_lr_target[k].get(); }
+    a.plan = c->d_lr_plan.get(); a.outer_iterations = o.outer_iterations;
+    a.info = c->d_lr_info.get(); a.dst = static_cast<aloam_graph_loop_result*>(d_dst) + r0;
+    const VoxArgs v = loop_vox_args(c, 2 * m);
+    HIP_TRY(c, hipMemsetAsync(c->d_lr_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));   // general-path count, the three LDS-filter lists
+    launch_loop_gather(a, v, c->stream);
+    launch_voxel_filter(v, c->lr_tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
+    launch_loop_grid(a, c->stream);
+    for (int it = 0; it < o.outer_iterations; ++it) {
+      launch_map_associate(a.map, it, c->stream);
+      launch_map_solve(a.map, it & 1, false, c->stream);   // no transformUpdate: a slot has no odometry frame
+    }
+    launch_pose_information_map(a.map, c->d_lr_list.get(), m, c->d_lr_info.get(), c->stream);
+    launch_loop_result(a, c->stream);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return ALOAM_OK;
+}
+
+int aloam_graph_loop_export_target(aloam_ctx* c, int slot, int feature_class, float* dst_xyzw, long long cap, int* count) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  if (const int rc = require_loops(c)) return rc;
+  if (slot < 0 || slot >= c->lr_slots) { c->err = "slot out of range"; return ALOAM_E_ARG; }
+  if (feature_class < 0 || feature_class > 1) { c->err = "feature_class must be 0 (corner) or 1 (surf)"; return ALOAM_E_ARG; }
+  if (cap < 0) { c->err = "negative cap"; return ALOAM_E_ARG; }
+  void *d_cnt = nullptr, *d_pts = nullptr;
+  if (const int rc = export_target(c, count, alignof(int), "count", &d_cnt)) return rc;
+  if ((dst_xyzw || cap > 0) && export_target(c, dst_xyzw, 16, "dst", &d_pts)) return ALOAM_E_ARG;
+  launch_loop_export_target(c->d_lr_seq.get() + slot, feature_class, c->d_lr_target[feature_class].get() + (size_t)slot * c->lr_cap[feature_class],
+                            static_cast<float4*>(d_pts), d_pts ? cap : 0, static_cast<int*>(d_cnt), c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return ALOAM_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,9 @@ namespace aloam {
 // ---- the store -------------------------------------------------------------------------------------------------------------------------
 // One descriptor per node: where its corner / surf cloud sits in the sequence's class rows.  Clouds are appended back to back, so
 // first[cls] of node k is first[cls] + count[cls] of node k - 1 (0 for node 0), also behind a node that was kept without clouds (count 0).
+// Invariant that readers rely on (k_graph_map_transform, k_keyframe_export, and k_loop_gather of loopreg_kernels.hip, which takes a class's
+// raw target as first + count of the last node minus first of the first): EVERY node's descriptor carries the row's fill position in
+// first[cls], a node kept without clouds included, so the clouds of nodes a .. b are the one range [first_a, first_b + count_b) of the row.
 struct KfDesc { int first[2], count[2]; };
 static_assert(sizeof(KfDesc) == 16, "16-byte descriptors");
 // Per sequence: the append cursors (points held, corner / surf), nodes kept without clouds and their points so far, four spare.

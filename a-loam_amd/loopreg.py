@@ -1,0 +1,118 @@
+"""Loop edges measured by registering keyframe clouds: the numpy model of aloam_graph_register_loops (include/aloam_mi355x.h, "loop edges
+measured on the device").
+
+A request (seq, i, j, first, count, pose, guess) registers the clouds of node j against a local target made of the clouds of nodes
+first .. first + count - 1 of the same sequence, moved into the frame of node i, and returns the edge (i, j, Z, info):
+
+    target_cloud(q, t, clouds, i, first, count, leaves, voxel_filter)   the two filtered target clouds, bit for bit what the device builds
+    edge_information(info_left, q_z)                                     the registration's left-tangent information in the edge's tangent
+    guess_from_match(...)                                                the guess of Z a place match stands for
+    edge_from_result(result, seq, i, j)                                  the aloam_graph_edge of a result record
+    room_sample(rng, ...), sensor_cloud(world, q, t, rng)                the hand-made scene the tests and tools/loop_register_rate.py share
+
+The registration itself (association, fits, Levenberg-Marquardt) is the mapping step's; tests/loopreg_model.py composes it from the
+oracle's pieces.  Everything here is float64 numpy on the host.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import places
+from .atlas import associate_to_map
+from .posegraph import EDGE_ROBUST, compose, info_full, info_upper, inverse, make_edges, qrot, relative_pose, rotmat
+
+LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
+GATE_CORNER, GATE_SURF = 10, 50                  # the filtered targets must hold MORE points than these (src/laserMapping.cpp:554)
+
+
+def target_poses(q, t, i, first, count):
+    """T_k = X_i^-1 o X_k of nodes first .. first + count - 1, as the header defines a relative pose: q_d = conj(q_i) q_k,
+    t_d = conj(q_i) (t_k - t_i), every operation a separately rounded f64 operation.  Node i goes through the same arithmetic."""
+    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    return [relative_pose(q[i], t[i], q[k], t[k]) for k in range(first, first + count)]
+
+
+def target_cloud(q, t, clouds, i, first, count, leaves, voxel_filter):
+    """The filtered target (corner, surf) of a request, in the frame of node i.  q [K, 4], t [K, 3]: the poses of the sequence's nodes
+    (entered or optimised, as the request says); clouds[k] = (corner, surf): node k's sensor-frame clouds, float32 [n, 4].  Per class the
+    points of the target nodes in node order, then point order, each through associate_to_map(p, T_k) (f64 rotation and translation,
+    stored to f32, intensity kept); the class's whole cloud is then filtered once with voxel_filter(points, leaves[class]), the caller's
+    input-order pcl::VoxelGrid."""
+    poses = target_poses(q, t, i, first, count)
+    out = []
+    for cls in (0, 1):
+        parts = [associate_to_map(clouds[first + k][cls], *poses[k]) for k in range(count) if len(clouds[first + k][cls])]
+        raw = np.concatenate(parts) if parts else np.zeros((0, 4), np.float32)
+        out.append(np.asarray(voxel_filter(raw, leaves[cls]), np.float32).reshape(-1, 4) if len(raw) else raw)
+    return out[0], out[1]
+
+
+def gate(target_corner, target_surf):
+    return len(target_corner) > GATE_CORNER and len(target_surf) > GATE_SURF
+
+
+def edge_information(info_left, q_z):
+    """The information of the edge (i, j, Z) from the registration's.  The registration's tangent is a LEFT perturbation of Z
+    (q <- exp(theta / 2) q, t <- t + dt); the graph's residual r = (2 q_E.xyz, t_E), E = Z^-1 o X_i^-1 o X_j, is a RIGHT perturbation
+    (q_Z <- q_Z exp(phi / 2), t_Z <- t_Z + R_Z tau).  So theta = R_Z phi, dt = R_Z tau and info = T^T info_left T with
+    T = blockdiag(R_Z, R_Z).  info_left: [6, 6] or its upper triangle [21]; returns the same shape."""
+    a = np.asarray(info_left, np.float64)
+    full = a if a.shape[-1] == 6 else info_full(a)
+    R = rotmat(np.asarray(q_z, np.float64))
+    T = np.zeros((6, 6))
+    T[:3, :3] = R
+    T[3:, 3:] = R
+    out = T.T @ (full @ T)
+    out = 0.5 * (out + out.T)
+    return out if a.shape[-1] == 6 else info_upper(out)
+
+
+def guess_from_match(q_i, t_i, place_q, place_t, shift, odom_q, odom_t):
+    """The guess of Z a place match stands for: places.guess_from_match gives the correction C that carries the sweep's odometry pose to
+    the stored place's pose turned by the match's yaw shift (in the frame the nodes live in); Z = X_i^-1 o C o X_odom."""
+    qc, tc = places.guess_from_match(place_q, place_t, shift, odom_q, odom_t)
+    qm, tm = compose(qc, tc, np.asarray(odom_q, np.float64), np.asarray(odom_t, np.float64))
+    qz, tz = relative_pose(q_i, t_i, qm, tm)
+    return qz / np.linalg.norm(qz), tz
+
+
+def edge_from_result(result, seq, i, j, robust=True):
+    """The aloam_graph_edge (posegraph.EDGE_DTYPE, one element) of an ALOAM_LOOP_OK result record; None for every other status.  Whether
+    an OK edge is a good loop is the caller's decision, from the counts, the cost and the information: hence robust by default."""
+    if int(result["status"]) != LOOP_OK:
+        return None
+    q = np.asarray(result["q"], np.float64)
+    return make_edges(seq, i, j, (q / np.linalg.norm(q))[None], np.asarray(result["t"], np.float64)[None], np.asarray(result["info"], np.float64)[None], robust)
+
+
+def room_sample(rng, n_corner=300, n_surf=1500):
+    """A random sample, in world coordinates (corner [n, 3], surf [m, 3], float64), of the room the loop-registration tests and
+    tools/loop_register_rate.py share: a floor (x -5 .. 15, y -6 .. 6), two perpendicular walls (y = 6 and x = 15, 3 m high), four vertical
+    poles and the walls' top edges; about 0.5 m between the surf samples, 0.15 m along the lines at the default sizes."""
+    u = rng.uniform
+    nf = (n_surf * 3) // 5
+    nw = (n_surf - nf) * 5 // 8
+    floor = np.stack([u(-5, 15, nf), u(-6, 6, nf), np.zeros(nf)], 1)
+    w1 = np.stack([u(-5, 15, nw), np.full(nw, 6.0), u(0, 3, nw)], 1)
+    w2 = np.stack([np.full(n_surf - nf - nw, 15.0), u(-6, 6, n_surf - nf - nw), u(0, 3, n_surf - nf - nw)], 1)
+    surf = np.concatenate([floor, w1, w2])
+    npole = n_corner // 10
+    poles = [np.stack([np.full(npole, x), np.full(npole, y), u(0, 3, npole)], 1) for x, y in ((0.0, -4.0), (4.0, 3.0), (9.0, -2.0), (12.0, 4.0))]
+    ne = n_corner - 4 * npole
+    e1 = np.stack([u(-5, 15, ne * 5 // 8), np.full(ne * 5 // 8, 6.0), np.full(ne * 5 // 8, 3.0)], 1)
+    e2 = np.stack([np.full(ne - ne * 5 // 8, 15.0), u(-6, 6, ne - ne * 5 // 8), np.full(ne - ne * 5 // 8, 3.0)], 1)
+    return np.concatenate(poles + [e1, e2]), surf
+
+
+def sensor_cloud(world_xyz, q, t, rng):
+    """X^-1 of world points as a float32 cloud [n, 4]; the intensity is a non-decreasing ring id (0 .. 15), as a sweep's clouds have it."""
+    qi, ti = inverse(np.asarray(q, np.float64), np.asarray(t, np.float64))
+    p = np.zeros((len(world_xyz), 4), np.float32)
+    if len(world_xyz):
+        p[:, :3] = (qrot(qi, np.asarray(world_xyz, np.float64)) + ti).astype(np.float32)
+        p[:, 3] = np.sort(rng.integers(0, 16, len(world_xyz)))
+    return p
+
+
+__all__ = ["EDGE_ROBUST", "LOOP_OK", "LOOP_NO_CLOUDS", "LOOP_TARGET_TOO_SMALL", "LOOP_TOO_LARGE", "LOOP_SOLVE_FAILED", "target_poses", "target_cloud",
+           "gate", "edge_information", "guess_from_match", "edge_from_result", "room_sample", "sensor_cloud"]

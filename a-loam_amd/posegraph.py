@@ -343,7 +343,10 @@ def anchor_from_localization(j, q_map, t_map, info, seq=0, robust=False):
 
 def loop_from_localization(i, q_place, t_place, j, q_reloc, t_reloc, info, seq=0, robust=False):
     """The sweep of node j was relocalized at (q_reloc, t_reloc) in the frame in which the stored place of node i has the pose
-    (q_place, t_place): the loop edge (i, j) with Z = X_place^-1 o X_reloc."""
+    (q_place, t_place): the loop edge (i, j) with Z = X_place^-1 o X_reloc.  `info` is passed through unchanged: a localization's
+    information is in the LEFT tangent of the relocalized pose, the graph's residual perturbs Z on the right, so this is exact only up to
+    the rotation of Z - harmless for near-isotropic information.  aloam_graph_register_loops (loopreg.edge_information) rotates the matrix,
+    info = T^T info_left T with T = blockdiag(R_Z, R_Z): that matters in a corridor whose weak direction is not the sensor's x axis."""
     qz, tz = relative_pose(q_place, t_place, q_reloc, t_reloc)
     return make_edges(seq, i, j, qz[None], tz[None], np.asarray(info)[None], robust)
 

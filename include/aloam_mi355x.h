@@ -862,6 +862,83 @@ typedef struct aloam_graph_apply_result {     /* 104 bytes                      
 } aloam_graph_apply_result;
 int aloam_graph_apply(aloam_ctx* ctx, const aloam_graph_apply_request* req, int n, aloam_graph_apply_result* dst /* [n] */);
 
+/* ---- loop edges measured on the device: batched keyframe registration -------------------------------------------------------------------
+ * aloam_places_match finds a revisit and aloam_graph_add_edges consumes a loop edge; this section measures it.  One stream-ordered call
+ * registers the clouds of node j against a local target made of the clouds of nodes [first, first + count) of the same sequence and returns
+ * the edge (i, j, Z, info) ready for aloam_graph_add_edges.  It uses neither the atlas nor a sequence slot, touches no live sequence and
+ * does not synchronise the host.  Opt-in and beside the reference: a context that never calls aloam_graph_loops_enable launches exactly
+ * what it launched before.  a-loam_amd/loopreg.py restates the definition in numpy; DESIGN.md §7n.
+ *
+ * For a request (seq, i, j, first, count, pose, guess q, t), every f64 operation separately rounded:
+ *   - X_k is node k's entered pose (q, t) or its estimate (q_opt, t_opt), chosen by pose.  Every target node k gets T_k = X_i^-1 o X_k as
+ *     this header defines a relative pose, q_d = conj(q_i) q_k, t_d = conj(q_i) (t_k - t_i); node i goes through the same arithmetic.
+ *   - per class the points of nodes first .. first + count - 1, in node order, then point order, become associate-to-map(p, T_k) (f64
+ *     rotation and translation, stored to f32, intensity kept); the class's whole target cloud is filtered once with pcl::VoxelGrid (leaf
+ *     mapping_line_resolution / mapping_plane_resolution, always the input-order sum, as in aloam_graph_export_map).  The target lives in
+ *     the frame of node i: its coordinates are tens of metres however far the drive has gone.
+ *   - the gate of src/laserMapping.cpp:554: the filtered corner target must hold more than 10 points and the surf target more than 50,
+ *     else ALOAM_LOOP_TARGET_TOO_SMALL and Z is the guess.
+ *   - the source is node j's two clouds as stored; `parameters` = the guess; then outer_iterations rounds of exactly what
+ *     aloam_mapping_step does between its grid build and transformUpdate (the same kernels): associate-to-map of every source point, the
+ *     five nearest by (f32 distance, index in the filtered target) all closer than 1 m, the line test and the plane fit, and the
+ *     Levenberg-Marquardt solve with lm_max_iterations over LidarEdgeFactor / LidarPlaneNormFactor, HuberLoss(0.1); a FAILURE restores the
+ *     round's entry pose.  These are the REQUEST's options, not the context's.
+ *   - Z = the final `parameters`, the pose of node j in the frame of node i.  One more evaluation of the last round's records at Z gives
+ *     the factor counts, the cost and info_left = J^T J in radians and metres, in the LEFT tangent of aloam_pose_information
+ *     (q <- exp(theta / 2) q, t <- t + dt).
+ *   - the graph's residual perturbs Z on the RIGHT (q_Z exp(phi / 2), t_Z + R_Z tau), so theta = R_Z phi, dt = R_Z tau and
+ *     info = T^T info_left T with T = blockdiag(R_Z, R_Z): that is what an aloam_graph_edge wants.  Both are upper triangles, 21 doubles.
+ * status: ALOAM_LOOP_OK; ALOAM_LOOP_NO_CLOUDS - node j or every target node was kept without clouds; ALOAM_LOOP_TARGET_TOO_SMALL;
+ *   ALOAM_LOOP_TOO_LARGE - the raw target of a class exceeds the enabled capacity (decided on the device, where the counts are);
+ *   ALOAM_LOOP_SOLVE_FAILED - the last round ended in FAILURE or info_left is not positive definite (no factor at all included).  With
+ *   every status but ALOAM_LOOP_OK Z is the guess and info, info_left are zero.  Whether an ALOAM_LOOP_OK edge is a GOOD loop is the
+ *   caller's decision, from the counts, the cost and the information; enter it with ALOAM_GRAPH_EDGE_ROBUST.
+ *
+ * aloam_graph_loops_enable(ctx, max_requests, max_target_corner_points, max_target_surf_points): once per context, after
+ *   aloam_graph_keyframes_enable, else ALOAM_E_STATE.  1 <= max_requests <= 32768, capacities in 1 .. 2^24, else ALOAM_E_ARG; nothing
+ *   stays allocated behind a refusal.  Allocates the scratch of max_requests slots (raw and filtered target, search grid, source copy,
+ *   neighbours, factor records, and a voxel-filter scratch of its own); when the device or the pinned memory for it cannot be had, or the
+ *   runtime refuses an event or the grid kernel's LDS size, it is ALOAM_E_HIP with the cause named by aloam_last_error, and again nothing
+ *   stays allocated.  Every other call of this section is ALOAM_E_STATE before it.
+ * aloam_graph_register_loops: req is host memory, read during the call; everything is checked before anything is queued, ALOAM_E_ARG with
+ *   nothing changed: seq in range; count >= 1 and [first, first + count) inside the sequence's nodes; first <= i < first + count; j a
+ *   node outside [first, first + count); pose 0 or 1; the guess finite and unit to 1e-6 (stored normalised, as aloam_graph_add_edges
+ *   does); outer_iterations >= 1, lm_max_iterations >= 0 (opt NULL = the defaults); dst device memory of the context's device or pinned
+ *   host memory, 8-byte aligned (classified like the exports).  n = 0 is ALOAM_OK.  A sequence, and a (seq, i, j), may be listed more than
+ *   once.  Stream-ordered, no host synchronisation, like aloam_graph_optimize: the requests go through a pinned staging ring, and
+ *   n > max_requests runs in rounds over the same scratch.  dst[r] belongs to req[r]; its bits do not depend on n, on the position in
+ *   the list, on the round or on the other requests.
+ * aloam_graph_loop_export_target (below, with the intermediate arrays): the filtered target of a scratch slot as the last call left it. */
+enum { ALOAM_LOOP_OK = 0, ALOAM_LOOP_NO_CLOUDS = 1, ALOAM_LOOP_TARGET_TOO_SMALL = 2, ALOAM_LOOP_TOO_LARGE = 3, ALOAM_LOOP_SOLVE_FAILED = 4 };
+typedef struct aloam_graph_loop_request {     /* 96 bytes                                                                               */
+  int seq, i, j;                              /* the edge: node j measured in the frame of node i                                       */
+  int first, count;                           /* the target: nodes [first, first + count), i among them, j not                          */
+  int pose;                                   /* ALOAM_GRAPH_POSE_ENTERED or ALOAM_GRAPH_POSE_OPTIMIZED: which poses place the target   */
+  int pad[2];
+  double q[4], t[3];                          /* the guess of Z                                                                         */
+  double reserved;
+} aloam_graph_loop_request;
+typedef struct aloam_graph_loop_options {     /* 8 bytes                                                                                */
+  int outer_iterations;                       /* 2: the reference's mapping value (src/laserMapping.cpp:562)                            */
+  int lm_max_iterations;                      /* 4: the reference's mapping value (:711)                                                */
+} aloam_graph_loop_options;
+typedef struct aloam_graph_loop_result {      /* 448 bytes                                                                              */
+  int status;                                 /* ALOAM_LOOP_OK ..                                                                       */
+  int n_line, n_plane;                        /* factors of the evaluation at Z                                                         */
+  int lm_iterations, lm_termination;          /* of the last round                                                                      */
+  int pad;
+  int target_points[2], target_raw[2];        /* the target after and before the filter: corner, surf                                   */
+  int source_points[2];                       /* node j's clouds                                                                        */
+  double cost;                                /* 1/2 sum rho at Z                                                                       */
+  double q[4], t[3];                          /* Z                                                                                      */
+  double info[21];                            /* the edge's information (right tangent of Z), upper triangle, order (theta_x .. t_z)    */
+  double info_left[21];                       /* the registration's (left tangent, as aloam_pose_information)                           */
+} aloam_graph_loop_result;
+void aloam_graph_loop_default_options(aloam_graph_loop_options* opt);
+int aloam_graph_loops_enable(aloam_ctx* ctx, int max_requests, int max_target_corner_points, int max_target_surf_points);
+int aloam_graph_register_loops(aloam_ctx* ctx, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt,
+                               aloam_graph_loop_result* dst /* [n] */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */
@@ -876,6 +953,10 @@ int aloam_get_correspondences(aloam_ctx* ctx, int seq, float* edges, int cap_edg
  * 256 stack points, stack order inside a tile): lines 9 doubles (cp, a, b), planes 7 doubles (cp, n, d) (src/laserMapping.cpp:618,683).
  * Counts of zero when the gate (:554) was false.  Synchronises. */
 int aloam_get_map_factors(aloam_ctx* ctx, int seq, double* lines, int cap_lines, int* n_lines, double* planes, int cap_planes, int* n_planes);
+/* The filtered target of scratch slot `slot` and class feature_class (0 corner, 1 surf) as the last aloam_graph_register_loops left it
+ * (request r of a call ran in slot r % max_requests).  Stream-ordered; dst_xyzw and count are classified like the exports' destinations;
+ * count is always written, the points only when they fit cap (0 with dst NULL: the size query). */
+int aloam_graph_loop_export_target(aloam_ctx* ctx, int slot, int feature_class, float* dst_xyzw, long long cap, int* count);
 
 /* How the ring ids of the clouds the last aloam_odometry_step searched (laserCloudCornerLast, laserCloudSurfLast of that step) are ordered, as
  * found when their kd-tree stand-ins were built (src/laserOdometry.cpp:567-568): 0 = int(intensity) never decreases with the index; 1 = it decreases, but never by more than 2 below an earlier

@@ -1,0 +1,229 @@
+"""The registration of aloam_graph_register_loops as a numpy model, composed from the oracle's exposed pieces the way relocalize_model.py is
+(oracle_py.knn_search, sym_eigen3, lstsq_5x3, lm_solve, voxel_filter(canonical=True)) plus information.information_from_factors, and the
+hand-made scene the loop-registration tests share.  a-loam_amd/loopreg.py holds the definitions that need no oracle (target, tangent).
+
+oracle_py.lm_solve takes LidarEdgeFactor and LidarPlaneFactor records.  A LidarPlaneNormFactor (n, d), r = n . lp + d, is handed to it as
+the LidarPlaneFactor with j = -d n, l = j - u, m = j - v for an orthonormal pair u x v = n: its normal (j - l) x (j - m) is n up to rounding
+and r = n . (lp - j) = n . lp + d."""
+import importlib
+import math
+
+import numpy as np
+
+import oracle_py
+from relocalize_model import associate_to_map
+
+LEAF = (0.2, 0.4)                                  # launch/aloam_velodyne_VLP_16.launch resolutions: corner, surf
+
+
+def _loopreg():
+    return importlib.import_module("a-loam_amd.loopreg")
+
+
+def voxel_filter(p, leaf):
+    return oracle_py.voxel_filter(p, leaf, canonical=True)
+
+
+# ---- factors ---------------------------------------------------------------------------------------------------------------------------
+def factors(src_corner, src_surf, tgt_corner, tgt_surf, par):
+    """(lines [n, 9] (cp, a, b), planes [m, 7] (cp, n, d)) of one round at the pose par = (q, t): what k_map_search / k_map_fit record, in
+    stack order.  The five nearest by (f32 distance, index), all closer than 1 m; vals[2] > 3 vals[1] and the +-0.1 points; the 5 x 3 plane
+    fit with the 0.2 test."""
+    lines, planes = [], []
+    if len(src_corner) and len(tgt_corner):
+        idx, d2 = oracle_py.knn_search(tgt_corner, associate_to_map(src_corner, par), 5)
+        for i in np.nonzero((idx[:, 4] >= 0) & (d2[:, 4] < np.float32(1.0)))[0]:
+            near = tgt_corner[idx[i], :3].astype(np.float64)
+            c = np.zeros(3)
+            for j in range(5):
+                c = c + near[j]
+            c = c / 5.0
+            cov = np.zeros((3, 3))
+            for j in range(5):
+                z = near[j] - c
+                cov = cov + np.outer(z, z)
+            vals, vecs = oracle_py.sym_eigen3(cov)
+            if vals[2] > 3 * vals[1]:
+                d = vecs[:, 2]
+                lines.append(np.concatenate([src_corner[i, :3].astype(np.float64), 0.1 * d + c, -0.1 * d + c]))
+    if len(src_surf) and len(tgt_surf):
+        idx, d2 = oracle_py.knn_search(tgt_surf, associate_to_map(src_surf, par), 5)
+        for i in np.nonzero((idx[:, 4] >= 0) & (d2[:, 4] < np.float32(1.0)))[0]:
+            near = tgt_surf[idx[i], :3].astype(np.float64)
+            x = oracle_py.lstsq_5x3(near, -np.ones(5))
+            ln = math.sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2])
+            if not ln > 0.0:
+                continue
+            d, n = 1 / ln, x / ln
+            if all(abs(n[0] * p[0] + n[1] * p[1] + n[2] * p[2] + d) <= 0.2 for p in near):
+                planes.append(np.concatenate([src_surf[i, :3].astype(np.float64), n, [d]]))
+    return np.array(lines).reshape(-1, 9), np.array(planes).reshape(-1, 7)
+
+
+def planes_as_point_factors(planes):
+    """[m, 7] (cp, n, d) -> [m, 12] (cp, j, l, m) LidarPlaneFactor records with the same residual (see the module docstring)."""
+    out = np.zeros((len(planes), 12))
+    for k, p in enumerate(planes):
+        n, d = p[3:6], p[6]
+        a = np.zeros(3)
+        a[int(np.argmin(np.abs(n)))] = 1.0
+        u = np.cross(n, a)
+        u = u / np.linalg.norm(u)
+        v = np.cross(n, u)
+        j = -d * n
+        out[k] = np.concatenate([p[:3], j, j - u, j - v])
+    return out
+
+
+def register(tgt_corner, tgt_surf, src_corner, src_surf, q_guess, t_guess, outer_iterations=2, lm_max_iterations=4):
+    """The model of one request behind its target: a dict with the fields of aloam_graph_loop_result (info and info_left as [6, 6]) and
+    `factors`, the last round's records."""
+    L, information = _loopreg(), importlib.import_module("a-loam_amd.information")
+    tgt_corner, tgt_surf = np.ascontiguousarray(tgt_corner, np.float32), np.ascontiguousarray(tgt_surf, np.float32)
+    src_corner, src_surf = np.asarray(src_corner, np.float32).reshape(-1, 4), np.asarray(src_surf, np.float32).reshape(-1, 4)
+    q0 = np.asarray(q_guess, np.float64) / np.linalg.norm(np.asarray(q_guess, np.float64))
+    t0 = np.asarray(t_guess, np.float64)
+    out = {"status": L.LOOP_OK, "n_line": 0, "n_plane": 0, "lm_iterations": 0, "lm_termination": 0, "cost": 0.0, "q": q0, "t": t0,
+           "info": np.zeros((6, 6)), "info_left": np.zeros((6, 6)), "target_points": (len(tgt_corner), len(tgt_surf)),
+           "source_points": (len(src_corner), len(src_surf)), "factors": (np.zeros((0, 9)), np.zeros((0, 7)))}
+    if len(src_corner) + len(src_surf) == 0 or len(tgt_corner) + len(tgt_surf) == 0:
+        out["status"] = L.LOOP_NO_CLOUDS
+        return out
+    if not L.gate(tgt_corner, tgt_surf):
+        out["status"] = L.LOOP_TARGET_TOO_SMALL
+        return out
+    q, t = q0.copy(), t0.copy()
+    for _ in range(outer_iterations):
+        out["par_last"] = np.concatenate([q, t])                                  # the pose the last round associated at
+        lines, planes = factors(src_corner, src_surf, tgt_corner, tgt_surf, np.concatenate([q, t]))
+        qn, tn, sm = oracle_py.lm_solve(lines, planes_as_point_factors(planes), q, t, max_iterations=lm_max_iterations)
+        if sm["termination"] != 5:                                                # a FAILURE restores the round's entry pose
+            q, t = qn, tn
+    rec = information.information_from_factors(lines, planes, q, t)
+    out.update(n_line=len(lines), n_plane=len(planes), lm_iterations=sm["iterations"], lm_termination=sm["termination"], cost=rec["cost"], factors=(lines, planes))
+    pd = len(lines) + len(planes) > 0
+    if pd:
+        try:
+            np.linalg.cholesky(rec["info"])
+        except np.linalg.LinAlgError:
+            pd = False
+    if sm["termination"] == 5 or not pd:
+        out["status"] = L.LOOP_SOLVE_FAILED
+        return out
+    out.update(q=q, t=t, info_left=rec["info"], info=L.edge_information(rec["info"], q))
+    return out
+
+
+def factor_bounds(src_corner, src_surf, tgt_corner, tgt_surf, par):
+    """(lower, upper) of n_line + n_plane at the pose par, in the manner of relocalize_model.factor_bounds (numpy's batched fits; the points
+    whose test quantity lies within 1e-9 of its threshold count in `upper` only)."""
+    import relocalize_model
+    lo, hi, _ = relocalize_model.factor_bounds(np.asarray(src_corner, np.float32), np.asarray(src_surf, np.float32), np.ascontiguousarray(tgt_corner, np.float32),
+                                               np.ascontiguousarray(tgt_surf, np.float32), par)
+    return lo, hi
+
+
+# ---- the scene -------------------------------------------------------------------------------------------------------------------------
+def quat_z(yaw, tilt=0.0):
+    """Unit quaternion (x, y, z, w): yaw about z, then a tilt about the (rotated) x axis."""
+    h, k = 0.5 * yaw, 0.5 * tilt
+    qz, qx = np.array([0.0, 0.0, math.sin(h), math.cos(h)]), np.array([math.sin(k), 0.0, 0.0, math.cos(k)])
+    P = importlib.import_module("a-loam_amd.posegraph")
+    q = P.qmul(qz, qx)
+    return q / np.linalg.norm(q)
+
+
+def world_sample(rng, n_corner=300, n_surf=1500, kind="room", noise=0.0, axis_yaw=0.0):
+    """A random sample of the scene in world coordinates, float64 (corner [n, 3], surf [m, 3]).
+    room:     loopreg.room_sample: a floor (x -5 .. 15, y -6 .. 6), two perpendicular walls (y = 6 and x = 15, 3 m high), four vertical poles and two horizontal
+              edges (the walls' top edges); about 0.5 m between surf samples of one keyframe, 0.15 m along the lines
+    floor:    the floor alone, no corner feature
+    corridor: the floor and two PARALLEL walls (y = +-3), edges only along the axis, and a sparse end wall (n_surf / 40 points) that keeps
+              the information positive definite; the whole scene turned by axis_yaw about z"""
+    u = rng.uniform
+    if kind == "floor":
+        surf = np.stack([u(-5, 15, n_surf), u(-6, 6, n_surf), np.zeros(n_surf)], 1)
+        corner = np.zeros((0, 3))
+    elif kind == "corridor":
+        nf = n_surf // 2
+        nw = (n_surf - nf) // 2
+        floor = np.stack([u(-5, 15, nf), u(-3, 3, nf), np.zeros(nf)], 1)
+        w1 = np.stack([u(-5, 15, nw), np.full(nw, 3.0), u(0, 3, nw)], 1)
+        w2 = np.stack([u(-5, 15, n_surf - nf - nw), np.full(n_surf - nf - nw, -3.0), u(0, 3, n_surf - nf - nw)], 1)
+        ne = max(n_surf // 40, 8)                                                 # a sparse end wall: the axis is weak, not unconstrained
+        end = np.stack([np.full(ne, 15.0), u(-3, 3, ne), u(0, 3, ne)], 1)
+        surf = np.concatenate([floor, w1, w2, end])
+        h = n_corner // 2
+        corner = np.concatenate([np.stack([u(-5, 15, h), np.full(h, 3.0), np.full(h, 3.0)], 1),
+                                 np.stack([u(-5, 15, n_corner - h), np.full(n_corner - h, -3.0), np.full(n_corner - h, 3.0)], 1)])
+    else:
+        corner, surf = _loopreg().room_sample(rng, n_corner, n_surf)
+    if noise:
+        corner, surf = corner + rng.normal(0.0, noise, corner.shape), surf + rng.normal(0.0, noise, surf.shape)
+    if axis_yaw:
+        c, s = math.cos(axis_yaw), math.sin(axis_yaw)
+        Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+        corner, surf = corner @ Rz.T, surf @ Rz.T
+    return corner, surf
+
+
+def sensor_cloud(world_xyz, q, t, rng):
+    return _loopreg().sensor_cloud(world_xyz, q, t, rng)
+
+
+def drive(n_target=9, length=8.0, yaw=0.05):
+    """True poses of the target nodes along `length` metres (a gentle yaw and tilt, sensor 1.2 m above the floor), then the source node,
+    which revisits the middle of the stretch turned by 0.3 rad."""
+    q, t = [], []
+    for k in range(n_target):
+        s = k / max(n_target - 1, 1)
+        q.append(quat_z(yaw * (k - n_target // 2), 0.01 * k))
+        t.append(np.array([length * s, 0.3 * math.sin(2.0 * s), 1.2]))
+    q.append(quat_z(0.3, -0.02))
+    t.append(np.array([0.5 * length + 0.35, -0.4, 1.25]))
+    return np.array(q), np.array(t)
+
+
+def drifted(q, t, dt=(0.3, -0.25, 0.08), dyaw=math.radians(4.0)):
+    """The entered pose of the source node: the true one moved by about 0.4 m and turned by 4 degrees."""
+    P = importlib.import_module("a-loam_amd.posegraph")
+    qd = P.qmul(quat_z(dyaw, 0.01), q)
+    return qd / np.linalg.norm(qd), np.asarray(t, np.float64) + np.asarray(dt)
+
+
+def pose_error(q, t, q_true, t_true):
+    """(rotation angle [rad], translation distance [m]) between two poses."""
+    P = importlib.import_module("a-loam_amd.posegraph")
+    e = P.qmul(P.qconj(q_true), np.asarray(q, np.float64) / np.linalg.norm(q))
+    return 2.0 * math.atan2(float(np.linalg.norm(e[:3])), abs(float(e[3]))), float(np.linalg.norm(np.asarray(t) - np.asarray(t_true)))
+
+
+def fixture(seed=7, noise=0.0, kind="room", n_target=9, n_corner=300, n_surf=1500, axis_yaw=0.0):
+    """Ten keyframes of the scene: q_true / t_true, the entered poses q / t (the targets' are the true ones, the source's is drifted), and
+    raw[k] = (corner, surf), node k's own random sample of the scene seen from its TRUE pose (what is fed to the mapping step; the
+    node's clouds are the voxel filter of it).  axis_yaw turns the scene and the path about z and leaves the sensors' headings alone."""
+    rng = np.random.default_rng(seed)
+    q_true, t_true = drive(n_target)
+    if axis_yaw:                                     # the scene and the PATH turn with the axis, the headings do not: every node looks
+        P = importlib.import_module("a-loam_amd.posegraph")   # along the world's x, so the axis lies axis_yaw off its own x axis
+        t_true = np.array([P.qrot(quat_z(axis_yaw), t) for t in t_true])
+    q, t = q_true.copy(), t_true.copy()
+    q[-1], t[-1] = drifted(q_true[-1], t_true[-1])
+    raw = []
+    for k in range(len(q_true)):
+        c, f = world_sample(rng, n_corner, n_surf, kind, noise, axis_yaw)
+        raw.append((sensor_cloud(c, q_true[k], t_true[k], rng), sensor_cloud(f, q_true[k], t_true[k], rng)))
+    return {"q_true": q_true, "t_true": t_true, "q": q, "t": t, "raw": raw, "i": n_target // 2, "j": n_target, "first": 0, "count": n_target}
+
+
+def keyframe_clouds(fx):
+    """The nodes' clouds as the mapping step leaves them in its stacks: each raw cloud through the class's voxel filter."""
+    return [(voxel_filter(c, LEAF[0]) if len(c) else c, voxel_filter(f, LEAF[1]) if len(f) else f) for c, f in fx["raw"]]
+
+
+def request_of(fx, pose_q=None, pose_t=None):
+    """(guess, truth) of Z for the fixture's request: X_i^-1 o X_j at the entered and at the true poses."""
+    P = importlib.import_module("a-loam_amd.posegraph")
+    q, t = (fx["q"], fx["t"]) if pose_q is None else (pose_q, pose_t)
+    i, j = fx["i"], fx["j"]
+    return P.relative_pose(q[i], t[i], q[j], t[j]), P.relative_pose(fx["q_true"][i], fx["t_true"][i], fx["q_true"][j], fx["t_true"][j])

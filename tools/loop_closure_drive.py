@@ -1,7 +1,7 @@
 """tools/loop_closure_drive.py — a loop closure inside one drive, with nothing but calls the project already has ("A loop
 edge inside a drive").
 
-    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply]
+    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -13,6 +13,11 @@ node with its clouds) and a place every few metres.  At the last keyframe:
   5. aloam_graph_export_map of all nodes at the entered and at the optimised poses.
 Printed against ground truth: the loop edge's error, ATE before and after the solve, tiles and points of the two maps.  One JSON object; a
 step that fails is named with what was known by then.
+
+With --device-loops the edge is also measured by the one-call route, aloam_graph_register_loops: node j against the same nodes around the
+matched keyframe, in the frame of node i, the guess from the match's yaw shift (loopreg.guess_from_match).  It is printed as
+device_loop_edge beside loop_edge, with its error against ground truth, its wall time, and the wall time of steps 2 and 3 it replaces
+(spare_slot_route_ms).  The edge that goes into the graph is still the spare-slot route's: the default path is unchanged.
 
 With --apply the whole chain runs twice, and both runs drive on for another quarter lap behind the solve: one after aloam_graph_apply of
 all nodes (pose and map), one without it.  Reported for each, without judging them: the ATE of the live map pose over the continued sweeps,
@@ -26,6 +31,7 @@ import json
 import math
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--neighbours", type=int, default=6, help="keyframes either side of the matched one that make the local atlas")
     ap.add_argument("--frozen-steps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--device-loops", action="store_true", help="also measure the edge with aloam_graph_register_loops from the same match, and print it beside the spare-slot route's")
     ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
     args = ap.parse_args()
 
@@ -96,6 +103,8 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
     gpu.graph_enable(n_key + 4, n_key + 8)
     gpu.graph_keyframes_enable(n_key * 2048, n_key * 16384)
     gpu.places_enable(n_key + 4, max_range=40.0, sensor_height=syn.SENSOR_HEIGHT)
+    if args.device_loops:
+        gpu.graph_loops_enable(1, (2 * args.neighbours + 1) * 2048, (2 * args.neighbours + 1) * 16384)
     info = np.diag([1.0 / 5e-3 ** 2] * 3 + [1.0 / 5e-2 ** 2] * 3)
     out = {"frames": frames, "keyframes": 0, "radius": args.radius, "step": args.step}
     key_frames = []
@@ -127,6 +136,21 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
         stage = "graph_export_map (local)"
         lo, hi = max(0, i - args.neighbours), min(j - args.gap, i + args.neighbours + 1)
         req = [(0, lo, hi - lo, binding.GRAPH_POSE_OPTIMIZED)]
+        if args.device_loops:
+            # the one-call route: node j against nodes lo .. hi - 1 in the frame of node i, the guess from the match's yaw shift
+            stage = "graph_register_loops"
+            lr = importlib.import_module("a-loam_amd.loopreg")
+            qg, tg = lr.guess_from_match(nodes["q_opt"][i], nodes["t_opt"][i], nodes["q_opt"][i], nodes["t_opt"][i], int(m["shift"]), nodes["q_opt"][j], nodes["t_opt"][j])
+            t0 = time.perf_counter()
+            r = gpu.graph_register_loops([(0, i, j, lo, hi - lo, binding.GRAPH_POSE_OPTIMIZED, qg, tg)])[0]
+            call_ms = 1e3 * (time.perf_counter() - t0)
+            qz, tz = pg.relative_pose(truth_q[i], truth_t[i], truth_q[j], truth_t[j])
+            dq = pg.qmul(pg.qconj(qz), r["q"])
+            out["device_loop_edge"] = {"status": int(r["status"]), "n_line": int(r["n_line"]), "n_plane": int(r["n_plane"]), "target_points": r["target_points"].tolist(),
+                                       "cost": float(r["cost"]), "guess_error_m": float(np.linalg.norm(tg - tz)), "translation_error_m": float(np.linalg.norm(r["t"] - tz)),
+                                       "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dq[:3]))))), "call_and_synchronize_ms": call_ms}
+            stage = "graph_export_map (local)"
+            t_spare = time.perf_counter()
         off = torch.zeros(4, dtype=torch.int64, pin_memory=True)
         gpu.graph_export_map_into(req, 0, 0, 0, 0, off.data_ptr())
         gpu.synchronize()
@@ -159,6 +183,8 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
         gpu.synchronize()
         mp = gpu.map_pose(1)
         pi = gpu.export_pose_information(binding.INFO_MAPPING, [1])[0]
+        if args.device_loops:
+            out["spare_slot_route_ms"] = 1e3 * (time.perf_counter() - t_spare)
         out["localization"] = {"status": int(pi["status"]), "n_line": int(pi["n_line"]), "n_plane": int(pi["n_plane"]),
                                "error_m": float(np.linalg.norm(mp["t_w"] - truth_t[j])), "drive_error_m": float(np.linalg.norm(nodes["t_opt"][j] - truth_t[j]))}
         gpu.atlas_attach(None)
