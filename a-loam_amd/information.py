@@ -111,7 +111,9 @@ def factor_rows(lines, planes, q, t, s=None):
         r_plane = np.einsum("ij,ij->i", lp - j, n)
     else:                                                                     # LidarPlaneNormFactor: r = n . lp + d
         n = P[:, 3:6]
-        r_plane = np.einsum("ij,ij->i", lp, n) + P[:, 6]
+        # every product and sum rounded on its own, in the order of map_evaluate (mapping_solve_device.hpp): at a converged pose r is a difference of terms ten orders above it,
+        # and another summation order (einsum's is not defined) moves a cost of 1e-23 by 1e-4 of itself
+        r_plane = ((n[:, 0] * lp[:, 0] + n[:, 1] * lp[:, 1]) + n[:, 2] * lp[:, 2]) + P[:, 6]
     J_plane = np.einsum("ij,ijk->ik", n, D)
     return r_line, J_line, r_plane, J_plane
 
@@ -151,20 +153,34 @@ def _eigen(m):
 
 
 def _schur(a, c, d):
-    """d - c^T a^-1 c through the Cholesky factor of a; None when a pivot does not exceed PIVOT_TOL times its diagonal entry."""
+    """d - c^T a^-1 c through the Cholesky factor of a; None when a pivot does not exceed PIVOT_TOL times its diagonal entry.  Operation by
+    operation as schur3 of information_device.hpp does it (a = L L^T with the products subtracted one by one, Y = L^-1 c by forward substitution, M_ij = d_ij -
+    ((Y_0i Y_0j + Y_1i Y_1j) + Y_2i Y_2j) on the upper triangle, mirrored): where the complement cancels completely - a matrix of rank <= 3
+    whose block `a` is still positive definite - what is left is the rounding of these very operations, and only the same operations give it."""
     L = np.zeros((3, 3))
     for i in range(3):
         for j in range(i + 1):
-            v = a[i, j] - np.dot(L[i, :j], L[j, :j])
+            v = float(a[i, j])
+            for k in range(j):
+                v -= L[i, k] * L[j, k]
             if i == j:
                 if not v > PIVOT_TOL * a[i, i]:
                     return None
                 L[i, i] = np.sqrt(v)
             else:
                 L[i, j] = v / L[j, j]
-    y = np.linalg.solve(L, c)
-    m = d - y.T @ y
-    return 0.5 * (m + m.T)
+    y = np.zeros((3, 3))
+    for col in range(3):
+        for i in range(3):
+            v = float(c[i, col])
+            for k in range(i):
+                v -= L[i, k] * y[k, col]
+            y[i, col] = v / L[i, i]
+    m = np.zeros((3, 3))
+    for i in range(3):
+        for j in range(i, 3):
+            m[i, j] = m[j, i] = d[i, j] - ((y[0, i] * y[0, j] + y[1, i] * y[1, j]) + y[2, i] * y[2, j])
+    return m
 
 
 def decompose(info):

@@ -147,6 +147,7 @@ int mapping_step(const orc_config& cfg, MapState* st, const double q_wodom[4], c
   voxel_filter(surf_last, st->plane_res, canonical, &st->surf_stack);
   st->corner_num[0] = st->corner_num[1] = st->surf_num[0] = st->surf_num[1] = 0;
   st->lm[0] = st->lm[1] = LmSummary();
+  st->lm[0].termination = st->lm[1].termination = 4;   // no solve below the gate (:554): "no residuals", what the device's record says there (a solve overwrites it)
   st->edges.clear(); st->norms.clear();
 
   if (st->from_map_corner > 10 && st->from_map_surf > 50) {                          // :554

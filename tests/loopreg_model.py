@@ -75,9 +75,33 @@ def planes_as_point_factors(planes):
     return out
 
 
-def register(tgt_corner, tgt_surf, src_corner, src_surf, q_guess, t_guess, outer_iterations=2, lm_max_iterations=4):
-    """The model of one request behind its target: a dict with the fields of aloam_graph_loop_result (info and info_left as [6, 6]) and
-    `factors`, the last round's records."""
+def positive_definite(H):
+    """The rule of k_loop_result and of information.decompose: a Cholesky factorisation in which every pivot exceeds information.PIVOT_TOL
+    times its diagonal entry.  (np.linalg.cholesky accepts any pivot above zero: a rank-deficient matrix whose zero pivot rounds to +1e-17
+    would pass it.)"""
+    tol = importlib.import_module("a-loam_amd.information").PIVOT_TOL
+    H = np.asarray(H, np.float64)
+    n = len(H)
+    Lc = np.zeros((n, n))
+    for i in range(n):
+        for j in range(i + 1):
+            v = H[i, j]
+            for k in range(j):
+                v -= Lc[i, k] * Lc[j, k]
+            if i == j:
+                if not v > tol * H[i, i]:
+                    return False
+                Lc[i, i] = math.sqrt(v)
+            else:
+                Lc[i, j] = v / Lc[j, j]
+    return True
+
+
+def register(tgt_corner, tgt_surf, src_corner, src_surf, q_guess, t_guess, outer_iterations=2, lm_max_iterations=4, analytic=False, reverse=False):
+    """The model of one request behind its target: a dict with the fields of aloam_graph_loop_result (info and info_left as [6, 6]),
+    `factors`, the last round's records, and `rounds`, every round's (n_line, n_plane, lm_solve summary, records, entry pose).  analytic: the
+    oracle's closed-form Jacobians instead of its dual numbers; reverse: the records handed to lm_solve last to first (another summation
+    order of the same problem)."""
     L, information = _loopreg(), importlib.import_module("a-loam_amd.information")
     tgt_corner, tgt_surf = np.ascontiguousarray(tgt_corner, np.float32), np.ascontiguousarray(tgt_surf, np.float32)
     src_corner, src_surf = np.asarray(src_corner, np.float32).reshape(-1, 4), np.asarray(src_surf, np.float32).reshape(-1, 4)
@@ -93,20 +117,18 @@ def register(tgt_corner, tgt_surf, src_corner, src_surf, q_guess, t_guess, outer
         out["status"] = L.LOOP_TARGET_TOO_SMALL
         return out
     q, t = q0.copy(), t0.copy()
+    out["rounds"] = []
+    step = -1 if reverse else 1
     for _ in range(outer_iterations):
         out["par_last"] = np.concatenate([q, t])                                  # the pose the last round associated at
         lines, planes = factors(src_corner, src_surf, tgt_corner, tgt_surf, np.concatenate([q, t]))
-        qn, tn, sm = oracle_py.lm_solve(lines, planes_as_point_factors(planes), q, t, max_iterations=lm_max_iterations)
+        qn, tn, sm = oracle_py.lm_solve(lines[::step], planes_as_point_factors(planes)[::step], q, t, max_iterations=lm_max_iterations, analytic=analytic)
+        out["rounds"].append({"n_line": len(lines), "n_plane": len(planes), "summary": sm, "factors": (lines, planes), "entry": out["par_last"]})
         if sm["termination"] != 5:                                                # a FAILURE restores the round's entry pose
             q, t = qn, tn
     rec = information.information_from_factors(lines, planes, q, t)
     out.update(n_line=len(lines), n_plane=len(planes), lm_iterations=sm["iterations"], lm_termination=sm["termination"], cost=rec["cost"], factors=(lines, planes))
-    pd = len(lines) + len(planes) > 0
-    if pd:
-        try:
-            np.linalg.cholesky(rec["info"])
-        except np.linalg.LinAlgError:
-            pd = False
+    pd = len(lines) + len(planes) > 0 and positive_definite(rec["info"])
     if sm["termination"] == 5 or not pd:
         out["status"] = L.LOOP_SOLVE_FAILED
         return out

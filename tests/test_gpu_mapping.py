@@ -21,6 +21,7 @@ from conftest import bits_equal, quat_angle
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MAP_GOLDENS = sorted(glob.glob(os.path.join(GOLDEN, "refmap_*.npz")))
+LM_KEYS = ("lm_iterations0", "lm_iterations1", "termination0")          # the solver's summary of the two solves, as far as the ABI shows it
 
 
 def _frames(g):
@@ -52,7 +53,7 @@ def test_mapping_matches_oracle_and_reference_code(O, binding, path):
         pg = gpu.mapping_step_inputs(q, t, c, s, f)
         gpu.synchronize()
         io, ig = orc.map_info(), gpu.map_info()
-        for key in ("cenW", "cenH", "cenD", "from_map_corner", "from_map_surf", "corner_stack", "surf_stack", "corner_num0", "corner_num1", "surf_num0", "surf_num1"):
+        for key in ("cenW", "cenH", "cenD", "from_map_corner", "from_map_surf", "corner_stack", "surf_stack", "corner_num0", "corner_num1", "surf_num0", "surf_num1") + LM_KEYS:
             assert io[key] == ig[key], (path, k, key, io, ig)
         assert bits_equal(orc.map_cloud(O.MAP_CORNER_STACK), gpu.map_cloud(binding.MAP_CORNER_STACK)), (path, k)
         assert bits_equal(orc.map_cloud(O.MAP_SURF_STACK), gpu.map_cloud(binding.MAP_SURF_STACK)), (path, k)
@@ -128,7 +129,7 @@ def test_full_pipeline_registration_odometry_mapping(O, binding, sequence, name,
         for key in ("q_w", "t_w", "q_wmap_wodom", "t_wmap_wodom"):
             assert np.abs(pm[key] - mg[key]).max() < 1e-8, (name, k, key, pm[key], mg[key])
         io, ig = orc.map_info(), gpu.map_info()
-        for key in ("from_map_corner", "from_map_surf", "corner_stack", "surf_stack", "corner_num1", "surf_num1"):
+        for key in ("from_map_corner", "from_map_surf", "corner_stack", "surf_stack", "corner_num1", "surf_num1") + LM_KEYS:
             assert io[key] == ig[key], (name, k, key, io, ig)
         for cls in (0, 1):
             _compare_maps(gpu.map_cubes(cls), orc.map_cubes(cls), (name, k, cls), exact=False)
@@ -178,6 +179,9 @@ def test_full_size_mapping_batch(O, binding, syn):
             mg = gpu.map_pose(b)
             for key in ("q_w", "t_w", "q_wmap_wodom", "t_wmap_wodom"):
                 assert np.abs(pm[key] - mg[key]).max() < 1e-8, (b, k, key)
+            io, ig = orc.map_info(), gpu.map_info(b)
+            for key in LM_KEYS:
+                assert io[key] == ig[key], (b, k, key, io, ig)
             for cls in (0, 1):
                 _compare_maps(gpu.map_cubes(cls, b), orc.map_cubes(cls), (b, k, cls), exact=False)
         for b in range(B):
