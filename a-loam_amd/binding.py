@@ -127,6 +127,22 @@ class AloamGraphLoopResult(C.Structure):
                 ("q", C.c_double * 4), ("t", C.c_double * 3), ("info", C.c_double * 21), ("info_left", C.c_double * 21)]
 
 
+class AloamGraphMarginalRequest(C.Structure):
+    """A candidate edge whose residual covariance and chi-square are wanted (aloam_graph_marginal_request, 248 bytes)."""
+    _fields_ = [("edge", AloamGraphEdge), ("mode", C.c_int), ("pad", C.c_int)]
+
+
+class AloamGraphMarginalOptions(C.Structure):
+    _fields_ = [("pcg_max_iterations", C.c_int), ("pad", C.c_int), ("pcg_tolerance", C.c_double), ("huber_delta", C.c_double)]
+
+
+class AloamGraphMarginalResult(C.Structure):
+    """Sigma_r, s_edge and chi2 of one request (aloam_graph_marginal_result, 440 bytes); a-loam_amd/posegraph.py marginals() holds the definitions."""
+    _fields_ = [("status", C.c_int), ("mode", C.c_int), ("seq", C.c_int), ("i", C.c_int), ("j", C.c_int), ("pcg_iterations", C.c_int), ("nodes", C.c_int),
+                ("edges", C.c_int), ("chi2", C.c_double), ("s_edge", C.c_double), ("r", C.c_double * 6), ("q", C.c_double * 4), ("t", C.c_double * 3),
+                ("cov", C.c_double * 36)]
+
+
 LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
 GRAPH_LOOP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32),
                                      ("pad", np.int32, 2), ("q", np.float64, 4), ("t", np.float64, 3), ("reserved", np.float64)])
@@ -152,6 +168,13 @@ GRAPH_EDGE_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32)
 GRAPH_RESULT_DTYPE = np.dtype([("status", np.int32), ("termination", np.int32), ("lm_iterations", np.int32), ("accepted_steps", np.int32),
                                ("pcg_iterations", np.int32), ("nodes", np.int32), ("edges", np.int32), ("pad", np.int32),
                                ("initial_cost", np.float64), ("final_cost", np.float64), ("gradient_max", np.float64), ("reserved", np.float64)])
+GRAPH_MARGINAL_MEASURED, GRAPH_MARGINAL_AT_ESTIMATE = 0, 1
+GRAPH_MARGINAL_OK, GRAPH_MARGINAL_NO_EDGES, GRAPH_MARGINAL_NOT_CONVERGED, GRAPH_MARGINAL_FAILED = 0, 1, 2, 3
+GRAPH_MARGINAL_REQUEST_DTYPE = np.dtype([("edge", GRAPH_EDGE_DTYPE), ("mode", np.int32), ("pad", np.int32)])
+GRAPH_MARGINAL_RESULT_DTYPE = np.dtype([("status", np.int32), ("mode", np.int32), ("seq", np.int32), ("i", np.int32), ("j", np.int32),
+                                        ("pcg_iterations", np.int32), ("nodes", np.int32), ("edges", np.int32), ("chi2", np.float64),
+                                        ("s_edge", np.float64), ("r", np.float64, 6), ("q", np.float64, 4), ("t", np.float64, 3),
+                                        ("cov", np.float64, (6, 6))])
 
 
 class AloamMapCorrection(C.Structure):
@@ -360,6 +383,8 @@ def lib():
         L.aloam_graph_loops_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.aloam_graph_register_loops.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopOptions), vp]
         L.aloam_graph_loop_export_target.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, vp]
+        L.aloam_graph_marginal_default_options.argtypes = [C.POINTER(AloamGraphMarginalOptions)]; L.aloam_graph_marginal_default_options.restype = None
+        L.aloam_graph_marginals.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphMarginalOptions), vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -940,6 +965,34 @@ class Aloam:
         self._check(lib().aloam_graph_loop_export_target(self.h, int(slot), int(feature_class), C.c_void_p(pts.data_ptr()), n, C.c_void_p(cnt.data_ptr())))
         self.synchronize()
         return pts.numpy()[:n].copy()
+
+    # ---- pose-graph marginals (posegraph.marginals holds the definition) -------------------------------------------------------------------
+    def graph_marginal_options(self, **kw):
+        o = AloamGraphMarginalOptions()
+        lib().aloam_graph_marginal_default_options(C.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def graph_marginals_into(self, requests, dst_ptr, options=None):
+        """Queue the marginals of each request (a structured array of GRAPH_MARGINAL_REQUEST_DTYPE, posegraph.marginal_request builds one; no
+        host synchronisation): dst_ptr receives one aloam_graph_marginal_result per request, device memory or pinned host memory."""
+        r = np.ascontiguousarray(requests, dtype=GRAPH_MARGINAL_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_marginals(self.h, _p(r) if len(r) else None, len(r), C.byref(options) if options is not None else None,
+                                                C.c_void_p(dst_ptr) if dst_ptr else None))
+
+    def graph_marginals(self, requests, options=None, pinned=True):
+        """Compute and wait: a structured array [len(requests)] of GRAPH_MARGINAL_RESULT_DTYPE.  options: None (the defaults), an
+        AloamGraphMarginalOptions, or a dict of its fields."""
+        import torch
+        if isinstance(options, dict):
+            options = self.graph_marginal_options(**options)
+        n, size = len(requests), GRAPH_MARGINAL_RESULT_DTYPE.itemsize
+        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_marginals_into(requests, buf.data_ptr(), options)
+        self.synchronize()
+        return buf.cpu().numpy()[:n * size].view(GRAPH_MARGINAL_RESULT_DTYPE).copy()
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

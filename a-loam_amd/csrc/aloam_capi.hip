@@ -395,6 +395,10 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
     }
     // the last aloam_graph_optimize: nodes and edges read once, the estimates and one result written (the iterations run out of L2)
     if (kernel == K_POSE_GRAPH) bytes = (double)(sizeof(aloam_graph_node) + 56) * c->pg_last_nodes + (double)sizeof(aloam_graph_edge) * c->pg_last_edges;
+    // the last aloam_graph_marginals: per request its graph's estimates and edges read once, one request read and one result written (the
+    // linearisation and the iterations run out of the request's scratch row)
+    if (kernel == K_GRAPH_MARGINALS)
+      bytes = 56.0 * c->mg_last_nodes + (double)sizeof(aloam_graph_edge) * c->mg_last_edges + (double)(sizeof(GraphMarginalItem) + sizeof(aloam_graph_marginal_result)) * c->mg_last_n;
     // the last aloam_graph_export_map: 16 B read + 16 B written per raw point (transform), the slot written and read and the point read and
     // written again (grouping, 40 B), 16 B per emitted point and 32 B per tile
     if (kernel == K_GRAPH_MAP && c->gm_last_segs >= 0) {

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include "export_kernels.hpp"
 #include "graphapply_kernels.hpp"
 #include "graphmap_kernels.hpp"
+#include "graphmarginal_kernels.hpp"
 #include "loopreg_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -32,11 +33,11 @@ using namespace aloam;
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
-                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_GRAPH_MAP, K_LOOP_REGISTER, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
+                K_MAP_VOXEL_CUBES, K_MAP_REGISTER, K_GRAPH_MARGINALS, K_EXPORT, K_POSE_INFO, K_POSE_GRAPH, K_GRAPH_MAP, K_LOOP_REGISTER, K_SAVE, K_LOAD, K_SCORE, K_APPLY, K_COUNT };
 const char* const kKernelNames[] = {"k_find_ends", "k_front", "k_ring_starts", "k_dense_cloud", "k_ring_features",
                                     "k_build_grids", "k_transform_queries", "k_associate[corner]", "k_associate[plane]",
                                     "k_solve", "k_advance", "map_begin", "map_voxel[stacks]", "map_grid", "map_associate", "map_solve",
-                                    "map_insert", "map_voxel[cubes]", "map_register", "export_clouds", "pose_information", "pose_graph", "graph_map", "loop_register", "save_sequences",
+                                    "map_insert", "map_voxel[cubes]", "map_register", "graph_marginals", "export_clouds", "pose_information", "pose_graph", "graph_map", "loop_register", "save_sequences",
                                     "load_sequences", "score_corrections", "apply_corrections"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per KernelId, in the same order");
 struct ProfRec { int kernel; hipEvent_t e0, e1; };
@@ -111,6 +112,7 @@ struct aloam_ctx {
   Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
   Event pg_stage_done[kGraphStageSlots];   // pose graphs: the copy that read a slot of h_pg_stage has run
   Event lr_stage_done[kLoopStageSlots];    // loop registration: the copy that read a slot of h_lr_stage has run
+  Event mg_stage_done[kMarginalStageSlots];   // pose-graph marginals: the copy that read a slot of h_mg_stage has run
   Event grid_fork, grids_done;       // main stream -> grid stream at the start of a step, grid stream -> main stream before k_advance
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
   // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
@@ -256,6 +258,13 @@ struct aloam_ctx {
   DevBuf<MapEdgeRec> d_lr_edges; DevBuf<MapNormRec> d_lr_norms;
   DevBuf<VoxSeg> d_lr_segs;
   DevBuf<aloam_pose_information> d_lr_info;
+  // pose-graph marginals (aloam_graph_marginals): nothing is allocated before the first call; used in stream order
+  DevBuf<GraphMarginalItem> d_mg_items;                             // [kMarginalStageItems] the round's requests
+  PinnedBuf<GraphMarginalItem> h_mg_stage;                          // pinned ring of kMarginalStageSlots x kMarginalStageItems requests
+  int mg_stage_slot = 0; bool mg_stage_used[kMarginalStageSlots] = {};
+  DevBuf<double> d_mg_f64; long long mg_f64_cap = 0;                // the scratch rows, one per request of a round
+  DevBuf<int> d_mg_i32; long long mg_i32_cap = 0;
+  long long mg_last_nodes = 0, mg_last_edges = 0; int mg_last_n = 0;   // the last call (algorithmic bytes)
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -439,6 +448,11 @@ void on_graph_edges_added(aloam_ctx* c, int seq, int count);
 void on_graph_cleared(aloam_ctx* c, const int* seqs, int n);
 int on_graph_applied(aloam_ctx* c, const int* seqs, int n);
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events);
+// capi_posegraph.hip
+int require_graph(aloam_ctx* c);
+// What aloam_graph_add_edges asks of an edge, for it and for the candidates of aloam_graph_marginals: seq, i and j always; with `measurement`
+// also flags, Z (q is normalised in place) and info.  nullptr, or what is wrong.
+const char* graph_edge_check(const aloam_ctx* c, aloam_graph_edge& e, bool measurement);
 // capi_mapping.hip
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);
 // capi_records.hip

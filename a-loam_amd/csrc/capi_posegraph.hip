@@ -7,7 +7,7 @@
 
 #include "capi_internal.hpp"
 
-static int require_graph(aloam_ctx* c) {
+int aloam::require_graph(aloam_ctx* c) {
   if (!c->graph_on) { c->err = "pose graphs are not enabled (aloam_graph_enable)"; return ALOAM_E_STATE; }
   return ALOAM_OK;
 }
@@ -26,6 +26,22 @@ static bool info_positive_definite(const double* u) {
       else L[i][j] = s / L[j][j];
     }
   return true;
+}
+
+const char* aloam::graph_edge_check(const aloam_ctx* c, aloam_graph_edge& e, bool measurement) {
+  if (e.seq < 0 || e.seq >= c->B) return "seq out of range";
+  const int nodes = c->seq[e.seq].graph_nodes;
+  if (e.i < -1 || e.i >= nodes || e.j < 0 || e.j >= nodes || e.i == e.j) return "need -1 <= i < nodes, 0 <= j < nodes, i != j";
+  if (!measurement) return nullptr;
+  if (e.flags & ~ALOAM_GRAPH_EDGE_ROBUST) return "unknown flags";
+  double nn = 0.0;
+  for (int a = 0; a < 4; ++a) { if (!std::isfinite(e.q[a])) return "q is not finite"; nn += e.q[a] * e.q[a]; }
+  nn = std::sqrt(nn);
+  if (!(std::fabs(nn - 1.0) <= 1e-6)) return "q is not within 1e-6 of unit norm";
+  for (int a = 0; a < 4; ++a) e.q[a] /= nn;
+  for (int a = 0; a < 3; ++a) if (!std::isfinite(e.t[a])) return "t is not finite";
+  if (!info_positive_definite(e.info)) return "info is not finite and positive definite";
+  return nullptr;
 }
 
 // The items of one call to device memory through the pinned ring h_pg_stage, as stage_ints does for ints: the caller fills the slot this
@@ -143,18 +159,7 @@ int aloam_graph_add_edges(aloam_ctx* c, const aloam_graph_edge* edges, int n) {
   std::vector<int> added(c->B, 0);
   for (int k = 0; k < n; ++k) {
     aloam_graph_edge& e = checked[k];
-    auto fail = [&](const char* what) { c->err = "edge " + std::to_string(k) + ": " + what; return ALOAM_E_ARG; };
-    if (e.seq < 0 || e.seq >= c->B) return fail("seq out of range");
-    const int nodes = c->seq[e.seq].graph_nodes;
-    if (e.i < -1 || e.i >= nodes || e.j < 0 || e.j >= nodes || e.i == e.j) return fail("need -1 <= i < nodes, 0 <= j < nodes, i != j");
-    if (e.flags & ~ALOAM_GRAPH_EDGE_ROBUST) return fail("unknown flags");
-    double nn = 0.0;
-    for (int a = 0; a < 4; ++a) { if (!std::isfinite(e.q[a])) return fail("q is not finite"); nn += e.q[a] * e.q[a]; }
-    nn = std::sqrt(nn);
-    if (!(std::fabs(nn - 1.0) <= 1e-6)) return fail("q is not within 1e-6 of unit norm");
-    for (int a = 0; a < 4; ++a) e.q[a] /= nn;
-    for (int a = 0; a < 3; ++a) if (!std::isfinite(e.t[a])) return fail("t is not finite");
-    if (!info_positive_definite(e.info)) return fail("info is not finite and positive definite");
+    if (const char* what = graph_edge_check(c, e, true)) { c->err = "edge " + std::to_string(k) + ": " + what; return ALOAM_E_ARG; }
     if (c->seq[e.seq].graph_edges + ++added[e.seq] > c->pg_max_edges) {
       c->err = "edge " + std::to_string(k) + ": the edge row of sequence " + std::to_string(e.seq) + " is full";
       return ALOAM_E_CAPACITY;

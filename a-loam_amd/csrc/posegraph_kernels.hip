@@ -476,6 +476,7 @@ __device__ void graph_build_incidence(const Work& w, int* s_scan) {
 
 }  // namespace
 
+#ifndef ALOAM_GRAPH_DEVICE_FUNCTIONS_ONLY      // graphmarginal_kernels.hip includes this file for the device functions above, without the kernels
 // ---- the store --------------------------------------------------------------------------------------------------------------------------
 // A thread per new node: the pose as aloam_export_poses reports it, the odometry edge Z = X[k-1]^-1 o X[k] of the entered poses, and the
 // estimate X_opt[k-1] o Z.
@@ -707,5 +708,7 @@ void launch_pose_graph(const GraphSolveArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(k_graph_incidence, dim3(a.n), dim3(kGraphThreads), 0, stream, a);
   hipLaunchKernelGGL(k_pose_graph, dim3(a.n), dim3(kGraphThreads), 0, stream, a);
 }
+
+#endif  // ALOAM_GRAPH_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace aloam

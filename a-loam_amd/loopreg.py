@@ -19,7 +19,7 @@ import numpy as np
 
 from . import places
 from .atlas import associate_to_map
-from .posegraph import EDGE_ROBUST, compose, info_full, info_upper, inverse, make_edges, qrot, relative_pose, rotmat
+from .posegraph import EDGE_ROBUST, MARGINAL_MEASURED, MARGINAL_REQUEST_DTYPE, compose, info_full, info_upper, inverse, make_edges, qrot, relative_pose, rotmat
 
 LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
 GATE_CORNER, GATE_SURF = 10, 50                  # the filtered targets must hold MORE points than these (src/laserMapping.cpp:554)
@@ -83,6 +83,17 @@ def edge_from_result(result, seq, i, j, robust=True):
         return None
     q = np.asarray(result["q"], np.float64)
     return make_edges(seq, i, j, (q / np.linalg.norm(q))[None], np.asarray(result["t"], np.float64)[None], np.asarray(result["info"], np.float64)[None], robust)
+
+
+def request_from_result(result, i, j, seq):
+    """The request of aloam_graph_marginals (posegraph.MARGINAL_REQUEST_DTYPE, one element, MEASURED) for an ALOAM_LOOP_OK result record: the
+    edge edge_from_result would enter, held against the graph first (its chi2 against posegraph.chi2_gate()).  None for every other status."""
+    e = edge_from_result(result, seq, i, j, robust=False)
+    if e is None:
+        return None
+    r = np.zeros(1, MARGINAL_REQUEST_DTYPE)
+    r["edge"], r["mode"] = e, MARGINAL_MEASURED
+    return r
 
 
 def room_sample(rng, n_corner=300, n_surf=1500):

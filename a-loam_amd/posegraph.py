@@ -335,6 +335,176 @@ def chain_pcg(q, t, edges, **options):
     return optimize(q, t, edges, solve=chain_solver(o["pcg_tolerance"], o["pcg_max_iterations"]), **o)
 
 
+# ---- marginals: the covariance of an edge's residual under the graph, and the chi-square gate ----------------------
+MARGINAL_MEASURED, MARGINAL_AT_ESTIMATE = 0, 1
+MARGINAL_OK, MARGINAL_NO_EDGES, MARGINAL_NOT_CONVERGED, MARGINAL_FAILED = 0, 1, 2, 3
+MARGINAL_REQUEST_DTYPE = np.dtype([("edge", EDGE_DTYPE), ("mode", np.int32), ("pad", np.int32)])
+MARGINAL_DEFAULTS = dict(pcg_max_iterations=200, pcg_tolerance=1e-10, huber_delta=1.0)
+INFO_PIVOT_TOL = 1e-12               # kInfoPivotTol: a Cholesky pivot counts as positive when it exceeds this times its diagonal entry
+
+
+def marginal_request(seq, i, j, q=None, t=None, info=None, mode=MARGINAL_MEASURED):
+    """Requests of aloam_graph_marginals, a structured array of MARGINAL_REQUEST_DTYPE: the candidate edges (i, j, Z = (q, t), info) in
+    the mode given (one for all, or one each).  AT_ESTIMATE ignores Z and info: they default to the identity."""
+    i = np.atleast_1d(np.asarray(i, np.int32))
+    n = len(i)
+    q = np.tile([0.0, 0.0, 0.0, 1.0], (n, 1)) if q is None else q
+    t = np.zeros((n, 3)) if t is None else t
+    info = np.tile(np.eye(6), (n, 1, 1)) if info is None else info
+    r = np.zeros(n, MARGINAL_REQUEST_DTYPE)
+    r["edge"] = make_edges(seq, i, j, q, t, info)
+    r["mode"] = mode
+    return r
+
+
+def chi2_gate(dof=6, p=0.999):
+    """The quantile a chi2 is held against: 22.46 for the 6 degrees of freedom of an edge at p = 0.999."""
+    from scipy.stats import chi2
+    return float(chi2.ppf(p, dof))
+
+
+def _cholesky6(A, tol=0.0):
+    """Lower factor of a 6 x 6 matrix in the order of the device (row by row, each sum in index order); False when a pivot is not above
+    tol times its diagonal entry."""
+    L = np.zeros((6, 6))
+    for a in range(6):
+        for b in range(a + 1):
+            s = A[a][b]
+            for m in range(b):
+                s -= L[a][m] * L[b][m]
+            if a == b:
+                if not s > tol * A[a][a]:
+                    return L, False
+                L[a][a] = np.sqrt(s)
+            else:
+                L[a][b] = s / L[b][b]
+    return L, True
+
+
+def innovation(r, cov, info21):
+    """s_edge = r^T Omega r and chi2 = r^T (cov + Omega^-1)^-1 r as the device's one thread computes them: Omega^-1 from the Cholesky factor of
+    Omega, S = cov + Omega^-1 factored with the INFO_PIVOT_TOL rule, chi2 = |L_S^-1 r|^2.  With cov = 0, chi2 is s_edge.  Returns
+    (s_edge, chi2, ok); ok False (chi2 0) when a factorisation fails."""
+    Om = info_full(info21)
+    s_edge = 0.0
+    for a in range(6):
+        o = 0.0
+        for b in range(6):
+            o += Om[a][b] * r[b]
+        s_edge += r[a] * o
+    if not np.any(cov):
+        return s_edge, s_edge, True
+    L, ok = _cholesky6(Om, INFO_PIVOT_TOL)
+    if not ok:
+        return s_edge, 0.0, False
+    X = np.zeros((6, 6))                               # L^-1, column by column, by forward substitution
+    for c in range(6):
+        for a in range(c, 6):
+            s = 1.0 if a == c else 0.0
+            for m in range(c, a):
+                s -= L[a][m] * X[m][c]
+            X[a][c] = s / L[a][a]
+    S = np.zeros((6, 6))
+    for a in range(6):
+        for b in range(a + 1):
+            s = 0.0
+            for m in range(a, 6):                      # (L^-T L^-1)[a][b], a >= b
+                s += X[m][a] * X[m][b]
+            S[a][b] = S[b][a] = cov[a][b] + s
+    Ls, ok = _cholesky6(S, INFO_PIVOT_TOL)
+    if not ok:
+        return s_edge, 0.0, False
+    chi2, y = 0.0, np.zeros(6)
+    for a in range(6):
+        s = r[a]
+        for m in range(a):
+            s -= Ls[a][m] * y[m]
+        y[a] = s / Ls[a][a]
+        chi2 += y[a] * y[a]
+    return s_edge, chi2, True
+
+
+def marginal_solver(tol=1e-10, max_iterations=200):
+    """chain_solver for the six right-hand sides of a marginal: the same chain-preconditioned PCG (pcg's stopping rule), with the banded factor
+    and a sparse copy of H kept while the same H comes back (every column of every candidate solves with one H).  Carries its cap so that
+    marginals() can tell a column that ran into it."""
+    kept = {}
+
+    def solve(H, D, g):
+        from scipy.linalg import cholesky_banded, cho_solve_banded
+        from scipy.sparse import csr_matrix
+        if kept.get("H") is not H or not np.array_equal(kept["D"], D):
+            A = H + np.diag(D)
+            n = len(g)
+            band = np.zeros((12, n))
+            for u in range(12):
+                d = np.diagonal(A, u).copy()
+                k = np.arange(n - u)
+                d[(k + u) // 6 - k // 6 > 1] = 0.0      # outside the block-tridiagonal chain (never true inside bandwidth 11)
+                band[11 - u, u:] = d
+            kept.update(H=H, D=np.array(D), A=csr_matrix(A), cb=cholesky_banded(band))
+        cb = kept["cb"]
+        return pcg(kept["A"], g, lambda r: cho_solve_banded((cb, False), r), tol, max_iterations)
+    solve.max_iterations = max_iterations
+    return solve
+
+
+def marginals(q, t, edges, cand, mode=MARGINAL_MEASURED, huber_delta=1.0, solve=None):
+    """aloam_graph_marginals restated.  For every candidate edge of `cand` (EDGE_DTYPE; never robustified) at the estimates (q, t) of a graph
+    with `edges`: H = sum rho' J^T Omega J over the graph's edges (normal_equations: node 0 fixed, no damping); r, J_i, J_j of the candidate
+    (linearize); Sigma_r = J H^-1 J^T from the six solves H y_c = (J^T)_c, symmetrised; s_edge and chi2 (innovation).  mode (one, or one per
+    candidate) AT_ESTIMATE replaces Z by X_i^-1 o X_j of the estimates (X_j for i = -1) and reports s_edge = chi2 = 0.
+    Dense by default (np.linalg.solve); `solve(H, D, b)` (chain_solver, marginal_solver) takes the chain-PCG route, a column at a time from
+    x = 0, a zero column in 0 iterations.  Returns a dict of arrays over the candidates: status, cov [n, 6, 6], chi2, s_edge, r [n, 6],
+    q, t (the Z used), pcg_iterations (the total of the six columns), nodes, edges."""
+    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    n, N = len(cand), len(q)
+    mode = np.broadcast_to(np.asarray(mode, np.int32), (n,))
+    out = dict(status=np.full(n, MARGINAL_OK, np.int32), cov=np.zeros((n, 6, 6)), chi2=np.zeros(n), s_edge=np.zeros(n), r=np.zeros((n, 6)),
+               q=np.array(cand["q"], np.float64).reshape(n, 4), t=np.array(cand["t"], np.float64).reshape(n, 3), pcg_iterations=np.zeros(n, np.int32),
+               nodes=np.full(n, N, np.int32), edges=np.full(n, len(edges), np.int32))
+    if N < 2 or len(edges) == 0:
+        out["status"][:] = MARGINAL_NO_EDGES
+        return out
+    H, _, c = normal_equations(q, t, edges, huber_delta)
+    D = np.zeros(len(H))
+    for k in range(n):
+        e = cand[k:k + 1].copy()
+        e["flags"] = 0
+        i, j = int(e["i"][0]), int(e["j"][0])
+        if mode[k] == MARGINAL_AT_ESTIMATE:
+            qi, ti = (np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3)) if i < 0 else (q[i], t[i])
+            e["q"][0], e["t"][0] = relative_pose(qi, ti, q[j], t[j])
+            out["q"][k], out["t"][k] = e["q"][0], e["t"][0]
+            e["info"][0] = info_upper(np.eye(6))                                   # the request's is ignored
+        r, _, Ji, Jj, _ = linearize(q, t, e)
+        out["r"][k] = r[0]
+        if not (np.isfinite(c) and np.all(np.isfinite(H))):
+            out["status"][k] = MARGINAL_FAILED
+            continue
+        J = np.zeros((6, 6 * (N - 1)))
+        if i >= 1: J[:, 6 * (i - 1):6 * i] = Ji[0]
+        if j >= 1: J[:, 6 * (j - 1):6 * j] = Jj[0]
+        if solve is None:
+            Y = np.linalg.solve(H, J.T)
+        else:
+            Y, capped = np.zeros((len(H), 6)), False
+            for col in range(6):
+                if np.any(J[col]):
+                    Y[:, col], its = solve(H, D, J[col].copy())
+                    out["pcg_iterations"][k] += its
+                    capped |= its >= getattr(solve, "max_iterations", np.inf)
+            if capped: out["status"][k] = MARGINAL_NOT_CONVERGED
+        M = J @ Y
+        out["cov"][k] = 0.5 * (M + M.T)
+        if mode[k] == MARGINAL_AT_ESTIMATE:
+            continue
+        out["s_edge"][k], out["chi2"][k], ok = innovation(r[0], out["cov"][k], e["info"][0])
+        if not ok:
+            out["status"][k], out["cov"][k], out["chi2"][k] = MARGINAL_FAILED, 0.0, 0.0
+    return out
+
+
 # ---- edges from a localization -------------------------------------------------------------------------------------------------------
 def anchor_from_localization(j, q_map, t_map, info, seq=0, robust=False):
     """Node j was localized at (q_map, t_map) in the fixed world (atlas) frame with information `info`: the anchor edge (-1, j)."""

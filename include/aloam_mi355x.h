@@ -939,6 +939,74 @@ int aloam_graph_loops_enable(aloam_ctx* ctx, int max_requests, int max_target_co
 int aloam_graph_register_loops(aloam_ctx* ctx, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt,
                                aloam_graph_loop_result* dst /* [n] */);
 
+/* ---- pose-graph marginals: the covariance of an edge's residual under the graph, and its chi-square --------------------------------------
+ * aloam_graph_register_loops measures a loop edge; whether it is a GOOD loop is decided here.  s = r^T Omega r is not the test: after a
+ * long drive the graph's own uncertainty about X_i^-1 o X_j dominates a correct edge's residual.  The test is the innovation
+ * chi2 = r^T (Sigma_r + Omega^-1)^-1 r against a 6-dof quantile (22.46 at p = 0.999), with Sigma_r the covariance of the residual under the
+ * graph alone.  One stream-ordered call computes it for a list of candidate edges, one workgroup each.  It reads the graphs and writes
+ * nothing in them.  Opt-in and beside the reference: a context that never calls aloam_graph_marginals launches exactly what it launched
+ * before.  a-loam_amd/posegraph.py restates the definition as marginals(); DESIGN.md §7p.
+ *
+ * For a request (edge = a candidate (seq, i, j, Z, Omega), mode), everything read on the device at that point of the stream:
+ *   - the linearisation point is the sequence's current estimates (q_opt, t_opt).  H = sum rho'_e J_e^T Omega_e J_e over the sequence's
+ *     edges, as aloam_graph_optimize builds it: node 0 fixed, edges flagged ALOAM_GRAPH_EDGE_ROBUST weighted by rho' at huber_delta, no
+ *     Levenberg-Marquardt damping.  H is positive definite whenever the graph has two nodes or more: the odometry chain ties every node to
+ *     node 0 with positive-definite information.
+ *   - r, J_i, J_j are the candidate's residual and Jacobians of the section "pose graphs" at the estimates; J_i is zero for i = -1 and the
+ *     block of node 0 is zero.  The candidate is never robustified (its flags are validated and ignored).
+ *   - Sigma_r = J H^-1 J^T, J = [J_i J_j]: six solves H y_c = (J^T)_c by the chain-preconditioned conjugate gradients of
+ *     aloam_graph_optimize from y = 0, one after the other; Sigma_r[:, c] = J_i y_c[i] + J_j y_c[j], symmetrised as (M + M^T) / 2.  It is
+ *     the covariance, under the graph alone, of r = (2 q_E.xyz, t_E): to first order the RIGHT tangent of Z, the one aloam_graph_edge.info
+ *     lives in.  A column whose right-hand side is zero (i = -1, j = 0) takes 0 iterations and is no failure.
+ *   - ALOAM_GRAPH_MARGINAL_MEASURED: Z and Omega as given.  s_edge = r^T Omega r; chi2 = r^T (Sigma_r + Omega^-1)^-1 r, by one thread:
+ *     Omega^-1 from a Cholesky factor of Omega, S = Sigma_r + Omega^-1 factored with every pivot above 1e-12 of its diagonal entry,
+ *     chi2 = |L_S^-1 r|^2.  With Sigma_r = 0, chi2 is s_edge.
+ *   - ALOAM_GRAPH_MARGINAL_AT_ESTIMATE: Z := X_i^-1 o X_j of the estimates (X_j for i = -1), as this header defines a relative pose; the
+ *     request's q, t and info are ignored and not validated.  r is what the arithmetic leaves (about 1e-17); s_edge and chi2 are 0.
+ *     Sigma_r is then the covariance of the relative pose of the two nodes, or of node j against the frame of the fixed node 0.
+ * status: ALOAM_GRAPH_MARGINAL_OK; ..._NO_EDGES - fewer than two nodes, nothing computed; ..._NOT_CONVERGED - a column ended at
+ *   pcg_max_iterations without meeting pcg_tolerance: everything is still written from what it had; ..._FAILED - a non-finite
+ *   linearisation, a chain factorisation that fails, p^T A p <= 0, or S not positive definite: cov and chi2 are zeros.
+ *   pcg_iterations: the total over the six columns.  nodes, edges: the counts used.  q, t: the Z the residual was taken against.
+ * Options (opt = NULL: the defaults): pcg_max_iterations >= 1 per column (200); pcg_tolerance >= 0 and finite (1e-10, relative in the
+ *   preconditioned norm); huber_delta > 0 and finite (1.0): else ALOAM_E_ARG.
+ *
+ * aloam_graph_marginals: req is host memory (pinned or pageable), read during the call; dst is device memory of the context's device or
+ *   pinned host memory, 8-byte aligned (classified like the exports).  Everything is checked before anything is queued and nothing changes
+ *   on a refusal: ALOAM_E_STATE before aloam_graph_enable; ALOAM_E_ARG for seq out of range, i or j out of range (-1 <= i < nodes,
+ *   0 <= j < nodes, i != j), a mode that is neither of the two, and in MEASURED mode a Z or Omega that aloam_graph_add_edges would refuse
+ *   (q stored normalised, as there).  n = 0 is ALOAM_OK.  Stream-ordered, no host synchronisation: the requests go through a pinned
+ *   staging ring.  A (seq, i, j) may be listed any number of times.  dst[r] belongs to req[r]; its bits do not depend on n, on r, on the
+ *   round or on the other requests.  Every request has a scratch row of its own (one linearisation of its sequence's graph: 200 doubles
+ *   per node and 115 per edge of the largest graph listed); at most as many rows as fit 1 GiB are allocated, on first use, and at least
+ *   one; more requests run in rounds over the same rows in stream order. */
+enum { ALOAM_GRAPH_MARGINAL_MEASURED = 0, ALOAM_GRAPH_MARGINAL_AT_ESTIMATE = 1 };
+enum { ALOAM_GRAPH_MARGINAL_OK = 0, ALOAM_GRAPH_MARGINAL_NO_EDGES = 1, ALOAM_GRAPH_MARGINAL_NOT_CONVERGED = 2, ALOAM_GRAPH_MARGINAL_FAILED = 3 };
+typedef struct aloam_graph_marginal_request { /* 248 bytes                                                                              */
+  aloam_graph_edge edge;                      /* the candidate: seq, i, j, Z = (q, t), info; flags 0 or ALOAM_GRAPH_EDGE_ROBUST, ignored */
+  int mode;                                   /* ALOAM_GRAPH_MARGINAL_MEASURED or ALOAM_GRAPH_MARGINAL_AT_ESTIMATE                      */
+  int pad;
+} aloam_graph_marginal_request;
+typedef struct aloam_graph_marginal_options { /* 24 bytes                                                                               */
+  int pcg_max_iterations;                     /* 200, per column                                                                        */
+  int pad;
+  double pcg_tolerance;                       /* 1e-10, relative in the preconditioned norm                                             */
+  double huber_delta;                         /* 1.0: the weight of the graph's robust edges, as aloam_graph_options.huber_delta        */
+} aloam_graph_marginal_options;
+typedef struct aloam_graph_marginal_result {  /* 440 bytes                                                                              */
+  int status, mode;
+  int seq, i, j;
+  int pcg_iterations;                         /* the six columns together                                                               */
+  int nodes, edges;                           /* of the sequence's graph, as used                                                       */
+  double chi2, s_edge;
+  double r[6];                                /* the candidate's residual at the estimates, order (theta_x .. t_z)                      */
+  double q[4], t[3];                          /* Z: as given (normalised), or X_i^-1 o X_j of the estimates                             */
+  double cov[36];                             /* Sigma_r, row-major, symmetric                                                          */
+} aloam_graph_marginal_result;
+void aloam_graph_marginal_default_options(aloam_graph_marginal_options* opt);
+int aloam_graph_marginals(aloam_ctx* ctx, const aloam_graph_marginal_request* req, int n, const aloam_graph_marginal_options* opt,
+                          aloam_graph_marginal_result* dst /* [n] */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

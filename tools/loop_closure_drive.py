@@ -17,7 +17,10 @@ step that fails is named with what was known by then.
 With --device-loops the edge is also measured by the one-call route, aloam_graph_register_loops: node j against the same nodes around the
 matched keyframe, in the frame of node i, the guess from the match's yaw shift (loopreg.guess_from_match).  It is printed as
 device_loop_edge beside loop_edge, with its error against ground truth, its wall time, and the wall time of steps 2 and 3 it replaces
-(spare_slot_route_ms).  The edge that goes into the graph is still the spare-slot route's: the default path is unchanged.
+(spare_slot_route_ms).  The measured edge is then held against the graph before anything is entered (aloam_graph_marginals,
+loopreg.request_from_result): its chi2 = r^T (Sigma_r + Omega^-1)^-1 r against posegraph.chi2_gate() and the verdict are printed as
+device_loop_gate, beside the same for a copy of the edge displaced by 1.5 m.  The edge that goes into the graph is still the spare-slot
+route's: the default path is unchanged.
 
 With --apply the whole chain runs twice, and both runs drive on for another quarter lap behind the solve: one after aloam_graph_apply of
 all nodes (pose and map), one without it.  Reported for each, without judging them: the ATE of the live map pose over the continued sweeps,
@@ -149,6 +152,17 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
             out["device_loop_edge"] = {"status": int(r["status"]), "n_line": int(r["n_line"]), "n_plane": int(r["n_plane"]), "target_points": r["target_points"].tolist(),
                                        "cost": float(r["cost"]), "guess_error_m": float(np.linalg.norm(tg - tz)), "translation_error_m": float(np.linalg.norm(r["t"] - tz)),
                                        "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dq[:3]))))), "call_and_synchronize_ms": call_ms}
+            # the gate: the measured edge, and a copy displaced by 1.5 m, against the graph's own uncertainty about X_i^-1 o X_j
+            stage = "graph_marginals"
+            rq = lr.request_from_result(r, i, j, 0)
+            if rq is not None:
+                moved = rq.copy()
+                moved["edge"]["t"][0, 0] += 1.5
+                gate = pg.chi2_gate()
+                mg = gpu.graph_marginals(np.concatenate([rq, moved]))
+                out["device_loop_gate"] = {"quantile": gate, "edges": [
+                    {"displaced_m": d, "status": int(g["status"]), "s_edge": float(g["s_edge"]), "chi2": float(g["chi2"]), "pcg_iterations": int(g["pcg_iterations"]),
+                     "accepted": bool(g["status"] == pg.MARGINAL_OK and g["chi2"] < gate)} for d, g in zip((0.0, 1.5), mg)]}
             stage = "graph_export_map (local)"
             t_spare = time.perf_counter()
         off = torch.zeros(4, dtype=torch.int64, pin_memory=True)
