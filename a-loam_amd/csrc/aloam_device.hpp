@@ -298,7 +298,7 @@ __device__ __forceinline__ void wave_box_reduce(float (&mn)[3], float (&mx)[3]) 
 // a pair whose upper partner lies beyond n is simply skipped, which removes a third of the LDS traffic at the typical
 // n ~ 0.7 * pow2ceil(n).  The stages that stay inside aligned groups of eight keys (the merges k = 2, 4 and 8, and the last
 // three half-cleaners of every later merge) run in registers: one read and one write of the group instead of one per stage.
-// Starts and ends with the data visible to the whole workgroup.
+// Starts and ends with the data visible to the whole workgroup.  (k_vox_keys_sort's sort; the ring kernel uses bitonic_sort_blocked below.)
 __device__ __forceinline__ int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 template <typename K>
 __device__ __forceinline__ void bitonic_cx(K& a, K& b) {
@@ -364,6 +364,78 @@ __device__ __forceinline__ void bitonic_sort_keys(K* keys, int n, int tid) {
   }
 }
 __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* keys, int n, int tid) { bitonic_sort_keys<unsigned long long>(keys, n, tid); }
+
+// The same network with EVERY half-cleaner in registers (the run keys of k_ring_features, which is bound by instruction issue: a
+// compare-exchange through LDS costs ~8 VALU of index arithmetic and guards on top of its two reads and two writes).  The half-cleaners
+// j = k / 4 .. 1 of a merge are taken three at a time from the bottom - strides (4 S, 2 S, S) for S = 1, 8, 64, 512 - and the topmost
+// group may hold one or two: a thread holds the eight keys i0 + u S of an aligned block of 8 S keys, one read and one write of the block
+// per pass.  Only the flip that opens a merge still goes pair by pair: 8 + 6 + 3 passes and 7 flips = 24 barriers for 1024 keys instead of 36.
+// CAP = the keys the array holds, a power of two: reads and writes inside a block that has any key below n are unguarded (what was read
+// from the slots n .. is replaced by +inf in registers and +inf sorts back to the top of the block), and a block never leaves the array
+// (8 S > CAP: the keys u S >= CAP of the one block are +inf and never touched).
+template <int S, int STAGES, bool FIRST, int CAP, typename K>
+__device__ __forceinline__ void bitonic_pass_of_eight(K* keys, int n, int tid) {
+  constexpr K kInf = (K)~(K)0;
+  constexpr int U = 8 * S <= CAP ? 8 : CAP / S;
+  for (int q = tid; (q & ~(S - 1)) * 8 < n; q += 256) {
+    const int i0 = (q & ~(S - 1)) * 8 + (q & (S - 1));
+    K* p = keys + i0;
+    K v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = u < U ? p[u * S] : kInf;
+#pragma unroll
+    for (int u = 0; u < U; ++u) if (i0 + u * S >= n) v[u] = kInf;
+    if (FIRST) {                                                             // merges k = 2, 4 and 8
+#pragma unroll
+      for (int b = 0; b < 8; b += 2) bitonic_cx(v[b], v[b + 1]);
+#pragma unroll
+      for (int b = 0; b < 8; b += 4) { bitonic_cx(v[b], v[b + 3]); bitonic_cx(v[b + 1], v[b + 2]); }
+#pragma unroll
+      for (int b = 0; b < 8; b += 2) bitonic_cx(v[b], v[b + 1]);
+#pragma unroll
+      for (int o = 0; o < 4; ++o) bitonic_cx(v[o], v[7 - o]);
+    } else if (STAGES == 3) {                                                // half-cleaner j = 4 S
+#pragma unroll
+      for (int o = 0; o < 4; ++o) bitonic_cx(v[o], v[o + 4]);
+    }
+    if (STAGES >= 2) {                                                       // j = 2 S
+#pragma unroll
+      for (int b = 0; b < 8; b += 4) { bitonic_cx(v[b], v[b + 2]); bitonic_cx(v[b + 1], v[b + 3]); }
+    }
+#pragma unroll
+    for (int b = 0; b < 8; b += 2) bitonic_cx(v[b], v[b + 1]);                 // j = S
+#pragma unroll
+    for (int u = 0; u < U; ++u) p[u * S] = v[u];
+  }
+  __syncthreads();
+}
+template <int S, int CAP, typename K>
+__device__ __forceinline__ void bitonic_level(K* keys, int n, int tid, int stages) {   // the 1 - 3 half-cleaners of a merge that have strides S .. 4 S
+  if (stages >= 3) bitonic_pass_of_eight<S, 3, false, CAP, K>(keys, n, tid);
+  else if (stages == 2) bitonic_pass_of_eight<S, 2, false, CAP, K>(keys, n, tid);
+  else if (stages == 1) bitonic_pass_of_eight<S, 1, false, CAP, K>(keys, n, tid);
+}
+template <typename K, int CAP>
+__device__ __forceinline__ void bitonic_sort_blocked(K* keys, int n, int tid) {
+  static_assert(CAP >= 512 && CAP <= 4096 && (CAP & (CAP - 1)) == 0, "levels S = 1, 8, 64 (and 512 from 2048 keys on)");
+  const int npad = pow2ceil(n);
+  bitonic_pass_of_eight<1, 3, true, CAP, K>(keys, n, tid);
+  for (int lk = 4; (1 << lk) <= npad; ++lk) {                                // merge k = 1 << lk: flip, then lk - 1 half-cleaners
+    const int k = 1 << lk, hk = k >> 1;
+    for (int t = tid; t < (npad >> 1); t += 256) {                           // flip stage: i <-> block end - i
+      const int off = t & (hk - 1), i = ((t - off) << 1) + off, l = i + (k - 1 - 2 * off);
+      if (l < n) {
+        const K x = keys[i], y = keys[l];
+        if (x > y) { keys[i] = y; keys[l] = x; }
+      }
+    }
+    __syncthreads();
+    if constexpr (CAP >= 2048) bitonic_level<512, CAP, K>(keys, n, tid, lk - 10);
+    bitonic_level<64, CAP, K>(keys, n, tid, lk - 7);
+    bitonic_level<8, CAP, K>(keys, n, tid, lk - 4);
+    bitonic_pass_of_eight<1, 3, false, CAP, K>(keys, n, tid);
+  }
+}
 
 
 }  // namespace aloam
