@@ -127,6 +127,22 @@ class AloamGraphLoopResult(C.Structure):
                 ("q", C.c_double * 4), ("t", C.c_double * 3), ("info", C.c_double * 21), ("info_left", C.c_double * 21)]
 
 
+class AloamMapScore(C.Structure):
+    """What one pose counts against a bucketed target (aloam_map_score, 32 bytes)."""
+    _fields_ = [("corner_factors", C.c_int), ("surf_factors", C.c_int), ("corner_found", C.c_int), ("surf_found", C.c_int), ("cost", C.c_double), ("pad", C.c_int * 2)]
+
+
+class AloamGraphLoopSearch(C.Structure):
+    """The pose grid around every request's guess (aloam_graph_loop_search, 32 bytes)."""
+    _fields_ = [("radius_m", C.c_double), ("step_m", C.c_double), ("yaw_deg", C.c_double), ("yaw_step_deg", C.c_double)]
+
+
+class AloamGraphLoopSearchResult(C.Structure):
+    """The node a searched registration started from (aloam_graph_loop_search_result, 160 bytes); a-loam_amd/loopreg.py holds the definitions."""
+    _fields_ = [("status", C.c_int), ("nodes", C.c_int), ("best", C.c_int), ("ix", C.c_int), ("iy", C.c_int), ("iyaw", C.c_int), ("pad", C.c_int * 2),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("reserved", C.c_double), ("best_score", AloamMapScore), ("guess_score", AloamMapScore)]
+
+
 class AloamGraphMarginalRequest(C.Structure):
     """A candidate edge whose residual covariance and chi-square are wanted (aloam_graph_marginal_request, 248 bytes)."""
     _fields_ = [("edge", AloamGraphEdge), ("mode", C.c_int), ("pad", C.c_int)]
@@ -212,6 +228,10 @@ MAP_TILE_DTYPE = np.dtype([("cube", np.int32, 3), ("feature_class", np.int32), (
 MAP_CORRECTION_DTYPE = np.dtype([("q_wmap_wodom", np.float64, 4), ("t_wmap_wodom", np.float64, 3), ("pad", np.float64)])
 MAP_SCORE_DTYPE = np.dtype([("corner_factors", np.int32), ("surf_factors", np.int32), ("corner_found", np.int32), ("surf_found", np.int32),
                             ("cost", np.float64), ("pad", np.int32, 2)])
+GRAPH_LOOP_SEARCH_DTYPE = np.dtype([("radius_m", np.float64), ("step_m", np.float64), ("yaw_deg", np.float64), ("yaw_step_deg", np.float64)])
+GRAPH_LOOP_SEARCH_RESULT_DTYPE = np.dtype([("status", np.int32), ("nodes", np.int32), ("best", np.int32), ("ix", np.int32), ("iy", np.int32), ("iyaw", np.int32),
+                                           ("pad", np.int32, 2), ("q", np.float64, 4), ("t", np.float64, 3), ("reserved", np.float64),
+                                           ("best_score", MAP_SCORE_DTYPE), ("guess_score", MAP_SCORE_DTYPE)])
 
 
 def map_corrections(q, t):
@@ -383,6 +403,8 @@ def lib():
         L.aloam_graph_loops_enable.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.aloam_graph_register_loops.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopOptions), vp]
         L.aloam_graph_loop_export_target.argtypes = [vp, C.c_int, C.c_int, vp, C.c_longlong, vp]
+        L.aloam_graph_loop_default_search.argtypes = [C.POINTER(AloamGraphLoopSearch)]; L.aloam_graph_loop_default_search.restype = None
+        L.aloam_graph_search_loops.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopSearch), C.POINTER(AloamGraphLoopOptions), vp, vp, vp]
         L.aloam_graph_marginal_default_options.argtypes = [C.POINTER(AloamGraphMarginalOptions)]; L.aloam_graph_marginal_default_options.restype = None
         L.aloam_graph_marginals.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphMarginalOptions), vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -953,6 +975,45 @@ class Aloam:
         self.graph_register_loops_into(requests, buf.data_ptr(), self.graph_loop_options(**options))
         self.synchronize()
         return buf.cpu().numpy()[:n * size].view(GRAPH_LOOP_RESULT_DTYPE).copy()
+
+    def graph_loop_search(self, **kw):
+        """The default grid of aloam_graph_search_loops (3 m in 0.5 m steps, 12.5 degrees in 2.5 degree steps) with the given fields replaced."""
+        g = AloamGraphLoopSearch()
+        lib().aloam_graph_loop_default_search(C.byref(g))
+        for k, v in kw.items():
+            assert hasattr(g, k), k
+            setattr(g, k, v)
+        return g
+
+    def graph_search_loops_into(self, requests, dst_ptr, search_dst_ptr, scores_ptr=0, search=None, options=None):
+        """Queue the searched registration of each request (no host synchronisation): dst_ptr receives one aloam_graph_loop_result and
+        search_dst_ptr one aloam_graph_loop_search_result per request, scores_ptr (or 0) the aloam_map_score of every (request, node);
+        device memory or pinned host memory."""
+        r = requests if isinstance(requests, np.ndarray) else self.graph_loop_requests(requests)
+        r = np.ascontiguousarray(r, dtype=GRAPH_LOOP_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_search_loops(self.h, _p(r) if len(r) else None, len(r), C.byref(search) if search is not None else None,
+                                                   C.byref(options) if options is not None else None, C.c_void_p(dst_ptr) if dst_ptr else None,
+                                                   C.c_void_p(search_dst_ptr) if search_dst_ptr else None, C.c_void_p(scores_ptr) if scores_ptr else None))
+
+    def graph_search_loops(self, requests, search=None, scores=False, pinned=True, **options):
+        """Search, register and wait: (results [n] of GRAPH_LOOP_RESULT_DTYPE, search results [n] of GRAPH_LOOP_SEARCH_RESULT_DTYPE[, scores
+        [n, K] of MAP_SCORE_DTYPE]).  search: an AloamGraphLoopSearch (graph_loop_search(...)), a dict of its fields, or None for the
+        defaults; keyword arguments are fields of aloam_graph_loop_options."""
+        import torch
+        from .relocalize import grid_axes
+        g = self.graph_loop_search(**search) if isinstance(search, dict) else search if search is not None else self.graph_loop_search()
+        lin, yaw = grid_axes(g.radius_m, g.step_m, g.yaw_deg, g.yaw_step_deg)
+        n, K = len(requests), len(yaw) * len(lin) * len(lin)
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        bufs = [torch.zeros(max(1, n) * size, dtype=torch.uint8, **where)
+                for size in (GRAPH_LOOP_RESULT_DTYPE.itemsize, GRAPH_LOOP_SEARCH_RESULT_DTYPE.itemsize, K * MAP_SCORE_DTYPE.itemsize if scores else 8)]
+        self.graph_search_loops_into(requests, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr() if scores else 0, g, self.graph_loop_options(**options))
+        self.synchronize()
+        out = (bufs[0].cpu().numpy()[:n * GRAPH_LOOP_RESULT_DTYPE.itemsize].view(GRAPH_LOOP_RESULT_DTYPE).copy(),
+               bufs[1].cpu().numpy()[:n * GRAPH_LOOP_SEARCH_RESULT_DTYPE.itemsize].view(GRAPH_LOOP_SEARCH_RESULT_DTYPE).copy())
+        if scores:
+            out += (bufs[2].cpu().numpy()[:n * K * MAP_SCORE_DTYPE.itemsize].view(MAP_SCORE_DTYPE).reshape(n, K).copy(),)
+        return out
 
     def graph_loop_target(self, slot=0, feature_class=0):
         """The filtered target of a scratch slot as the last graph_register_loops left it (parity tests): float32 [n, 4]."""

@@ -21,6 +21,7 @@
 #include "graphmap_kernels.hpp"
 #include "graphmarginal_kernels.hpp"
 #include "loopreg_kernels.hpp"
+#include "loopsearch_kernels.hpp"
 #include "mapping_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "places_kernels.hpp"
@@ -258,6 +259,7 @@ struct aloam_ctx {
   DevBuf<MapEdgeRec> d_lr_edges; DevBuf<MapNormRec> d_lr_norms;
   DevBuf<VoxSeg> d_lr_segs;
   DevBuf<aloam_pose_information> d_lr_info;
+  DevBuf<LoopSearchPartial> d_ls_part; long long ls_part_cap = 0;   // aloam_graph_search_loops: [round][K][kLoopSearchParts], nothing before its first call
   // pose-graph marginals (aloam_graph_marginals): nothing is allocated before the first call; used in stream order
   DevBuf<GraphMarginalItem> d_mg_items;                             // [kMarginalStageItems] the round's requests
   PinnedBuf<GraphMarginalItem> h_mg_stage;                          // pinned ring of kMarginalStageSlots x kMarginalStageItems requests

@@ -2,7 +2,8 @@
 // aloam_graph_register_loops / aloam_graph_loop_export_target).  A request runs in a scratch slot; the slots are the
 // "sequences" of a scratch MapArgs, so association, fit, solve and information are the launches of the mapping step over other buffers.
 // Everything is checked before anything is queued; nothing synchronises the host (a slot of the pinned request ring is waited for only when
-// kLoopStageSlots later rounds have been queued behind it).
+// kLoopStageSlots later rounds have been queued behind it).  aloam_graph_search_loops is the same call with a pose grid
+// scored around every guess between the grid build and the first association (loopsearch_kernels.hip).
 #include <algorithm>
 #include <cmath>
 
@@ -112,9 +113,43 @@ int aloam_graph_loops_enable(aloam_ctx* c, int max_requests, int max_target_corn
   return ALOAM_OK;
 }
 
-int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst) {
-  DeviceScope device_scope(c);
-  if (!c) return ALOAM_E_ARG;
+void aloam_graph_loop_default_search(aloam_graph_loop_search* s) {
+  if (!s) return;
+  s->radius_m = 3.0; s->step_m = 0.5; s->yaw_deg = 12.5; s->yaw_step_deg = 2.5;
+}
+
+// What a searched call adds to a plain one: the grid with its yaw table, and where the search record and the score table go.
+struct LoopSearchCall {
+  LoopSearchGrid grid;
+  void* d_search = nullptr;            // aloam_graph_loop_search_result [n], as the device reaches it
+  void* d_scores = nullptr;            // aloam_map_score [n][K] or nullptr
+};
+
+// The axes and the yaw table of a grid (a-loam_amd/loopreg.py search_grid restates this); ALOAM_E_ARG for what cannot be searched.
+static int loop_search_grid(aloam_ctx* c, const aloam_graph_loop_search& s, LoopSearchGrid* g) {
+  const double v[4] = {s.radius_m, s.step_m, s.yaw_deg, s.yaw_step_deg};
+  for (double x : v) if (!std::isfinite(x) || x < 0.0) { c->err = "the search grid's values must be finite and >= 0"; return ALOAM_E_ARG; }
+  const double md = s.step_m > 0.0 ? std::floor(s.radius_m / s.step_m + 1e-9) : 0.0;
+  const double ad = s.yaw_step_deg > 0.0 ? std::floor(s.yaw_deg / s.yaw_step_deg + 1e-9) : 0.0;
+  if (!(ad <= (double)kLoopSearchMaxYaw)) { c->err = "the search grid has more than 31 yaw steps to either side"; return ALOAM_E_ARG; }
+  if (!(md <= 64.0)) { c->err = "the search grid has more than 2^14 nodes"; return ALOAM_E_ARG; }
+  const int m = (int)md, a = (int)ad;
+  const long long K = (long long)(2 * a + 1) * (2 * m + 1) * (2 * m + 1);
+  if (K < 1 || K > kLoopSearchMaxNodes) { c->err = "the search grid has more than 2^14 nodes"; return ALOAM_E_ARG; }
+  *g = LoopSearchGrid{};
+  g->m = m; g->a = a; g->K = (int)K; g->step_m = s.step_m;
+  for (int iyaw = -a; iyaw <= a; ++iyaw) {
+    const double dyaw = (double)iyaw * s.yaw_step_deg;
+    const double h = (dyaw * (M_PI / 180.0)) / 2;
+    g->half[iyaw + a][0] = std::sin(h); g->half[iyaw + a][1] = std::cos(h);
+  }
+  return ALOAM_OK;
+}
+
+// aloam_graph_register_loops (search == nullptr) and aloam_graph_search_loops: checks, ring, gather, filter, grid, then search and pick when a
+// grid is given, rounds, information, result.  The plain call queues exactly the launches it queued before the search existed.
+static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst,
+                          const aloam_graph_loop_search* search_or_default, bool searched, aloam_graph_loop_search_result* search_dst, aloam_map_score* scores) {
   if (const int rc = require_loops(c)) return rc;
   // ---- everything is checked before anything is queued
   if (n < 0 || (n > 0 && !req)) { c->err = "bad request list"; return ALOAM_E_ARG; }
@@ -122,6 +157,13 @@ int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req
   aloam_graph_loop_default_options(&o);
   if (opt) o = *opt;
   if (o.outer_iterations < 1 || o.lm_max_iterations < 0) { c->err = "need outer_iterations >= 1 and lm_max_iterations >= 0"; return ALOAM_E_ARG; }
+  LoopSearchCall sc;
+  if (searched) {
+    aloam_graph_loop_search g;
+    aloam_graph_loop_default_search(&g);
+    if (search_or_default) g = *search_or_default;
+    if (const int rc = loop_search_grid(c, g, &sc.grid)) return rc;
+  }
   if (n == 0) return ALOAM_OK;
   {
     void* dev = nullptr;
@@ -130,6 +172,10 @@ int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req
   }
   void* d_dst = nullptr;
   if (const int rc = export_target(c, dst, 8, "dst", &d_dst)) return rc;
+  if (searched) {
+    if (const int rc = export_target(c, search_dst, 8, "search_dst", &sc.d_search)) return rc;
+    if (scores) if (const int rc = export_target(c, scores, 8, "scores", &sc.d_scores)) return rc;
+  }
   std::vector<aloam_graph_loop_request> checked(req, req + n);
   for (int r = 0; r < n; ++r) {
     aloam_graph_loop_request& q = checked[r];
@@ -148,14 +194,28 @@ int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req
     for (int a = 0; a < 3; ++a) if (!std::isfinite(q.t[a])) return fail("the guess t is not finite");
     q.pad[0] = 0; q.pad[1] = 0; q.reserved = 0.0;
   }
-  // ---- rounds of at most lr_slots requests over the same scratch, in stream order
+  // ---- rounds of at most lr_slots requests (searched: and at most 2^18 (slot, node) pairs) over the same scratch, in stream order
+  const int per_round = searched ? (int)std::min<long long>(c->lr_slots, kLoopSearchMaxPairs / sc.grid.K) : c->lr_slots;
+  if (searched)
+    if (const int rc = grow_scratch(c, c->d_ls_part, c->ls_part_cap, (long long)std::min(per_round, n) * sc.grid.K * kLoopSearchParts)) {
+      (void)hipGetLastError();
+      c->err = "search scratch of " + std::to_string(std::min(per_round, n)) + " x " + std::to_string(sc.grid.K) + " (request, node) pairs: device allocation failed";
+      return rc;
+    }
   ProfScope prof(c, K_LOOP_REGISTER);
-  for (int r0 = 0; r0 < n; r0 += c->lr_slots) {
-    const int m = std::min(c->lr_slots, n - r0);
-    const int ns = c->lr_stage_slot;
-    c->lr_stage_slot = (ns + 1) % kLoopStageSlots;
-    if (c->lr_stage_used[ns]) HIP_TRY(c, hipEventSynchronize(c->lr_stage_done[ns]));
-    aloam_graph_loop_request* slot = c->h_lr_stage.get() + (size_t)ns * c->lr_slots;
+  // A slot of the pinned ring holds lr_slots requests: one round of the plain call, as many whole rounds of a searched call as fit (its
+  // rounds are the shorter of the two bounds), so that a searched call waits for the ring no sooner than a plain call of the same n.
+  int ns = 0, ring_at = 0, ring_left = 0;
+  for (int r0 = 0; r0 < n; r0 += per_round) {
+    const int m = std::min(per_round, n - r0);
+    if (ring_left < m) {
+      ns = c->lr_stage_slot;
+      c->lr_stage_slot = (ns + 1) % kLoopStageSlots;
+      if (c->lr_stage_used[ns]) HIP_TRY(c, hipEventSynchronize(c->lr_stage_done[ns]));
+      ring_at = 0; ring_left = c->lr_slots;
+    }
+    aloam_graph_loop_request* slot = c->h_lr_stage.get() + (size_t)ns * c->lr_slots + ring_at;
+    ring_at += m; ring_left -= m;
     std::copy(checked.begin() + r0, checked.begin() + r0 + m, slot);
     HIP_TRY(c, hipMemcpyAsync(c->d_lr_req.get(), slot, sizeof(aloam_graph_loop_request) * (size_t)m, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(c->lr_stage_done[ns], c->stream));
@@ -174,6 +234,16 @@ int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req
     launch_loop_gather(a, v, c->stream);
     launch_voxel_filter(v, c->lr_tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
     launch_loop_grid(a, c->stream);
+    if (searched) {
+      LoopSearchArgs sa{};
+      sa.n = m;
+      sa.splits = m < 8 ? std::max(1, std::min(8 / m, sc.grid.K)) : 1;   // fewer than 8 slots: their nodes are dealt over the XCDs left idle
+      sa.kper = (sc.grid.K + sa.splits - 1) / sa.splits;
+      sa.req = a.req; sa.map = a.map; sa.plan = a.plan; sa.plan_ints = kLoopPlanInts; sa.grid = sc.grid; sa.part = c->d_ls_part.get();
+      sa.scores = sc.d_scores ? static_cast<aloam_map_score*>(sc.d_scores) + (size_t)r0 * sc.grid.K : nullptr;
+      sa.dst = static_cast<aloam_graph_loop_search_result*>(sc.d_search) + r0;
+      launch_loop_search(sa, c->stream);
+    }
     for (int it = 0; it < o.outer_iterations; ++it) {
       launch_map_associate(a.map, it, c->stream);
       launch_map_solve(a.map, it & 1, false, c->stream);   // no transformUpdate: a slot has no odometry frame
@@ -183,6 +253,19 @@ int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req
   }
   HIP_TRY(c, hipGetLastError());
   return ALOAM_OK;
+}
+
+int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  return register_loops(c, req, n, opt, dst, nullptr, false, nullptr, nullptr);
+}
+
+int aloam_graph_search_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_search* search, const aloam_graph_loop_options* opt,
+                             aloam_graph_loop_result* dst, aloam_graph_loop_search_result* search_dst, aloam_map_score* scores) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  return register_loops(c, req, n, opt, dst, search, true, search_dst, scores);
 }
 
 int aloam_graph_loop_export_target(aloam_ctx* c, int slot, int feature_class, float* dst_xyzw, long long cap, int* count) {

@@ -8,6 +8,8 @@ first .. first + count - 1 of the same sequence, moved into the frame of node i,
     edge_information(info_left, q_z)                                     the registration's left-tangent information in the edge's tangent
     guess_from_match(...)                                                the guess of Z a place match stands for
     edge_from_result(result, seq, i, j)                                  the aloam_graph_edge of a result record
+    search_grid(q_g, t_g, radius_m, step_m, yaw_deg, yaw_step_deg)       the pose grid aloam_graph_search_loops scores around a guess
+    search_best(scores, centre)                                          the node it takes
     room_sample(rng, ...), sensor_cloud(world, q, t, rng)                the hand-made scene the tests and tools/loop_register_rate.py share
 
 The registration itself (association, fits, Levenberg-Marquardt) is the mapping step's; tests/loopreg_model.py composes it from the
@@ -15,10 +17,13 @@ oracle's pieces.  Everything here is float64 numpy on the host.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 from . import places
 from .atlas import associate_to_map
+from .relocalize import grid_axes
 from .posegraph import EDGE_ROBUST, MARGINAL_MEASURED, MARGINAL_REQUEST_DTYPE, compose, info_full, info_upper, inverse, make_edges, qrot, relative_pose, rotmat
 
 LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
@@ -96,6 +101,57 @@ def request_from_result(result, i, j, seq):
     return r
 
 
+SEARCH_MAX_YAW, SEARCH_MAX_NODES = 31, 1 << 14   # yaw steps to either side, nodes of one grid (aloam_graph_search_loops)
+
+
+def search_grid(q_g, t_g, radius_m, step_m, yaw_deg, yaw_step_deg):
+    """The grid of aloam_graph_search_loops around the guess (q_g, t_g) of Z, the pose of node j in the frame of node i: (q [K, 4], t [K, 3],
+    nodes [K, 3] int = ix, iy, iyaw).  The axes are relocalize.grid_axes; K = (2a + 1)(2m + 1)^2, yaw outermost, then y, then x, as
+    relocalize.correction_grid orders them.  Node (ix, iy, iyaw) turns the guess by dyaw = iyaw * yaw_step_deg about the z axis of node i's
+    frame through the guessed sensor position, then shifts it by (ix * step_m, iy * step_m, 0): q_c = dq q_g (Hamilton product, evaluated
+    left to right as the device's quat_mul) with dq = (0, 0, sin h, cos h), h = (dyaw * (pi / 180)) / 2, t_c = t_g + (dx, dy, 0); every
+    operation a separately rounded f64 operation.  iyaw == 0 keeps q_g itself and a zero index keeps its coordinate: the centre node is the
+    guess bit for bit.  math.sin / math.cos are the C library's, which is what the host side of the call fills its table with."""
+    q_g, t_g = np.asarray(q_g, np.float64), np.asarray(t_g, np.float64)
+    lin, yaw = grid_axes(radius_m, step_m, yaw_deg, yaw_step_deg)
+    m, a = (len(lin) - 1) // 2, (len(yaw) - 1) // 2
+    if a > SEARCH_MAX_YAW or not 1 <= len(yaw) * len(lin) * len(lin) <= SEARCH_MAX_NODES:
+        raise ValueError("a search grid has at most 31 yaw steps to either side and 2^14 nodes")
+    step_m, yaw_step_deg = float(step_m), float(yaw_step_deg)
+    qs, ts, nodes = [], [], []
+    for iyaw in range(-a, a + 1):
+        if iyaw == 0:
+            q = q_g.copy()
+        else:
+            h = ((float(iyaw) * yaw_step_deg) * (math.pi / 180.0)) / 2
+            d = (0.0, 0.0, math.sin(h), math.cos(h))
+            b = [float(v) for v in q_g]
+            q = np.array([d[3] * b[0] + d[0] * b[3] + d[1] * b[2] - d[2] * b[1],
+                          d[3] * b[1] + d[1] * b[3] + d[2] * b[0] - d[0] * b[2],
+                          d[3] * b[2] + d[2] * b[3] + d[0] * b[1] - d[1] * b[0],
+                          d[3] * b[3] - d[0] * b[0] - d[1] * b[1] - d[2] * b[2]])
+        for iy in range(-m, m + 1):
+            for ix in range(-m, m + 1):
+                t = t_g.copy()
+                if ix != 0:
+                    t[0] = t[0] + float(ix) * step_m
+                if iy != 0:
+                    t[1] = t[1] + float(iy) * step_m
+                qs.append(q); ts.append(t); nodes.append((ix, iy, iyaw))
+    return np.array(qs), np.array(ts), np.array(nodes, np.int64).reshape(-1, 3)
+
+
+def search_best(scores, centre):
+    """The node aloam_graph_search_loops takes: the ranking of aloam_score_map_corrections - most corner_factors + surf_factors, then the
+    lower cost (NaN ranks as +infinity), then the lower index - and, when even the winner has no factor, the centre node (the guess; index
+    0 is a corner of the grid).  scores: a structured array or a sequence of mappings with the fields of aloam_map_score."""
+    def key(c):
+        cost = float(scores[c]["cost"])
+        return (-(int(scores[c]["corner_factors"]) + int(scores[c]["surf_factors"])), cost if cost == cost else math.inf, c)
+    w = min(range(len(scores)), key=key)
+    return w if int(scores[w]["corner_factors"]) + int(scores[w]["surf_factors"]) > 0 else int(centre)
+
+
 def room_sample(rng, n_corner=300, n_surf=1500):
     """A random sample, in world coordinates (corner [n, 3], surf [m, 3], float64), of the room the loop-registration tests and
     tools/loop_register_rate.py share: a floor (x -5 .. 15, y -6 .. 6), two perpendicular walls (y = 6 and x = 15, 3 m high), four vertical
@@ -126,4 +182,4 @@ def sensor_cloud(world_xyz, q, t, rng):
 
 
 __all__ = ["EDGE_ROBUST", "LOOP_OK", "LOOP_NO_CLOUDS", "LOOP_TARGET_TOO_SMALL", "LOOP_TOO_LARGE", "LOOP_SOLVE_FAILED", "target_poses", "target_cloud",
-           "gate", "edge_information", "guess_from_match", "edge_from_result", "room_sample", "sensor_cloud"]
+           "gate", "edge_information", "guess_from_match", "edge_from_result", "search_grid", "search_best", "room_sample", "sensor_cloud"]

@@ -939,6 +939,65 @@ int aloam_graph_loops_enable(aloam_ctx* ctx, int max_requests, int max_target_co
 int aloam_graph_register_loops(aloam_ctx* ctx, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt,
                                aloam_graph_loop_result* dst /* [n] */);
 
+/* ---- a pose grid searched around a loop guess ---------------------------------------------------------------------------------------------
+ * aloam_graph_register_loops converges from a guess inside the registration's basin: a source point is kept only when its fifth neighbour
+ * lies within 1 m, so the basin is a few decimetres and a few degrees.  A place match gives the guess to 6 degrees of yaw and puts the
+ * sweep AT the stored place; a revisit in the other lane, or after metres of drift, is metres off, and the registration then ends
+ * somewhere with status ALOAM_LOOP_OK.  aloam_graph_search_loops searches a grid of poses around every request's guess first, scores each
+ * node by what the registration's first association would count from it, and runs the registration from the best node: one stream-ordered
+ * call, no host synchronisation.  Opt-in and beside the reference: aloam_graph_register_loops keeps its behaviour and its launches, and a
+ * context that never calls aloam_graph_search_loops allocates and launches exactly what it did before.  a-loam_amd/loopreg.py restates the
+ * definition as search_grid() / search_best(); DESIGN.md §7q.
+ *
+ * For a request (seq, i, j, first, count, pose, guess q_g, t_g) and a grid (radius_m, step_m, yaw_deg, yaw_step_deg); every f64
+ * operation is separately rounded:
+ *   - axes: m = floor(radius_m / step_m + 1e-9), or 0 when step_m == 0; a = floor(yaw_deg / yaw_step_deg + 1e-9), or 0 when
+ *     yaw_step_deg == 0.  K = (2a + 1)(2m + 1)^2 nodes, yaw outermost, then y, then x: node (ix, iy, iyaw), each index symmetric about 0,
+ *     has index ((iyaw + a)(2m + 1) + (iy + m))(2m + 1) + (ix + m).
+ *   - a node's pose: dx = ix * step_m, dy = iy * step_m, dyaw = iyaw * yaw_step_deg.  Z is the pose of node j in the frame of node i; the
+ *     node turns the guess about the z axis of node i's frame through the guessed sensor position, then shifts it along node i's x and
+ *     y: q_c = dq q_g (Hamilton product) with dq = (0, 0, sin h, cos h), h = (dyaw * (pi / 180)) / 2, and t_c = t_g + (dx, dy, 0).  For
+ *     iyaw == 0 the quaternion is q_g itself and a zero offset leaves its coordinate untouched: the centre node is the guess bit for bit.
+ *     Roll, pitch and z are not searched.  sin h and cos h are computed on the host (the C library's sin / cos) and reach the kernel as a
+ *     table, so a model that calls the same library scores the same poses bit for bit; hence a <= 31.
+ *   - a score: the aloam_map_score of aloam_score_map_corrections taken at `parameters` = (q_c, t_c) directly (a slot has no odometry
+ *     frame, so there is no transformAssociateToMap).  For every source point - node j's two clouds as stored - associate-to-map, the five
+ *     nearest in the filtered target by (f32 distance, index), all closer than 1 m, the line test or the plane fit, and each valid
+ *     factor's residual under HuberLoss(0.1) at that pose.  The counts are those of round 0 of a registration started from that node, as
+ *     integers.
+ *   - ranking: the rule of aloam_score_map_corrections - most corner_factors + surf_factors, then the lower cost (NaN ranks as
+ *     +infinity), then the lower index - with one addition: if the winner has zero factors, the centre node (the guess) is taken, not
+ *     index 0, which is a corner of the grid.
+ *   - registration: `parameters` := the best node's pose; everything after that is aloam_graph_register_loops as it is (outer_iterations
+ *     rounds, the evaluation, the information).  For every status but ALOAM_LOOP_OK, Z in the loop result is still the request's guess.
+ *   - skipped: a slot whose status before the solve is not ALOAM_LOOP_OK (NO_CLOUDS, TOO_LARGE, TARGET_TOO_SMALL) is not searched: best =
+ *     -1, zero scores, q, t equal to the guess.
+ * The request checks are those of aloam_graph_register_loops.  search NULL = the defaults; its values finite and >= 0, a <= 31 and
+ * 1 <= K <= 2^14, else ALOAM_E_ARG.  search_dst [n] and scores ([n][K], may be NULL) are device memory of the context's device or pinned
+ * host memory, 8-byte aligned, classified like dst.  Everything is checked before anything is queued; n = 0 is ALOAM_OK; ALOAM_E_STATE
+ * before aloam_graph_loops_enable.  A round holds at most min(max_requests, 2^18 / K) requests.  The search scratch (32 bytes x 4 per
+ * request and node of a round) is allocated by the first call that needs it and grown by a larger one; when that fails it is ALOAM_E_HIP
+ * and nothing of it stays allocated.
+ * Determinism: a node's score, best, and every bit of dst[r] and search_dst[r] do not depend on n, on the position in the list, on the
+ * round, on the other requests or on the rest of the grid; a node's score depends only on its pose and the slot's clouds.  Counts are
+ * integer sums; the cost is summed in a fixed order that depends on the source clouds alone; no floating-point atomics.  With a grid of
+ * one node (radius_m = yaw_deg = 0) dst is byte for byte what aloam_graph_register_loops writes for the same requests. */
+typedef struct aloam_graph_loop_search {        /* 32 bytes: the grid around every request's guess */
+  double radius_m, step_m, yaw_deg, yaw_step_deg;
+} aloam_graph_loop_search;
+typedef struct aloam_graph_loop_search_result { /* 160 bytes */
+  int status;                 /* the plan / gate status the search saw (ALOAM_LOOP_*) */
+  int nodes, best;            /* K; index of the node taken, -1 when nothing was searched */
+  int ix, iy, iyaw;           /* its grid indices */
+  int pad[2];
+  double q[4], t[3], reserved;              /* the pose the registration started from */
+  aloam_map_score best_score, guess_score;  /* of that node and of the centre node */
+} aloam_graph_loop_search_result;
+void aloam_graph_loop_default_search(aloam_graph_loop_search* s);   /* 3.0, 0.5, 12.5, 2.5 (relocalize()'s steps) */
+int aloam_graph_search_loops(aloam_ctx* ctx, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_search* search,
+                             const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst /* [n] */,
+                             aloam_graph_loop_search_result* search_dst /* [n] */, aloam_map_score* scores /* [n][K] or NULL */);
+
 /* ---- pose-graph marginals: the covariance of an edge's residual under the graph, and its chi-square --------------------------------------
  * aloam_graph_register_loops measures a loop edge; whether it is a GOOD loop is decided here.  s = r^T Omega r is not the test: after a
  * long drive the graph's own uncertainty about X_i^-1 o X_j dominates a correct edge's residual.  The test is the innovation

@@ -1,7 +1,7 @@
 """tools/loop_closure_drive.py — a loop closure inside one drive, with nothing but calls the project already has ("A loop
 edge inside a drive").
 
-    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops]
+    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -21,6 +21,9 @@ device_loop_edge beside loop_edge, with its error against ground truth, its wall
 loopreg.request_from_result): its chi2 = r^T (Sigma_r + Omega^-1)^-1 r against posegraph.chi2_gate() and the verdict are printed as
 device_loop_gate, beside the same for a copy of the edge displaced by 1.5 m.  The edge that goes into the graph is still the spare-slot
 route's: the default path is unchanged.
+
+With --device-loops --search the match's guess is also searched (aloam_graph_search_loops, the default grid): the best node, its score and
+the guess's, and the edge's error are printed as device_loop_search beside device_loop_edge, the unsearched call from the same guess.
 
 With --apply the whole chain runs twice, and both runs drive on for another quarter lap behind the solve: one after aloam_graph_apply of
 all nodes (pose and map), one without it.  Reported for each, without judging them: the ATE of the live map pose over the continued sweeps,
@@ -67,6 +70,7 @@ def main():
     ap.add_argument("--frozen-steps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--device-loops", action="store_true", help="also measure the edge with aloam_graph_register_loops from the same match, and print it beside the spare-slot route's")
+    ap.add_argument("--search", action="store_true", help="with --device-loops: also search a pose grid around the match's guess (aloam_graph_search_loops) and print it beside the unsearched call")
     ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
     args = ap.parse_args()
 
@@ -152,6 +156,18 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
             out["device_loop_edge"] = {"status": int(r["status"]), "n_line": int(r["n_line"]), "n_plane": int(r["n_plane"]), "target_points": r["target_points"].tolist(),
                                        "cost": float(r["cost"]), "guess_error_m": float(np.linalg.norm(tg - tz)), "translation_error_m": float(np.linalg.norm(r["t"] - tz)),
                                        "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dq[:3]))))), "call_and_synchronize_ms": call_ms}
+            if args.search:
+                stage = "graph_search_loops"
+                t0 = time.perf_counter()
+                rs, ss = gpu.graph_search_loops([(0, i, j, lo, hi - lo, binding.GRAPH_POSE_OPTIMIZED, qg, tg)])
+                search_ms = 1e3 * (time.perf_counter() - t0)
+                rs, ss = rs[0], ss[0]
+                dqs = pg.qmul(pg.qconj(qz), rs["q"])
+                score = lambda v: {k: (float(v[k]) if k == "cost" else int(v[k])) for k in ("corner_factors", "surf_factors", "corner_found", "surf_found", "cost")}
+                out["device_loop_search"] = {"status": int(rs["status"]), "nodes": int(ss["nodes"]), "best": int(ss["best"]), "best_node": [int(ss["ix"]), int(ss["iy"]), int(ss["iyaw"])],
+                                             "best_score": score(ss["best_score"]), "guess_score": score(ss["guess_score"]), "n_line": int(rs["n_line"]), "n_plane": int(rs["n_plane"]),
+                                             "translation_error_m": float(np.linalg.norm(rs["t"] - tz)), "unsearched_translation_error_m": float(np.linalg.norm(r["t"] - tz)),
+                                             "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dqs[:3]))))), "call_and_synchronize_ms": search_ms}
             # the gate: the measured edge, and a copy displaced by 1.5 m, against the graph's own uncertainty about X_i^-1 o X_j
             stage = "graph_marginals"
             rq = lr.request_from_result(r, i, j, 0)

@@ -1,6 +1,6 @@
 """tools/loop_register_rate.py — what one aloam_graph_register_loops call costs.
 
-    python tools/loop_register_rate.py [--shapes 1,256,2048] [--sequences 16] [--repeats 5] [--out FILE.json]
+    python tools/loop_register_rate.py [--shapes 1,256,2048] [--sequences 16] [--repeats 5] [--search R STEP YAW YAWSTEP] [--out FILE.json]
 
 Every sequence holds 14 hand-made keyframes of a room (loopreg.room_sample: a floor, two walls, four poles, two edges; about 300 corner and 1500 surf points fed
 per keyframe, VLP-16-sized, down-sampled by a mapping step with the solver off): 13 target nodes along 8 m and one source node entered
@@ -13,6 +13,11 @@ with the statuses, the mean factor counts and the mean translation error before 
 aloam_graph_loops_enable took for the largest shape.  The spare-slot route of one edge is timed by
 tools/loop_closure_drive.py --device-loops, in the same process as the call it replaces.  For a per-kernel profile run this tool under
 rocprofv3 --kernel-trace --stats.  Prints one JSON object.
+
+--search R STEP YAW YAWSTEP: the same shapes with FAR guesses (the truth moved by (2.2, -1.6, 0.08) m and turned by 11 degrees) through
+aloam_graph_search_loops with that grid (metres, metres, degrees, degrees).  Per shape, under "search": queue_ms, call_ms and stream_ms of
+the searched call, nodes per request, us_per_request_node, the mean error, and beside them ("plain") the plain call from the same far
+guesses.
 """
 from __future__ import annotations
 
@@ -38,6 +43,8 @@ def main():
     ap.add_argument("--shapes", default="1,256,2048", help="requests per call, comma-separated")
     ap.add_argument("--sequences", type=int, default=16, help="sequences the requests are spread over")
     ap.add_argument("--repeats", type=int, default=5, help="timed calls per shape (median, min and max are reported)")
+    ap.add_argument("--search", nargs=4, type=float, metavar=("R", "STEP", "YAW", "YAWSTEP"), default=None,
+                    help="time aloam_graph_search_loops with this grid (m, m, deg, deg) from far guesses, the plain call beside it")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -81,6 +88,46 @@ def main():
     res = {"sequences": B, "target_nodes": TARGETS, "points_per_keyframe": [held["points"][0] / (TARGETS + 1), held["points"][1] / (TARGETS + 1)],
            "guess_error_m": float(np.linalg.norm(tg - tz)), "scratch_slots": max(shapes), "scratch_bytes": int(scratch), "shapes": []}
     size = binding.GRAPH_LOOP_RESULT_DTYPE.itemsize
+    stat = lambda v: {"median": float(np.median(v)), "min": min(v), "max": max(v)}
+
+    def timed(call):
+        call()                                                             # (warm-up: the first launch of every kernel, the scratch)
+        gpu.synchronize()
+        queue_ms, call_ms, stream_ms = [], [], []
+        for _ in range(args.repeats):
+            gpu.profile_enable(True)
+            t0 = time.perf_counter()
+            call()
+            t1 = time.perf_counter()
+            gpu.synchronize()
+            t2 = time.perf_counter()
+            queue_ms.append(1e3 * (t1 - t0))
+            call_ms.append(1e3 * (t2 - t0))
+            stream_ms.append(gpu.profile()["loop_register"]["total_ms"])
+        gpu.profile_enable(False)
+        return {"queue_ms": stat(queue_ms), "call_ms": stat(call_ms), "stream_ms": stat(stream_ms)}
+
+    if args.search:
+        grid = gpu.graph_loop_search(radius_m=args.search[0], step_m=args.search[1], yaw_deg=args.search[2], yaw_step_deg=args.search[3])
+        K = len(lr.search_grid(qz, tz, *args.search)[0])
+        qf = pg.qmul(yaw(math.radians(11.0)), qz)
+        qf, tf = qf / np.linalg.norm(qf), tz + np.array([2.2, -1.6, 0.08])
+        res.update(search=list(args.search), nodes_per_request=K, far_guess_error_m=float(np.linalg.norm(tf - tz)))
+        ssize = binding.GRAPH_LOOP_SEARCH_RESULT_DTYPE.itemsize
+        for n in shapes:
+            reqs = gpu.graph_loop_requests([(r % B, i, j, 0, TARGETS, binding.GRAPH_POSE_ENTERED, qf, tf) for r in range(n)])
+            dst = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
+            sdst = torch.zeros(n * ssize, dtype=torch.uint8, device="cuda")
+            opt = gpu.graph_loop_options()
+            plain = timed(lambda: gpu.graph_register_loops_into(reqs, dst.data_ptr(), opt))
+            plain["error_m"] = float(np.linalg.norm(dst.cpu().numpy().view(binding.GRAPH_LOOP_RESULT_DTYPE)["t"] - tz, axis=1).mean())
+            found = timed(lambda: gpu.graph_search_loops_into(reqs, dst.data_ptr(), sdst.data_ptr(), 0, grid, opt))
+            out, sout = dst.cpu().numpy().view(binding.GRAPH_LOOP_RESULT_DTYPE), sdst.cpu().numpy().view(binding.GRAPH_LOOP_SEARCH_RESULT_DTYPE)
+            found.update(error_m=float(np.linalg.norm(out["t"] - tz, axis=1).mean()), nodes=K, us_per_request_node=1e3 * found["stream_ms"]["median"] / (n * K),
+                         best=sorted({int(b) for b in sout["best"]}), statuses={int(s): int(c) for s, c in zip(*np.unique(out["status"], return_counts=True))},
+                         factors=[float(out["n_line"].mean()), float(out["n_plane"].mean())])
+            res["shapes"].append({"requests": n, "search": found, "plain": plain})
+        shapes = []
     for n in shapes:
         reqs = gpu.graph_loop_requests([(r % B, i, j, 0, TARGETS, binding.GRAPH_POSE_ENTERED, qg, tg) for r in range(n)])
         dst = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
@@ -100,7 +147,6 @@ def main():
             stream_ms.append(gpu.profile()["loop_register"]["total_ms"])
         gpu.profile_enable(False)
         out = dst.cpu().numpy().view(binding.GRAPH_LOOP_RESULT_DTYPE)
-        stat = lambda v: {"median": float(np.median(v)), "min": min(v), "max": max(v)}
         res["shapes"].append({"requests": n, "statuses": {int(s): int(c) for s, c in zip(*np.unique(out["status"], return_counts=True))},
                               "target_raw": out["target_raw"].mean(0).tolist(), "target_points": out["target_points"].mean(0).tolist(),
                               "factors": [float(out["n_line"].mean()), float(out["n_plane"].mean())],
