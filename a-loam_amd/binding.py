@@ -128,7 +128,7 @@ class AloamGraphLoopResult(C.Structure):
 
 
 class AloamMapScore(C.Structure):
-    """What one pose counts against a bucketed target (aloam_map_score, 32 bytes)."""
+    """What one pose counts against a bucketed target: a (sequence, candidate) pair, a node of a loop search (aloam_map_score, 32 bytes)."""
     _fields_ = [("corner_factors", C.c_int), ("surf_factors", C.c_int), ("corner_found", C.c_int), ("surf_found", C.c_int), ("cost", C.c_double), ("pad", C.c_int * 2)]
 
 
@@ -196,12 +196,6 @@ GRAPH_MARGINAL_RESULT_DTYPE = np.dtype([("status", np.int32), ("mode", np.int32)
 class AloamMapCorrection(C.Structure):
     """One candidate map <- odometry correction (aloam_map_correction, 64 bytes)."""
     _fields_ = [("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3), ("pad", C.c_double)]
-
-
-class AloamMapScore(C.Structure):
-    """The score of one (sequence, candidate) pair (aloam_map_score, 32 bytes)."""
-    _fields_ = [("corner_factors", C.c_int), ("surf_factors", C.c_int), ("corner_found", C.c_int), ("surf_found", C.c_int),
-                ("cost", C.c_double), ("pad", C.c_int * 2)]
 
 
 class AloamMapTile(C.Structure):

@@ -19,18 +19,13 @@ hipEvent_t prof_event(aloam_ctx* c) {
   return c->prof_events.back();
 }
 
-// n ints to device memory through the pinned ring: returns at once, the H2D copy runs in stream order (the slot is reused kNinSlots calls later,
-// after the copy that read it has run).
+// n ints to device memory through the pinned ring c->nin: returns at once, the H2D copy runs in stream order.
 int stage_ints(aloam_ctx* c, const int* src, int n, int* dst) {
-  const int ns = c->h_nin_slot;
-  c->h_nin_slot = (ns + 1) % kNinSlots;
-  int* slot = c->h_nin.get() + (size_t)ns * c->B;
-  if (c->nin_used[ns]) HIP_TRY(c, hipEventSynchronize(c->nin_done[ns]));   // the copy queued kNinSlots launches ago has read it
+  int* slot = nullptr;
+  int ns = 0;
+  if (const int rc = c->nin.acquire(c, &slot, &ns)) return rc;
   std::memcpy(slot, src, sizeof(int) * n);
-  HIP_TRY(c, hipMemcpyAsync(dst, slot, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(c->nin_done[ns], c->stream));
-  c->nin_used[ns] = true;
-  return ALOAM_OK;
+  return c->nin.queue(c, ns, slot, sizeof(int) * n, dst, c->stream);
 }
 
 int check_seq(aloam_ctx* c, int seq) {
@@ -134,8 +129,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
   c->npad = cfg->max_ring_points <= 2059 ? 2048 : 4096;
   const size_t B = c->B, cap = c->cap, R = c->R, NB = c->NB;
   int rc = 0;
-  { int* p = nullptr; HIP_TRY(c, hipHostMalloc((void**)&p, sizeof(int) * B * kNinSlots, hipHostMallocDefault)); c->h_nin.reset(p); }
-  for (Event& e : c->nin_done) HIP_TRY(c, hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+  if (const char* what = c->nin.create(sizeof(int) * B)) { c->err = std::string("input counts, ") + what; return ALOAM_E_HIP; }
   const bool reg = stages & ALOAM_STAGE_REGISTRATION, odo = stages & ALOAM_STAGE_ODOMETRY, map = stages & ALOAM_STAGE_MAPPING;
   // hash tables of the correspondence search sized by the clouds they index (power of two; the surf table must fit k_build_grids' LDS)
   c->grid_H[0] = R > 64 ? 8192 : 4096;
@@ -394,17 +388,17 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
       }
     }
     // the last aloam_graph_optimize: nodes and edges read once, the estimates and one result written (the iterations run out of L2)
-    if (kernel == K_POSE_GRAPH) bytes = (double)(sizeof(aloam_graph_node) + 56) * c->pg_last_nodes + (double)sizeof(aloam_graph_edge) * c->pg_last_edges;
+    if (kernel == K_POSE_GRAPH) bytes = (double)(sizeof(aloam_graph_node) + 56) * c->pg.last_nodes + (double)sizeof(aloam_graph_edge) * c->pg.last_edges;
     // the last aloam_graph_marginals: per request its graph's estimates and edges read once, one request read and one result written (the
     // linearisation and the iterations run out of the request's scratch row)
     if (kernel == K_GRAPH_MARGINALS)
-      bytes = 56.0 * c->mg_last_nodes + (double)sizeof(aloam_graph_edge) * c->mg_last_edges + (double)(sizeof(GraphMarginalItem) + sizeof(aloam_graph_marginal_result)) * c->mg_last_n;
+      bytes = 56.0 * c->mg.last_nodes + (double)sizeof(aloam_graph_edge) * c->mg.last_edges + (double)(sizeof(GraphMarginalItem) + sizeof(aloam_graph_marginal_result)) * c->mg.last_n;
     // the last aloam_graph_export_map: 16 B read + 16 B written per raw point (transform), the slot written and read and the point read and
     // written again (grouping, 40 B), 16 B per emitted point and 32 B per tile
-    if (kernel == K_GRAPH_MAP && c->gm_last_segs >= 0) {
+    if (kernel == K_GRAPH_MAP && c->gm.last_segs >= 0) {
       long long emitted = 0;
-      HIP_TRY(c, hipMemcpy(&emitted, c->d_gm_point_off.get() + c->gm_last_segs, sizeof(emitted), hipMemcpyDeviceToHost));
-      bytes = 72.0 * c->gm_last_raw + 16.0 * emitted + 32.0 * c->gm_last_segs;
+      HIP_TRY(c, hipMemcpy(&emitted, c->gm.point_off.get() + c->gm.last_segs, sizeof(emitted), hipMemcpyDeviceToHost));
+      bytes = 72.0 * c->gm.last_raw + 16.0 * emitted + 32.0 * c->gm.last_segs;
     }
     if (kernel == K_APPLY) bytes = c->rl_apply_n * (4.0 + 4.0 + 64.0 + 56.0);   // id, choice, candidate in, correction out
     *algorithmic_bytes = bytes;

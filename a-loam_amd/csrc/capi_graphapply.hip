@@ -13,15 +13,11 @@ int aloam_graph_apply(aloam_ctx* c, const aloam_graph_apply_request* req, int n,
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
   // ---- everything is checked before anything is queued
-  if (!c->graph_on) { c->err = "aloam_graph_apply before aloam_graph_enable"; return ALOAM_E_STATE; }
+  if (!c->pg.on) { c->err = "aloam_graph_apply before aloam_graph_enable"; return ALOAM_E_STATE; }
   if (!c->map_on) { c->err = "aloam_graph_apply before aloam_mapping_enable"; return ALOAM_E_STATE; }
   if (n < 0 || n > c->B || (n > 0 && !req)) { c->err = "bad request list (0 <= n <= batch)"; return ALOAM_E_ARG; }
   if (n == 0) return ALOAM_OK;
-  {
-    void* dev = nullptr;
-    const CallerMem m = classify_pointer(c, req, &dev);
-    if (m != kMemPageable && m != kMemPinned) { c->err = "req must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
-  }
+  if (const int rc = require_host_list(c, req, "req")) return rc;
   std::vector<char> listed((size_t)c->B, 0);
   bool any_map = false;
   for (int r = 0; r < n; ++r) {
@@ -34,7 +30,7 @@ int aloam_graph_apply(aloam_ctx* c, const aloam_graph_apply_request* req, int n,
     if (q.flags != ALOAM_GRAPH_APPLY_POSE && q.flags != (ALOAM_GRAPH_APPLY_POSE | ALOAM_GRAPH_APPLY_MAP)) return fail("flags must be ALOAM_GRAPH_APPLY_POSE or ALOAM_GRAPH_APPLY_POSE | ALOAM_GRAPH_APPLY_MAP");
     any_map |= (q.flags & ALOAM_GRAPH_APPLY_MAP) != 0;
   }
-  if (any_map && !c->kf_on) { c->err = "ALOAM_GRAPH_APPLY_MAP before aloam_graph_keyframes_enable"; return ALOAM_E_STATE; }
+  if (any_map && !c->kf.on) { c->err = "ALOAM_GRAPH_APPLY_MAP before aloam_graph_keyframes_enable"; return ALOAM_E_STATE; }
   for (int r = 0; r < n; ++r) {
     const SeqHost& s = c->seq[req[r].seq];
     if (s.frozen || s.attached) {
@@ -57,23 +53,23 @@ int aloam_graph_apply(aloam_ctx* c, const aloam_graph_apply_request* req, int n,
     seqs[(size_t)r] = q.seq;
   }
   int rc;
-  if ((rc = grow_scratch(c, c->d_ga_items, c->ga_items_cap, (long long)c->B))) return rc;
+  if ((rc = c->ga.items.grow(c, c->B))) return rc;
   const int n_maps = (int)maps.size();
   if (n_maps > 0) {
-    if ((rc = grow_scratch(c, c->d_ga_off, c->ga_off_cap, 2LL * c->B + 2))) return rc;
+    if ((rc = c->ga.off.grow(c, 2LL * c->B + 2))) return rc;
     // transform, group, filter and offsets into the scratch of the map pass; nothing is emitted (caps of 0).  Synchronises.
-    if ((rc = aloam_graph_export_map(c, maps.data(), n_maps, nullptr, 0, nullptr, 0, c->d_ga_off.get(), nullptr))) return rc;
+    if ((rc = aloam_graph_export_map(c, maps.data(), n_maps, nullptr, 0, nullptr, 0, c->ga.off.get(), nullptr))) return rc;
     // One more synchronisation: the filtered size of every (request, class, cube) comes back.  Where the sensor will be is known on the
     // device only, so a pool row is sized for the largest 21 x 21 x 11 box of each map (the sliding sums of aloam_atlas_load).
-    const int n_segs = c->gm_last_segs;
+    const int n_segs = c->gm.last_segs;
     std::vector<GmRequestOut> out((size_t)n_maps + 1);
     std::vector<GmSegInfo> seg((size_t)std::max(n_segs, 0));
     std::vector<int> cnt(seg.size());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out.data(), c->d_gm_req_out.get(), sizeof(GmRequestOut) * out.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out.data(), c->gm.req_out.get(), sizeof(GmRequestOut) * out.size(), hipMemcpyDeviceToHost));
     if (n_segs > 0) {
-      HIP_TRY(c, hipMemcpy(seg.data(), c->d_gm_seg.get(), sizeof(GmSegInfo) * seg.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(c, hipMemcpy(cnt.data(), c->d_gm_counts.get(), sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(c, hipMemcpy(seg.data(), c->gm.seg.get(), sizeof(GmSegInfo) * seg.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(c, hipMemcpy(cnt.data(), c->gm.counts.get(), sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
     }
     long long need[2] = {0, 0};
     for (int m = 0; m < n_maps; ++m)
@@ -97,13 +93,13 @@ int aloam_graph_apply(aloam_ctx* c, const aloam_graph_apply_request* req, int n,
     for (int k = 0; k < 2; ++k) c->h_map_report[1 + k] = std::max((int)c->h_map_report[1 + k], (int)need[k]);   // the pools are sized from this until the next step reports
   }
   // ---- from here everything is stream-ordered
-  HIP_TRY(c, hipMemcpyAsync(c->d_ga_items.get(), items.data(), sizeof(GaItem) * items.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->ga.items.get(), items.data(), sizeof(GaItem) * items.size(), hipMemcpyHostToDevice, c->stream));
   GraphApplyArgs a{};
-  a.n = n; a.items = c->d_ga_items.get();
-  a.nodes = c->d_pg_nodes.get(); a.max_nodes = c->pg_max_nodes;
+  a.n = n; a.items = c->ga.items.get();
+  a.nodes = c->pg.nodes.get(); a.max_nodes = c->pg.max_nodes;
   a.seq = c->d_mapseq.get(); a.cubes = c->d_cubes.get();
   a.pool[0] = c->map.pool[0].get(); a.pool[1] = c->map.pool[1].get(); a.pool_cap = c->map.points;
-  a.req = c->d_gm_req_out.get(); a.jobs = c->d_gm_jobs.get(); a.seg = c->d_gm_seg.get(); a.counts = c->d_gm_counts.get(); a.grouped = c->d_gm_grouped.get();
+  a.req = c->gm.req_out.get(); a.jobs = c->gm.jobs.get(); a.seg = c->gm.seg.get(); a.counts = c->gm.counts.get(); a.grouped = c->gm.grouped.get();
   a.dst = static_cast<aloam_graph_apply_result*>(d_dst);
   {
     ProfScope p(c, K_GRAPH_MAP);

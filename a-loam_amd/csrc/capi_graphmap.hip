@@ -9,26 +9,26 @@
 #include "capi_internal.hpp"
 
 static int require_keyframes(aloam_ctx* c) {
-  if (!c->kf_on) { c->err = "keyframe clouds are not enabled (aloam_graph_keyframes_enable)"; return ALOAM_E_STATE; }
+  if (!c->kf.on) { c->err = "keyframe clouds are not enabled (aloam_graph_keyframes_enable)"; return ALOAM_E_STATE; }
   return ALOAM_OK;
 }
 
-static KfStore kf_store(aloam_ctx* c) {
+KfStore aloam::kf_store(aloam_ctx* c) {
   KfStore k{};
-  k.points[0] = c->d_kf_points[0].get(); k.points[1] = c->d_kf_points[1].get(); k.desc = c->d_kf_desc.get(); k.counters = c->d_kf_counters.get();
-  k.cap[0] = c->kf_cap[0]; k.cap[1] = c->kf_cap[1]; k.max_nodes = c->pg_max_nodes;
+  k.points[0] = c->kf.points[0].get(); k.points[1] = c->kf.points[1].get(); k.desc = c->kf.desc.get(); k.counters = c->kf.counters.get();
+  k.cap[0] = c->kf.cap[0]; k.cap[1] = c->kf.cap[1]; k.max_nodes = c->pg.max_nodes;
   return k;
 }
 
-// Scratch that several buffers share one size for: all released, then all allocated anew (their contents are not needed).
-template <typename... T>
-static int grow_together(aloam_ctx* c, long long& have, long long need, DevBuf<T>&... p) {
-  if (have >= need) return ALOAM_OK;
-  have = 0;
-  (p.reset(), ...);
-  const bool ok = ((dalloc(p, (size_t)need) == hipSuccess) && ...);
-  if (!ok) { (void)hipGetLastError(); (p.reset(), ...); c->err = "map at the graph's poses: scratch allocation failed"; return ALOAM_E_HIP; }
-  have = need;
+// Two scratch buffers that share one size: both released, then both allocated anew (their contents are not needed), or neither.
+template <typename T>
+static int grow_together(aloam_ctx* c, Scratch<T>& a, Scratch<T>& b, long long need) {
+  if (a.cap >= need && b.cap >= need) return ALOAM_OK;
+  a.release(); b.release();
+  if (dalloc(a.p, (size_t)need) != hipSuccess || dalloc(b.p, (size_t)need) != hipSuccess) {
+    (void)hipGetLastError(); a.release(); b.release(); c->err = "map at the graph's poses: scratch allocation failed"; return ALOAM_E_HIP;
+  }
+  a.cap = b.cap = need;
   return ALOAM_OK;
 }
 
@@ -36,7 +36,7 @@ namespace aloam {
 
 // aloam_graph_add_nodes with the store enabled: every listed sequence must hold the stacks of a mapping step.
 int keyframe_add_check(aloam_ctx* c, const int* seqs, int n) {
-  if (!c->kf_on) return ALOAM_OK;
+  if (!c->kf.on) return ALOAM_OK;
   for (int i = 0; i < n; ++i)
     if (!c->seq[seqs[i]].has_stacks) {
       c->err = "sequence " + std::to_string(seqs[i]) + " has not been active in a mapping step since it was created, reset or loaded: it holds no stacks to keep as a keyframe";
@@ -45,11 +45,11 @@ int keyframe_add_check(aloam_ctx* c, const int* seqs, int n) {
   return ALOAM_OK;
 }
 
-// Behind k_graph_add_nodes: d_pg_add holds the (sequence, node) items of the call.
+// Behind k_graph_add_nodes: pg.add holds the (sequence, node) items of the call.
 void queue_keyframe_capture(aloam_ctx* c, int n) {
-  if (!c->kf_on || n <= 0) return;
+  if (!c->kf.on || n <= 0) return;
   KfCaptureArgs a{};
-  a.n = n; a.items = c->d_pg_add.get(); a.mapseq = c->d_mapseq.get();
+  a.n = n; a.items = c->pg.add.get(); a.mapseq = c->d_mapseq.get();
   a.stack[0] = c->d_stack[0].get(); a.stack[1] = c->d_stack[1].get();
   a.stack_row[0] = (long long)c->R * kLessSharpPerRing; a.stack_row[1] = c->cap;
   a.kf = kf_store(c);
@@ -59,21 +59,21 @@ void queue_keyframe_capture(aloam_ctx* c, int n) {
 
 // aloam_graph_clear: the listed sequences' cursors back to 0, in stream order (node 0 of the next drive starts its rows again).
 int queue_keyframe_rewind(aloam_ctx* c, const int* seqs, int n) {
-  if (!c->kf_on) return ALOAM_OK;
-  for (int i = 0; i < n; ++i) HIP_TRY(c, hipMemsetAsync(c->d_kf_counters.get() + (size_t)seqs[i] * kKfInts + kKfCursor, 0, 2 * sizeof(int), c->stream));
+  if (!c->kf.on) return ALOAM_OK;
+  for (int i = 0; i < n; ++i) HIP_TRY(c, hipMemsetAsync(c->kf.counters.get() + (size_t)seqs[i] * kKfInts + kKfCursor, 0, 2 * sizeof(int), c->stream));
   return ALOAM_OK;
 }
 
 // aloam_synchronize: nodes kept without clouds since the last call (0 = none).  The stream has drained.
 int keyframes_dropped_since(aloam_ctx* c, long long* fresh) {
   *fresh = 0;
-  if (!c->kf_on) return ALOAM_OK;
+  if (!c->kf.on) return ALOAM_OK;
   std::vector<int> cnt((size_t)c->B * kKfInts);
-  HIP_TRY(c, hipMemcpy(cnt.data(), c->d_kf_counters.get(), sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(cnt.data(), c->kf.counters.get(), sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
   long long dropped = 0;
   for (int b = 0; b < c->B; ++b) dropped += cnt[(size_t)b * kKfInts + kKfDroppedNodes];
-  *fresh = dropped - c->kf_dropped_reported;
-  c->kf_dropped_reported = dropped;
+  *fresh = dropped - c->kf.dropped_reported;
+  c->kf.dropped_reported = dropped;
   return ALOAM_OK;
 }
 
@@ -84,9 +84,9 @@ extern "C" {
 int aloam_graph_keyframes_enable(aloam_ctx* c, int max_corner_points, int max_surf_points) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  if (!c->graph_on) { c->err = "aloam_graph_keyframes_enable before aloam_graph_enable"; return ALOAM_E_STATE; }
+  if (!c->pg.on) { c->err = "aloam_graph_keyframes_enable before aloam_graph_enable"; return ALOAM_E_STATE; }
   if (!c->map_on) { c->err = "aloam_graph_keyframes_enable before aloam_mapping_enable"; return ALOAM_E_STATE; }
-  if (c->kf_on) { c->err = "keyframe clouds already enabled"; return ALOAM_E_STATE; }
+  if (c->kf.on) { c->err = "keyframe clouds already enabled"; return ALOAM_E_STATE; }
   for (int b = 0; b < c->B; ++b)
     if (c->seq[b].graph_nodes > 0) { c->err = "the graph of sequence " + std::to_string(b) + " already holds nodes: enable the keyframe clouds while every graph is empty"; return ALOAM_E_STATE; }
   if (max_corner_points < 1 || max_corner_points > kKfRowMax || max_surf_points < 1 || max_surf_points > kKfRowMax) {
@@ -94,17 +94,18 @@ int aloam_graph_keyframes_enable(aloam_ctx* c, int max_corner_points, int max_su
     return ALOAM_E_ARG;
   }
   const size_t B = c->B;
-  const bool ok = dalloc(c->d_kf_points[0], B * (size_t)max_corner_points) == hipSuccess && dalloc(c->d_kf_points[1], B * (size_t)max_surf_points) == hipSuccess &&
-                  dalloc(c->d_kf_desc, B * (size_t)c->pg_max_nodes) == hipSuccess && dalloc(c->d_kf_counters, B * kKfInts) == hipSuccess &&
-                  hipMemsetAsync(c->d_kf_counters.get(), 0, sizeof(int) * B * kKfInts, c->stream) == hipSuccess;
-  if (!ok) {                           // nothing stays allocated behind a refusal
+  KeyframeStore k;                     // committed with one move: nothing stays allocated behind a refusal
+  const bool ok = dalloc(k.points[0], B * (size_t)max_corner_points) == hipSuccess && dalloc(k.points[1], B * (size_t)max_surf_points) == hipSuccess &&
+                  dalloc(k.desc, B * (size_t)c->pg.max_nodes) == hipSuccess && dalloc(k.counters, B * kKfInts) == hipSuccess &&
+                  hipMemsetAsync(k.counters.get(), 0, sizeof(int) * B * kKfInts, c->stream) == hipSuccess;
+  if (!ok) {
     (void)hipGetLastError();
-    c->d_kf_points[0].reset(); c->d_kf_points[1].reset(); c->d_kf_desc.reset(); c->d_kf_counters.reset();
     c->err = "keyframe store of " + std::to_string(max_corner_points) + " + " + std::to_string(max_surf_points) + " points per sequence: allocation failed";
     return ALOAM_E_HIP;
   }
-  c->kf_cap[0] = max_corner_points; c->kf_cap[1] = max_surf_points; c->kf_dropped_reported = 0;
-  c->kf_on = true;
+  k.cap[0] = max_corner_points; k.cap[1] = max_surf_points;
+  k.on = true;
+  c->kf = std::move(k);
   return ALOAM_OK;
 }
 
@@ -120,8 +121,8 @@ int aloam_graph_export_keyframes(aloam_ctx* c, int seq, int first, int count, in
   if (const int rc = export_target(c, dst_offsets, alignof(long long), "dst_offsets", &d_off)) return rc;
   if ((points_dst_xyzw || cap_points > 0) && export_target(c, points_dst_xyzw, 16, "points_dst", &d_pts)) return ALOAM_E_ARG;
   KfExportArgs a{};
-  a.desc = c->d_kf_desc.get() + (size_t)seq * c->pg_max_nodes;
-  a.points = c->d_kf_points[feature_class].get() + (size_t)seq * c->kf_cap[feature_class];
+  a.desc = c->kf.desc.get() + (size_t)seq * c->pg.max_nodes;
+  a.points = c->kf.points[feature_class].get() + (size_t)seq * c->kf.cap[feature_class];
   a.first = first; a.count = count; a.cls = feature_class;
   a.dst = static_cast<float4*>(d_pts); a.cap = d_pts ? cap_points : 0; a.dst_off = static_cast<long long*>(d_off);
   launch_keyframe_export(a, c->stream);
@@ -136,8 +137,8 @@ int aloam_graph_keyframe_info(aloam_ctx* c, int seq, long long out[8]) {
   if (const int rc = check_seq(c, seq)) return rc;
   int cnt[kKfInts];
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(cnt, c->d_kf_counters.get() + (size_t)seq * kKfInts, sizeof(cnt), hipMemcpyDeviceToHost));
-  const long long v[8] = {cnt[kKfCursor], cnt[kKfCursor + 1], c->kf_cap[0], c->kf_cap[1], cnt[kKfDroppedNodes], cnt[kKfDroppedPoints], 0, 0};
+  HIP_TRY(c, hipMemcpy(cnt, c->kf.counters.get() + (size_t)seq * kKfInts, sizeof(cnt), hipMemcpyDeviceToHost));
+  const long long v[8] = {cnt[kKfCursor], cnt[kKfCursor + 1], c->kf.cap[0], c->kf.cap[1], cnt[kKfDroppedNodes], cnt[kKfDroppedPoints], 0, 0};
   std::copy(v, v + 8, out);
   return ALOAM_OK;
 }
@@ -149,11 +150,7 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
   if (const int rc = require_keyframes(c)) return rc;
   // ---- everything is checked before anything is queued
   if (n < 0 || n > kGmMaxRequests || (n > 0 && !req)) { c->err = "bad request list (0 <= n <= 32768)"; return ALOAM_E_ARG; }
-  if (n > 0) {
-    void* dev = nullptr;
-    const CallerMem m = classify_pointer(c, req, &dev);
-    if (m != kMemPageable && m != kMemPinned) { c->err = "req must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
-  }
+  if (n > 0) if (const int rc = require_host_list(c, req, "req")) return rc;
   for (int r = 0; r < n; ++r) {
     const aloam_graph_map_request& q = req[r];
     auto fail = [&](const char* what) { c->err = "request " + std::to_string(r) + ": " + what; return ALOAM_E_ARG; };
@@ -176,7 +173,7 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
   for (int r = 0; r < n; ++r) {
     rq[r] = GmRequest{req[r].seq, req[r].first, req[r].count, req[r].pose, {0, 0}};
     for (int cls = 0; cls < 2; ++cls) {
-      const long long bound = std::min<long long>(c->kf_cap[cls], row[cls] * req[r].count);
+      const long long bound = std::min<long long>(c->kf.cap[cls], row[cls] * req[r].count);
       rq[r].at[cls] = bound_points;
       piece_first[2 * r + cls] = n_pieces;
       bound_points += bound;
@@ -186,36 +183,36 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
   }
   piece_first[2 * (size_t)n] = n_pieces;
   int rc;
-  if ((rc = grow_together(c, c->gm_points_cap, std::max<long long>(bound_points, 1), c->d_gm_world, c->d_gm_grouped))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_slot, c->gm_slot_cap, std::max<long long>(bound_points, 1)))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_req, c->gm_req_cap, (long long)std::max(n, 1)))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_req_out, c->gm_req_out_cap, (long long)n + 1))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_ints, c->gm_ints_cap, 3LL * n + 2))) return rc;   // piece_first [2 n + 1], outside [n], flags [1]
-  int* d_piece_first = c->d_gm_ints.get();
+  if ((rc = grow_together(c, c->gm.world, c->gm.grouped, std::max<long long>(bound_points, 1)))) return rc;
+  if ((rc = c->gm.slot.grow(c, std::max<long long>(bound_points, 1)))) return rc;
+  if ((rc = c->gm.req.grow(c, (long long)std::max(n, 1)))) return rc;
+  if ((rc = c->gm.req_out.grow(c, (long long)n + 1))) return rc;
+  if ((rc = c->gm.ints.grow(c, 3LL * n + 2))) return rc;   // piece_first [2 n + 1], outside [n], flags [1]
+  int* d_piece_first = c->gm.ints.get();
   int* d_outside = d_piece_first + 2 * (size_t)n + 1;
   int* d_flags = d_outside + n;
-  if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->d_gm_req.get(), rq.data(), sizeof(GmRequest) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->gm.req.get(), rq.data(), sizeof(GmRequest) * (size_t)n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(d_piece_first, piece_first.data(), sizeof(int) * piece_first.size(), hipMemcpyHostToDevice, c->stream));
-  c->gm_last_segs = -1;                                    // the scratch of the last call's algorithmic bytes is about to be reused
+  c->gm.last_segs = -1;                                    // the scratch of the last call's algorithmic bytes is about to be reused
   // The directory starts at 128 slots per piece (a sweep's points fall into about a dozen cubes), or where an earlier call had to grow it
   // to; a call whose pieces scatter over more cubes than that runs the transform again with the directory doubled, up to kGmDirMax.
-  long long dir_size = std::max<long long>(4096, c->gm_dir_hint);
+  long long dir_size = std::max<long long>(4096, c->gm.dir_hint);
   while (dir_size < 128LL * n_pieces && dir_size < kGmDirMax) dir_size <<= 1;
   GmArgs g{};
   std::vector<unsigned long long> keys;
   std::vector<int> counts;
   for (;;) {
-    if ((rc = grow_scratch(c, c->d_gm_dir_key, c->gm_dir_key_cap, dir_size))) return rc;
-    if ((rc = grow_scratch(c, c->d_gm_dir_count, c->gm_dir_count_cap, dir_size))) return rc;
-    if ((rc = grow_scratch(c, c->d_gm_dir_base, c->gm_dir_base_cap, dir_size))) return rc;
+    if ((rc = c->gm.dir_key.grow(c, dir_size))) return rc;
+    if ((rc = c->gm.dir_count.grow(c, dir_size))) return rc;
+    if ((rc = c->gm.dir_base.grow(c, dir_size))) return rc;
     HIP_TRY(c, hipMemsetAsync(d_outside, 0, sizeof(int) * ((size_t)n + 1), c->stream));   // (and the flag behind it)
-    HIP_TRY(c, hipMemsetAsync(c->d_gm_dir_key.get(), 0xff, sizeof(unsigned long long) * (size_t)dir_size, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_gm_dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->gm.dir_key.get(), 0xff, sizeof(unsigned long long) * (size_t)dir_size, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->gm.dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
     g = GmArgs{};
-    g.n = n; g.req = c->d_gm_req.get(); g.piece_first = d_piece_first; g.n_pieces = n_pieces; g.kf = kf_store(c);
-    g.nodes = c->d_pg_nodes.get(); g.max_nodes = c->pg_max_nodes;
-    g.world = c->d_gm_world.get(); g.slot = c->d_gm_slot.get(); g.grouped = c->d_gm_grouped.get();
-    g.dir_key = c->d_gm_dir_key.get(); g.dir_count = c->d_gm_dir_count.get(); g.dir_base = c->d_gm_dir_base.get(); g.dir_mask = (unsigned)(dir_size - 1);
+    g.n = n; g.req = c->gm.req.get(); g.piece_first = d_piece_first; g.n_pieces = n_pieces; g.kf = kf_store(c);
+    g.nodes = c->pg.nodes.get(); g.max_nodes = c->pg.max_nodes;
+    g.world = c->gm.world.get(); g.slot = c->gm.slot.get(); g.grouped = c->gm.grouped.get();
+    g.dir_key = c->gm.dir_key.get(); g.dir_count = c->gm.dir_count.get(); g.dir_base = c->gm.dir_base.get(); g.dir_mask = (unsigned)(dir_size - 1);
     g.outside = d_outside; g.flags = d_flags;
     {
       ProfScope p(c, K_GRAPH_MAP);
@@ -233,10 +230,10 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
     }
     dir_size <<= 1;
   }
-  c->gm_dir_hint = dir_size;
+  c->gm.dir_hint = dir_size;
   keys.resize((size_t)dir_size); counts.resize((size_t)dir_size);
-  HIP_TRY(c, hipMemcpy(keys.data(), c->d_gm_dir_key.get(), sizeof(unsigned long long) * keys.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(counts.data(), c->d_gm_dir_count.get(), sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(keys.data(), c->gm.dir_key.get(), sizeof(unsigned long long) * keys.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(counts.data(), c->gm.dir_count.get(), sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
   struct Entry { unsigned long long key; int slot; };
   std::vector<Entry> ent;
   for (long long h = 0; h < dir_size; ++h) if (keys[(size_t)h] != kGmEmpty) ent.push_back(Entry{keys[(size_t)h], (int)h});
@@ -282,17 +279,17 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
     round_end.push_back((int)j1);
     j0 = j1;
   }
-  if ((rc = grow_scratch(c, c->d_gm_jobs, c->gm_jobs_cap, (long long)std::max(n_segs, 1)))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_seg, c->gm_seg_info_cap, (long long)std::max(n_segs, 1)))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_counts, c->gm_counts_cap, (long long)std::max(n_segs, 1)))) return rc;
-  if ((rc = grow_scratch(c, c->d_gm_point_off, c->gm_point_off_cap, (long long)n_segs + 1))) return rc;
+  if ((rc = c->gm.jobs.grow(c, (long long)std::max(n_segs, 1)))) return rc;
+  if ((rc = c->gm.seg.grow(c, (long long)std::max(n_segs, 1)))) return rc;
+  if ((rc = c->gm.counts.grow(c, (long long)std::max(n_segs, 1)))) return rc;
+  if ((rc = c->gm.point_off.grow(c, (long long)n_segs + 1))) return rc;
   // ---- from here everything is stream-ordered
-  HIP_TRY(c, hipMemcpyAsync(c->d_gm_dir_base.get(), dir_base.data(), sizeof(long long) * dir_base.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_gm_dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_gm_req_out.get(), out.data(), sizeof(GmRequestOut) * out.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->gm.dir_base.get(), dir_base.data(), sizeof(long long) * dir_base.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->gm.dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->gm.req_out.get(), out.data(), sizeof(GmRequestOut) * out.size(), hipMemcpyHostToDevice, c->stream));
   if (n_segs > 0) {
-    HIP_TRY(c, hipMemcpyAsync(c->d_gm_jobs.get(), jobs.data(), sizeof(AtlasMergeJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_gm_seg.get(), segs.data(), sizeof(GmSegInfo) * segs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->gm.jobs.get(), jobs.data(), sizeof(AtlasMergeJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->gm.seg.get(), segs.data(), sizeof(GmSegInfo) * segs.size(), hipMemcpyHostToDevice, c->stream));
   }
   {
     ProfScope p(c, K_GRAPH_MAP);
@@ -301,7 +298,7 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
     for (const int j1 : round_end) {
       const VoxArgs v = vox_args(c, j1 - j0, c->map.cube_levels);
       AtlasMergeArgs m{};
-      m.jobs = c->d_gm_jobs.get() + j0; m.n_jobs = j1 - j0; m.points[0] = c->d_gm_grouped.get(); m.points[1] = c->d_gm_grouped.get(); m.counts = c->d_gm_counts.get();
+      m.jobs = c->gm.jobs.get() + j0; m.n_jobs = j1 - j0; m.points[0] = c->gm.grouped.get(); m.points[1] = c->gm.grouped.get(); m.counts = c->gm.counts.get();
       m.leaf[0] = c->map_line_res; m.leaf[1] = c->map_plane_res;
       HIP_TRY(c, hipMemsetAsync(c->d_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));
       launch_atlas_merge_segments(m, v, c->stream);
@@ -309,15 +306,15 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
       j0 = j1;
     }
     GmEmitArgs e{};
-    e.n = n; e.n_segs = n_segs; e.req = c->d_gm_req_out.get(); e.jobs = c->d_gm_jobs.get(); e.seg = c->d_gm_seg.get(); e.counts = c->d_gm_counts.get();
-    e.point_off = c->d_gm_point_off.get(); e.outside = d_outside; e.grouped = c->d_gm_grouped.get();
+    e.n = n; e.n_segs = n_segs; e.req = c->gm.req_out.get(); e.jobs = c->gm.jobs.get(); e.seg = c->gm.seg.get(); e.counts = c->gm.counts.get();
+    e.point_off = c->gm.point_off.get(); e.outside = d_outside; e.grouped = c->gm.grouped.get();
     e.tiles_dst = static_cast<aloam_map_tile*>(d_tiles); e.cap_tiles = d_tiles ? cap_tiles : 0;
     e.points_dst = static_cast<float4*>(d_pts); e.cap_points = d_pts ? cap_points : 0;
     e.dst_off = static_cast<long long*>(d_off); e.stats = static_cast<aloam_graph_map_stats*>(d_stats);
     launch_graph_map_emit(e, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
-  c->gm_last_raw = total; c->gm_last_segs = n_segs;
+  c->gm.last_raw = total; c->gm.last_segs = n_segs;
   return ALOAM_OK;
 }
 

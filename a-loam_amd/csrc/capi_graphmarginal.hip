@@ -12,22 +12,14 @@
 static_assert(kMarginalPivotTol == kInfoPivotTol, "the positive-definiteness rule of k_graph_marginals is k_loop_result's");
 static_assert(sizeof(GraphMarginalItem) % 8 == 0, "items lie back to back in the ring and on the device");
 
-// The ring, the device copy of a round's requests and the events, on first use; nothing stays allocated behind a refusal.
+// The ring and the device copy of a round's requests, on first use; nothing stays allocated behind a refusal.
 static int marginal_staging(aloam_ctx* c) {
-  if (c->h_mg_stage) return ALOAM_OK;
-  GraphMarginalItem* ring = nullptr;
-  bool ok = dalloc(c->d_mg_items, kMarginalStageItems) == hipSuccess &&
-            hipHostMalloc((void**)&ring, sizeof(GraphMarginalItem) * kMarginalStageItems * kMarginalStageSlots, hipHostMallocDefault) == hipSuccess;
-  for (Event& e : c->mg_stage_done) ok = ok && (e.h || hipEventCreateWithFlags(&e.h, hipEventDisableTiming) == hipSuccess);
-  if (!ok) {
-    (void)hipGetLastError();
-    if (ring) (void)hipHostFree(ring);
-    c->d_mg_items.reset();
-    c->err = "pose-graph marginals: allocating the request ring failed";
-    return ALOAM_E_HIP;
-  }
-  c->h_mg_stage.reset(ring);
-  return ALOAM_OK;
+  if (c->mg.items) return ALOAM_OK;
+  if (dalloc(c->mg.items, kMarginalStageItems) == hipSuccess && !c->mg.ring.create(sizeof(GraphMarginalItem) * kMarginalStageItems)) return ALOAM_OK;
+  (void)hipGetLastError();
+  c->mg.items.reset();
+  c->err = "pose-graph marginals: allocating the request ring failed";
+  return ALOAM_E_HIP;
 }
 
 extern "C" {
@@ -52,11 +44,7 @@ int aloam_graph_marginals(aloam_ctx* c, const aloam_graph_marginal_request* req,
   }
   o.pad = 0;
   if (n == 0) return ALOAM_OK;
-  {
-    void* dev = nullptr;
-    const CallerMem m = classify_pointer(c, req, &dev);
-    if (m != kMemPageable && m != kMemPinned) { c->err = "req must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
-  }
+  if (const int rc = require_host_list(c, req, "req")) return rc;
   void* d_dst = nullptr;
   if (const int rc = export_target(c, dst, 8, "dst", &d_dst)) return rc;
   std::vector<GraphMarginalItem> checked(n);
@@ -79,29 +67,25 @@ int aloam_graph_marginals(aloam_ctx* c, const aloam_graph_marginal_request* req,
   const long long f64_row = graph_f64_row(row_nodes, row_edges), i32_row = graph_i32_row(row_nodes, row_edges);
   const long long fit = std::max(1LL, kMarginalScratchBytes / (8 * f64_row + 4 * i32_row));
   const int rows = (int)std::min<long long>({fit, (long long)n, (long long)kMarginalStageItems});
-  if (const int rc = grow_scratch(c, c->d_mg_f64, c->mg_f64_cap, f64_row * rows)) return rc;
-  if (const int rc = grow_scratch(c, c->d_mg_i32, c->mg_i32_cap, i32_row * rows)) return rc;
+  if (const int rc = c->mg.f64.grow(c, f64_row * rows)) return rc;
+  if (const int rc = c->mg.i32.grow(c, i32_row * rows)) return rc;
   // ---- rounds of at most `rows` requests over the same rows, in stream order
   ProfScope prof(c, K_GRAPH_MARGINALS);
   for (int r0 = 0; r0 < n; r0 += rows) {
     const int m = std::min(rows, n - r0);
-    const int ns = c->mg_stage_slot;
-    c->mg_stage_slot = (ns + 1) % kMarginalStageSlots;
-    if (c->mg_stage_used[ns]) HIP_TRY(c, hipEventSynchronize(c->mg_stage_done[ns]));
-    GraphMarginalItem* slot = c->h_mg_stage.get() + (size_t)ns * kMarginalStageItems;
+    GraphMarginalItem* slot = nullptr; int ns = 0;
+    if (const int rc = c->mg.ring.acquire(c, &slot, &ns)) return rc;
     std::copy(checked.begin() + r0, checked.begin() + r0 + m, slot);
-    HIP_TRY(c, hipMemcpyAsync(c->d_mg_items.get(), slot, sizeof(GraphMarginalItem) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(c->mg_stage_done[ns], c->stream));
-    c->mg_stage_used[ns] = true;
+    if (const int rc = c->mg.ring.queue(c, ns, slot, sizeof(GraphMarginalItem) * (size_t)m, c->mg.items.get(), c->stream)) return rc;
     GraphMarginalArgs a{};
-    a.n = m; a.items = c->d_mg_items.get(); a.nodes = c->d_pg_nodes.get(); a.edges = c->d_pg_edges.get();
-    a.max_nodes = c->pg_max_nodes; a.max_edges = c->pg_max_edges; a.row_nodes = row_nodes; a.row_edges = row_edges; a.opt = o;
-    a.f64 = c->d_mg_f64.get(); a.f64_row = f64_row; a.i32 = c->d_mg_i32.get(); a.i32_row = i32_row;
+    a.n = m; a.items = c->mg.items.get(); a.nodes = c->pg.nodes.get(); a.edges = c->pg.edges.get();
+    a.max_nodes = c->pg.max_nodes; a.max_edges = c->pg.max_edges; a.row_nodes = row_nodes; a.row_edges = row_edges; a.opt = o;
+    a.f64 = c->mg.f64.get(); a.f64_row = f64_row; a.i32 = c->mg.i32.get(); a.i32_row = i32_row;
     a.dst = static_cast<aloam_graph_marginal_result*>(d_dst) + r0;
     launch_graph_marginals(a, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
-  c->mg_last_nodes = nodes; c->mg_last_edges = edges; c->mg_last_n = n;
+  c->mg.last_nodes = nodes; c->mg.last_edges = edges; c->mg.last_n = n;
   return ALOAM_OK;
 }
 

@@ -1,8 +1,10 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
-// aloam_capi.hip (context, input staging ring, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
+// aloam_capi.hip (context, staging of input counts, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
 // setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
+// Stated once here for all of them: the pinned staging ring (StageRing), a scratch buffer with its capacity (Scratch), and one struct per
+// graph-family feature (GraphStore ... MarginalScratch) that its enable builds fresh and commits with one move, as MapPool.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +33,7 @@
 
 using namespace aloam;
 
+struct aloam_ctx;
 namespace aloam {
 enum KernelId { K_FIND_ENDS = 0, K_FRONT, K_RING_STARTS, K_DENSE_CLOUD, K_RING_FEATURES, K_BUILD_GRIDS, K_TRANSFORM, K_ASSOC_CORNER,
                 K_ASSOC_PLANE, K_SOLVE, K_ADVANCE, K_MAP_BEGIN, K_MAP_VOXEL_STACK, K_MAP_GRID, K_MAP_ASSOC, K_MAP_SOLVE, K_MAP_INSERT,
@@ -56,7 +59,8 @@ template <typename H, hipError_t (*Destroy)(H)>
 struct Handle {
   H h = nullptr;
   Handle() = default;
-  Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}   // (no copies, no assignment)
+  Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}   // (no copies)
+  Handle& operator=(Handle&& o) noexcept { if (this != &o) { reset(); h = std::exchange(o.h, nullptr); } return *this; }
   ~Handle() { reset(); }
   void reset() { if (h) (void)Destroy(h); h = nullptr; }
   operator H() const { return h; }
@@ -73,6 +77,42 @@ hipError_t dalloc(DevBuf<T>& p, size_t count) {
   return e;
 }
 
+// A pinned ring of Slots slots: the caller fills the slot that acquire() hands out and queues it (or pieces of it) with queue(); the call
+// returns at once and the H2D copy runs in stream order.  A slot comes round again Slots acquires later, and acquire() then waits for
+// the copy that last read it, and for nothing else.  The events stand before the memory: they are destroyed after it.
+template <int Slots>
+struct StageRing {
+  Event done[Slots];                 // the copy that last read a slot has run
+  PinnedBuf<char> mem;
+  size_t slot_bytes = 0;
+  int cursor = 0;
+  bool used[Slots] = {};
+  // Once per ring (a second call changes nothing).  nullptr, or what failed: then nothing stays allocated.
+  const char* create(size_t bytes) {
+    if (mem) return nullptr;
+    char* p = nullptr;
+    if (hipHostMalloc((void**)&p, bytes * Slots, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return "pinned request ring: allocation failed"; }
+    mem.reset(p); slot_bytes = bytes;
+    for (Event& e : done)
+      if (hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); *this = StageRing(); return "event creation failed"; }
+    return nullptr;
+  }
+  template <typename T> int acquire(aloam_ctx* c, T** slot, int* index);
+  // `bytes` at `src`, which lies in slot `index`, to `dst` on `stream`; the slot counts as read when this copy has run.
+  int queue(aloam_ctx* c, int index, const void* src, size_t bytes, void* dst, hipStream_t stream);
+};
+
+// A scratch buffer and the elements it holds.  grow(): to `need` elements when it holds fewer; the old buffer is released first (its
+// contents are not needed), and a failed allocation leaves it empty.
+template <typename T>
+struct Scratch {
+  DevBuf<T> p;
+  long long cap = 0;
+  T* get() const { return p.get(); }
+  void release() { cap = 0; p.reset(); }
+  int grow(aloam_ctx* c, long long need);
+};
+
 // Everything whose size follows the map pool (map_alloc_pool): built fresh and committed with one move when the pool grows.
 struct MapPool {
   int points = 0, H = 0;             // pool points per sequence and class, buckets of the submap grid
@@ -81,6 +121,66 @@ struct MapPool {
   DevBuf<float4> pool[2], grid_sorted[2], voxtmp;
   DevBuf<int> grid_start[2], tile_seg, tile_heads, tile_pref;
   DevBuf<unsigned long long> keys[2];
+};
+
+// The graph family, one struct per feature: its buffers, its ring, its sizes and whether it is on.  An enable builds one fresh and moves it
+// into the context when everything succeeded, so a refusal leaves nothing allocated and the context as it was.
+struct GraphStore {                  // pose graphs (aloam_graph_enable): one row of nodes and one of edges per sequence; the counts are SeqHost fields
+  bool on = false;
+  int max_nodes = 0, max_edges = 0;
+  DevBuf<aloam_graph_node> nodes;                                   // [B][max_nodes]
+  DevBuf<aloam_graph_edge> edges;                                   // [B][max_edges]
+  DevBuf<GraphAddItem> add;                                         // [B] the nodes of one aloam_graph_add_nodes
+  DevBuf<GraphSolveItem> items;                                     // [B] the listed sequences of one aloam_graph_optimize
+  StageRing<kGraphStageSlots> ring;                                 // a slot holds the B items of one add / optimize
+  Scratch<double> f64; Scratch<int> i32;                            // the solve's scratch rows, grown on first use
+  long long last_nodes = 0, last_edges = 0;                         // the last solve (algorithmic bytes)
+};
+struct KeyframeStore {               // keyframe clouds (aloam_graph_keyframes_enable): per sequence and class a row of sensor-frame points, per node a descriptor
+  bool on = false;
+  int cap[2] = {0, 0};                                              // points per sequence: corner, surf
+  DevBuf<float4> points[2];                                         // [B][cap[cls]]
+  DevBuf<KfDesc> desc;                                              // [B][GraphStore::max_nodes]
+  DevBuf<int> counters;                                             // [B][kKfInts]
+  long long dropped_reported = 0;                                   // nodes kept without clouds aloam_synchronize has already returned
+};
+struct GraphMapScratch {             // the map at the graph's poses (aloam_graph_export_map): grown on first use, used in stream order
+  Scratch<float4> world, grouped;                                   // transformed points as laid out for the bounds; grouped by (request, class, cube)
+  Scratch<int> slot;                                                // directory slot of every transformed point
+  Scratch<unsigned long long> dir_key; Scratch<int> dir_count; Scratch<long long> dir_base;   // the directory of (request, class, cube, piece): keys, counts / cursors, bases
+  Scratch<GmRequest> req; Scratch<GmRequestOut> req_out;
+  Scratch<int> ints;                                                // first piece per (request, class), points outside per request, the overflow flag
+  Scratch<AtlasMergeJob> jobs;                                      // one per (request, class, cube), with its filtered size and point offset
+  Scratch<GmSegInfo> seg; Scratch<int> counts; Scratch<long long> point_off;
+  long long dir_hint = 0;                                           // the directory size an earlier call had to grow to
+  long long last_raw = 0; int last_segs = -1;                       // the last call that succeeded (algorithmic bytes); -1 while its scratch is not valid
+};
+struct GraphApplyScratch {           // a solved graph carried into the live state (aloam_graph_apply): grown on first use, used in stream order
+  Scratch<GaItem> items;                                            // the listed sequences of one call
+  Scratch<long long> off;                                           // the offsets the map pass writes for its requests
+};
+// Loop edges (aloam_graph_loops_enable): the scratch of `slots` registrations, used in stream order; the slots are the "sequences" of a
+// scratch MapArgs (loopreg_kernels.hpp), so every per-sequence array of the mapping step has a per-slot twin here.
+struct LoopScratch {
+  bool on = false;
+  int slots = 0, H = 0, tile_bound = 0, tile_cap = 0, levels = 0;
+  long long cap[2] = {0, 0}, key_cap = 0;                           // raw target points per slot: corner, surf; keys of the general voxel path
+  DevBuf<aloam_graph_loop_request> req;                             // [slots] the round's requests
+  StageRing<kLoopStageSlots> ring;                                  // a slot holds `slots` requests
+  DevBuf<float4> raw[2], target[2], sorted[2], stack[2], knn, voxtmp;
+  DevBuf<int> start[2], plan, rec_tiles, list, vox_counters, vox_lists, bbox, tile_seg, tile_heads, tile_pref;
+  DevBuf<unsigned long long> keys[2];
+  DevBuf<MapSeq> seq;
+  DevBuf<MapEdgeRec> edges; DevBuf<MapNormRec> norms;
+  DevBuf<VoxSeg> segs;
+  DevBuf<aloam_pose_information> info;
+  Scratch<LoopSearchPartial> search_part;                           // aloam_graph_search_loops: [round][K][kLoopSearchParts], nothing before its first call
+};
+struct MarginalScratch {             // pose-graph marginals (aloam_graph_marginals): nothing is allocated before the first call; used in stream order
+  DevBuf<GraphMarginalItem> items;                                  // [kMarginalStageItems] the round's requests
+  StageRing<kMarginalStageSlots> ring;                              // a slot holds kMarginalStageItems requests
+  Scratch<double> f64; Scratch<int> i32;                            // the scratch rows, one per request of a round
+  long long last_nodes = 0, last_edges = 0; int last_n = 0;         // the last call (algorithmic bytes)
 };
 
 // What the host knows about one sequence without asking the device (mirrors of device state that only host calls change, then its map, then what the device
@@ -107,13 +207,11 @@ struct SeqHost {
 }  // namespace aloam
 
 struct aloam_ctx {
-  // Streams and events first: members are destroyed in reverse order, so every buffer is released before them.
+  // Streams and events first: members are destroyed in reverse order, so every buffer is released before them (a StageRing further
+  // down keeps its own events: aloam_destroy has drained every stream before anything is destroyed).
   Stream stream, copy_stream;
   Stream grid_stream;                // the build of the next step's search grids runs here, beside the association and the solve (aloam_odometry_step)
-  Event in_copied[2], in_consumed[2], nin_done[kNinSlots], map_step_done[4];
-  Event pg_stage_done[kGraphStageSlots];   // pose graphs: the copy that read a slot of h_pg_stage has run
-  Event lr_stage_done[kLoopStageSlots];    // loop registration: the copy that read a slot of h_lr_stage has run
-  Event mg_stage_done[kMarginalStageSlots];   // pose-graph marginals: the copy that read a slot of h_mg_stage has run
+  Event in_copied[2], in_consumed[2], map_step_done[4];
   Event grid_fork, grids_done;       // main stream -> grid stream at the start of a step, grid stream -> main stream before k_advance
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
   // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
@@ -126,12 +224,11 @@ struct aloam_ctx {
   std::string err;
   // input staging (host-input path only)
   // two device slabs: the H2D copy of call k + 1 (copy stream) overlaps the kernels of call k (compute stream)
-  DevBuf<char> d_in[2]; size_t d_in_bytes[2] = {0, 0};
+  Scratch<char> d_in[2];
   int in_slot = 0;
   bool in_used[2] = {false, false};
   DevBuf<int> d_nin;
-  PinnedBuf<int> h_nin; int h_nin_slot = 0;         // pinned ring of kNinSlots x B ints (counts, masks, reset ids): an async H2D copy reads its slot later
-  bool nin_used[kNinSlots] = {};
+  StageRing<kNinSlots> nin;                         // a slot holds B ints (counts, masks, reset ids): stage_ints
   std::vector<SeqHost> seq;                         // [B] per-sequence host state
   bool all_active = true, any_frozen = false, any_attached = false;   // aggregates of seq[].active / frozen / attached, each recomputed by that field's event
   bool reg_pending = false;
@@ -189,84 +286,31 @@ struct aloam_ctx {
   DevBuf<int> d_exp_pref[2];                                         // entry prefixes of the cube lists, [B][151] surround, [B][9703] full map (on first use)
   int exp_last_segs = 0;                                             // segments of the last export (its algorithmic bytes)
   int gather_blocks = 2048;                                          // workgroups of the persistent k_export_gather: 8 per CU
-  DevBuf<float4> d_exp_tmp; long long exp_tmp_cap = 0;              // aloam_get_map_cloud(SURROUND / FULL): the segment of one sequence
+  Scratch<float4> d_exp_tmp;                                        // aloam_get_map_cloud(SURROUND / FULL): the segment of one sequence
   DevBuf<long long> d_exp_tmp_off;
   // sequence records (aloam_save_sequences / aloam_load_sequences): scratch sized for `batch` records on first use, used in stream order
   DevBuf<int> d_ck_seqs, d_ck_info, d_ck_units, d_ck_chunk, d_ck_pref; DevBuf<long long> d_ck_uoff;   // save: ids, counts, lengths, prefixes
   PinnedBuf<char> h_ck; char* d_ck_host = nullptr;                  // load: headers read back, then the staged offsets / chunks / counts (pinned, mapped)
   DevBuf<char> d_ck_load;                                           // load: the same staged arrays in device memory
-  DevBuf<char> d_ck_stage; size_t ck_stage_bytes = 0;               // load: records from pageable host memory
+  Scratch<char> d_ck_stage;                                         // load: records from pageable host memory
   int ck_save_n = 0; long long ck_load_bytes = 0;                   // the last save / load (algorithmic bytes)
   // map-pose hypotheses (aloam_score_map_corrections / aloam_apply_map_corrections)
   DevBuf<int> d_rl_seqs, d_rl_bad;                                  // [B] listed ids; [1] choices found outside 0 .. K-1 by k_apply_corrections
-  DevBuf<ScorePartial> d_rl_part; long long rl_part_cap = 0;        // [n][K][kScoreParts] per-workgroup partials
-  DevBuf<aloam_map_correction> d_rl_cand; long long rl_cand_cap = 0;   // candidates handed in as pageable host memory
+  Scratch<ScorePartial> d_rl_part;                                  // [n][K][kScoreParts] per-workgroup partials
+  Scratch<aloam_map_correction> d_rl_cand;                          // candidates handed in as pageable host memory
   long long rl_bad_reported = 0;                                    // of d_rl_bad, already returned by aloam_synchronize
   std::vector<int> rl_last_seqs; int rl_last_K = 0;                 // the last scoring call: its listed sequences and K (algorithmic bytes)
   int rl_apply_n = 0;
   // pose information (aloam_export_pose_information)
   DevBuf<int> d_info_list;                                          // [B] listed ids with their "solved" bit
   std::vector<int> info_last_list; int info_last_which = 0;         // the last call (algorithmic bytes)
-  // pose graphs (aloam_graph_enable): one row of nodes and one of edges per sequence; the counts are SeqHost fields
-  bool graph_on = false;
-  int pg_max_nodes = 0, pg_max_edges = 0;
-  DevBuf<aloam_graph_node> d_pg_nodes;                              // [B][max_nodes]
-  DevBuf<aloam_graph_edge> d_pg_edges;                              // [B][max_edges]
-  DevBuf<GraphAddItem> d_pg_add;                                    // [B] the nodes of one aloam_graph_add_nodes
-  DevBuf<GraphSolveItem> d_pg_items;                                // [B] the listed sequences of one aloam_graph_optimize
-  PinnedBuf<char> h_pg_stage; size_t pg_stage_bytes = 0;            // pinned ring of kGraphStageSlots x pg_stage_bytes: the items of one add / optimize,
-  int pg_stage_slot = 0; bool pg_stage_used[kGraphStageSlots] = {}; //   read later by an async H2D copy (as h_nin)
-  DevBuf<double> d_pg_f64; long long pg_f64_cap = 0;                // the solve's scratch rows, grown on first use
-  DevBuf<int> d_pg_i32; long long pg_i32_cap = 0;
-  long long pg_last_nodes = 0, pg_last_edges = 0;                   // the last solve (algorithmic bytes)
-  // keyframe clouds of the pose graphs (aloam_graph_keyframes_enable): per sequence and class a row of sensor-frame points, per node a descriptor
-  bool kf_on = false;
-  int kf_cap[2] = {0, 0};                                           // points per sequence: corner, surf
-  DevBuf<float4> d_kf_points[2];                                    // [B][kf_cap[cls]]
-  DevBuf<KfDesc> d_kf_desc;                                         // [B][pg_max_nodes]
-  DevBuf<int> d_kf_counters;                                        // [B][kKfInts]
-  long long kf_dropped_reported = 0;                                // nodes kept without clouds aloam_synchronize has already returned
-  // the map at the graph's poses (aloam_graph_export_map): scratch grown on first use, used in stream order
-  DevBuf<float4> d_gm_world, d_gm_grouped; long long gm_points_cap = 0;   // transformed points as laid out for the bounds; grouped by (request, class, cube)
-  DevBuf<int> d_gm_slot; long long gm_slot_cap = 0;                 // directory slot of every transformed point
-  DevBuf<unsigned long long> d_gm_dir_key; long long gm_dir_key_cap = 0;   // the directory of (request, class, cube, piece): keys, counts / cursors, bases
-  DevBuf<int> d_gm_dir_count; long long gm_dir_count_cap = 0;
-  DevBuf<long long> d_gm_dir_base; long long gm_dir_base_cap = 0;
-  DevBuf<GmRequest> d_gm_req; long long gm_req_cap = 0;
-  DevBuf<GmRequestOut> d_gm_req_out; long long gm_req_out_cap = 0;
-  DevBuf<int> d_gm_ints; long long gm_ints_cap = 0;                 // first piece per (request, class), points outside per request, the overflow flag
-  DevBuf<AtlasMergeJob> d_gm_jobs; long long gm_jobs_cap = 0;       // one per (request, class, cube), with its filtered size and point offset
-  DevBuf<GmSegInfo> d_gm_seg; long long gm_seg_info_cap = 0;
-  DevBuf<int> d_gm_counts; long long gm_counts_cap = 0;
-  DevBuf<long long> d_gm_point_off; long long gm_point_off_cap = 0;
-  long long gm_dir_hint = 0;                                        // the directory size an earlier call had to grow to
-  long long gm_last_raw = 0; int gm_last_segs = -1;                 // the last call that succeeded (algorithmic bytes); -1 while its scratch is not valid
-  // a solved graph carried into the live state (aloam_graph_apply): scratch grown on first use, used in stream order
-  DevBuf<GaItem> d_ga_items; long long ga_items_cap = 0;            // the listed sequences of one call
-  DevBuf<long long> d_ga_off; long long ga_off_cap = 0;             // the offsets the map pass writes for its requests
-  // loop edges (aloam_graph_loops_enable): the scratch of lr_slots registrations, used in stream order; the slots are the "sequences" of a
-  // scratch MapArgs (loopreg_kernels.hpp), so every per-sequence array of the mapping step has a per-slot twin here
-  bool lr_on = false;
-  int lr_slots = 0, lr_H = 0, lr_tile_bound = 0, lr_tile_cap = 0, lr_levels = 0;
-  long long lr_cap[2] = {0, 0}, lr_key_cap = 0;                     // raw target points per slot: corner, surf; keys of the general voxel path
-  DevBuf<aloam_graph_loop_request> d_lr_req;                        // [slots] the round's requests
-  PinnedBuf<aloam_graph_loop_request> h_lr_stage;                   // pinned ring of kLoopStageSlots x slots requests
-  int lr_stage_slot = 0; bool lr_stage_used[kLoopStageSlots] = {};
-  DevBuf<float4> d_lr_raw[2], d_lr_target[2], d_lr_sorted[2], d_lr_stack[2], d_lr_knn, d_lr_voxtmp;
-  DevBuf<int> d_lr_start[2], d_lr_plan, d_lr_rec_tiles, d_lr_list, d_lr_vox_counters, d_lr_vox_lists, d_lr_bbox, d_lr_tile_seg, d_lr_tile_heads, d_lr_tile_pref;
-  DevBuf<unsigned long long> d_lr_keys[2];
-  DevBuf<MapSeq> d_lr_seq;
-  DevBuf<MapEdgeRec> d_lr_edges; DevBuf<MapNormRec> d_lr_norms;
-  DevBuf<VoxSeg> d_lr_segs;
-  DevBuf<aloam_pose_information> d_lr_info;
-  DevBuf<LoopSearchPartial> d_ls_part; long long ls_part_cap = 0;   // aloam_graph_search_loops: [round][K][kLoopSearchParts], nothing before its first call
-  // pose-graph marginals (aloam_graph_marginals): nothing is allocated before the first call; used in stream order
-  DevBuf<GraphMarginalItem> d_mg_items;                             // [kMarginalStageItems] the round's requests
-  PinnedBuf<GraphMarginalItem> h_mg_stage;                          // pinned ring of kMarginalStageSlots x kMarginalStageItems requests
-  int mg_stage_slot = 0; bool mg_stage_used[kMarginalStageSlots] = {};
-  DevBuf<double> d_mg_f64; long long mg_f64_cap = 0;                // the scratch rows, one per request of a round
-  DevBuf<int> d_mg_i32; long long mg_i32_cap = 0;
-  long long mg_last_nodes = 0, mg_last_edges = 0; int mg_last_n = 0;   // the last call (algorithmic bytes)
+  // the graph family (aloam_graph_*): each feature's state is one struct, above
+  GraphStore pg;
+  KeyframeStore kf;
+  GraphMapScratch gm;
+  GraphApplyScratch ga;
+  LoopScratch lr;
+  MarginalScratch mg;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -288,7 +332,7 @@ struct aloam_ctx {
   DevBuf<aloam_place> d_pl_store;                                   // [capacity]
   DevBuf<float> d_pl_unit; DevBuf<unsigned long long> d_pl_masks;   // [capacity][1200] unit-normalised columns, [capacity] non-zero columns
   DevBuf<int> d_pl_seqs, d_pl_wanted, d_pl_lo, d_pl_hi;             // [B] each: listed ids, descriptors to make, the ranges of a match
-  DevBuf<int2> d_pl_pairs; long long pl_pairs_cap = 0;              // [n][longest range] per-entry results of a match
+  Scratch<int2> d_pl_pairs;                                         // [n][longest range] per-entry results of a match
   // range-image input (aloam_set_range_decoder, capi_range.hip): the decoder's scalars and the device copies of its tables
   bool range_on = false;
   int rd_rows = 0, rd_n_az = 0, rd_order = 0; float rd_scale = 0.f;
@@ -372,14 +416,30 @@ int edit_seq(aloam_ctx* c, T* dev, Edit edit) {
   return ALOAM_OK;
 }
 
-// A scratch buffer of `have` elements grown to hold `need`; the old one is released first: its contents are not needed.
-template <typename T, typename N>
-int grow_scratch(aloam_ctx* c, DevBuf<T>& p, N& have, N need) {
-  if (have >= need) return ALOAM_OK;
-  have = 0;
-  p.reset();
+template <typename T>
+int Scratch<T>::grow(aloam_ctx* c, long long need) {
+  if (cap >= need) return ALOAM_OK;
+  release();
   HIP_TRY(c, dalloc(p, (size_t)need));
-  have = need;
+  cap = need;
+  return ALOAM_OK;
+}
+
+template <int Slots>
+template <typename T>
+int StageRing<Slots>::acquire(aloam_ctx* c, T** slot, int* index) {
+  const int ns = cursor;
+  cursor = (ns + 1) % Slots;
+  if (used[ns]) HIP_TRY(c, hipEventSynchronize(done[ns]));
+  *slot = reinterpret_cast<T*>(mem.get() + (size_t)ns * slot_bytes);
+  *index = ns;
+  return ALOAM_OK;
+}
+template <int Slots>
+int StageRing<Slots>::queue(aloam_ctx* c, int index, const void* src, size_t bytes, void* dst, hipStream_t stream) {
+  HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(c, hipEventRecord(done[index], stream));
+  used[index] = true;
   return ALOAM_OK;
 }
 
@@ -417,8 +477,9 @@ bool queue_atlas_window(aloam_ctx* c, const int* mask);  // k_atlas_window when 
 // The largest number of points any 21 x 21 x 11 box of cubes holds (keys: atlas_key of every cube, lo / hi: their bounding box); *exact = false: the class total instead
 long long largest_window(const std::vector<int>& keys, const std::vector<int>& counts, const int lo[3], const int hi[3], bool* exact);
 // capi_graphmap.hip
+KfStore kf_store(aloam_ctx* c);                                      // the keyframe store as the kernels see it
 int keyframe_add_check(aloam_ctx* c, const int* seqs, int n);        // ALOAM_E_STATE when a listed sequence holds no stacks (store enabled)
-void queue_keyframe_capture(aloam_ctx* c, int n);                    // k_keyframe_capture behind k_graph_add_nodes, for the items in d_pg_add
+void queue_keyframe_capture(aloam_ctx* c, int n);                    // k_keyframe_capture behind k_graph_add_nodes, for the items in pg.add
 int queue_keyframe_rewind(aloam_ctx* c, const int* seqs, int n);     // aloam_graph_clear: the listed cursors back to 0, in stream order
 int keyframes_dropped_since(aloam_ctx* c, long long* fresh);
 // capi_seq.hip: the one "does sequence b take part in this step", a stage's mask, and what happens to a sequence, each with its whole consequence
@@ -460,6 +521,7 @@ VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);
 // capi_records.hip
 enum CallerMem { kMemPageable, kMemDevice, kMemPinned, kMemManaged, kMemOtherDevice };
 CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev);
+int require_host_list(aloam_ctx* c, const void* p, const char* name);   // ALOAM_E_ARG unless a request list is host memory, pinned or pageable
 int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out);
 int get_cube_list(aloam_ctx* c, int seq, int which, float* out, int cap_points);
 

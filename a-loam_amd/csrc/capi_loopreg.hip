@@ -11,7 +11,7 @@
 #include "information_device.hpp"
 
 static int require_loops(aloam_ctx* c) {
-  if (!c->lr_on) { c->err = "loop registration is not enabled (aloam_graph_loops_enable)"; return ALOAM_E_STATE; }
+  if (!c->lr.on) { c->err = "loop registration is not enabled (aloam_graph_loops_enable)"; return ALOAM_E_STATE; }
   return ALOAM_OK;
 }
 
@@ -19,14 +19,14 @@ static int require_loops(aloam_ctx* c) {
 static MapArgs loop_map_args(aloam_ctx* c, int n, int lm_max_iterations) {
   MapArgs a{};
   a.B = n; a.cap = c->cap; a.R = c->R;
-  a.seq = c->d_lr_seq.get();
+  a.seq = c->lr.seq.get();
   a.line_res = c->map_line_res; a.plane_res = c->map_plane_res;
-  a.pool_cap = (int)std::max(c->lr_cap[0], c->lr_cap[1]);
-  for (int k = 0; k < 2; ++k) { a.stack[k] = c->d_lr_stack[k].get(); a.grid_sorted[k] = c->d_lr_sorted[k].get(); a.grid_start[k] = c->d_lr_start[k].get(); }
-  a.grid_H = c->lr_H;
-  a.knn = c->d_lr_knn.get(); a.edges = c->d_lr_edges.get(); a.norms = c->d_lr_norms.get();
+  a.pool_cap = (int)std::max(c->lr.cap[0], c->lr.cap[1]);
+  for (int k = 0; k < 2; ++k) { a.stack[k] = c->lr.stack[k].get(); a.grid_sorted[k] = c->lr.sorted[k].get(); a.grid_start[k] = c->lr.start[k].get(); }
+  a.grid_H = c->lr.H;
+  a.knn = c->lr.knn.get(); a.edges = c->lr.edges.get(); a.norms = c->lr.norms.get();
   a.lm_max_iterations = lm_max_iterations;
-  a.rec_tiles = c->d_lr_rec_tiles.get(); a.rec_tiles_per_seq = c->rec_tiles_per_seq; a.rec_tiles_corner = c->rec_tiles_corner;
+  a.rec_tiles = c->lr.rec_tiles.get(); a.rec_tiles_per_seq = c->rec_tiles_per_seq; a.rec_tiles_corner = c->rec_tiles_corner;
   a.active = nullptr;
   return a;
 }
@@ -34,17 +34,10 @@ static MapArgs loop_map_args(aloam_ctx* c, int n, int lm_max_iterations) {
 // The feature's own voxel-filter scratch (the mapping step's is in use by the live sequences' steps in the same stream).
 static VoxArgs loop_vox_args(aloam_ctx* c, int n_segs) {
   VoxArgs v{};
-  v.segs = c->d_lr_segs.get(); v.n_segs = n_segs; v.tile_seg = c->d_lr_tile_seg.get(); v.tile_heads = c->d_lr_tile_heads.get(); v.tile_pref = c->d_lr_tile_pref.get();
-  v.counters = c->d_lr_vox_counters.get(); v.keys[0] = c->d_lr_keys[0].get(); v.keys[1] = c->d_lr_keys[1].get(); v.tmp = c->d_lr_voxtmp.get();
-  v.bbox = c->d_lr_bbox.get(); v.tile_cap = c->lr_tile_cap; v.key_cap = c->lr_key_cap; v.levels = c->lr_levels; v.lists = c->d_lr_vox_lists.get();
+  v.segs = c->lr.segs.get(); v.n_segs = n_segs; v.tile_seg = c->lr.tile_seg.get(); v.tile_heads = c->lr.tile_heads.get(); v.tile_pref = c->lr.tile_pref.get();
+  v.counters = c->lr.vox_counters.get(); v.keys[0] = c->lr.keys[0].get(); v.keys[1] = c->lr.keys[1].get(); v.tmp = c->lr.voxtmp.get();
+  v.bbox = c->lr.bbox.get(); v.tile_cap = c->lr.tile_cap; v.key_cap = c->lr.key_cap; v.levels = c->lr.levels; v.lists = c->lr.vox_lists.get();
   return v;
-}
-
-static void loops_release(aloam_ctx* c) {
-  c->d_lr_req.reset(); c->h_lr_stage.reset(); c->d_lr_knn.reset(); c->d_lr_voxtmp.reset(); c->d_lr_plan.reset(); c->d_lr_rec_tiles.reset(); c->d_lr_list.reset();
-  c->d_lr_vox_counters.reset(); c->d_lr_vox_lists.reset(); c->d_lr_bbox.reset(); c->d_lr_tile_seg.reset(); c->d_lr_tile_heads.reset(); c->d_lr_tile_pref.reset();
-  c->d_lr_seq.reset(); c->d_lr_edges.reset(); c->d_lr_norms.reset(); c->d_lr_segs.reset(); c->d_lr_info.reset();
-  for (int k = 0; k < 2; ++k) { c->d_lr_raw[k].reset(); c->d_lr_target[k].reset(); c->d_lr_sorted[k].reset(); c->d_lr_stack[k].reset(); c->d_lr_start[k].reset(); c->d_lr_keys[k].reset(); }
 }
 
 extern "C" {
@@ -57,8 +50,8 @@ void aloam_graph_loop_default_options(aloam_graph_loop_options* opt) {
 int aloam_graph_loops_enable(aloam_ctx* c, int max_requests, int max_target_corner_points, int max_target_surf_points) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  if (!c->kf_on) { c->err = "aloam_graph_loops_enable before aloam_graph_keyframes_enable"; return ALOAM_E_STATE; }
-  if (c->lr_on) { c->err = "loop registration already enabled"; return ALOAM_E_STATE; }
+  if (!c->kf.on) { c->err = "aloam_graph_loops_enable before aloam_graph_keyframes_enable"; return ALOAM_E_STATE; }
+  if (c->lr.on) { c->err = "loop registration already enabled"; return ALOAM_E_STATE; }
   if (max_requests < 1 || max_requests > kLoopMaxRequests || max_target_corner_points < 1 || max_target_corner_points > kLoopTargetMax || max_target_surf_points < 1 ||
       max_target_surf_points > kLoopTargetMax) {
     c->err = "bad loop registration sizes (1 <= max_requests <= 32768, 1 <= max_target_corner_points, max_target_surf_points <= 2^24)";
@@ -72,44 +65,40 @@ int aloam_graph_loops_enable(aloam_ctx* c, int max_requests, int max_target_corn
   // the general path of the voxel filter takes whatever the single-workgroup filters pass on (more runs than their tables hold): sized for all of it
   const size_t key_cap = S * (tc[0] + tc[1]), tile_cap = S * ((tc[0] + T - 1) / T + (tc[1] + T - 1) / T);
   if (tile_cap > 0x7fffffffu) { c->err = "loop registration scratch: more voxel-filter tiles than an int counts"; return ALOAM_E_ARG; }
+  LoopScratch l;                       // committed with one move: nothing stays allocated behind a refusal
   bool ok = true;
   const char* cause = "device allocation failed";
   auto grab = [&](auto& p, size_t count) { if (ok && dalloc(p, count) != hipSuccess) { ok = false; (void)hipGetLastError(); } };
   for (int k = 0; k < 2; ++k) {
-    grab(c->d_lr_raw[k], S * tc[k]); grab(c->d_lr_target[k], S * tc[k]); grab(c->d_lr_sorted[k], S * pool); grab(c->d_lr_start[k], S * ((size_t)H + 1));
-    grab(c->d_lr_stack[k], S * (k == 0 ? rowc : cap)); grab(c->d_lr_keys[k], key_cap);
+    grab(l.raw[k], S * tc[k]); grab(l.target[k], S * tc[k]); grab(l.sorted[k], S * pool); grab(l.start[k], S * ((size_t)H + 1));
+    grab(l.stack[k], S * (k == 0 ? rowc : cap)); grab(l.keys[k], key_cap);
   }
-  grab(c->d_lr_voxtmp, key_cap); grab(c->d_lr_tile_seg, tile_cap); grab(c->d_lr_tile_heads, tile_cap); grab(c->d_lr_tile_pref, tile_cap + 1);
-  grab(c->d_lr_req, S); grab(c->d_lr_knn, S * cap * 4); grab(c->d_lr_edges, S * rowc); grab(c->d_lr_norms, S * cap);
-  grab(c->d_lr_rec_tiles, S * (size_t)c->rec_tiles_per_seq); grab(c->d_lr_seq, S); grab(c->d_lr_plan, S * kLoopPlanInts); grab(c->d_lr_list, S);
-  grab(c->d_lr_segs, 2 * S); grab(c->d_lr_vox_lists, 3 * 2 * S); grab(c->d_lr_vox_counters, 8); grab(c->d_lr_bbox, 2 * S * 6); grab(c->d_lr_info, S);
-  aloam_graph_loop_request* ring = nullptr;
-  if (ok && hipHostMalloc((void**)&ring, sizeof(aloam_graph_loop_request) * S * kLoopStageSlots, hipHostMallocDefault) != hipSuccess) { ok = false; cause = "pinned request ring: allocation failed"; }
-  c->h_lr_stage.reset(ring);
-  for (Event& e : c->lr_stage_done)
-    if (ok && !e.h && hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess) { ok = false; cause = "event creation failed"; }
+  grab(l.voxtmp, key_cap); grab(l.tile_seg, tile_cap); grab(l.tile_heads, tile_cap); grab(l.tile_pref, tile_cap + 1);
+  grab(l.req, S); grab(l.knn, S * cap * 4); grab(l.edges, S * rowc); grab(l.norms, S * cap);
+  grab(l.rec_tiles, S * (size_t)c->rec_tiles_per_seq); grab(l.seq, S); grab(l.plan, S * kLoopPlanInts); grab(l.list, S);
+  grab(l.segs, 2 * S); grab(l.vox_lists, 3 * 2 * S); grab(l.vox_counters, 8); grab(l.bbox, 2 * S * 6); grab(l.info, S);
+  if (ok) if (const char* what = l.ring.create(sizeof(aloam_graph_loop_request) * S)) { ok = false; cause = what; }
   if (ok && prepare_loop_grid(H) != 0) { ok = false; cause = "k_loop_grid: dynamic LDS size rejected"; }
   if (ok) {
     // every slot counts as solved for k_pose_information_map: a slot whose gate is false holds no record and comes back without factors
     std::vector<int> list(S);
     for (size_t s = 0; s < S; ++s) list[s] = (int)s | kInfoSolvedBit;
-    ok = hipMemcpyAsync(c->d_lr_list.get(), list.data(), sizeof(int) * S, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-         hipMemsetAsync(c->d_lr_vox_counters.get(), 0, 8 * sizeof(int), c->stream) == hipSuccess &&
-         hipMemsetAsync(c->d_lr_seq.get(), 0, sizeof(MapSeq) * S, c->stream) == hipSuccess &&
-         hipMemsetAsync(c->d_lr_plan.get(), 0, sizeof(int) * S * kLoopPlanInts, c->stream) == hipSuccess &&
+    ok = hipMemcpyAsync(l.list.get(), list.data(), sizeof(int) * S, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+         hipMemsetAsync(l.vox_counters.get(), 0, 8 * sizeof(int), c->stream) == hipSuccess &&
+         hipMemsetAsync(l.seq.get(), 0, sizeof(MapSeq) * S, c->stream) == hipSuccess &&
+         hipMemsetAsync(l.plan.get(), 0, sizeof(int) * S * kLoopPlanInts, c->stream) == hipSuccess &&
          hipStreamSynchronize(c->stream) == hipSuccess;                          // (list is a local)
     if (!ok) cause = "initialising the scratch failed";
   }
-  if (!ok) {                           // nothing stays allocated behind a refusal
+  if (!ok) {
     (void)hipGetLastError();
-    loops_release(c);
     c->err = "loop registration scratch of " + std::to_string(max_requests) + " slots: " + cause;
     return ALOAM_E_HIP;
   }
-  c->lr_slots = max_requests; c->lr_H = H; c->lr_levels = levels; c->lr_cap[0] = (long long)tc[0]; c->lr_cap[1] = (long long)tc[1];
-  c->lr_key_cap = (long long)key_cap; c->lr_tile_cap = (int)tile_cap; c->lr_tile_bound = (int)std::max<size_t>(tile_cap, 1);
-  c->lr_stage_slot = 0;
-  c->lr_on = true;
+  l.slots = max_requests; l.H = H; l.levels = levels; l.cap[0] = (long long)tc[0]; l.cap[1] = (long long)tc[1];
+  l.key_cap = (long long)key_cap; l.tile_cap = (int)tile_cap; l.tile_bound = (int)std::max<size_t>(tile_cap, 1);
+  l.on = true;
+  c->lr = std::move(l);
   return ALOAM_OK;
 }
 
@@ -165,11 +154,7 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
     if (const int rc = loop_search_grid(c, g, &sc.grid)) return rc;
   }
   if (n == 0) return ALOAM_OK;
-  {
-    void* dev = nullptr;
-    const CallerMem m = classify_pointer(c, req, &dev);
-    if (m != kMemPageable && m != kMemPinned) { c->err = "req must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
-  }
+  if (const int rc = require_host_list(c, req, "req")) return rc;
   void* d_dst = nullptr;
   if (const int rc = export_target(c, dst, 8, "dst", &d_dst)) return rc;
   if (searched) {
@@ -195,9 +180,9 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
     q.pad[0] = 0; q.pad[1] = 0; q.reserved = 0.0;
   }
   // ---- rounds of at most lr_slots requests (searched: and at most 2^18 (slot, node) pairs) over the same scratch, in stream order
-  const int per_round = searched ? (int)std::min<long long>(c->lr_slots, kLoopSearchMaxPairs / sc.grid.K) : c->lr_slots;
+  const int per_round = searched ? (int)std::min<long long>(c->lr.slots, kLoopSearchMaxPairs / sc.grid.K) : c->lr.slots;
   if (searched)
-    if (const int rc = grow_scratch(c, c->d_ls_part, c->ls_part_cap, (long long)std::min(per_round, n) * sc.grid.K * kLoopSearchParts)) {
+    if (const int rc = c->lr.search_part.grow(c, (long long)std::min(per_round, n) * sc.grid.K * kLoopSearchParts)) {
       (void)hipGetLastError();
       c->err = "search scratch of " + std::to_string(std::min(per_round, n)) + " x " + std::to_string(sc.grid.K) + " (request, node) pairs: device allocation failed";
       return rc;
@@ -205,41 +190,36 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
   ProfScope prof(c, K_LOOP_REGISTER);
   // A slot of the pinned ring holds lr_slots requests: one round of the plain call, as many whole rounds of a searched call as fit (its
   // rounds are the shorter of the two bounds), so that a searched call waits for the ring no sooner than a plain call of the same n.
-  int ns = 0, ring_at = 0, ring_left = 0;
+  aloam_graph_loop_request* ring_slot = nullptr; int ns = 0, ring_at = 0, ring_left = 0;
   for (int r0 = 0; r0 < n; r0 += per_round) {
     const int m = std::min(per_round, n - r0);
     if (ring_left < m) {
-      ns = c->lr_stage_slot;
-      c->lr_stage_slot = (ns + 1) % kLoopStageSlots;
-      if (c->lr_stage_used[ns]) HIP_TRY(c, hipEventSynchronize(c->lr_stage_done[ns]));
-      ring_at = 0; ring_left = c->lr_slots;
+      if (const int rc = c->lr.ring.acquire(c, &ring_slot, &ns)) return rc;
+      ring_at = 0; ring_left = c->lr.slots;
     }
-    aloam_graph_loop_request* slot = c->h_lr_stage.get() + (size_t)ns * c->lr_slots + ring_at;
+    aloam_graph_loop_request* slot = ring_slot + ring_at;
     ring_at += m; ring_left -= m;
     std::copy(checked.begin() + r0, checked.begin() + r0 + m, slot);
-    HIP_TRY(c, hipMemcpyAsync(c->d_lr_req.get(), slot, sizeof(aloam_graph_loop_request) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(c->lr_stage_done[ns], c->stream));
-    c->lr_stage_used[ns] = true;
+    if (const int rc = c->lr.ring.queue(c, ns, slot, sizeof(aloam_graph_loop_request) * (size_t)m, c->lr.req.get(), c->stream)) return rc;
     LoopArgs a{};
-    a.n = m; a.req = c->d_lr_req.get();
-    a.kf.points[0] = c->d_kf_points[0].get(); a.kf.points[1] = c->d_kf_points[1].get(); a.kf.desc = c->d_kf_desc.get(); a.kf.counters = c->d_kf_counters.get();
-    a.kf.cap[0] = c->kf_cap[0]; a.kf.cap[1] = c->kf_cap[1]; a.kf.max_nodes = c->pg_max_nodes;
-    a.nodes = c->d_pg_nodes.get(); a.max_nodes = c->pg_max_nodes;
+    a.n = m; a.req = c->lr.req.get();
+    a.kf = kf_store(c);
+    a.nodes = c->pg.nodes.get(); a.max_nodes = c->pg.max_nodes;
     a.map = loop_map_args(c, m, o.lm_max_iterations);
-    for (int k = 0; k < 2; ++k) { a.raw[k] = c->d_lr_raw[k].get(); a.raw_cap[k] = c->lr_cap[k]; a.target[k] = c->d_lr_target[k].get(); }
-    a.plan = c->d_lr_plan.get(); a.outer_iterations = o.outer_iterations;
-    a.info = c->d_lr_info.get(); a.dst = static_cast<aloam_graph_loop_result*>(d_dst) + r0;
+    for (int k = 0; k < 2; ++k) { a.raw[k] = c->lr.raw[k].get(); a.raw_cap[k] = c->lr.cap[k]; a.target[k] = c->lr.target[k].get(); }
+    a.plan = c->lr.plan.get(); a.outer_iterations = o.outer_iterations;
+    a.info = c->lr.info.get(); a.dst = static_cast<aloam_graph_loop_result*>(d_dst) + r0;
     const VoxArgs v = loop_vox_args(c, 2 * m);
-    HIP_TRY(c, hipMemsetAsync(c->d_lr_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));   // general-path count, the three LDS-filter lists
+    HIP_TRY(c, hipMemsetAsync(c->lr.vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));   // general-path count, the three LDS-filter lists
     launch_loop_gather(a, v, c->stream);
-    launch_voxel_filter(v, c->lr_tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
+    launch_voxel_filter(v, c->lr.tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
     launch_loop_grid(a, c->stream);
     if (searched) {
       LoopSearchArgs sa{};
       sa.n = m;
       sa.splits = m < 8 ? std::max(1, std::min(8 / m, sc.grid.K)) : 1;   // fewer than 8 slots: their nodes are dealt over the XCDs left idle
       sa.kper = (sc.grid.K + sa.splits - 1) / sa.splits;
-      sa.req = a.req; sa.map = a.map; sa.plan = a.plan; sa.plan_ints = kLoopPlanInts; sa.grid = sc.grid; sa.part = c->d_ls_part.get();
+      sa.req = a.req; sa.map = a.map; sa.plan = a.plan; sa.plan_ints = kLoopPlanInts; sa.grid = sc.grid; sa.part = c->lr.search_part.get();
       sa.scores = sc.d_scores ? static_cast<aloam_map_score*>(sc.d_scores) + (size_t)r0 * sc.grid.K : nullptr;
       sa.dst = static_cast<aloam_graph_loop_search_result*>(sc.d_search) + r0;
       launch_loop_search(sa, c->stream);
@@ -248,7 +228,7 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
       launch_map_associate(a.map, it, c->stream);
       launch_map_solve(a.map, it & 1, false, c->stream);   // no transformUpdate: a slot has no odometry frame
     }
-    launch_pose_information_map(a.map, c->d_lr_list.get(), m, c->d_lr_info.get(), c->stream);
+    launch_pose_information_map(a.map, c->lr.list.get(), m, c->lr.info.get(), c->stream);
     launch_loop_result(a, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
@@ -272,13 +252,13 @@ int aloam_graph_loop_export_target(aloam_ctx* c, int slot, int feature_class, fl
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_loops(c)) return rc;
-  if (slot < 0 || slot >= c->lr_slots) { c->err = "slot out of range"; return ALOAM_E_ARG; }
+  if (slot < 0 || slot >= c->lr.slots) { c->err = "slot out of range"; return ALOAM_E_ARG; }
   if (feature_class < 0 || feature_class > 1) { c->err = "feature_class must be 0 (corner) or 1 (surf)"; return ALOAM_E_ARG; }
   if (cap < 0) { c->err = "negative cap"; return ALOAM_E_ARG; }
   void *d_cnt = nullptr, *d_pts = nullptr;
   if (const int rc = export_target(c, count, alignof(int), "count", &d_cnt)) return rc;
   if ((dst_xyzw || cap > 0) && export_target(c, dst_xyzw, 16, "dst", &d_pts)) return ALOAM_E_ARG;
-  launch_loop_export_target(c->d_lr_seq.get() + slot, feature_class, c->d_lr_target[feature_class].get() + (size_t)slot * c->lr_cap[feature_class],
+  launch_loop_export_target(c->lr.seq.get() + slot, feature_class, c->lr.target[feature_class].get() + (size_t)slot * c->lr.cap[feature_class],
                             static_cast<float4*>(d_pts), d_pts ? cap : 0, static_cast<int*>(d_cnt), c->stream);
   HIP_TRY(c, hipGetLastError());
   return ALOAM_OK;

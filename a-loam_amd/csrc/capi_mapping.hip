@@ -154,7 +154,7 @@ int aloam_mapping_enable(aloam_ctx* c, float line_res, float plane_res, int pool
   { int* p = nullptr; HIP_TRY(c, hipHostMalloc((void**)&p, sizeof(int) * 8, hipHostMallocMapped)); c->h_map_report.reset(p); }
   for (int k = 0; k < 8; ++k) c->h_map_report[k] = 0;
   HIP_TRY(c, hipHostGetDevicePointer((void**)&c->d_map_report_host, (void*)c->h_map_report.get(), 0));
-  for (Event& e : c->map_step_done) HIP_TRY(c, hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+  for (Event& e : c->map_step_done) if (!e.h) HIP_TRY(c, hipEventCreateWithFlags(&e.h, hipEventDisableTiming));   // (once: an enable retried after a failure)
   for (int k = 0; k < 2; ++k) {
     const size_t per = k == 0 ? R * kLessSharpPerRing : cap;
     if ((rc = dmalloc(c, c->d_stack[k], B * per))) return rc;

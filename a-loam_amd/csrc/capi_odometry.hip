@@ -161,7 +161,7 @@ static int acquire_slab(aloam_ctx* c, size_t need, int* slot_out) {
   const int s = c->in_slot;
   c->in_slot ^= 1;
   if (c->in_used[s]) HIP_TRY(c, hipEventSynchronize(c->in_consumed[s]));
-  if (const int rc = grow_scratch(c, c->d_in[s], c->d_in_bytes[s], need)) return rc;
+  if (const int rc = c->d_in[s].grow(c, need)) return rc;
   *slot_out = s;
   return ALOAM_OK;
 }

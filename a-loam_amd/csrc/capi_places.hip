@@ -114,7 +114,7 @@ int aloam_places_match(aloam_ctx* c, const int* seqs, int n, const int* ranges, 
   void* d_dst = nullptr;
   if (const int rc = export_target(c, dst, alignof(aloam_place_match), "dst", &d_dst)) return rc;
   if (n == 0) return ALOAM_OK;
-  if (const int rc = grow_scratch(c, c->d_pl_pairs, c->pl_pairs_cap, std::max(1LL, (long long)n * longest))) return rc;
+  if (const int rc = c->d_pl_pairs.grow(c, std::max(1LL, (long long)n * longest))) return rc;
   if (const int rc = ensure_descriptors(c, seqs, n)) return rc;
   if (const int rc = stage_ints(c, seqs, n, c->d_pl_seqs.get())) return rc;
   if (const int rc = stage_ints(c, lo.data(), n, c->d_pl_lo.get())) return rc;

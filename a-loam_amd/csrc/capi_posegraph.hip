@@ -8,7 +8,7 @@
 #include "capi_internal.hpp"
 
 int aloam::require_graph(aloam_ctx* c) {
-  if (!c->graph_on) { c->err = "pose graphs are not enabled (aloam_graph_enable)"; return ALOAM_E_STATE; }
+  if (!c->pg.on) { c->err = "pose graphs are not enabled (aloam_graph_enable)"; return ALOAM_E_STATE; }
   return ALOAM_OK;
 }
 
@@ -44,26 +44,6 @@ const char* aloam::graph_edge_check(const aloam_ctx* c, aloam_graph_edge& e, boo
   return nullptr;
 }
 
-// The items of one call to device memory through the pinned ring h_pg_stage, as stage_ints does for ints: the caller fills the slot this
-// returns and queues it with queue_items; the call returns at once and the H2D copy runs in stream order.  A slot is reused
-// kGraphStageSlots calls later, after the copy that read it has run.
-template <typename T>
-static int stage_slot(aloam_ctx* c, T** slot, int* index) {
-  const int ns = c->pg_stage_slot;
-  c->pg_stage_slot = (ns + 1) % kGraphStageSlots;
-  if (c->pg_stage_used[ns]) HIP_TRY(c, hipEventSynchronize(c->pg_stage_done[ns]));
-  *slot = reinterpret_cast<T*>(c->h_pg_stage.get() + (size_t)ns * c->pg_stage_bytes);
-  *index = ns;
-  return ALOAM_OK;
-}
-template <typename T>
-static int queue_items(aloam_ctx* c, const T* slot, int index, int n, T* dst) {
-  HIP_TRY(c, hipMemcpyAsync(dst, slot, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipEventRecord(c->pg_stage_done[index], c->stream));
-  c->pg_stage_used[index] = true;
-  return ALOAM_OK;
-}
-
 // (seq has been checked by the caller, which read `have` from its SeqHost)
 static int export_rows(aloam_ctx* c, int seq, int first, int count, int have, const void* base, size_t row, size_t item, void* dst) {
   if (first < 0 || count < 0 || first + (long long)count > have) { c->err = "[first, first + count) must lie inside what the sequence's graph holds"; return ALOAM_E_ARG; }
@@ -87,26 +67,17 @@ int aloam_graph_enable(aloam_ctx* c, int max_nodes, int max_edges) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_stage(c, ALOAM_STAGE_ODOMETRY)) return rc;
-  if (c->graph_on) { c->err = "pose graphs already enabled"; return ALOAM_E_STATE; }
+  if (c->pg.on) { c->err = "pose graphs already enabled"; return ALOAM_E_STATE; }
   if (max_nodes < 1 || max_nodes > (1 << 20) || max_edges < 1 || max_edges > (1 << 22)) { c->err = "need 1 <= max_nodes <= 2^20 and 1 <= max_edges <= 2^22"; return ALOAM_E_ARG; }
   const size_t B = c->B;
   static_assert(sizeof(GraphAddItem) >= sizeof(GraphSolveItem) && sizeof(GraphAddItem) % 8 == 0, "a slot of the ring holds B items of either kind");
-  const size_t slot_bytes = B * sizeof(GraphAddItem);
-  char* ring = nullptr;
-  bool ok = dalloc(c->d_pg_nodes, B * max_nodes) == hipSuccess && dalloc(c->d_pg_edges, B * max_edges) == hipSuccess &&
-            dalloc(c->d_pg_add, B) == hipSuccess && dalloc(c->d_pg_items, B) == hipSuccess &&
-            hipHostMalloc((void**)&ring, slot_bytes * kGraphStageSlots, hipHostMallocDefault) == hipSuccess;
-  c->h_pg_stage.reset(ring);
-  for (Event& e : c->pg_stage_done) ok = ok && (e.h || hipEventCreateWithFlags(&e.h, hipEventDisableTiming) == hipSuccess);
-  if (!ok) {                           // nothing stays allocated behind a refusal
-    (void)hipGetLastError();
-    c->d_pg_nodes.reset(); c->d_pg_edges.reset(); c->d_pg_add.reset(); c->d_pg_items.reset(); c->h_pg_stage.reset();
-    c->err = "pose graph store: allocation failed";
-    return ALOAM_E_HIP;
-  }
-  c->pg_stage_bytes = slot_bytes;
-  c->pg_max_nodes = max_nodes; c->pg_max_edges = max_edges;
-  c->graph_on = true;
+  GraphStore g;                        // committed with one move: nothing stays allocated behind a refusal
+  const bool ok = dalloc(g.nodes, B * max_nodes) == hipSuccess && dalloc(g.edges, B * max_edges) == hipSuccess &&
+                  dalloc(g.add, B) == hipSuccess && dalloc(g.items, B) == hipSuccess && !g.ring.create(B * sizeof(GraphAddItem));
+  if (!ok) { (void)hipGetLastError(); c->err = "pose graph store: allocation failed"; return ALOAM_E_HIP; }
+  g.max_nodes = max_nodes; g.max_edges = max_edges;
+  g.on = true;
+  c->pg = std::move(g);
   return ALOAM_OK;
 }
 
@@ -119,7 +90,7 @@ int aloam_graph_add_nodes(aloam_ctx* c, const int* seqs, int n, const double* od
   for (int i = 0; i < n; ++i) {                 // everything is checked before the ring is touched
     const SeqHost& s = c->seq[seqs[i]];
     if (!info_positive_definite(odom_info + 21 * (size_t)i)) { c->err = "odom_info " + std::to_string(i) + " is not finite and positive definite"; return ALOAM_E_ARG; }
-    if (s.graph_nodes >= c->pg_max_nodes || (s.graph_nodes > 0 && s.graph_edges >= c->pg_max_edges)) {
+    if (s.graph_nodes >= c->pg.max_nodes || (s.graph_nodes > 0 && s.graph_edges >= c->pg.max_edges)) {
       c->err = "the graph of sequence " + std::to_string(seqs[i]) + " is full (" + std::to_string(s.graph_nodes) + " nodes, " + std::to_string(s.graph_edges) + " edges)";
       return ALOAM_E_CAPACITY;
     }
@@ -128,16 +99,16 @@ int aloam_graph_add_nodes(aloam_ctx* c, const int* seqs, int n, const double* od
   if (n == 0) return ALOAM_OK;
   GraphAddItem* items = nullptr;
   int slot = 0;
-  if (const int rc = stage_slot(c, &items, &slot)) return rc;
+  if (const int rc = c->pg.ring.acquire(c, &items, &slot)) return rc;
   for (int i = 0; i < n; ++i) {
     const SeqHost& s = c->seq[seqs[i]];
     items[i].seq = seqs[i]; items[i].node = s.graph_nodes; items[i].edge = s.graph_edges; items[i].pad = 0;
     std::copy(odom_info + 21 * (size_t)i, odom_info + 21 * (size_t)(i + 1), items[i].info);
   }
-  if (const int rc = queue_items(c, items, slot, n, c->d_pg_add.get())) return rc;
+  if (const int rc = c->pg.ring.queue(c, slot, items, sizeof(GraphAddItem) * (size_t)n, c->pg.add.get(), c->stream)) return rc;
   GraphAddArgs a{};
-  a.n = n; a.items = c->d_pg_add.get(); a.odom = c->d_state.get(); a.mapseq = c->map_on ? c->d_mapseq.get() : nullptr;
-  a.nodes = c->d_pg_nodes.get(); a.edges = c->d_pg_edges.get(); a.max_nodes = c->pg_max_nodes; a.max_edges = c->pg_max_edges;
+  a.n = n; a.items = c->pg.add.get(); a.odom = c->d_state.get(); a.mapseq = c->map_on ? c->d_mapseq.get() : nullptr;
+  a.nodes = c->pg.nodes.get(); a.edges = c->pg.edges.get(); a.max_nodes = c->pg.max_nodes; a.max_edges = c->pg.max_edges;
   launch_graph_add_nodes(a, c->stream);
   queue_keyframe_capture(c, n);        // the stacks of the listed sequences become the new nodes' clouds (aloam_graph_keyframes_enable)
   HIP_TRY(c, hipGetLastError());
@@ -150,17 +121,13 @@ int aloam_graph_add_edges(aloam_ctx* c, const aloam_graph_edge* edges, int n) {
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_graph(c)) return rc;
   if (n < 0 || (n > 0 && !edges)) { c->err = "bad edge list"; return ALOAM_E_ARG; }
-  if (n > 0) {
-    void* dev = nullptr;
-    const CallerMem m = classify_pointer(c, edges, &dev);
-    if (m != kMemPageable && m != kMemPinned) { c->err = "edges must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
-  }
+  if (n > 0) if (const int rc = require_host_list(c, edges, "edges")) return rc;
   std::vector<aloam_graph_edge> checked(edges, edges + n);
   std::vector<int> added(c->B, 0);
   for (int k = 0; k < n; ++k) {
     aloam_graph_edge& e = checked[k];
     if (const char* what = graph_edge_check(c, e, true)) { c->err = "edge " + std::to_string(k) + ": " + what; return ALOAM_E_ARG; }
-    if (c->seq[e.seq].graph_edges + ++added[e.seq] > c->pg_max_edges) {
+    if (c->seq[e.seq].graph_edges + ++added[e.seq] > c->pg.max_edges) {
       c->err = "edge " + std::to_string(k) + ": the edge row of sequence " + std::to_string(e.seq) + " is full";
       return ALOAM_E_CAPACITY;
     }
@@ -170,7 +137,7 @@ int aloam_graph_add_edges(aloam_ctx* c, const aloam_graph_edge* edges, int n) {
     int m = k + 1;
     while (m < n && checked[m].seq == checked[k].seq) ++m;
     const int seq = checked[k].seq;
-    aloam_graph_edge* at = c->d_pg_edges.get() + (size_t)seq * c->pg_max_edges + c->seq[seq].graph_edges;
+    aloam_graph_edge* at = c->pg.edges.get() + (size_t)seq * c->pg.max_edges + c->seq[seq].graph_edges;
     HIP_TRY(c, hipMemcpyAsync(at, checked.data() + k, sizeof(aloam_graph_edge) * (size_t)(m - k), hipMemcpyHostToDevice, c->stream));
     on_graph_edges_added(c, seq, m - k);
     k = m;
@@ -183,7 +150,7 @@ int aloam_graph_export(aloam_ctx* c, int seq, int first, int count, aloam_graph_
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_graph(c)) return rc;
   if (const int rc = check_seq(c, seq)) return rc;
-  return export_rows(c, seq, first, count, c->seq[seq].graph_nodes, c->d_pg_nodes.get(), c->pg_max_nodes, sizeof(aloam_graph_node), dst);
+  return export_rows(c, seq, first, count, c->seq[seq].graph_nodes, c->pg.nodes.get(), c->pg.max_nodes, sizeof(aloam_graph_node), dst);
 }
 
 int aloam_graph_export_edges(aloam_ctx* c, int seq, int first, int count, aloam_graph_edge* dst) {
@@ -191,7 +158,7 @@ int aloam_graph_export_edges(aloam_ctx* c, int seq, int first, int count, aloam_
   if (!c) return ALOAM_E_ARG;
   if (const int rc = require_graph(c)) return rc;
   if (const int rc = check_seq(c, seq)) return rc;
-  return export_rows(c, seq, first, count, c->seq[seq].graph_edges, c->d_pg_edges.get(), c->pg_max_edges, sizeof(aloam_graph_edge), dst);
+  return export_rows(c, seq, first, count, c->seq[seq].graph_edges, c->pg.edges.get(), c->pg.max_edges, sizeof(aloam_graph_edge), dst);
 }
 
 int aloam_graph_clear(aloam_ctx* c, const int* seqs, int n) {
@@ -206,7 +173,7 @@ int aloam_graph_info(aloam_ctx* c, int seq, int out[4]) {
   if (!c || !out) return ALOAM_E_ARG;
   if (const int rc = require_graph(c)) return rc;
   if (const int rc = check_seq(c, seq)) return rc;
-  out[0] = c->seq[seq].graph_nodes; out[1] = c->seq[seq].graph_edges; out[2] = c->pg_max_nodes; out[3] = c->pg_max_edges;
+  out[0] = c->seq[seq].graph_nodes; out[1] = c->seq[seq].graph_edges; out[2] = c->pg.max_nodes; out[3] = c->pg.max_edges;
   return ALOAM_OK;
 }
 
@@ -235,24 +202,24 @@ int aloam_graph_optimize(aloam_ctx* c, const int* seqs, int n, const aloam_graph
     nodes += s.graph_nodes; edges += s.graph_edges;
   }
   const long long f64_row = graph_f64_row(row_nodes, row_edges), i32_row = graph_i32_row(row_nodes, row_edges);
-  if (const int rc = grow_scratch(c, c->d_pg_f64, c->pg_f64_cap, f64_row * n)) return rc;
-  if (const int rc = grow_scratch(c, c->d_pg_i32, c->pg_i32_cap, i32_row * n)) return rc;
+  if (const int rc = c->pg.f64.grow(c, f64_row * n)) return rc;
+  if (const int rc = c->pg.i32.grow(c, i32_row * n)) return rc;
   GraphSolveItem* items = nullptr;
   int slot = 0;
-  if (const int rc = stage_slot(c, &items, &slot)) return rc;
+  if (const int rc = c->pg.ring.acquire(c, &items, &slot)) return rc;
   for (int i = 0; i < n; ++i) items[i] = GraphSolveItem{seqs[i], c->seq[seqs[i]].graph_nodes, c->seq[seqs[i]].graph_edges, 0};
-  if (const int rc = queue_items(c, items, slot, n, c->d_pg_items.get())) return rc;
+  if (const int rc = c->pg.ring.queue(c, slot, items, sizeof(GraphSolveItem) * (size_t)n, c->pg.items.get(), c->stream)) return rc;
   GraphSolveArgs a{};
-  a.n = n; a.items = c->d_pg_items.get(); a.nodes = c->d_pg_nodes.get(); a.edges = c->d_pg_edges.get();
-  a.max_nodes = c->pg_max_nodes; a.max_edges = c->pg_max_edges; a.row_nodes = row_nodes; a.row_edges = row_edges; a.opt = o;
-  a.f64 = c->d_pg_f64.get(); a.f64_row = f64_row; a.i32 = c->d_pg_i32.get(); a.i32_row = i32_row;
+  a.n = n; a.items = c->pg.items.get(); a.nodes = c->pg.nodes.get(); a.edges = c->pg.edges.get();
+  a.max_nodes = c->pg.max_nodes; a.max_edges = c->pg.max_edges; a.row_nodes = row_nodes; a.row_edges = row_edges; a.opt = o;
+  a.f64 = c->pg.f64.get(); a.f64_row = f64_row; a.i32 = c->pg.i32.get(); a.i32_row = i32_row;
   a.dst = static_cast<aloam_graph_result*>(d);
   {
     ProfScope p(c, K_POSE_GRAPH);
     launch_pose_graph(a, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
-  c->pg_last_nodes = nodes; c->pg_last_edges = edges;
+  c->pg.last_nodes = nodes; c->pg.last_edges = edges;
   return ALOAM_OK;
 }
 

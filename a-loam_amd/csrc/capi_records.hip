@@ -26,6 +26,14 @@ CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev) {
   return kMemPageable;
 }
 
+// A request list that the host reads before anything is queued: host memory, pinned or pageable.
+int require_host_list(aloam_ctx* c, const void* p, const char* name) {
+  void* dev = nullptr;
+  const CallerMem m = classify_pointer(c, p, &dev);
+  if (m != kMemPageable && m != kMemPinned) { c->err = std::string(name) + " must be host memory, pinned or pageable"; return ALOAM_E_ARG; }
+  return ALOAM_OK;
+}
+
 // The address a kernel writes `p` through: device memory of the context's device as it is, pinned host memory through its device mapping.
 // Pageable host memory (with XNACK off a kernel store there faults the device), managed memory, another device's memory and NULL are refused.
 int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out) {
@@ -88,11 +96,11 @@ int get_cube_list(aloam_ctx* c, int seq, int which, float* out, int cap_points) 
   if (!c->d_exp_tmp_off) HIP_TRY(c, dalloc(c->d_exp_tmp_off, 2));
   long long off[2] = {0, 0};
   for (int pass = 0; pass < 2; ++pass) {                  // a second pass only when the scratch was too small for the points asked for
-    if ((rc = queue_export(c, &src, 1, false, seq, 1, c->d_exp_tmp.get(), c->exp_tmp_cap, c->d_exp_tmp_off.get()))) return rc;
+    if ((rc = queue_export(c, &src, 1, false, seq, 1, c->d_exp_tmp.get(), c->d_exp_tmp.cap, c->d_exp_tmp_off.get()))) return rc;
     HIP_TRY(c, hipMemcpyAsync(off, c->d_exp_tmp_off.get(), sizeof(off), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (cap_points <= 0 || off[1] <= c->exp_tmp_cap) break;
-    if ((rc = grow_scratch(c, c->d_exp_tmp, c->exp_tmp_cap, off[1]))) return rc;
+    if (cap_points <= 0 || off[1] <= c->d_exp_tmp.cap) break;
+    if ((rc = c->d_exp_tmp.grow(c, off[1]))) return rc;
   }
   const long long k = std::min<long long>(off[1], cap_points);
   if (k > 0) HIP_TRY(c, hipMemcpy(out, c->d_exp_tmp.get(), sizeof(float4) * k, hipMemcpyDeviceToHost));
@@ -303,7 +311,7 @@ int aloam_load_sequences(aloam_ctx* c, const int* slots, int n, const void* src,
   const char* base = static_cast<const char*>(d_src);
   if (!base) {                                            // pageable host memory: staged into device memory (the span of the n records)
     const size_t span = (size_t)(off[n] - off[0]);
-    if (const int rc = grow_scratch(c, c->d_ck_stage, c->ck_stage_bytes, span)) return rc;
+    if (const int rc = c->d_ck_stage.grow(c, span)) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_ck_stage.get(), static_cast<const char*>(src) + off[0], span, hipMemcpyHostToDevice, c->stream));
     base = c->d_ck_stage.get() - off[0];
   }

@@ -20,7 +20,7 @@ static int check_candidates(aloam_ctx* c, const aloam_map_correction* cand, cons
 }
 static int stage_candidates(aloam_ctx* c, const aloam_map_correction* cand, int K, const aloam_map_correction** dev) {
   if (*dev) return ALOAM_OK;
-  if (const int rc = grow_scratch(c, c->d_rl_cand, c->rl_cand_cap, (long long)K)) return rc;
+  if (const int rc = c->d_rl_cand.grow(c, K)) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_rl_cand.get(), cand, sizeof(aloam_map_correction) * (size_t)K, hipMemcpyHostToDevice, c->stream));
   *dev = c->d_rl_cand.get();
   return ALOAM_OK;
@@ -53,7 +53,7 @@ int aloam_score_map_corrections(aloam_ctx* c, const int* seqs, int n, const aloa
   if (const int rc = check_candidates(c, cand, &d_cand)) return rc;
   if (n == 0) return ALOAM_OK;
   if (!c->d_rl_seqs) HIP_TRY(c, dalloc(c->d_rl_seqs, (size_t)c->B));
-  if (const int rc = grow_scratch(c, c->d_rl_part, c->rl_part_cap, (long long)n * K * kScoreParts)) return rc;
+  if (const int rc = c->d_rl_part.grow(c, (long long)n * K * kScoreParts)) return rc;
   if (const int rc = stage_candidates(c, cand, K, &d_cand)) return rc;
   if (const int rc = stage_ints(c, seqs, n, c->d_rl_seqs.get())) return rc;
   ScoreArgs a{};

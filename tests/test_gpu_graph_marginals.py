@@ -127,6 +127,21 @@ def test_results_do_not_depend_on_the_list(world):
     assert bits(device) == bits(a)
 
 
+def test_a_call_of_six_rounds_wraps_the_request_ring(world):
+    """5130 requests in one call: six rounds of at most 1024 through the pinned ring of four slots, so rounds five and six fill the slots
+    of rounds one and two, whose copies were queued in the same call.  The result bytes are the 18-request result tiled, as the 1170-request
+    call of test_results_do_not_depend_on_the_list compares."""
+    c40, c300 = mc.candidates(world["cases"][STEP100], STEP100), mc.candidates(world["cases"][LAPS], LAPS)
+    two = pg.marginal_request(TWO, [0, -1], [1, 1], mode=[0, 1])
+    mixed = np.concatenate([two, mc.requests(c300[:3]), mc.requests(c40), two[::-1], mc.requests(c300[3:])])
+    o = dict(DEVICE_OPTIONS)
+    a = world["gpu"].graph_marginals(mixed, o)
+    many = np.concatenate([mixed] * 285)
+    assert len(mixed) == 18 and len(many) == 5130 > 4 * 1024
+    big = world["gpu"].graph_marginals(many, o)
+    assert bits(big) == bits(np.concatenate([a] * 285))
+
+
 def test_the_graph_is_only_read(world):
     gpu = world["gpu"]
     before = [(bits(gpu.graph_export(b)), bits(gpu.graph_export(b, edges=True))) for b in (STEP100, TWO, ONE)]

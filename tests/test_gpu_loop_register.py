@@ -256,6 +256,21 @@ def test_a_result_does_not_depend_on_the_other_requests(binding, world, twins, P
     assert raw(on["nodes"]) == raw(nd[0][:10]) and raw(on["gpu"].graph_register_loops([b])[0]) == alone
 
 
+def test_a_call_of_six_rounds_wraps_the_request_ring(binding, twins, P):
+    """5 * max_requests + 1 requests in one plain call: six rounds through the pinned ring of four slots, so rounds five and six fill the
+    slots of rounds one and two.  Five different requests in turn (a round holds eight: every round differs from the one whose slot it
+    takes); every result is byte-identical to the same request run alone."""
+    fx, (on, off) = twins
+    gpu, nd = on["gpu"], on["nodes"]
+    kinds = [(0, 4, 9, 0, 9, 0) + guess_of(P, nd, 4, 9), (0, 0, 9, 0, 3, 0) + guess_of(P, nd, 0, 9), (0, 2, 9, 1, 5, 0) + guess_of(P, nd, 2, 9),
+             (0, 8, 0, 5, 4, 0) + guess_of(P, nd, 8, 0), (0, 6, 1, 3, 6, 0) + guess_of(P, nd, 6, 1)]
+    lone = [raw(gpu.graph_register_loops([k])[0]) for k in kinds]
+    assert len(set(lone)) == len(kinds)
+    n = 5 * SLOTS + 1
+    many = gpu.graph_register_loops([kinds[k % 5] for k in range(n)])
+    assert len(many) == n and [raw(many[k]) for k in range(n)] == [lone[k % 5] for k in range(n)]
+
+
 def test_statuses(binding, world, L, P):
     gpu = world["gpu"]
     nd = world["nodes"]

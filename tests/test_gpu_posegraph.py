@@ -105,6 +105,32 @@ def test_nodes_are_the_exported_poses_and_edges_the_relative_poses(binding):
     gpu.close()
 
 
+def test_six_adds_in_a_row_wrap_the_staging_ring(binding):
+    """Six aloam_graph_add_nodes calls with nothing synchronising between them: the pinned ring of four slots wraps, so calls five and six
+    fill the slots of calls one and two.  Every call lists other sequences with another information, so a slot filled too early shows as a
+    node in the wrong row or an edge with the wrong information.  Nodes and edges equal those of a context that synchronised after every
+    call, byte for byte."""
+    d = pg.drifted_laps(5, 4, 0)
+    lists = [[0, 1, 2, 3], [3, 1], [2], [0, 3, 2], [1, 0], [3, 2, 1, 0]]
+    out = []
+    for wait in (False, True):
+        gpu = ctx(binding, 4, max_nodes=8, max_edges=8)
+        for b in range(4):
+            gpu.set_state(pc.IDENT_Q, pc.ZERO_T, d["q"][b], d["t"][b], seq=b)
+        for k, listed in enumerate(lists):
+            gpu.graph_add_nodes(listed, np.stack([np.eye(6) * (10.0 * k + b + 1) for b in listed]))
+            if wait:
+                gpu.synchronize()
+        out.append([state(gpu, b) for b in range(4)])
+        gpu.close()
+    for b in range(4):
+        (n0, e0), (n1, e1) = out[0][b], out[1][b]
+        calls = [k for k, listed in enumerate(lists) if b in listed]
+        assert len(n0) == len(calls) == len(n1) and len(e0) == len(calls) - 1 == len(e1)
+        assert n0.tobytes() == n1.tobytes() and e0.tobytes() == e1.tobytes()
+        assert np.array_equal(e0["info"], np.stack([pg.info_upper(np.eye(6) * (10.0 * k + b + 1)) for k in calls[1:]]))
+
+
 def test_with_mapping_the_node_is_the_map_pose(binding):
     import torch
     gpu = ctx(binding, 2, graph=False)
