@@ -10,6 +10,7 @@
 
 #include <cstdio>
 #include <memory>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -201,8 +202,9 @@ struct SeqHost {
   int graph_nodes = 0, graph_edges = 0;   // its pose graph (aloam_graph_*): what its rows of the store hold.  Host state only, and not the sequence's
                                      // but the slot's: reset and load leave it, aloam_graph_clear empties it
   bool has_stacks = false;           // took part in a mapping step since creation / reset / load: its stacks can be kept as a keyframe's clouds
-  bool grid_built = false;           // the grid set of its LAST clouds holds their grids: set by the step that made them the last ones (it built
-                                     // them beside its solve), cleared by whatever writes or replaces the last clouds outside a step
+  bool grid_built = false;           // the grid set of its LAST clouds holds their grids: set by the step that made them the last ones if it built
+                                     // them beside its solve (aloam_odometry_step; not aloam_process_*, which build inside the next call),
+                                     // cleared by whatever writes or replaces the last clouds outside a step
 };
 }  // namespace aloam
 
@@ -210,9 +212,9 @@ struct aloam_ctx {
   // Streams and events first: members are destroyed in reverse order, so every buffer is released before them (a StageRing further
   // down keeps its own events: aloam_destroy has drained every stream before anything is destroyed).
   Stream stream, copy_stream;
-  Stream grid_stream;                // the build of the next step's search grids runs here, beside the association and the solve (aloam_odometry_step)
+  Stream grid_stream;                // a step's grid build runs here: beside the registration of the same call (aloam_process_*), or the next step's beside the association and the solve (aloam_odometry_step)
   Event in_copied[2], in_consumed[2], map_step_done[4];
-  Event grid_fork, grids_done;       // main stream -> grid stream at the start of a step, grid stream -> main stream before k_advance
+  Event grid_fork, grids_done;       // main stream -> grid stream where the build is forked, grid stream -> main stream where it is joined (GridFork, capi_odometry.hip)
   std::vector<Event> prof_events;    // every profiling event created (prof_event); prof_free lists the idle ones
   // small batches (the ROS shims run batch 1): the ~15 dependent launches of an odometry step as ONE hipGraph launch; [0] every sequence
   // solves (no mask), [1] through the staged mask d_mask_odo
@@ -458,7 +460,7 @@ int check_ids(aloam_ctx* c, const int* ids, int n);
 // capi_odometry.hip
 // One registration of a checked batch: n_in = points per sequence; n_cols != nullptr: the sweeps are range images of that many columns (capi_range.hip).
 int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot = -1, bool debug_arrays = true,
-                    const int* n_cols = nullptr);
+                    const int* n_cols = nullptr, const std::function<void()>* after_front = nullptr);
 // A host-resident batch into the next staging slab, on the copy stream: rows 0 .. B-2 with `row` bytes each, the last with `last`; the compute stream waits for it.
 int stage_batch(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, size_t row, size_t last, size_t d_seq_stride, int* slot, char** d_in);
 int ensure_dense(aloam_ctx* c);
@@ -495,7 +497,7 @@ void on_frozen_mask_set(aloam_ctx* c, const int* frozen);
 int on_slots_reset(aloam_ctx* c, const int* seqs, int n);
 void on_slot_loaded(aloam_ctx* c, int seq, bool inited, long long err_events);
 void on_sweep_registered(aloam_ctx* c);
-void on_odometry_advanced(aloam_ctx* c, const StageMask& m);
+void on_odometry_advanced(aloam_ctx* c, const StageMask& m, bool built_next);
 void on_last_clouds_replaced(aloam_ctx* c, int seq);
 void on_odometry_inputs_replaced(aloam_ctx* c, int seq);
 void on_map_corrections_applied(aloam_ctx* c, const int* seqs, int n);

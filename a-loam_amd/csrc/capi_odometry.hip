@@ -2,6 +2,7 @@
 // launches, the process_* entries, the per-sequence getters and setters and the intermediate arrays.
 #include <algorithm>
 #include <cstring>
+#include <functional>
 
 #include "capi_internal.hpp"
 
@@ -67,7 +68,8 @@ namespace aloam {
 
 // debug_arrays: also write cloudCurvature / cloudLabel (the per-point entry points aloam_get_curvature / aloam_get_labels);
 // the throughput entries (aloam_process_device / aloam_process_host) leave those 5 bytes per point out.  The batch has passed check_batch.
-int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot, bool debug_arrays, const int* n_cols) {
+int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot, bool debug_arrays, const int* n_cols,
+                    const std::function<void()>* after_front) {
   int rc = ALOAM_OK;
   // A sequence that sits out keeps its dense cloud: made now from its slabs if the last registration's was never asked for (a no-op otherwise)
   if (!c->all_active && (rc = ensure_dense(c))) return rc;
@@ -91,6 +93,7 @@ int register_launch(aloam_ctx* c, const void* d_scans, long long seq_stride, con
     { ProfScope p(c, K_FIND_ENDS); launch_find_ends(a, c->d_nin.get(), c->stream); }
     { ProfScope p(c, K_FRONT); launch_front(a, c->stream); }
   }
+  if (after_front) (*after_front)();                         // (aloam_process_*: the grid build of the step is forked here, odometry_fork_build)
   { ProfScope p(c, K_RING_STARTS); launch_ring_starts(a, c->stream); }
   c->dense_valid = false;
   if (slot >= 0) { HIP_TRY(c, hipEventRecord(c->in_consumed[slot], c->stream)); c->in_used[slot] = true; }   // the raw sweep is not read after this
@@ -186,101 +189,120 @@ int stage_batch(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, s
 
 }  // namespace aloam
 
-extern "C" {
+namespace {
 
-int aloam_scan_register_device(aloam_ctx* c, const void* d_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
-  DeviceScope device_scope(c);
-  if (!c || !d_scans || !n_in) return ALOAM_E_ARG;
-  if (const int rc = check_batch(c, n_in, stride_bytes)) return rc;
-  return register_launch(c, d_scans, seq_stride_bytes, n_in, stride_bytes);
-}
+// The grid stream, forked from the context's stream for one build and joined into it again inside one call (aloam_odometry_step, aloam_process_*), so
+// that nothing else has to know about it: however the call ends after the fork, the context's stream has been made to wait for what was forked.
+struct GridFork {
+  aloam_ctx* c;
+  bool open = false;
+  hipError_t err = hipSuccess;                          // the first failure of any of its calls
+  explicit GridFork(aloam_ctx* c_) : c(c_) {}
+  GridFork(const GridFork&) = delete;
+  GridFork& operator=(const GridFork&) = delete;
+  ~GridFork() { join(); }
+  void note(hipError_t e) { if (err == hipSuccess) err = e; }
+  void begin() {                                        // everything queued so far, the staged mask included, is in front of the build
+    const hipError_t e = hipEventRecord(c->grid_fork, c->stream);
+    note(e);
+    if (e == hipSuccess) note(hipStreamWaitEvent(c->grid_stream, c->grid_fork, 0));
+    open = true;
+  }
+  void launched() { note(hipEventRecord(c->grids_done, c->grid_stream)); }
+  void join() {
+    if (open && err == hipSuccess) note(hipStreamWaitEvent(c->stream, c->grids_done, 0));
+    open = false;
+  }
+};
 
-int aloam_scan_register(aloam_ctx* c, const void* const* scans, const int* n_in, int stride_bytes) {
-  DeviceScope device_scope(c);
-  if (!c || !scans || !n_in) return ALOAM_E_ARG;
-  int rc = check_batch(c, n_in, stride_bytes);
-  if (rc) return rc;
-  const size_t seq_stride = (size_t)c->cap * stride_bytes;
-  int slot = 0;
-  if ((rc = acquire_slab(c, seq_stride * c->B, &slot))) return rc;
-  char* d_in = c->d_in[slot].get();
-  for (int b = 0; b < c->B; ++b)
-    if (n_in[b] > 0) HIP_TRY(c, hipMemcpyAsync(d_in + b * seq_stride, scans[b], (size_t)n_in[b] * stride_bytes, hipMemcpyHostToDevice, c->stream));
-  if ((rc = register_launch(c, d_in, (long long)seq_stride, n_in, stride_bytes, slot))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // the host buffers may be reused on return
+// Workgroups of the persistent build that runs beside k_ring_features.  Measured at batch 2048 (HISTORY, round 9): below 64 the build is bound by its
+// CUs and outlasts the ring kernel (48: 6.2 ms), from 64 to 128 the step is flat within 0.1 ms, above that the ring kernel loses more CUs than the
+// build gains (192: + 0.35 ms, 256: + 1.0).  96: the build and the ring kernel end together.
+constexpr int kGridWgsBesideRegistration = 96;
+
+// One odometry step while it is being queued.  aloam_process_* begin it in front of their registration (odometry_begin) and fork its grid build
+// inside the registration (odometry_fork_build); aloam_odometry_step on its own has only odometry_finish.
+struct OdomStep {
+  StageMask m;
+  bool masked = false;                                  // m is this step's mask, staged
+  bool beside_registration = false;                     // the grids this step searches are built, or were found built, by the time the fork is joined
+  bool build = false;                                   // ... built: the registration of the call forks the build behind its k_front
+  GridFork fork;
+  explicit OdomStep(aloam_ctx* c) : fork(c) {}
+};
+
+// Per sequence: kSeqActive = takes part (swaps), kSeqSolve = takes part and is past its first frame (src/laserOdometry.cpp:267-271).  The
+// kernels get no mask at all when every sequence solves: the launches of a lock-step batch are those of a context without the feature.
+int odometry_mask(aloam_ctx* c, OdomStep* st) {         // (a first frame of the whole batch needs no mask either: k_advance swaps all)
+  if (const int rc = stage_mask(c, c->d_mask_odo, [](const SeqHost& s) { return s.inited ? (int)kSeqSolve : 0; },
+                                [](const aloam_ctx* x, const StageMask& k) { return k.all_solve || (!k.any_solve && x->all_active); }, &st->m)) return rc;
+  st->masked = true;
   return ALOAM_OK;
 }
 
-// Host-resident batch in ONE buffer (sequence b at h_scans + b * seq_stride_bytes): one batched H2D copy on the context's copy
-// stream into the next of two device slabs, the kernels wait for it on the compute stream — so the copy of call k + 1 runs
-// under the kernels of call k.  Truly asynchronous only from pinned memory (hipHostMalloc / hipHostRegister); the runtime stages
-// pageable memory synchronously.  The buffer must stay unmodified until aloam_input_consumed() / aloam_synchronize().
-static int stage_and_register(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes, bool debug_arrays) {
-  if (!c || !h_scans || !n_in) return ALOAM_E_ARG;
-  int rc = check_batch(c, n_in, stride_bytes);
-  if (rc) return rc;
-  const size_t d_seq_stride = (size_t)c->cap * stride_bytes;
-  int slot = 0;
-  char* d_in = nullptr;
-  if ((rc = stage_batch(c, h_scans, seq_stride_bytes, (size_t)*std::max_element(n_in, n_in + c->B) * stride_bytes, (size_t)n_in[c->B - 1] * stride_bytes, d_seq_stride, &slot, &d_in))) return rc;
-  return register_launch(c, d_in, (long long)d_seq_stride, n_in, stride_bytes, slot, debug_arrays);
-}
-
-int aloam_scan_register_host(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
-  DeviceScope device_scope(c);
-  return stage_and_register(c, h_scans, seq_stride_bytes, n_in, stride_bytes, true);
-}
-
-int aloam_process_host(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
-  DeviceScope device_scope(c);
-  const int rc = stage_and_register(c, h_scans, seq_stride_bytes, n_in, stride_bytes, false);
-  if (rc) return rc;
-  return aloam_odometry_step(c);
-}
-
-int aloam_input_consumed(aloam_ctx* c) {
-  DeviceScope device_scope(c);
-  if (!c) return ALOAM_E_ARG;
-  for (int s = 0; s < 2; ++s) if (c->in_used[s]) HIP_TRY(c, hipEventSynchronize(c->in_consumed[s]));
+// A call that registers a sweep and runs its odometry step (aloam_process_*) knows the step's mask before it queues anything: who takes part and who
+// is past its first frame do not depend on the registration.  So it stages the mask first, and its registration can fork the build of the last
+// clouds' grids - complete since the previous step swapped - onto the grid stream.  A context without the odometry stage, or with the serial chain
+// (ALOAM_GRID_OVERLAP=0, use_graph, debug_sync), begins nothing here.
+int odometry_begin(aloam_ctx* c, OdomStep* st) {
+  if (!(c->stages & ALOAM_STAGE_ODOMETRY) || !c->grid_overlap) return ALOAM_OK;
+  if (const int rc = odometry_mask(c, st)) return rc;
+  st->beside_registration = true;                       // (a sequence that comes from an aloam_odometry_step of its own has its grids already)
+  for (int b = 0; b < c->B; ++b) st->build |= (st->m.bits[b] & kSeqSolve) && !c->seq[b].grid_built;
   return ALOAM_OK;
 }
 
-int aloam_odometry_step(aloam_ctx* c) {
-  DeviceScope device_scope(c);
-  if (!c) return ALOAM_E_ARG;
+// The fork, called by the registration between k_front and k_ring_starts.  The registration shares no data with the build: it writes the slabs,
+// the feature buffers [parity] and its own SeqMeta fields (field stores, find_ends_body), the build reads the clouds [1 - parity], parity and
+// n_*_last.  Where the fork stands is measured (HISTORY, round 9).  At the start of the call the build runs beside k_front, two kernels bound by
+// memory traffic: k_front takes 3.9 instead of 2.1 ms and the build 7.9 instead of 3.2, which loses what the association gains.  k_ring_features is
+// bound by instruction issue and shares better (5.2 instead of 3.7 ms for a build hidden whole).  Forked here, the build's 1024-thread workgroups
+// are placed on an empty chip while the one-wave k_ring_starts runs; behind the launch of k_ring_features they would wait for it to drain.
+void odometry_fork_build(aloam_ctx* c, OdomStep* st) {
+  OdomArgs a = odom_args(c);
+  a.active = st->m.dev;
+  st->fork.begin();
+  { ProfScope p(c, K_BUILD_GRIDS, c->grid_stream); launch_build_grids(a, GridBuild::kPersistentLast, kGridWgsBesideRegistration, c->grid_stream); }
+  st->fork.launched();
+}
+
+// The registration of an aloam_process_* call with its step's fork in it.
+int register_with_step(aloam_ctx* c, OdomStep* st, const void* d_scans, long long seq_stride, const int* n_in, int stride_bytes, int slot) {
+  const std::function<void()> fork = [c, st]() { odometry_fork_build(c, st); };
+  return register_launch(c, d_scans, seq_stride, n_in, stride_bytes, slot, /*debug_arrays=*/false, nullptr, st->build ? &fork : nullptr);
+}
+
+int odometry_finish(aloam_ctx* c, OdomStep* st) {
   if (const int rc = require_stage(c, ALOAM_STAGE_ODOMETRY)) return rc;
   if (!c->have_features) { c->err = "aloam_odometry_step before any features were registered / set"; return ALOAM_E_STATE; }
-  // Per sequence: kSeqActive = takes part (swaps), kSeqSolve = takes part and is past its first frame (src/laserOdometry.cpp:267-271).  The
-  // kernels get no mask at all when every sequence solves: the launches of a lock-step batch are those of a context without the feature.
-  StageMask m;                                                   // (a first frame of the whole batch needs no mask either: k_advance swaps all)
-  if (const int rc = stage_mask(c, c->d_mask_odo, [](const SeqHost& s) { return s.inited ? (int)kSeqSolve : 0; },
-                                [](const aloam_ctx* x, const StageMask& k) { return k.all_solve || (!k.any_solve && x->all_active); }, &m)) return rc;
+  if (!st->masked) if (const int rc = odometry_mask(c, st)) return rc;
+  const StageMask& m = st->m;
   const int* mask = m.dev;
   const bool any_solve = m.any_solve;
   // The kd-tree stand-in of a step (launch_build_grids) covers clouds that were complete before the step began, so it need not wait for the step
-  // that searches it.  With grid_overlap every step builds, on the grid stream and beside its own association and solve, the grids of the sweep it
-  // is about to make the last one (the "next" form, into the grid set of that cloud buffer); the step after it finds them built (grid_built) and
-  // starts with the association.  The build is forked from and joined into the main stream inside this call, in front of k_advance, so nothing
-  // else has to know about the grid stream.  A solving sequence whose last clouds came from somewhere else (aloam_set_last, a loaded record)
-  // sends the step through the serial "last" build first, which is also the whole schedule without grid_overlap.
-  const bool overlap = c->grid_overlap;
-  bool build_last = !overlap;
+  // that searches it.  Where the registration is part of the call, the build has run beside its k_ring_features (odometry_fork_build) and is joined
+  // here, in front of the first k_transform_queries; such a step builds nothing for the next one.  An aloam_odometry_step on its own has no such
+  // window: with grid_overlap it builds, on the grid stream and beside its own association and solve, the grids of the sweep it is about to make
+  // the last one (the "next" form, into the grid set of that cloud buffer); the step after it finds them built (grid_built) and starts with the
+  // association.  Either way the build is forked from and joined into the main stream inside the call.  A solving sequence of such a step whose
+  // last clouds came from somewhere else (aloam_set_last, a loaded record, a step that built beside its registration) sends the step through the
+  // serial "last" build first, which is also the whole schedule without grid_overlap.
+  st->fork.join();
+  const bool overlap = c->grid_overlap && !st->beside_registration;
+  bool build_last = !c->grid_overlap;
   if (overlap) for (int b = 0; b < c->B; ++b) build_last |= (m.bits[b] & kSeqSolve) && !c->seq[b].grid_built;
-  hipError_t join_err = hipSuccess;
   const int cus = c->gather_blocks / 8;                                           // (aloam_create: eight gather workgroups per CU)
   auto launch_all = [&]() {
     OdomArgs a = odom_args(c);
     a.active = mask;
     if (overlap) {
-      hipError_t e = hipEventRecord(c->grid_fork, c->stream);                     // everything registered so far, and the staged mask, are in front of it
-      if (e == hipSuccess) e = hipStreamWaitEvent(c->grid_stream, c->grid_fork, 0);
-      { ProfScope p(c, K_BUILD_GRIDS, c->grid_stream); launch_build_grids(a, true, cus, c->grid_stream); }
-      if (e == hipSuccess) e = hipEventRecord(c->grids_done, c->grid_stream);
-      join_err = e;
+      st->fork.begin();
+      { ProfScope p(c, K_BUILD_GRIDS, c->grid_stream); launch_build_grids(a, GridBuild::kPersistentNext, cus / 2, c->grid_stream); }
+      st->fork.launched();
     }
     if (any_solve && build_last) {
-      if (overlap) launch_build_grids(a, false, cus, c->stream);                       // (K_BUILD_GRIDS stays the one launch per step on the grid stream)
-      else { ProfScope p(c, K_BUILD_GRIDS); launch_build_grids(a, false, cus, c->stream); }   // kd-tree stand-in over the last clouds
+      if (overlap) launch_build_grids(a, GridBuild::kSerialLast, 0, c->stream);        // (K_BUILD_GRIDS stays the one launch per step on the grid stream)
+      else { ProfScope p(c, K_BUILD_GRIDS); launch_build_grids(a, GridBuild::kSerialLast, 0, c->stream); }   // kd-tree stand-in over the last clouds
     }
     for (int outer = 0; any_solve && outer < c->cfg.outer_iterations; ++outer) {  // (a first frame of every active sequence: no solve, src/laserOdometry.cpp:267-271)
       a.outer = outer;
@@ -290,7 +312,7 @@ int aloam_odometry_step(aloam_ctx* c) {
       { ProfScope p(c, K_ASSOC_PLANE); launch_associate(a, true, c->stream); }
       { ProfScope p(c, K_SOLVE); launch_solve(a, c->stream); }
     }
-    if (overlap && join_err == hipSuccess) join_err = hipStreamWaitEvent(c->stream, c->grids_done, 0);
+    st->fork.join();                                               // the next step's grids, in front of the swap
     { ProfScope p(c, K_ADVANCE); launch_advance(a, c->stream); }   // swap (src/laserOdometry.cpp:554-563)
   };
   if (!any_solve) {
@@ -323,18 +345,91 @@ int aloam_odometry_step(aloam_ctx* c) {
   } else {
     launch_all();
   }
-  HIP_TRY(c, join_err);
+  HIP_TRY(c, st->fork.err);
   HIP_TRY(c, hipGetLastError());
-  on_odometry_advanced(c, m);
+  on_odometry_advanced(c, m, /*built_next=*/overlap);
   return ALOAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aloam_scan_register_device(aloam_ctx* c, const void* d_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
+  DeviceScope device_scope(c);
+  if (!c || !d_scans || !n_in) return ALOAM_E_ARG;
+  if (const int rc = check_batch(c, n_in, stride_bytes)) return rc;
+  return register_launch(c, d_scans, seq_stride_bytes, n_in, stride_bytes);
+}
+
+int aloam_scan_register(aloam_ctx* c, const void* const* scans, const int* n_in, int stride_bytes) {
+  DeviceScope device_scope(c);
+  if (!c || !scans || !n_in) return ALOAM_E_ARG;
+  int rc = check_batch(c, n_in, stride_bytes);
+  if (rc) return rc;
+  const size_t seq_stride = (size_t)c->cap * stride_bytes;
+  int slot = 0;
+  if ((rc = acquire_slab(c, seq_stride * c->B, &slot))) return rc;
+  char* d_in = c->d_in[slot].get();
+  for (int b = 0; b < c->B; ++b)
+    if (n_in[b] > 0) HIP_TRY(c, hipMemcpyAsync(d_in + b * seq_stride, scans[b], (size_t)n_in[b] * stride_bytes, hipMemcpyHostToDevice, c->stream));
+  if ((rc = register_launch(c, d_in, (long long)seq_stride, n_in, stride_bytes, slot))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // the host buffers may be reused on return
+  return ALOAM_OK;
+}
+
+// Host-resident batch in ONE buffer (sequence b at h_scans + b * seq_stride_bytes): one batched H2D copy on the context's copy
+// stream into the next of two device slabs, the kernels wait for it on the compute stream — so the copy of call k + 1 runs
+// under the kernels of call k.  Truly asynchronous only from pinned memory (hipHostMalloc / hipHostRegister); the runtime stages
+// pageable memory synchronously.  The buffer must stay unmodified until aloam_input_consumed() / aloam_synchronize().
+// step: the odometry step of the same call (aloam_process_host), begun as soon as the batch has passed its checks; the throughput entry keeps no debug arrays.
+static int stage_and_register(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes, bool debug_arrays, OdomStep* step = nullptr) {
+  if (!c || !h_scans || !n_in) return ALOAM_E_ARG;
+  int rc = check_batch(c, n_in, stride_bytes);
+  if (rc || (step && (rc = odometry_begin(c, step)))) return rc;
+  const size_t d_seq_stride = (size_t)c->cap * stride_bytes;
+  int slot = 0;
+  char* d_in = nullptr;
+  if ((rc = stage_batch(c, h_scans, seq_stride_bytes, (size_t)*std::max_element(n_in, n_in + c->B) * stride_bytes, (size_t)n_in[c->B - 1] * stride_bytes, d_seq_stride, &slot, &d_in))) return rc;
+  if (step) return register_with_step(c, step, d_in, (long long)d_seq_stride, n_in, stride_bytes, slot);
+  return register_launch(c, d_in, (long long)d_seq_stride, n_in, stride_bytes, slot, debug_arrays);
+}
+
+int aloam_scan_register_host(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
+  DeviceScope device_scope(c);
+  return stage_and_register(c, h_scans, seq_stride_bytes, n_in, stride_bytes, true);
+}
+
+int aloam_process_host(aloam_ctx* c, const void* h_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  OdomStep st(c);
+  if (const int rc = stage_and_register(c, h_scans, seq_stride_bytes, n_in, stride_bytes, false, &st)) return rc;
+  return odometry_finish(c, &st);
+}
+
+int aloam_input_consumed(aloam_ctx* c) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  for (int s = 0; s < 2; ++s) if (c->in_used[s]) HIP_TRY(c, hipEventSynchronize(c->in_consumed[s]));
+  return ALOAM_OK;
+}
+
+int aloam_odometry_step(aloam_ctx* c) {
+  DeviceScope device_scope(c);
+  if (!c) return ALOAM_E_ARG;
+  OdomStep st(c);
+  return odometry_finish(c, &st);
 }
 
 int aloam_process_device(aloam_ctx* c, const void* d_scans, long long seq_stride_bytes, const int* n_in, int stride_bytes) {
   DeviceScope device_scope(c);
   if (!c || !d_scans || !n_in) return ALOAM_E_ARG;
   int rc = check_batch(c, n_in, stride_bytes);
-  if (rc || (rc = register_launch(c, d_scans, seq_stride_bytes, n_in, stride_bytes, -1, /*debug_arrays=*/false))) return rc;
-  return aloam_odometry_step(c);
+  if (rc) return rc;
+  OdomStep st(c);                                       // (joins the grid stream on every way out)
+  if ((rc = odometry_begin(c, &st)) || (rc = register_with_step(c, &st, d_scans, seq_stride_bytes, n_in, stride_bytes, -1))) return rc;
+  return odometry_finish(c, &st);
 }
 
 // ---- results ---------------------------------------------------------------------------------------------

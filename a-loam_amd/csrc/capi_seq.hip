@@ -77,12 +77,13 @@ void on_sweep_registered(aloam_ctx* c) {
   if (odo) c->reg_pending = true;
 }
 
-// An odometry step has been queued: who took part swapped its clouds (k_advance) and has the grids of the new last ones if the step built them beside its solve.
-void on_odometry_advanced(aloam_ctx* c, const StageMask& m) {
+// An odometry step has been queued: who took part swapped its clouds (k_advance) and has the grids of the new last ones if the step built them beside its
+// solve (built_next; a step whose grids were built beside the registration of the same call builds none, and neither does the serial chain).
+void on_odometry_advanced(aloam_ctx* c, const StageMask& m, bool built_next) {
   for (int b = 0; b < c->B; ++b) {
     SeqHost& s = c->seq[b];
     if (m.bits[b] & kSeqActive) {
-      s.parity ^= 1; s.inited = 1; s.needs_odom = false; s.grid_built = c->grid_overlap;
+      s.parity ^= 1; s.inited = 1; s.needs_odom = false; s.grid_built = built_next;
       s.info_odom = (m.bits[b] & kSeqSolve) && c->cfg.outer_iterations > 0;   // a first frame solves nothing
     }
   }

@@ -290,6 +290,16 @@ __global__ __launch_bounds__(1024) void k_build_grids_fused_next(OdomArgs a) {
   }
 }
 
+// The persistent walk over the "last" form: the build of a step that runs beside k_ring_features of the same call (aloam_process_*), whose workgroups
+// keep the chip as full as the association's do, so these too are placed once: when k_front has ended, while k_ring_starts runs.
+__global__ __launch_bounds__(1024) void k_build_grids_fused_last(OdomArgs a) {
+  const int G = gridDim.x;
+  for (int r = 0, i = blockIdx.x; i < 2 * a.B; ++r, i += G) {
+    build_grids_fused<false>(a, i >> 1, (i ^ r) & 1);
+    __syncthreads();
+  }
+}
+
 constexpr int kBgWaves = 4;   // waves per SIMD the register budget is sized for
 constexpr int kBgUnroll = 4;
 template <bool NEXT>
@@ -1375,23 +1385,33 @@ int prepare_build_grids(int H_surf) {
   const int fused = (int)build_grids_fused_lds_bytes(kFusedMaxH), per_grid = (int)build_grids_lds_bytes(H_surf, kMaxRings);
   if (hipFuncSetAttribute((const void*)k_build_grids_fused, hipFuncAttributeMaxDynamicSharedMemorySize, fused) != hipSuccess) return -1;
   if (hipFuncSetAttribute((const void*)k_build_grids_fused_next, hipFuncAttributeMaxDynamicSharedMemorySize, fused) != hipSuccess) return -1;
+  if (hipFuncSetAttribute((const void*)k_build_grids_fused_last, hipFuncAttributeMaxDynamicSharedMemorySize, fused) != hipSuccess) return -1;
   if (hipFuncSetAttribute((const void*)k_build_grids, hipFuncAttributeMaxDynamicSharedMemorySize, per_grid) != hipSuccess) return -1;
   return hipFuncSetAttribute((const void*)k_build_grids_next, hipFuncAttributeMaxDynamicSharedMemorySize, per_grid) == hipSuccess ? 0 : -1;
 }
-// next: the grids of the sweep just registered, for the step after this one (BuildSrc); else those of the last clouds, for this step
-void launch_build_grids(const OdomArgs& a, bool next, int cus, hipStream_t s) {
+// The "next" forms build the grids of the sweep just registered, for the step after this one (BuildSrc); the "last" forms those of the last clouds,
+// for this step.  wgs: workgroups of a persistent form (made even: a round of the walk takes both clouds of a sequence).
+void launch_build_grids(const OdomArgs& a, GridBuild form, int wgs, hipStream_t s) {
   // clouds of up to 65535 points: all three grids by one workgroup from two reads; the per-grid workgroups below return at once for those
   // (always launched: which kernel owns a cloud is decided per cloud by fused_takes() in both kernels; LDS sized for the larger table
   // that can be fused)
   const int hc = a.grid_H_corner <= kFusedMaxH ? a.grid_H_corner : 0, hs = a.grid_H_surf <= kFusedMaxH ? a.grid_H_surf : 0;
   const size_t fused = build_grids_fused_lds_bytes(hc > hs ? hc : hs), per_grid = build_grids_lds_bytes(a.grid_H_surf, a.R);
-  if (next) {
-    const int wgs = cus / 2 >= 2 ? (cus / 2) & ~1 : 2;
-    if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused_next, dim3(2 * a.B < wgs ? 2 * a.B : wgs), dim3(1024), fused, s, a);
-    hipLaunchKernelGGL(k_build_grids_next, dim3(6, a.B), dim3(1024), per_grid, s, a);
-  } else {
-    if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused, dim3(2, a.B), dim3(1024), fused, s, a);
-    hipLaunchKernelGGL(k_build_grids, dim3(6, a.B), dim3(1024), per_grid, s, a);
+  const int even = wgs >= 2 ? wgs & ~1 : 2;
+  const dim3 walk(2 * a.B < even ? 2 * a.B : even);
+  switch (form) {
+    case GridBuild::kPersistentNext:
+      if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused_next, walk, dim3(1024), fused, s, a);
+      hipLaunchKernelGGL(k_build_grids_next, dim3(6, a.B), dim3(1024), per_grid, s, a);
+      break;
+    case GridBuild::kPersistentLast:
+      if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused_last, walk, dim3(1024), fused, s, a);
+      hipLaunchKernelGGL(k_build_grids, dim3(6, a.B), dim3(1024), per_grid, s, a);
+      break;
+    case GridBuild::kSerialLast:
+      if (hc || hs) hipLaunchKernelGGL(k_build_grids_fused, dim3(2, a.B), dim3(1024), fused, s, a);
+      hipLaunchKernelGGL(k_build_grids, dim3(6, a.B), dim3(1024), per_grid, s, a);
+      break;
   }
 }
 void launch_transform_queries(const OdomArgs& a, hipStream_t s) {

@@ -7,7 +7,10 @@ struct aloam_pose_information;
 namespace aloam {
 size_t build_grids_lds_bytes(int H, int R);
 int prepare_build_grids(int H_surf);
-void launch_build_grids(const OdomArgs& a, bool next, int cus, hipStream_t s);   // cus: workgroups of the persistent "next" form
+// Which clouds a build covers and how its workgroups are laid out: one per cloud of the last clouds (serial, in front of the association), or a
+// fixed number placed once that walk through the clouds (beside other kernels): of the sweep just registered, or of the last clouds.
+enum class GridBuild { kSerialLast, kPersistentNext, kPersistentLast };
+void launch_build_grids(const OdomArgs& a, GridBuild form, int wgs, hipStream_t s);   // wgs: workgroups of a persistent form
 void launch_transform_queries(const OdomArgs& a, hipStream_t s);
 void launch_associate(const OdomArgs& a, bool plane, hipStream_t s);
 void launch_solve(const OdomArgs& a, hipStream_t s);

@@ -112,17 +112,19 @@ __device__ __forceinline__ void find_ends_body(const RegArgs& a, const int b, co
   }
   __syncthreads();
   if (tid == 0) {
-    SeqMeta m = a.meta[b];
+    // Field stores, not a read-modify-write of the struct: the grid build of the same call reads parity and n_*_last of this SeqMeta on
+    // another stream while this kernel runs (aloam_process_*), so the registration writes nothing that the build reads.
+    SeqMeta& m = a.meta[b];
+    int err = 0;
     m.n_in = n;
     m.first_kept = s_first;
     m.last_kept = s_last;
     m.half_idx = 0x7fffffff;
-    m.err = 0;
     m.n_cloud = 0;
     m.start_ori = 0.f;
     m.end_ori = 0.f;
     if (s_last < 0) {
-      m.err = kErrEmpty;
+      err = kErrEmpty;
     } else {
       const float4 p0 = load(s_first);
       const float4 p1 = load(s_last);
@@ -133,8 +135,8 @@ __device__ __forceinline__ void find_ends_body(const RegArgs& a, const int b, co
       m.start_ori = startOri;
       m.end_ori = endOri;
     }
-    if (n > a.cap) m.err |= kErrPointCap;
-    a.meta[b] = m;
+    if (n > a.cap) err |= kErrPointCap;
+    m.err = err;
   }
 }
 __global__ __launch_bounds__(1024) void k_find_ends(RegArgs a, const int* __restrict__ n_in) {
