@@ -267,6 +267,21 @@ class AloamSeqRecordHeader(C.Structure):
                 ("map_seq_bytes", C.c_int), ("pad", C.c_int * 6)]
 
 
+class AloamGraphRecordHeader(C.Structure):
+    """The first 128 bytes of a graph record (aloam_graph_record_header)."""
+    _fields_ = [("magic", C.c_uint), ("version", C.c_uint), ("bytes", C.c_longlong), ("parts", C.c_int), ("nodes", C.c_int), ("edges", C.c_int),
+                ("kf_points", C.c_int * 2), ("seq", C.c_int), ("line_res_bits", C.c_uint), ("plane_res_bits", C.c_uint), ("node_bytes", C.c_int),
+                ("edge_bytes", C.c_int), ("desc_bytes", C.c_int), ("point_bytes", C.c_int), ("pad", C.c_int * 16)]
+
+
+GRAPH_RECORD_MAGIC, GRAPH_RECORD_VERSION = 0x52474C41, 1
+GRAPH_PART_GRAPH, GRAPH_PART_KEYFRAMES = 1, 2
+GRAPH_RECORD_HEADER_DTYPE = np.dtype([("magic", np.uint32), ("version", np.uint32), ("bytes", np.int64), ("parts", np.int32), ("nodes", np.int32),
+                                      ("edges", np.int32), ("kf_points", np.int32, 2), ("seq", np.int32), ("line_res_bits", np.uint32),
+                                      ("plane_res_bits", np.uint32), ("node_bytes", np.int32), ("edge_bytes", np.int32), ("desc_bytes", np.int32),
+                                      ("point_bytes", np.int32), ("pad", np.int32, 16)])
+
+
 class AloamError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"aloam error {code}: {msg}")
@@ -401,6 +416,8 @@ def lib():
         L.aloam_graph_search_loops.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopSearch), C.POINTER(AloamGraphLoopOptions), vp, vp, vp]
         L.aloam_graph_marginal_default_options.argtypes = [C.POINTER(AloamGraphMarginalOptions)]; L.aloam_graph_marginal_default_options.restype = None
         L.aloam_graph_marginals.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphMarginalOptions), vp]
+        L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
+        L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
         L.aloam_profile_kernel_count.argtypes = []
         L.aloam_profile_kernel_name.argtypes = [C.c_int]; L.aloam_profile_kernel_name.restype = C.c_char_p
@@ -1048,6 +1065,37 @@ class Aloam:
         self.graph_marginals_into(requests, buf.data_ptr(), options)
         self.synchronize()
         return buf.cpu().numpy()[:n * size].view(GRAPH_MARGINAL_RESULT_DTYPE).copy()
+
+    # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
+    def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):
+        """Queue the graph records of `seqs` into dst_ptr (device memory or pinned host memory; 0 with cap_bytes 0 = the size query);
+        offsets_ptr receives len(seqs) + 1 int64 byte offsets.  Stream-ordered: wait with synchronize()."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_graph_save(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None,
+                                           int(cap_bytes), C.c_void_p(offsets_ptr) if offsets_ptr else None))
+
+    def graph_save(self, seqs, pinned=True):
+        """Graph records of `seqs`: a size query, one allocation (pinned host memory, or device memory with pinned=False), the save and a
+        synchronise.  Returns (blob, offsets) shaped like save_sequences'."""
+        import torch
+        off = torch.zeros(len(seqs) + 1, dtype=torch.int64, pin_memory=True)
+        self.graph_save_into(seqs, 0, 0, off.data_ptr())
+        self.synchronize()
+        total = int(off[-1])
+        blob = torch.empty(max(total, 16), dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        self.graph_save_into(seqs, blob.data_ptr(), total, off.data_ptr())
+        self.synchronize()
+        return (blob[:total].numpy() if pinned else blob[:total]), off.numpy().copy()
+
+    def graph_load(self, slots, blob, offsets):
+        """Graph record i of blob (numpy array - pageable or a pinned view - or torch tensor on this device or pinned), at
+        [offsets[i], offsets[i + 1]), into the empty graph of slots[i].  The blob is kept referenced until the next load (the copy is
+        stream-ordered)."""
+        ids = np.ascontiguousarray([int(v) for v in slots], dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ptr = blob.data_ptr() if hasattr(blob, "data_ptr") else blob.ctypes.data
+        self._graph_load_keep = (blob, off)
+        self._check(lib().aloam_graph_load(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(ptr) if ptr else None, _p(off)))
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, staging of input counts, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 // Stated once here for all of them: the pinned staging ring (StageRing), a scratch buffer with its capacity (Scratch), and one struct per
 // graph-family feature (GraphStore ... MarginalScratch) that its enable builds fresh and commits with one move, as MapPool.
@@ -23,6 +23,7 @@
 #include "graphapply_kernels.hpp"
 #include "graphmap_kernels.hpp"
 #include "graphmarginal_kernels.hpp"
+#include "graphrecord_kernels.hpp"
 #include "loopreg_kernels.hpp"
 #include "loopsearch_kernels.hpp"
 #include "mapping_kernels.hpp"
@@ -184,6 +185,15 @@ struct MarginalScratch {             // pose-graph marginals (aloam_graph_margin
   long long last_nodes = 0, last_edges = 0; int last_n = 0;         // the last call (algorithmic bytes)
 };
 
+struct GraphRecordScratch {          // graph records (aloam_graph_save / aloam_graph_load): sized for `batch` records on first use, used in stream order
+  DevBuf<GraphRecItem> items;                                       // [B] the records of one call
+  DevBuf<int> units, chunk; DevBuf<long long> uoff;                 // save: lengths, [B + 1] chunk / unit offsets
+  PinnedBuf<char> h; char* d_h = nullptr;                           // load (pinned, mapped): the offsets the check reads, the headers and verdicts it
+                                                                    // writes; behind them the offsets / chunks / items staged for the unpack
+  DevBuf<char> staged;                                              // load: that last part in device memory
+  Scratch<char> stage;                                              // load: records from pageable host memory
+};
+
 // What the host knows about one sequence without asking the device (mirrors of device state that only host calls change, then its map, then what the device
 // holds for its sweep and last clouds).  Written only by aloam_create_stages and the events of capi_seq.hip (the table of events against fields).
 struct SeqHost {
@@ -313,6 +323,7 @@ struct aloam_ctx {
   GraphApplyScratch ga;
   LoopScratch lr;
   MarginalScratch mg;
+  GraphRecordScratch gr;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
   int spill_max_tiles = 0, spill_max_points = 0;
@@ -512,6 +523,7 @@ void on_graph_nodes_added(aloam_ctx* c, const int* seqs, int n);
 void on_graph_edges_added(aloam_ctx* c, int seq, int count);
 void on_graph_cleared(aloam_ctx* c, const int* seqs, int n);
 int on_graph_applied(aloam_ctx* c, const int* seqs, int n);
+void on_graph_loaded(aloam_ctx* c, int seq, int nodes, int edges);
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events);
 // capi_posegraph.hip
 int require_graph(aloam_ctx* c);
@@ -526,5 +538,8 @@ CallerMem classify_pointer(const aloam_ctx* c, const void* p, void** dev);
 int require_host_list(aloam_ctx* c, const void* p, const char* name);   // ALOAM_E_ARG unless a request list is host memory, pinned or pageable
 int export_target(aloam_ctx* c, const void* p, size_t align, const char* what, void** out);
 int get_cube_list(aloam_ctx* c, int seq, int which, float* out, int cap_points);
+// Where a load reads `p` from: *dev = the address the kernels use (device memory of the context's device, pinned host memory), or nullptr for
+// pageable host memory, which is staged.  Another device's memory, managed memory and NULL are refused.
+int load_source(aloam_ctx* c, const void* p, const char* what, const void** dev, bool* on_host);
 
 }  // namespace aloam

@@ -191,7 +191,7 @@ static int ck_load_scratch(aloam_ctx* c) {
 
 // Where a load reads `p` from: device memory of the context's device or pinned host memory (*dev = the address the kernels use), or
 // pageable host memory (*dev = nullptr: read by the host, staged).  Another device's memory, managed memory and NULL are refused.
-static int load_source(aloam_ctx* c, const void* p, const char* what, const void** dev, bool* on_host) {
+int aloam::load_source(aloam_ctx* c, const void* p, const char* what, const void** dev, bool* on_host) {
   *dev = nullptr; *on_host = true;
   if (!p) { c->err = std::string(what) + " is NULL"; return ALOAM_E_ARG; }
   void* d = nullptr;

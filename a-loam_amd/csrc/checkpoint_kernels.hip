@@ -18,13 +18,6 @@ __device__ __forceinline__ RecLayout layout_of(const int* info, bool map) {
   return rec_layout(map, info[0], info[1], nc, np);
 }
 
-// The part of [q0, q1) (float4s of a record) that falls into [lo, lo + n): its start and length, 0 if none.
-__device__ __forceinline__ int overlap(long long q0, long long q1, long long lo, int n, long long* at) {
-  const long long a = q0 > lo ? q0 : lo, b = q1 < lo + n ? q1 : lo + n;
-  *at = a;
-  return b > a ? (int)(b - a) : 0;
-}
-
 // ---- save -------------------------------------------------------------------------------------------------------------------
 // One workgroup per record: the last clouds' sizes, and per class the exclusive prefix of the cube counts over the 4851 descriptors (what
 // the pack walks), their total and the number of non-empty cubes.

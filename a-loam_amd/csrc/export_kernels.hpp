@@ -68,6 +68,13 @@ __device__ __forceinline__ int last_le(const T* v, int lo, int hi, long long x) 
   return lo;
 }
 
+// The part of [q0, q1) (float4s of a record: the chunk a workgroup holds) that falls into [lo, lo + n): its start and length, 0 if none.
+__device__ __forceinline__ int overlap(long long q0, long long q1, long long lo, int n, long long* at) {
+  const long long a = q0 > lo ? q0 : lo, b = q1 < lo + n ? q1 : lo + n;
+  *at = a;
+  return b > a ? (int)(b - a) : 0;
+}
+
 void launch_export_poses(const OdomState* odom, const MapSeq* mapseq, int B, aloam_pose_record* dst, hipStream_t s);
 // count (+ cube prefixes) -> scan -> gather, all on stream s.  gather_blocks: workgroups of the persistent gather.
 void launch_export_clouds(const ExportArgs& a, int gather_blocks, hipStream_t s);

@@ -1066,6 +1066,73 @@ void aloam_graph_marginal_default_options(aloam_graph_marginal_options* opt);
 int aloam_graph_marginals(aloam_ctx* ctx, const aloam_graph_marginal_request* req, int n, const aloam_graph_marginal_options* opt,
                           aloam_graph_marginal_result* dst /* [n] */);
 
+/* ---- graph records: save and load pose graphs with their keyframe clouds ---------------------------------------------------------------
+ * A sequence record leaves the graph family out.  A graph record is its counterpart: the nodes and edges of one sequence's pose graph and,
+ * when the keyframe store is enabled, every node's descriptor and clouds, in a position-independent byte layout, packed and unpacked on the
+ * device.  Opt-in and beside the reference: a context that never calls the two functions launches exactly what it launched before, and
+ * sequence records keep their format (ALOAM_SEQ_RECORD_VERSION is unchanged).  a-loam_amd/graph_records.py restates the format in numpy;
+ * DESIGN.md §7r.
+ *
+ * Layout, every section a whole number of 16-byte units (nodes 128 bytes, edges 240, descriptors 16, points 16):
+ *   header (128) | nodes[N] | edges[E] [ | descriptors[N] | corner points | surf points ] | zeros up to a multiple of 256.
+ *   A descriptor is {first corner, first surf, count corner, count surf}: where the node's clouds lie in the two point sections.  The
+ *   padding is written as zeros, so the bytes of a record depend on the graph alone, not on n, on the record's position in the list or on
+ *   the other records.  The edges carry the saving slot in `seq`, as aloam_graph_export_edges returns them.  The keyframe part
+ *   (ALOAM_GRAPH_PART_KEYFRAMES) is held exactly when the store is enabled; a node kept without clouds is saved as it is, its descriptor
+ *   carrying the rows' fill positions with counts of 0.
+ *
+ * aloam_graph_save: records of the graphs of the n sequences seqs[0 .. n) (distinct, in range; an empty graph gives a record of a header),
+ *   with the contract of aloam_save_sequences: queued on the context's stream with no host synchronisation and no read-back, holding the
+ *   state at that point of the stream; dst and dst_offsets are device memory of the context's device or pinned host memory (classified
+ *   like the exports' destinations, else ALOAM_E_ARG before anything is queued; dst may be NULL when cap_bytes is 0), dst 16-byte
+ *   aligned.  dst_offsets[0 .. n] is always written, in bytes; a record is written whole, and only when it ends at or before cap_bytes;
+ *   cap_bytes = 0 is the size query.  ALOAM_E_STATE before aloam_graph_enable.
+ *
+ * aloam_graph_load: record i of src (at [src_offsets[i], src_offsets[i + 1])) into slot slots[i], for n distinct slots; the offsets rise
+ *   by whole records.  A record is position independent: listing its bytes once per slot forks a graph.  src and src_offsets may be
+ *   device memory of the context's device, pinned host memory, or pageable host memory (staged through context scratch, so a record read
+ *   from a file loads directly); src 16-byte aligned.  The call synchronises the context's stream once (offsets handed in as device
+ *   memory are read back before, with a wait of their own).  Before that wait the records that the device cannot reach are staged and a
+ *   check kernel runs over every record; the host then reads the n headers and one verdict per record, and everything is decided
+ *   before anything of the context changes: a refused load changes nothing.
+ *   - ALOAM_E_STATE: before aloam_graph_enable; a target slot whose graph is not empty (aloam_graph_clear it first).
+ *   - ALOAM_E_ARG, the field named by aloam_last_error: magic, version, `bytes` different from the offsets' difference or from what the
+ *     counts give, section sizes, parts other than what the context holds (the keyframe part if and only if the store is enabled), and,
+ *     with the keyframe part, mapping resolutions other than the context's (the clouds are stacks filtered at those leaves).
+ *   - ALOAM_E_CAPACITY: more nodes than max_nodes, more edges than max_edges, more points of a class than the keyframe row holds.
+ *   - ALOAM_E_ARG with "payload" in the error text, decided by the check kernel: an edge outside -1 <= i < nodes, 0 <= j < nodes, i != j,
+ *     or with a flag other than ALOAM_GRAPH_EDGE_ROBUST; descriptors that are not back to back from 0 (first[k] = first[k-1] + count[k-1],
+ *     counts >= 0), or whose last one does not end at kf_points.  These are the values the solve and the gather kernels index with: a
+ *     damaged file is refused before any of them runs.  The numeric payload (poses, measurements, information matrices, points) is
+ *     trusted, as sequence records trust theirs; a record carries no checksum.
+ *   The rest is asynchronous: the nodes, the edges with `seq` rewritten to the target slot, the descriptors, the points and the slot's
+ *   two append cursors are written in stream order, and src must stay unchanged until aloam_synchronize or an event on aloam_stream.  The
+ *   slot's count of nodes kept without clouds (aloam_graph_keyframe_info) is the slot's history and is left alone.  Batch, device,
+ *   max_nodes, max_edges and the keyframe row sizes may differ from the saving context's.
+ * Taken together: a sequence record and a graph record of the same sequence, saved at the same point of the stream and loaded into one
+ *   slot of a compatible context, continue bit for bit - later aloam_graph_add_nodes (the odometry edge from the loaded last node),
+ *   aloam_graph_add_edges, aloam_graph_optimize, aloam_graph_export_map, aloam_graph_apply, aloam_graph_register_loops /
+ *   aloam_graph_search_loops and aloam_graph_marginals.  (After aloam_load_sequences a slot takes part in a mapping step before
+ *   aloam_graph_add_nodes may keep its stacks, as after a reset.)
+ * Profiling: the pack runs in the slot save_sequences and the unpack in load_sequences; aloam_profile_get's algorithmic bytes of those two
+ *   slots keep describing the last sequence save / load, and a graph call's bytes are the offsets it returns. */
+enum { ALOAM_GRAPH_RECORD_MAGIC = 0x52474c41, ALOAM_GRAPH_RECORD_VERSION = 1 };   /* magic: the bytes "ALGR" */
+enum { ALOAM_GRAPH_PART_GRAPH = 1, ALOAM_GRAPH_PART_KEYFRAMES = 2 };
+typedef struct aloam_graph_record_header {    /* first 128 bytes of a record                                                            */
+  unsigned int magic;                         /* ALOAM_GRAPH_RECORD_MAGIC                                                               */
+  unsigned int version;                       /* ALOAM_GRAPH_RECORD_VERSION                                                             */
+  long long bytes;                            /* whole record, a multiple of 256                                                        */
+  int parts;                                  /* ALOAM_GRAPH_PART_* held                                                                */
+  int nodes, edges;
+  int kf_points[2];                           /* points of the keyframe clouds, corner / surf; 0 without the keyframe part              */
+  int seq;                                    /* the slot it was saved from (informational)                                             */
+  unsigned int line_res_bits, plane_res_bits; /* mapping resolutions as IEEE-754 bits with the keyframe part, else 0                    */
+  int node_bytes, edge_bytes, desc_bytes, point_bytes;   /* strides of the sections: 128, 240, 16, 16                                   */
+  int pad[16];
+} aloam_graph_record_header;
+int aloam_graph_save(aloam_ctx* ctx, const int* seqs, int n, void* dst, long long cap_bytes, long long* dst_offsets /* [n + 1] */);
+int aloam_graph_load(aloam_ctx* ctx, const int* slots, int n, const void* src, const long long* src_offsets /* [n + 1] */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

@@ -1,7 +1,7 @@
 """tools/loop_closure_drive.py — a loop closure inside one drive, with nothing but calls the project already has ("A loop
 edge inside a drive").
 
-    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]]
+    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]] [--resume-at K]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -28,6 +28,11 @@ the guess's, and the edge's error are printed as device_loop_search beside devic
 With --apply the whole chain runs twice, and both runs drive on for another quarter lap behind the solve: one after aloam_graph_apply of
 all nodes (pose and map), one without it.  Reported for each, without judging them: the ATE of the live map pose over the continued sweeps,
 and the residual of the ground-truth loop edge between the last keyframe and the keyframe it revisits, at the graph's entered poses.
+
+With --resume-at K nothing of the above runs: the drive alone, and when keyframe K has been entered the sequence record and the graph record
+of slot 0 (aloam_save_sequences, aloam_graph_save) are written to a temporary file, read back and loaded into a fresh context
+(aloam_load_sequences, aloam_graph_load).  Both contexts then drive on over the same sweeps.  Printed: the bytes of the two records, and
+whether the final nodes, edges and the tiles and points of the map at the entered poses are byte-equal.
 """
 from __future__ import annotations
 
@@ -37,6 +42,7 @@ import json
 import math
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,6 +78,7 @@ def main():
     ap.add_argument("--device-loops", action="store_true", help="also measure the edge with aloam_graph_register_loops from the same match, and print it beside the spare-slot route's")
     ap.add_argument("--search", action="store_true", help="with --device-loops: also search a pose grid around the match's guess (aloam_graph_search_loops) and print it beside the unsearched call")
     ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
+    ap.add_argument("--resume-at", type=int, default=None, metavar="K", help="only drive: at keyframe K save the sequence record and the graph record to a temporary file, load both into a fresh context, drive on in both and compare")
     args = ap.parse_args()
 
     import torch
@@ -94,11 +101,68 @@ def main():
     q_true = np.array([quat_of(R[0].T @ R[k]) for k in range(frames + more)])
     t_true = np.array([R[0].T @ (t[k] - t[0]) for k in range(frames + more)])
     mods = (torch, binding, pg, places, reloc, syn, model)
+    if args.resume_at is not None:
+        print(json.dumps(resume(args, mods, scans, frames, every)))
+        return
     if not args.apply:
         print(json.dumps(drive(args, mods, scans, q_true, t_true, frames, 0, every, False)))
         return
     runs = {name: drive(args, mods, scans, q_true, t_true, frames, more, every, apply) for name, apply in (("applied", True), ("not_applied", False))}
     print(json.dumps(runs))
+
+
+def resume(args, mods, scans, frames, every):
+    """The drive in slot 0; at keyframe --resume-at both records go through a file into slot 0 of a fresh context, which drives on beside it."""
+    torch, binding, pg, places, reloc, syn, model = mods
+    nan_row = np.full((1, 4), np.nan, np.float32)
+    n_key = (frames + every - 1) // every + 1
+    info = np.diag([1.0 / 5e-3 ** 2] * 3 + [1.0 / 5e-2 ** 2] * 3)
+
+    def make():
+        g = binding.Aloam(n_scans=16, min_range=model.min_range, batch=2, max_points=max(len(s) for s in scans) + 64)
+        g.mapping_enable(0.4, 0.8, pool_points=1 << 17)
+        g.graph_enable(n_key + 4, n_key + 8)
+        g.graph_keyframes_enable(n_key * 2048, n_key * 16384)
+        g.set_active([1, 0])
+        return g
+    ctx = [make()]
+    out = {"frames": frames, "resume_at": args.resume_at, "resumed": False}
+    keys = 0
+    for k in range(frames):
+        for g in ctx:
+            g.scan_register([scans[k], nan_row], check=False)
+            g.odometry_step()
+            g.mapping_step()
+            if k % every == 0 or k == frames - 1:
+                g.graph_add_nodes([0], info)
+        if k % every == 0 or k == frames - 1:
+            keys += 1
+            if keys == args.resume_at + 1 and len(ctx) == 1:
+                seq_blob, seq_off = ctx[0].save_sequences([0])
+                graph_blob, graph_off = ctx[0].graph_save([0])
+                with tempfile.TemporaryDirectory() as d:
+                    np.concatenate([seq_blob, graph_blob]).tofile(os.path.join(d, "drive.rec"))
+                    both = np.fromfile(os.path.join(d, "drive.rec"), np.uint8)
+                fresh = make()
+                fresh.load_sequences([0], both[:len(seq_blob)], seq_off)
+                fresh.graph_load([0], both[len(seq_blob):], graph_off)
+                ctx.append(fresh)
+                out.update(resumed=True, at_sweep=k, sequence_record_bytes=int(len(seq_blob)), graph_record_bytes=int(len(graph_blob)))
+    out["keyframes"] = keys
+    if len(ctx) == 2:
+        same = {}
+        a, b = ctx
+        same["nodes"] = a.graph_export(0).tobytes() == b.graph_export(0).tobytes()
+        same["edges"] = a.graph_export(0, edges=True).tobytes() == b.graph_export(0, edges=True).tobytes()
+        ma, mb = (g.graph_export_map([(0, 0, keys, binding.GRAPH_POSE_ENTERED)]) for g in ctx)
+        same["map_tiles"] = ma[0].tobytes() == mb[0].tobytes()
+        same["map_points"] = ma[1].tobytes() == mb[1].tobytes()
+        same["live_map_pose"] = all(v.tobytes() == b.map_pose(0)[key].tobytes() for key, v in a.map_pose(0).items())
+        out["byte_equal"] = same
+        out["map"] = {"tiles": len(ma[0]), "points": len(ma[1])}
+    for g in ctx:
+        g.close()
+    return out
 
 
 def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
