@@ -159,6 +159,17 @@ class AloamGraphMarginalResult(C.Structure):
                 ("cov", C.c_double * 36)]
 
 
+class AloamGraphRobustOptions(C.Structure):
+    """The outer loop of aloam_graph_optimize_robust (aloam_graph_robust_options, 32 bytes)."""
+    _fields_ = [("max_outer_iterations", C.c_int), ("pad", C.c_int), ("inlier_chi2", C.c_double), ("mu_step", C.c_double), ("reserved", C.c_double)]
+
+
+class AloamGraphRobustResult(C.Structure):
+    """The outcome of one sequence's robust solve (aloam_graph_robust_result, 128 bytes); a-loam_amd/posegraph.py optimize_robust() holds the definitions."""
+    _fields_ = [("solve", AloamGraphResult), ("outer_iterations", C.c_int), ("robust_edges", C.c_int), ("inliers", C.c_int), ("outliers", C.c_int),
+                ("mu", C.c_double), ("s_max", C.c_double), ("truncated_cost", C.c_double), ("reserved", C.c_double * 3)]
+
+
 LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
 GRAPH_LOOP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32),
                                      ("pad", np.int32, 2), ("q", np.float64, 4), ("t", np.float64, 3), ("reserved", np.float64)])
@@ -184,6 +195,9 @@ GRAPH_EDGE_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32)
 GRAPH_RESULT_DTYPE = np.dtype([("status", np.int32), ("termination", np.int32), ("lm_iterations", np.int32), ("accepted_steps", np.int32),
                                ("pcg_iterations", np.int32), ("nodes", np.int32), ("edges", np.int32), ("pad", np.int32),
                                ("initial_cost", np.float64), ("final_cost", np.float64), ("gradient_max", np.float64), ("reserved", np.float64)])
+GRAPH_ROBUST_RESULT_DTYPE = np.dtype([("solve", GRAPH_RESULT_DTYPE), ("outer_iterations", np.int32), ("robust_edges", np.int32), ("inliers", np.int32),
+                                      ("outliers", np.int32), ("mu", np.float64), ("s_max", np.float64), ("truncated_cost", np.float64),
+                                      ("reserved", np.float64, 3)])
 GRAPH_MARGINAL_MEASURED, GRAPH_MARGINAL_AT_ESTIMATE = 0, 1
 GRAPH_MARGINAL_OK, GRAPH_MARGINAL_NO_EDGES, GRAPH_MARGINAL_NOT_CONVERGED, GRAPH_MARGINAL_FAILED = 0, 1, 2, 3
 GRAPH_MARGINAL_REQUEST_DTYPE = np.dtype([("edge", GRAPH_EDGE_DTYPE), ("mode", np.int32), ("pad", np.int32)])
@@ -416,6 +430,8 @@ def lib():
         L.aloam_graph_search_loops.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopSearch), C.POINTER(AloamGraphLoopOptions), vp, vp, vp]
         L.aloam_graph_marginal_default_options.argtypes = [C.POINTER(AloamGraphMarginalOptions)]; L.aloam_graph_marginal_default_options.restype = None
         L.aloam_graph_marginals.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphMarginalOptions), vp]
+        L.aloam_graph_robust_default_options.argtypes = [C.POINTER(AloamGraphRobustOptions)]; L.aloam_graph_robust_default_options.restype = None
+        L.aloam_graph_optimize_robust.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphOptions), C.POINTER(AloamGraphRobustOptions), vp, vp, C.c_longlong]
         L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -1065,6 +1081,40 @@ class Aloam:
         self.graph_marginals_into(requests, buf.data_ptr(), options)
         self.synchronize()
         return buf.cpu().numpy()[:n * size].view(GRAPH_MARGINAL_RESULT_DTYPE).copy()
+
+    # ---- the robust solve (posegraph.optimize_robust holds the definition) ----------------------------------------------------------------
+    def graph_robust_options(self, **kw):
+        o = AloamGraphRobustOptions()
+        lib().aloam_graph_robust_default_options(C.byref(o))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def graph_optimize_robust_into(self, seqs, dst_ptr, options=None, robust=None, weights_ptr=0, weights_stride=0):
+        """Queue the robust solve of the listed sequences' graphs (no host synchronisation): dst_ptr receives one aloam_graph_robust_result
+        each, weights_ptr (or 0) one row of weights_stride doubles each; device memory or pinned host memory."""
+        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        self._check(lib().aloam_graph_optimize_robust(self.h, _p(ids) if len(ids) else None, len(ids), C.byref(options) if options is not None else None,
+                                                      C.byref(robust) if robust is not None else None, C.c_void_p(dst_ptr) if dst_ptr else None,
+                                                      C.c_void_p(weights_ptr) if weights_ptr else None, int(weights_stride)))
+
+    def graph_optimize_robust(self, seqs, robust=None, pinned=True, weights_stride=None, sentinel=np.nan, **options):
+        """Solve and wait: (a structured array [len(seqs)] of GRAPH_ROBUST_RESULT_DTYPE, the weights [len(seqs), weights_stride]: a row holds
+        one weight per edge of its sequence and `sentinel` behind them).  robust: None (the defaults), an AloamGraphRobustOptions, or a dict of
+        its fields; keyword arguments are fields of aloam_graph_options."""
+        import torch
+        if isinstance(robust, dict):
+            robust = self.graph_robust_options(**robust)
+        n, size = len(seqs), GRAPH_ROBUST_RESULT_DTYPE.itemsize
+        if weights_stride is None:
+            weights_stride = max([self.graph_info(int(b))["edges"] for b in seqs] + [1])
+        where = {"pin_memory": True} if pinned else {"device": "cuda"}
+        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **where)
+        wts = torch.full((max(1, n), int(weights_stride)), float(sentinel), dtype=torch.float64, **where)
+        self.graph_optimize_robust_into(seqs, buf.data_ptr(), self.graph_options(**options), robust, wts.data_ptr(), weights_stride)
+        self.synchronize()
+        return buf.cpu().numpy()[:n * size].view(GRAPH_ROBUST_RESULT_DTYPE).copy(), wts.cpu().numpy()[:n].copy()
 
     # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
     def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

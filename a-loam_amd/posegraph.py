@@ -10,8 +10,9 @@ A pose X = (q, t) maps a point of the node's frame into the frame the graph live
     node 0 is fixed; the tangent of node k is a LEFT perturbation q' = exp(theta / 2) q, t' = t + dt, order (theta, t).
 
 Everything here is float64 numpy on the host: the definition the device is tested against, a dense Levenberg-Marquardt reference
-(optimize), the chain-preconditioned conjugate gradients of the device restated (chain_pcg), the two lines of algebra that turn a
-relocalized pose into an edge, and the fixture generator of the tests (drifted_laps).
+(optimize), the chain-preconditioned conjugate gradients of the device restated (chain_pcg), the robust solve over the flagged edges
+(optimize_robust: GNC-TLS), the two lines of algebra that turn a relocalized pose into an edge, and the fixture generators of the tests
+(drifted_laps, false_loops).
 """
 from __future__ import annotations
 
@@ -335,6 +336,101 @@ def chain_pcg(q, t, edges, **options):
     return optimize(q, t, edges, solve=chain_solver(o["pcg_tolerance"], o["pcg_max_iterations"]), **o)
 
 
+# ---- the robust solve: graduated non-convexity with a truncated least-squares loss over the flagged edges ----------
+ROBUST_DEFAULTS = dict(inlier_chi2=22.46, mu_step=1.4, max_outer_iterations=100)
+
+
+def edge_chi2(q, t, edges):
+    """s [E] = r^T Omega r of every edge with its own information, at the poses (q, t)."""
+    r = residual(q, t, edges)
+    return np.einsum("ea,eab,eb->e", r, info_full(edges["info"]), r)
+
+
+def gnc_thresholds(mu, c2):
+    """(lo, hi): a flagged edge with s <= lo has weight 1, with s >= hi weight 0."""
+    return mu / (mu + 1.0) * c2, (mu + 1.0) / mu * c2
+
+
+def gnc_weights(s, mu, c2):
+    """The GNC-TLS weights of flagged edges with the squared Mahalanobis distances s, at mu: 1 up to lo, 0 from hi, between them
+    sqrt(c2 mu (mu + 1) / s) - mu, which is 1 at lo and 0 at hi."""
+    s = np.asarray(s, np.float64)
+    lo, hi = gnc_thresholds(mu, c2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mid = np.sqrt(c2 * mu * (mu + 1.0) / s) - mu
+    return np.where(s <= lo, 1.0, np.where(s >= hi, 0.0, mid))
+
+
+def weighted_edges(edges, weights):
+    """The weighted problem: every edge's information scaled by its weight, every flag cleared."""
+    e = edges.copy()
+    e["info"] = edges["info"] * np.asarray(weights, np.float64)[:, None]
+    e["flags"] = 0
+    return e
+
+
+def optimize_robust(q, t, edges, inlier_chi2=22.46, mu_step=1.4, max_outer_iterations=100, solve=None, trace=None, **options):
+    """aloam_graph_optimize_robust restated: GNC-TLS (Yang, Antonante, Tzoumas, Carlone, RA-L 2020) over the edges flagged EDGE_ROBUST, an
+    outer loop of weighted solves by optimize().  R = the flagged edges, s_e = r^T Omega r with the edge's own information, c2 = inlier_chi2.
+    The weighted problem for weights w is the plain problem with Omega_e <- w_e Omega_e for e in R and every flag cleared: no Huber here,
+    huber_delta is unused.
+
+      1. s at the entry estimates, s_max = max over R.  A non-finite s or pose: FAILED with termination 5, nothing changes.
+      2. R empty or 2 s_max - c2 <= 0: GNC is skipped, one solve with w = 1; outer_iterations = 1, mu = 0, every flagged edge an inlier.
+      3. mu = c2 / (2 s_max - c2); for it = 1 .. max_outer_iterations: s at the current estimates; gnc_weights(s, mu, c2) on R; optimize()
+         on the weighted problem from the current estimates; stop after the solve of the first iteration in which every weight was exactly
+         0 or 1, otherwise mu *= mu_step.
+      4. An inner solve that ended as a failure: FAILED, the estimates are the entry's.  One that accepts nothing is no failure.
+
+    `solve` is optimize()'s hook (chain_solver); `options` are optimize()'s.  `trace`, a list, receives one dict per outer iteration: mu,
+    lo, hi, s (of the flagged edges, before the solve), weights (of the flagged edges) and the inner solve's result.  Returns q, t and a
+    dict with the fields of aloam_graph_robust_result (the fields of its `solve` at the top level) and `weights` [E]: 1 for unflagged edges."""
+    q, t = np.array(q, np.float64), np.array(t, np.float64)
+    N, E, c2 = len(q), len(edges), float(inlier_chi2)
+    res = dict(status=1, termination=0, lm_iterations=0, accepted_steps=0, pcg_iterations=0, nodes=N, edges=E, initial_cost=0.0, final_cost=0.0,
+               gradient_max=0.0, outer_iterations=0, robust_edges=0, inliers=0, outliers=0, mu=0.0, s_max=0.0, truncated_cost=0.0, weights=np.ones(E))
+    if N < 2 or E == 0:
+        return q, t, res
+    flagged = (edges["flags"] & EDGE_ROBUST) != 0
+    options = {k: v for k, v in options.items() if k != "huber_delta"}
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = edge_chi2(q, t, edges)
+    res.update(status=0, robust_edges=int(flagged.sum()), initial_cost=0.5 * float(s.sum()), final_cost=0.5 * float(s.sum()))
+    if not (np.all(np.isfinite(s)) and np.all(np.isfinite(q)) and np.all(np.isfinite(t))):
+        res.update(status=2, termination=5)
+        return q, t, res
+    s_max = float(s[flagged].max()) if flagged.any() else 0.0
+    res["s_max"] = s_max
+    skip = not flagged.any() or 2.0 * s_max - c2 <= 0.0
+    mu = 0.0 if skip else c2 / (2.0 * s_max - c2)
+    q0, t0, w, failed = q.copy(), t.copy(), np.ones(E), False
+    for it in range(1, 2 if skip else max_outer_iterations + 1):
+        lo, hi = (0.0, 0.0) if skip else gnc_thresholds(mu, c2)
+        if not skip:
+            with np.errstate(over="ignore", invalid="ignore"):
+                s = edge_chi2(q, t, edges)
+            w = np.where(flagged, gnc_weights(s, mu, c2), 1.0)
+        q, t, inner = optimize(q, t, weighted_edges(edges, w), solve=solve, **options)
+        for k in ("lm_iterations", "accepted_steps", "pcg_iterations"):
+            res[k] += inner[k]
+        res.update(termination=inner["termination"], gradient_max=inner["gradient_max"], final_cost=inner["final_cost"], outer_iterations=it, mu=mu)
+        if trace is not None:
+            trace.append(dict(mu=mu, lo=lo, hi=hi, s=s[flagged].copy(), weights=w[flagged].copy(), solve=inner))
+        if inner["status"] == 2:
+            failed = True
+            break
+        if skip or np.all((w == 0.0) | (w == 1.0)):
+            break
+        mu *= mu_step
+    if failed:
+        q, t = q0, t0
+        res.update(status=2, final_cost=res["initial_cost"])
+    s = edge_chi2(q, t, edges)
+    res.update(weights=w, inliers=int((w[flagged] == 1.0).sum()), outliers=int((w[flagged] == 0.0).sum()),
+               truncated_cost=0.5 * float(s[~flagged].sum() + np.minimum(s[flagged], c2).sum()))
+    return q, t, res
+
+
 # ---- marginals: the covariance of an edge's residual under the graph, and the chi-square gate (DESIGN.md §7p) ----------------------
 MARGINAL_MEASURED, MARGINAL_AT_ESTIMATE = 0, 1
 MARGINAL_OK, MARGINAL_NO_EDGES, MARGINAL_NOT_CONVERGED, MARGINAL_FAILED = 0, 1, 2, 3
@@ -558,6 +654,19 @@ def drifted_laps(seed, nodes, loops, radius=10.0, per_lap=None, sigma_theta=5e-3
         ql, tl = noisy(ql, tl, loops)
     loop = make_edges(0, is_, js, ql.reshape(-1, 4), tl.reshape(-1, 3), info)
     return dict(q_true=q_true, t_true=t_true, q=q, t=t, odom=odom, loop=loop, info=info)
+
+
+def false_loops(g, n, seed):
+    """n wrong loop edges for the graph g of drifted_laps, flagged robust: between nodes a quarter to a half of the graph apart, the true
+    relative pose displaced by up to 8 m per axis and rotated by up to 0.5 rad per axis, with g's information."""
+    rng = np.random.default_rng(seed)
+    N = len(g["q"])
+    fi = rng.integers(0, N // 2, n)
+    fj = fi + rng.integers(N // 4, N // 2, n)
+    qz, tz = relative_pose(g["q_true"][fi], g["t_true"][fi], g["q_true"][fj], g["t_true"][fj])
+    tz = tz + rng.uniform(-8, 8, (n, 3))
+    qz = qmul(qz, qexp(rng.uniform(-0.5, 0.5, (n, 3))))
+    return make_edges(0, fi, fj, qz, tz, g["info"], robust=True)
 
 
 def apply_correction(q, t, q_opt, t_opt, live):

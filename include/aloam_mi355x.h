@@ -1133,6 +1133,65 @@ typedef struct aloam_graph_record_header {    /* first 128 bytes of a record    
 int aloam_graph_save(aloam_ctx* ctx, const int* seqs, int n, void* dst, long long cap_bytes, long long* dst_offsets /* [n + 1] */);
 int aloam_graph_load(aloam_ctx* ctx, const int* slots, int n, const void* src, const long long* src_offsets /* [n + 1] */);
 
+/* ---- the robust solve: graduated non-convexity over the flagged edges --------------------------------------------------------------------
+ * The chi-square gate of aloam_graph_marginals judges a candidate against the graph's own covariance, which grows with drift; and the Huber
+ * loss of aloam_graph_optimize does not redescend: a wrong loop edge that got in keeps pulling with constant force.
+ * aloam_graph_optimize_robust solves a graph so that such edges end with no force at all: GNC-TLS, graduated non-convexity with a
+ * truncated least-squares loss (Yang, Antonante, Tzoumas, Carlone, RA-L 2020; GTSAM's GncOptimizer), an outer loop of weighted
+ * least-squares solves that runs inside one kernel, one workgroup per listed graph.  Opt-in and beside the reference: a context that never
+ * calls it launches exactly what it launched before.  a-loam_amd/posegraph.py restates the definition as optimize_robust(); DESIGN.md §7s.
+ *
+ * Definition.  R = the edges flagged ALOAM_GRAPH_EDGE_ROBUST; s_e = r^T Omega r with the edge's own information; c2 = inlier_chi2.  The
+ * weighted problem for weights w is the plain problem of the section "pose graphs" with Omega_e <- w_e Omega_e for e in R and every flag
+ * cleared.  There is no Huber in this call: huber_delta is unused.
+ *   1. s at the entry estimates; s_max = max over R.  A non-finite s_e or pose: ALOAM_GRAPH_FAILED with termination 5, nothing written back.
+ *   2. R empty, or 2 s_max - c2 <= 0: GNC is skipped.  One weighted solve with w = 1; outer_iterations = 1, mu = 0, and every flagged edge
+ *      counts as an inlier.
+ *   3. Otherwise mu = c2 / (2 s_max - c2), and for it = 1 .. max_outer_iterations:
+ *        thresholds, with s at the current estimates: lo = mu / (mu + 1) * c2, hi = (mu + 1) / mu * c2;
+ *        weights: w_e = 1 if s_e <= lo, w_e = 0 if s_e >= hi, otherwise w_e = sqrt(c2 * mu * (mu + 1) / s_e) - mu;
+ *        solve: the trust-region Levenberg-Marquardt of aloam_graph_optimize on the weighted problem, from the current estimates, with opt;
+ *        stop after the solve of the first iteration in which every weight was exactly 0 or 1, otherwise mu *= mu_step.
+ *   4. The estimates (q_opt, t_opt) are written back only if no inner solve ended as a failure; if one did, the call reports
+ *      ALOAM_GRAPH_FAILED and leaves the estimates as they were.  An inner solve that accepts nothing is not a failure.
+ *      ALOAM_GRAPH_NO_EDGES is reported as by aloam_graph_optimize.
+ * A weight of 0 gives an edge no information at all, so what ties the nodes together must not be flagged: flag loop and anchor edges only,
+ * and leave the odometry edges unflagged - they keep the chain positive definite.
+ *
+ * aloam_graph_optimize_robust: stream-ordered, no host synchronisation; nothing is queued on any error.  seqs, opt and dst are validated
+ *   as in aloam_graph_optimize (ALOAM_E_STATE before aloam_graph_enable; distinct sequences in range; dst device memory of the context's
+ *   device or pinned host memory).  robust = NULL: the defaults; max_outer_iterations >= 1, inlier_chi2 > 0 and finite, mu_step > 1 and
+ *   finite, else ALOAM_E_ARG.  weights_dst may be NULL; otherwise it is classified like dst, as device or pinned memory, and
+ *   weights_stride (in doubles) must be at least the largest edge count listed, else ALOAM_E_ARG.  Row i of weights_dst receives one double
+ *   per edge of seqs[i]: 1.0 for unflagged edges, the final weight for flagged ones; entries beyond the edge count are not written.
+ *   Every bit written for seqs[i] - the result, the weights and the exported nodes - is independent of n, of i and of the other
+ *   sequences listed.
+ *   The call changes only q_opt / t_opt: edges, flags, counts and the entered poses stay byte for byte, and nothing is stored between
+ *   calls.  A later aloam_graph_optimize sees the graph exactly as entered, the rejected edges with their full information: a graph with
+ *   rejected edges should keep being solved with the robust call.
+ *   Scratch: beside the rows of aloam_graph_optimize (shared with it), n * row_edges * 256 B for the scaled copy of the edges, w and s,
+ *   row_edges the largest edge count listed.  Timed under the profiling slot pose_graph. */
+typedef struct aloam_graph_robust_options {   /* 32 bytes                                                                               */
+  int max_outer_iterations;                   /* 100                                                                                    */
+  int pad;
+  double inlier_chi2;                         /* 22.46: c^2, the squared Mahalanobis distance beyond which an edge is an outlier
+                                                 (the 6-dof chi-square quantile at p = 0.999, as the gate of aloam_graph_marginals)     */
+  double mu_step;                             /* 1.4                                                                                    */
+  double reserved;
+} aloam_graph_robust_options;
+typedef struct aloam_graph_robust_result {    /* 128 bytes                                                                              */
+  aloam_graph_result solve;                   /* status; termination and gradient_max of the LAST inner solve; lm_iterations,
+                                                 accepted_steps, pcg_iterations summed over all inner solves; initial_cost: all weights 1
+                                                 at the entry estimates; final_cost: final weights at the final estimates               */
+  int outer_iterations, robust_edges, inliers, outliers;   /* w == 1 / w == 0 among the flagged edges; the rest were undecided at the cap */
+  double mu, s_max, truncated_cost;           /* last mu used (0: GNC skipped); largest flagged s at entry;
+                                                 1/2 (sum_unflagged s + sum_flagged min(s, c^2)) at the end                             */
+  double reserved[3];
+} aloam_graph_robust_result;
+void aloam_graph_robust_default_options(aloam_graph_robust_options* opt);
+int aloam_graph_optimize_robust(aloam_ctx* ctx, const int* seqs, int n, const aloam_graph_options* opt, const aloam_graph_robust_options* robust,
+                                aloam_graph_robust_result* dst /* [n] */, double* weights_dst /* [n][weights_stride] or NULL */, long long weights_stride);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

@@ -1,7 +1,7 @@
 """tools/loop_closure_drive.py — a loop closure inside one drive, with nothing but calls the project already has ("A loop
 edge inside a drive").
 
-    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]] [--resume-at K]
+    python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]] [--false-loops K] [--resume-at K]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -24,6 +24,11 @@ route's: the default path is unchanged.
 
 With --device-loops --search the match's guess is also searched (aloam_graph_search_loops, the default grid): the best node, its score and
 the guess's, and the edge's error are printed as device_loop_search beside device_loop_edge, the unsearched call from the same guess.
+
+With --false-loops K the measured edge goes into the graph flagged ALOAM_GRAPH_EDGE_ROBUST beside K copies of itself displaced by up to
+8 m and 0.5 rad per axis (what a place-recognition alias looks like to the graph), flagged too.  The graph is solved by aloam_graph_optimize
+(Huber) and, from the same estimates (a graph record saved before and loaded back), by aloam_graph_optimize_robust: printed as false_loops,
+the ATE after each and the weights the robust solve ended with (the true edge first).  The rest of the chain goes on from the robust solve.
 
 With --apply the whole chain runs twice, and both runs drive on for another quarter lap behind the solve: one after aloam_graph_apply of
 all nodes (pose and map), one without it.  Reported for each, without judging them: the ATE of the live map pose over the continued sweeps,
@@ -77,6 +82,8 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--device-loops", action="store_true", help="also measure the edge with aloam_graph_register_loops from the same match, and print it beside the spare-slot route's")
     ap.add_argument("--search", action="store_true", help="with --device-loops: also search a pose grid around the match's guess (aloam_graph_search_loops) and print it beside the unsearched call")
+    ap.add_argument("--false-loops", type=int, default=0, metavar="K", help="enter K displaced copies of the measured edge beside it, all flagged robust, and print the distance to ground truth "
+                    "after aloam_graph_optimize and after aloam_graph_optimize_robust, with the weights")
     ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
     ap.add_argument("--resume-at", type=int, default=None, metavar="K", help="only drive: at keyframe K save the sequence record and the graph record to a temporary file, load both into a fresh context, drive on in both and compare")
     args = ap.parse_args()
@@ -294,9 +301,35 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
         out["loop_edge"] = {"i": i, "j": j, "translation_error_m": float(np.linalg.norm(edge["t"][0] - tz)),
                             "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dq[:3])))))}
         stage = "graph_optimize"
-        gpu.graph_add_edges(edge)
-        res = gpu.graph_optimize([0])[0]
-        after = gpu.graph_export(0)
+        if args.false_loops:
+            # K displaced copies of the measured edge beside the true one, all flagged robust (posegraph.false_loops' displacement): the plain
+            # solve (Huber on the flagged edges) and, from the same estimates (the graph record saved before it), the robust solve
+            K = args.false_loops
+            rng = np.random.default_rng(args.seed)
+            true = edge.copy()
+            true["flags"] = pg.EDGE_ROBUST
+            false = np.repeat(true, K)
+            false["t"] += rng.uniform(-8, 8, (K, 3))
+            false["q"] = pg.qmul(false["q"], pg.qexp(rng.uniform(-0.5, 0.5, (K, 3))))
+            gpu.graph_add_edges(np.concatenate([true, false]))
+            blob, offsets = gpu.graph_save([0])
+            plain = gpu.graph_optimize([0])[0]
+            plain_after = gpu.graph_export(0)
+            stage = "graph_optimize_robust"
+            gpu.graph_clear([0])
+            gpu.graph_load([0], blob, offsets)
+            robust, weights = gpu.graph_optimize_robust([0])
+            res = robust[0]["solve"]
+            after = gpu.graph_export(0)
+            out["false_loops"] = {"entered": K, "plain": {"status": int(plain["status"]), "lm_iterations": int(plain["lm_iterations"]),
+                                                          "ate_m": pg.ate(plain_after["t_opt"], truth_t)},
+                                  "robust": {"status": int(res["status"]), "outer_iterations": int(robust[0]["outer_iterations"]), "lm_iterations": int(res["lm_iterations"]),
+                                             "inliers": int(robust[0]["inliers"]), "outliers": int(robust[0]["outliers"]), "ate_m": pg.ate(after["t_opt"], truth_t),
+                                             "weights": weights[0][-(K + 1):].tolist()}}
+        else:
+            gpu.graph_add_edges(edge)
+            res = gpu.graph_optimize([0])[0]
+            after = gpu.graph_export(0)
         out["solve"] = {"status": int(res["status"]), "lm_iterations": int(res["lm_iterations"]), "initial_cost": float(res["initial_cost"]), "final_cost": float(res["final_cost"])}
         out["ate_after"] = pg.ate(after["t_opt"], truth_t)
 
