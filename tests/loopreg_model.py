@@ -51,12 +51,14 @@ def factors(src_corner, src_surf, tgt_corner, tgt_surf, par):
         for i in np.nonzero((idx[:, 4] >= 0) & (d2[:, 4] < np.float32(1.0)))[0]:
             near = tgt_surf[idx[i], :3].astype(np.float64)
             x = oracle_py.lstsq_5x3(near, -np.ones(5))
-            ln = math.sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2])
-            if not ln > 0.0:
-                continue
-            d, n = 1 / ln, x / ln
-            if all(abs(n[0] * p[0] + n[1] * p[1] + n[2] * p[2] + d) <= 0.2 for p in near):
-                planes.append(np.concatenate([src_surf[i, :3].astype(np.float64), n, [d]]))
+            # Five neighbours AT the origin solve to x = 0: the reference goes on with 1 / 0 and 0 / 0 (src/laserMapping.cpp:664-665 as the oracle and
+            # k_map_fit restate Eigen's normalize(): a plain division) and keeps the point, because its test asks `fabs(...) > 0.2` (:672-678) and a
+            # NaN is not greater than anything.  The model says what they say: no test of the length, and a record is dropped only by `> 0.2`.
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ln = np.sqrt(np.float64(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]))
+                d, n = np.float64(1.0) / ln, x / ln
+                if not any(abs(n[0] * p[0] + n[1] * p[1] + n[2] * p[2] + d) > 0.2 for p in near):
+                    planes.append(np.concatenate([src_surf[i, :3].astype(np.float64), n, [d]]))
     return np.array(lines).reshape(-1, 9), np.array(planes).reshape(-1, 7)
 
 
