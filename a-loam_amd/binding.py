@@ -391,6 +391,8 @@ def lib():
         L.aloam_get_curvature.argtypes = [vp, C.c_int, vp, C.c_int]
         L.aloam_get_labels.argtypes = [vp, C.c_int, vp, C.c_int]
         L.aloam_get_last_cloud_order.argtypes = [vp, C.c_int, vp]
+        if hasattr(L, "aloam_get_solve_lds"):              # absent from an A/B variant built from an older tree (ALOAM_MI355X_LIB)
+            L.aloam_get_solve_lds.argtypes = [vp, vp]
         L.aloam_get_correspondences.argtypes = [vp, C.c_int, vp, C.c_int, ip, vp, vp, C.c_int, ip, vp]
         L.aloam_mapping_enable.argtypes = [vp, C.c_float, C.c_float, C.c_int]
         L.aloam_mapping_step.argtypes = [vp]
@@ -1194,6 +1196,12 @@ class Aloam:
         v = np.zeros(2, np.int32)
         self._check(lib().aloam_get_last_cloud_order(self.h, seq, _p(v)))
         return int(v[0]), int(v[1])
+
+    def solve_lds(self):
+        """(plane slots per thread, edge slots per thread, bytes of dynamic LDS) the odometry solve keeps; zeros with ALOAM_SOLVE_STAGE=0."""
+        v = np.zeros(3, np.int32)
+        self._check(lib().aloam_get_solve_lds(self.h, _p(v)))
+        return int(v[0]), int(v[1]), int(v[2])
 
     def correspondences(self, seq=0):
         cap_e, cap_p = self.n_scans * 12, self.n_scans * 24

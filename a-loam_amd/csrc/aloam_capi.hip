@@ -125,6 +125,9 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
   // The next step's search grids are built beside the association and the solve (aloam_odometry_step) unless ALOAM_GRID_OVERLAP=0 asks for the serial
   // build at the start of every step; a captured step stays a single chain, and a step that waits after every stage has nothing to run beside.
   { const char* e = std::getenv("ALOAM_GRID_OVERLAP"); c->grid_overlap = !(e && e[0] == '0') && !c->use_graph && !c->debug_sync; }
+  // k_solve reads its factor records from global memory once per solve and from LDS after that unless ALOAM_SOLVE_STAGE=0 asks for global memory in every pass
+  // (same results bit for bit; the switch is there to measure and to test one against the other).
+  { const char* e = std::getenv("ALOAM_SOLVE_STAGE"); c->solve_stage = !(e && e[0] == '0'); }
   c->NB = (c->cap + kBlockPts - 1) / kBlockPts;
   c->npad = cfg->max_ring_points <= 2059 ? 2048 : 4096;
   const size_t B = c->B, cap = c->cap, R = c->R, NB = c->NB;
@@ -185,6 +188,7 @@ int aloam_create_stages(const aloam_config* cfg, int stages, aloam_ctx** out) {
     if ((rc = dmalloc(c, c->d_sel_sharp, B * R * kSharpPerRing))) return rc;
     if ((rc = dmalloc(c, c->d_sel_flat, B * R * kFlatPerRing))) return rc;
     if ((rc = prepare_build_grids(c->grid_H[1]))) { c->err = "k_build_grids: dynamic LDS size rejected"; return ALOAM_E_HIP; }
+    if (c->solve_stage && (rc = prepare_solve())) { c->err = "k_solve: dynamic LDS size rejected"; return ALOAM_E_HIP; }
   }
   // identity poses (src/laserOdometry.cpp:93-98)
   std::vector<OdomState> init(B);

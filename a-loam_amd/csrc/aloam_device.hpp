@@ -132,6 +132,7 @@ struct OdomArgs {
   int last_outer;            // 1: integrate the pose after solving (src/laserOdometry.cpp:504-505)
   int lm_max_iterations;
   int distortion;            // 1: per-point interpolation ratio (reference DISTORTION 1); 0: s = 1
+  int solve_stage;           // 1: k_solve keeps its factor records in LDS from the first evaluation of a solve on (odometry_solve_device.hpp); 0: every pass reads global memory
 };
 
 // One row of a double-buffered cloud: buffer `k` (0 / 1) of sequence b, with `per` points per sequence.  A select, not an index into the

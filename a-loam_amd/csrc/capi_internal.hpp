@@ -265,6 +265,7 @@ struct aloam_ctx {
   DevBuf<int> d_grid_start3c[2][2];
   DevBuf<int> d_grid_flags[2][2], d_grid_walk[2][2];
   int grid_H[2] = {4096, 16384};
+  bool solve_stage = true;           // environment ALOAM_SOLVE_STAGE (default on), read once at creation: k_solve keeps its factor records in LDS across the passes of a solve
   bool grid_overlap = false;         // environment ALOAM_GRID_OVERLAP (default on), read once at creation; off with use_graph / debug_sync
   DevBuf<EdgeRec> d_edges; DevBuf<PlaneRec> d_planes;
   DevBuf<float4> d_sel_sharp, d_sel_flat;

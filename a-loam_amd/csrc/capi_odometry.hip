@@ -43,6 +43,7 @@ OdomArgs odom_args(aloam_ctx* c) {
   a.sel_sharp = c->d_sel_sharp.get(); a.sel_flat = c->d_sel_flat.get();
   a.lm_max_iterations = c->cfg.lm_max_iterations;
   a.distortion = c->cfg.distortion != 0;
+  a.solve_stage = c->solve_stage ? 1 : 0;
   return a;
 }
 
@@ -578,6 +579,14 @@ int aloam_get_labels(aloam_ctx* c, int seq, int* out, int cap) {
   if (k > 0) HIP_TRY(c, hipMemcpy(tmp.data(), c->d_label.get() + (size_t)seq * c->cap, k, hipMemcpyDeviceToHost));
   for (int i = 0; i < k; ++i) out[i] = tmp[i];
   return m.n_cloud;
+}
+
+// What the k_solve launches of this context keep in LDS (odometry_solve_device.hpp): plane slots and edge slots per thread, bytes of dynamic LDS.
+int aloam_get_solve_lds(aloam_ctx* c, int out[3]) {
+  if (!c || !out) return ALOAM_E_ARG;
+  if (!c->d_edges) { c->err = "this context has no odometry stage"; return ALOAM_E_STATE; }
+  solve_launch_lds(odom_args(c), out);
+  return ALOAM_OK;
 }
 
 // Which association kernels owned the clouds the sequence's last step searched (k_build_grids_fused): per cloud 0 = ring-sorted keys (pair kernel), 1 = nearly

@@ -31,7 +31,8 @@ __global__ __launch_bounds__(kSolveThreads) void k_pose_information_odom(OdomArg
 #pragma unroll
       for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(t[k]));
     }
-    evaluate<true, DISTORT>(a, b, q, t, acc, &ne, &np);
+    // one record fetched ahead without distortion; with it the registers of a second record would pass the budget (tests/test_information_budgets.py)
+    evaluate<true, DISTORT, 0, DISTORT ? 0 : 1>(a, b, q, t, acc, &ne, &np);
   }
   double cnt[2] = {(double)ne, (double)np};
   block_sum<28, kSolveWaves>(acc, s_red);

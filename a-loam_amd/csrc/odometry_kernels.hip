@@ -1325,8 +1325,16 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(OdomArgs a) {
   double q[4] = {st.para_q[0], st.para_q[1], st.para_q[2], st.para_q[3]};
   double t[3] = {st.para_t[0], st.para_t[1], st.para_t[2]};
 
-  const LmResult lm = lm_solve_block<kSolveWaves>([&](bool with_jac, const double* qq, const double* tt, double* acc, int* ne, int* np) {
-    if (with_jac) evaluate<true, DISTORT>(a, b, qq, tt, acc, ne, np); else evaluate<false, DISTORT>(a, b, qq, tt, acc, ne, np);
+  // The first evaluation of the solve fetches every record and leaves in LDS what the later ones need of the slots that fit (odometry_solve_device.hpp);
+  // without a.solve_stage no slot is kept and every evaluation reads global memory.  lm_solve_block asks for the Jacobian at every point (one pass per
+  // candidate yields cost and Jacobian), so its flag is not looked at.  `first` is per thread, and every thread of the workgroup sees the same sequence of
+  // calls (the trust-region logic is uniform: it runs on the block sums), so all of them write in the same call and read in the ones behind it; a thread
+  // reads only what it wrote itself.
+  SolveKeep keep = {a.solve_stage ? solve_stage(a.R, DISTORT) : SolveStage{0, 0, 0}, 0u, 0u};
+  bool first = true;
+  const LmResult lm = lm_solve_block<kSolveWaves>([&](bool, const double* qq, const double* tt, double* acc, int* ne, int* np) __attribute__((always_inline)) {
+    if (first) { first = false; evaluate<true, DISTORT, 1, kSolveAhead>(a, b, qq, tt, acc, ne, np, &keep); }
+    else evaluate<true, DISTORT, 2, kSolveAhead>(a, b, qq, tt, acc, ne, np, &keep);
   }, q, t, a.lm_max_iterations, s_red);
   const int n_edges = lm.n_a, n_planes = lm.n_b, iterations = lm.iterations, successful = lm.successful, termination = lm.termination;
   const double initial_cost = lm.initial_cost, cost = lm.final_cost;
@@ -1437,9 +1445,23 @@ void launch_associate(const OdomArgs& a, bool plane, hipStream_t s) {
     else { hipLaunchKernelGGL((k_associate_pair<false, false>), grid, block, 0, s, a); hipLaunchKernelGGL((k_associate_nearly<false, false>), gridn, block, 0, s, a); hipLaunchKernelGGL((k_associate_flagged<false, false>), gridf, blockf, 0, s, a); }
   }
 }
+// The records a solve keeps take more than 64 KiB of dynamic LDS from 64 rings on: the attribute, once per context like prepare_build_grids.
+int prepare_solve() {
+  const int most = kSolveLdsBudget - kSolveStaticLds;
+  if (hipFuncSetAttribute((const void*)k_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) return -1;
+  return hipFuncSetAttribute((const void*)k_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) == hipSuccess ? 0 : -1;
+}
+// What a k_solve launch with these arguments keeps in LDS: {plane slots per thread, edge slots per thread, bytes of dynamic LDS}; all zero without a.solve_stage.
+void solve_launch_lds(const OdomArgs& a, int out[3]) {
+  const SolveStage st = a.solve_stage ? solve_stage(a.R, a.distortion != 0) : SolveStage{0, 0, 0};
+  out[0] = st.plane_slots; out[1] = st.edge_slots; out[2] = st.bytes;
+}
 void launch_solve(const OdomArgs& a, hipStream_t s) {
-  if (a.distortion) hipLaunchKernelGGL(k_solve<true>, dim3(a.B), dim3(kSolveThreads), 0, s, a);
-  else hipLaunchKernelGGL(k_solve<false>, dim3(a.B), dim3(kSolveThreads), 0, s, a);
+  int keep[3];
+  solve_launch_lds(a, keep);
+  const size_t lds = (size_t)keep[2];
+  if (a.distortion) hipLaunchKernelGGL(k_solve<true>, dim3(a.B), dim3(kSolveThreads), lds, s, a);
+  else hipLaunchKernelGGL(k_solve<false>, dim3(a.B), dim3(kSolveThreads), lds, s, a);
 }
 }  // namespace aloam
 

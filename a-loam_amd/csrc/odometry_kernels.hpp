@@ -13,6 +13,8 @@ enum class GridBuild { kSerialLast, kPersistentNext, kPersistentLast };
 void launch_build_grids(const OdomArgs& a, GridBuild form, int wgs, hipStream_t s);   // wgs: workgroups of a persistent form
 void launch_transform_queries(const OdomArgs& a, hipStream_t s);
 void launch_associate(const OdomArgs& a, bool plane, hipStream_t s);
+int prepare_solve();
+void solve_launch_lds(const OdomArgs& a, int out[3]);
 void launch_solve(const OdomArgs& a, hipStream_t s);
 void launch_advance(const OdomArgs& a, hipStream_t s);             // the swap of every active sequence (a.active bit kSeqActive)
 // list[n]: sequence | kInfoSolvedBit (information_device.hpp); dst[n] as the device reaches it

@@ -83,21 +83,98 @@ __device__ __forceinline__ void deskew_jacobian_row(const double a[3], const dou
 }
 
 // -------------------------------------------------------------------------------------------------------
-constexpr int kSolveWaves = 2;   // waves per sequence in k_solve; measured at batch 512: 1: 0.62 ms, 2: 0.44, 4: 0.53, 8: 0.87 (two launches)
+// Waves per sequence in k_solve.  Measured at batch 512 on the kernel of rounds 1 - 9, whose every factor cost two dependent global round trips in every
+// pass: 1: 0.62 ms, 2: 0.44, 4: 0.53, 8: 0.87 (two launches).  Not measured again since the records are fetched ahead and kept in LDS (HISTORY round 10): the
+// LDS layout below and the thread's validity masks are sized for this value.
+constexpr int kSolveWaves = 2;
 constexpr int kSolveThreads = 64 * kSolveWaves;
-template <bool WITH_JAC, bool DISTORT>
-__device__ void evaluate(const OdomArgs& a, int b, const double q[4], const double t[3], double* acc, int* n_edge, int* n_plane) {
+constexpr int kSolveAhead = 2;   // records k_solve fetches ahead of the one it works on: 16 registers each; the kernel must stay within 512 with nothing in scratch
+
+// ---- a thread's factor records: its slots ----------------------------------------------------------------
+// Thread t owns records t, t + kSolveThreads, ... of each class, its slots 0, 1, ..., and adds their terms to its sums in that order, edges first, invalid
+// records skipped in place (the order of the f64 sums is part of the result).  A record is fetched whole, `valid` with it, and the fetch of the thread's
+// next record(s) is issued before the f64 work of the current one: k_solve runs one wave per SIMD, nothing else covers a round trip to memory.
+//
+// k_solve keeps in LDS what the evaluations after the first need of a valid record: the pose-independent values the first one has computed anyway,
+//   plane   cp, j as f32; the unit normal as three f64           48 B   (l and m are needed for the normal only)
+//   edge    cp, a, b as f32; 1 / |a - b| as f64                  44 B
+// plus the f32 interpolation fraction with distortion, field-major and thread-minor (a wave's ds_read_b64 / b32 of one field are consecutive: no bank
+// conflict), and which of its slots are valid in two registers.  The writer of a slot is its only reader: no barrier.  Every later value is produced by
+// the same operations on the same operands as without the copy.  One wave per SIMD means two workgroups per CU, so a workgroup may take half of the
+// 160 KiB; the planes are kept first (they save the normal: a cross product, a square root and three divisions), the edges take what is left, and the
+// slots that do not fit are read from global memory in every pass, as all are with ALOAM_SOLVE_STAGE=0.
+// Beside a grid build: aloam_odometry_step called on its own builds the next step's grids beside association and solve (k_build_grids_fused_next, 1024
+// threads and 98 KB of LDS per workgroup).  With 448 B a solve workgroup fitted on a CU that holds a build workgroup; with 80 KiB it does not (178 of
+// 160 KiB) and waits for a CU without one.  That build's persistent workgroups number half the CUs and, at the headline shape, end 2.9 ms into a chain whose
+// first solve starts behind both associations, 4.5 ms in (HISTORY round 9), so the two rarely meet; the headline path (aloam_process_*) builds beside
+// k_ring_features and never beside the solve.  The step called on its own is measured at batch 1 only (bench.py's latency leg, faster than before).
+constexpr int kSolveLdsBudget = 80 * 1024;
+constexpr int kSolveStaticLds = kSolveWaves * 28 * (int)sizeof(double);     // s_red of the block reductions
+constexpr int kPlaneKeepBytes = 6 * 4 + 3 * 8, kEdgeKeepBytes = 9 * 4 + 8;
+struct SolveStage { int plane_slots, edge_slots, bytes; };                  // slots per thread kept in LDS, and the dynamic LDS they take
+__host__ __device__ constexpr int solve_slots(int records) { return (records + kSolveThreads - 1) / kSolveThreads; }
+__host__ __device__ constexpr SolveStage solve_stage(int R, bool distort) {
+  const int per_plane = (kPlaneKeepBytes + (distort ? 4 : 0)) * kSolveThreads, per_edge = (kEdgeKeepBytes + (distort ? 4 : 0)) * kSolveThreads;
+  const int room = kSolveLdsBudget - kSolveStaticLds;
+  const int all_p = solve_slots(R * kFlatPerRing), all_e = solve_slots(R * kSharpPerRing);
+  const int np = room / per_plane < all_p ? room / per_plane : all_p;
+  const int ne = (room - np * per_plane) / per_edge < all_e ? (room - np * per_plane) / per_edge : all_e;
+  return SolveStage{np, ne, np * per_plane + ne * per_edge};
+}
+static_assert(solve_slots(kMaxRings * kFlatPerRing) <= 32 && solve_slots(kMaxRings * kSharpPerRing) <= 32, "a thread's validity masks are 32 bits per class");
+struct SolveKeep { SolveStage lds; unsigned plane_valid, edge_valid; };     // per thread, from the first evaluation of a solve to its last
+
+struct EdgeFetch { float4 v[3]; };                // cp a | a b | b valid pad pad
+struct PlaneFetch { float4 v[4]; };               // cp j | j l | l m | valid pad pad pad
+struct EdgeKept { float cp[3], a[3], b[3], frac; double inv; };
+struct PlaneKept { float cp[3], j[3], frac; double n[3]; };
+
+// Slots k0 .. k1 - 1 in order: term(load(k), k), with the loads of the next AHEAD slots issued before the term of the current one (past the last slot
+// the last one's address is loaded again, not the one behind it).
+template <int AHEAD, class Load, class Term>
+__device__ __forceinline__ void walk_ahead(int k0, int k1, Load&& load, Term&& term) {
+  if (k0 >= k1) return;
+  if constexpr (AHEAD == 0) {
+    for (int k = k0; k < k1; ++k) term(load(k), k);
+    return;
+  }
+  decltype(load(0)) r[AHEAD > 0 ? AHEAD : 1];
+#pragma unroll
+  for (int d = 0; d < AHEAD; ++d) r[d] = load(k0 + d < k1 ? k0 + d : k1 - 1);
+  for (int k = k0; k < k1; k += AHEAD) {
+#pragma unroll
+    for (int d = 0; d < AHEAD; ++d) {
+      if (k + d < k1) {
+        const auto cur = r[d];
+        r[d] = load(k + d + AHEAD < k1 ? k + d + AHEAD : k1 - 1);
+        term(cur, k + d);
+      }
+    }
+  }
+}
+
+// STAGE 0: every record from global memory (k_pose_information_odom; any evaluation is correct in this form).  1: the same, and what the slots of
+// keep->lds need later goes to LDS (the first evaluation of a solve).  2: those slots from LDS, the others from global memory.
+template <bool WITH_JAC, bool DISTORT, int STAGE = 0, int AHEAD = 1>
+__device__ __forceinline__ void evaluate(const OdomArgs& a, int b, const double q[4], const double t[3], double* acc, int* n_edge, int* n_plane, SolveKeep* keep = nullptr) {
+  constexpr int T = kSolveThreads, NPF = 6 + (DISTORT ? 1 : 0), NEF = 9 + (DISTORT ? 1 : 0);
+  extern __shared__ double s_keep[];
   const int tid = threadIdx.x;
   const SeqMeta m = a.meta[b];
-  const EdgeRec* E = a.edges + (long long)b * a.R * kSharpPerRing;
-  const PlaneRec* P = a.planes + (long long)b * a.R * kFlatPerRing;
+  const float4* E = reinterpret_cast<const float4*>(a.edges + (long long)b * a.R * kSharpPerRing);
+  const float4* P = reinterpret_cast<const float4*>(a.planes + (long long)b * a.R * kFlatPerRing);
+  const int slots_e = tid < m.n_sharp ? (m.n_sharp - tid + T - 1) / T : 0, slots_p = tid < m.n_flat ? (m.n_flat - tid + T - 1) / T : 0;
+  const int kept_p = STAGE ? keep->lds.plane_slots : 0, kept_e = STAGE ? keep->lds.edge_slots : 0;
+  double* const s_pn = s_keep + tid;                                            // [kept_p][3][T]
+  double* const s_inv = s_keep + kept_p * 3 * T + tid;                          // [kept_e][T]
+  float* const s_pf = reinterpret_cast<float*>(s_keep + (kept_p * 3 + kept_e) * T) + tid;   // [kept_p][NPF][T]
+  float* const s_ef = reinterpret_cast<float*>(s_keep + (kept_p * 3 + kept_e) * T) + kept_p * NPF * T + tid;   // [kept_e][NEF][T]
   int ne = 0, np = 0;
-  for (int i = tid; i < m.n_sharp; i += kSolveThreads) {
-    const EdgeRec e = E[i];
-    if (!e.valid) continue;
+
+  auto edge_term = [&](const EdgeKept& e) {
     ++ne;
     double rcp[3], lp[3], M[3][4];
-    const double s = DISTORT ? interpolation_ratio(__int_as_float(e.pad[0])) : 1.0;
+    const double s = DISTORT ? interpolation_ratio(e.frac) : 1.0;
     if (DISTORT) deskew_point(q, t, s, (double)e.cp[0], (double)e.cp[1], (double)e.cp[2], lp, WITH_JAC ? M : nullptr);
     else {
       quat_rotate(q, (double)e.cp[0], (double)e.cp[1], (double)e.cp[2], rcp);
@@ -105,7 +182,7 @@ __device__ void evaluate(const OdomArgs& a, int b, const double q[4], const doub
     }
     const double ax = e.a[0], ay = e.a[1], az = e.a[2], bx = e.b[0], by = e.b[1], bz = e.b[2];
     const double dex = ax - bx, dey = ay - by, dez = az - bz;
-    const double inv = 1.0 / sqrt(dex * dex + dey * dey + dez * dez);
+    const double inv = e.inv;
     const double ux = lp[0] - ax, uy = lp[1] - ay, uz = lp[2] - az, vx = lp[0] - bx, vy = lp[1] - by, vz = lp[2] - bz;
     const double r0 = (uy * vz - uz * vy) * inv, r1 = (uz * vx - ux * vz) * inv, r2 = (ux * vy - uy * vx) * inv;
     double rho0, rho1;
@@ -131,20 +208,46 @@ __device__ void evaluate(const OdomArgs& a, int b, const double q[4], const doub
         add_row(acc, J, rr[row], rho1);
       }
     }
+  };
+  // a record as it lies in global memory: LidarEdgeFactor's 1 / |a - b| computed here, kept if the slot is
+  auto edge_record = [&](const EdgeFetch& f, int k) {
+    if (!__float_as_int(f.v[2].y)) return;
+    EdgeKept e = {{f.v[0].x, f.v[0].y, f.v[0].z}, {f.v[0].w, f.v[1].x, f.v[1].y}, {f.v[1].z, f.v[1].w, f.v[2].x}, f.v[2].z, 0.0};
+    const double dex = (double)e.a[0] - (double)e.b[0], dey = (double)e.a[1] - (double)e.b[1], dez = (double)e.a[2] - (double)e.b[2];
+    e.inv = 1.0 / sqrt(dex * dex + dey * dey + dez * dez);
+    if (STAGE == 1 && k < kept_e) {
+      keep->edge_valid |= 1u << k;
+      float* const f32 = s_ef + k * NEF * T;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { f32[c * T] = e.cp[c]; f32[(3 + c) * T] = e.a[c]; f32[(6 + c) * T] = e.b[c]; }
+      if (DISTORT) f32[9 * T] = e.frac;
+      s_inv[k * T] = e.inv;
+    }
+    edge_term(e);
+  };
+  auto edge_global = [&](int k) { const float4* p = E + (long long)(tid + k * T) * 3; return EdgeFetch{{p[0], p[1], p[2]}}; };
+  int first_e = 0;
+  if (STAGE == 1) keep->edge_valid = 0;
+  if (STAGE == 2) {
+    first_e = slots_e < kept_e ? slots_e : kept_e;
+    walk_ahead<1>(0, first_e, [&](int k) {
+      EdgeKept e;
+      const float* const f32 = s_ef + k * NEF * T;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { e.cp[c] = f32[c * T]; e.a[c] = f32[(3 + c) * T]; e.b[c] = f32[(6 + c) * T]; }
+      e.frac = DISTORT ? f32[9 * T] : 0.0f;
+      e.inv = s_inv[k * T];
+      return e;
+    }, [&](const EdgeKept& e, int k) { if (keep->edge_valid >> k & 1u) edge_term(e); });
   }
-  for (int i = tid; i < m.n_flat; i += kSolveThreads) {
-    const PlaneRec p = P[i];
-    if (!p.valid) continue;
+  walk_ahead<AHEAD>(first_e, slots_e, edge_global, edge_record);
+
+  auto plane_term = [&](const PlaneKept& p) {
     ++np;
-    // LidarPlaneFactor ctor: n = normalize((j - l) x (j - m))  (reference src/lidarFactor.hpp:64-65)
     const double jx = p.j[0], jy = p.j[1], jz = p.j[2];
-    const double e1x = jx - (double)p.l[0], e1y = jy - (double)p.l[1], e1z = jz - (double)p.l[2];
-    const double e2x = jx - (double)p.m[0], e2y = jy - (double)p.m[1], e2z = jz - (double)p.m[2];
-    double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-    const double len = sqrt(nx * nx + ny * ny + nz * nz);
-    nx /= len; ny /= len; nz /= len;
+    const double nx = p.n[0], ny = p.n[1], nz = p.n[2];
     double rcp[3] = {0.0, 0.0, 0.0}, lp[3], M[3][4];
-    const double s = DISTORT ? interpolation_ratio(__int_as_float(p.pad[0])) : 1.0;
+    const double s = DISTORT ? interpolation_ratio(p.frac) : 1.0;
     if (DISTORT) deskew_point(q, t, s, (double)p.cp[0], (double)p.cp[1], (double)p.cp[2], lp, WITH_JAC ? M : nullptr);
     else {
       quat_rotate(q, (double)p.cp[0], (double)p.cp[1], (double)p.cp[2], rcp);
@@ -161,7 +264,41 @@ __device__ void evaluate(const OdomArgs& a, int b, const double q[4], const doub
       else { J[0] = 2.0 * (nz * rcp[1] - ny * rcp[2]); J[1] = 2.0 * (nx * rcp[2] - nz * rcp[0]); J[2] = 2.0 * (ny * rcp[0] - nx * rcp[1]); J[3] = nx; J[4] = ny; J[5] = nz; }
       add_row(acc, J, r, rho1);
     }
+  };
+  auto plane_record = [&](const PlaneFetch& f, int k) {
+    if (!__float_as_int(f.v[3].x)) return;
+    PlaneKept p = {{f.v[0].x, f.v[0].y, f.v[0].z}, {f.v[0].w, f.v[1].x, f.v[1].y}, f.v[3].y, {0.0, 0.0, 0.0}};
+    // LidarPlaneFactor ctor: n = normalize((j - l) x (j - m))  (reference src/lidarFactor.hpp:64-65)
+    const double jx = p.j[0], jy = p.j[1], jz = p.j[2];
+    const double e1x = jx - (double)f.v[1].z, e1y = jy - (double)f.v[1].w, e1z = jz - (double)f.v[2].x;
+    const double e2x = jx - (double)f.v[2].y, e2y = jy - (double)f.v[2].z, e2z = jz - (double)f.v[2].w;
+    double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const double len = sqrt(nx * nx + ny * ny + nz * nz);
+    p.n[0] = nx / len; p.n[1] = ny / len; p.n[2] = nz / len;
+    if (STAGE == 1 && k < kept_p) {
+      keep->plane_valid |= 1u << k;
+      float* const f32 = s_pf + k * NPF * T;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { f32[c * T] = p.cp[c]; f32[(3 + c) * T] = p.j[c]; s_pn[(k * 3 + c) * T] = p.n[c]; }
+      if (DISTORT) f32[6 * T] = p.frac;
+    }
+    plane_term(p);
+  };
+  auto plane_global = [&](int k) { const float4* p = P + (long long)(tid + k * T) * 4; return PlaneFetch{{p[0], p[1], p[2], p[3]}}; };
+  int first_p = 0;
+  if (STAGE == 1) keep->plane_valid = 0;
+  if (STAGE == 2) {
+    first_p = slots_p < kept_p ? slots_p : kept_p;
+    walk_ahead<1>(0, first_p, [&](int k) {
+      PlaneKept p;
+      const float* const f32 = s_pf + k * NPF * T;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { p.cp[c] = f32[c * T]; p.j[c] = f32[(3 + c) * T]; p.n[c] = s_pn[(k * 3 + c) * T]; }
+      p.frac = DISTORT ? f32[6 * T] : 0.0f;
+      return p;
+    }, [&](const PlaneKept& p, int k) { if (keep->plane_valid >> k & 1u) plane_term(p); });
   }
+  walk_ahead<AHEAD>(first_p, slots_p, plane_global, plane_record);
   *n_edge = ne;
   *n_plane = np;
 }

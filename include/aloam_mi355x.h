@@ -1218,6 +1218,11 @@ int aloam_graph_loop_export_target(aloam_ctx* ctx, int slot, int feature_class, 
  * -1 = ring ids / coordinates outside the range the grids are exact for (literal search). */
 int aloam_get_last_cloud_order(aloam_ctx* ctx, int seq, int out[2]);
 
+/* What the odometry solve of this context keeps in LDS across the passes of a solve: out[0] = plane factor slots per thread, out[1] = edge factor
+ * slots per thread, out[2] = bytes of dynamic LDS per workgroup.  All zero in a context created with ALOAM_SOLVE_STAGE=0 in the environment (every
+ * pass then reads the factor records from global memory; the results are the same bits).  No device work; ALOAM_E_STATE without the odometry stage. */
+int aloam_get_solve_lds(aloam_ctx* ctx, int out[3]);
+
 /* ---- per-kernel timing (hipEvents on the context's stream), for bench.py's roofline object ----------------- */
 int aloam_profile_enable(aloam_ctx* ctx, int on);
 int aloam_profile_kernel_count(void);
