@@ -150,7 +150,8 @@ def test_ring_sort_run_counts_widths_and_paths(O, binding):
     """batch 3 x 8 rings through k_ring_features<2048>: every cloud of every sequence bit-equal to the oracle"""
     ref = reference(O)
     xs = [ref[name][0] for name in "012"]
-    gpu = binding.Aloam(n_scans=RINGS, min_range=0.3, ring_from_field=True, batch=3, max_points=max(len(x) for x in xs) + 64)
+    gpu = binding.Aloam(n_scans=RINGS, min_range=0.3, ring_from_field=True, batch=3, max_points=max(len(x) for x in xs) + 64,
+                        max_ring_points=2059)                                # the default capacity, 4107, is the <4096> instance
     gpu.scan_register(xs)
     for b, name in enumerate("012"):
         _assert_features_equal(ref[name][2], gpu.features(b), ("sweep", name))
