@@ -10,10 +10,11 @@ from __future__ import annotations
 
 import numpy as np
 
+from .records import MAP_TILE_DTYPE as TILE_DTYPE
+
 W, H, D = 21, 21, 11                                    # reference src/laserMapping.cpp:75-77
 DIMS = (W, H, D)
 N_CUBES = W * H * D
-TILE_DTYPE = np.dtype([("cube", np.int32, 3), ("feature_class", np.int32), ("count", np.int32), ("frame", np.int32), ("first_point", np.int64)])
 assert TILE_DTYPE.itemsize == 32
 
 

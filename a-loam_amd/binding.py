@@ -12,288 +12,15 @@ import subprocess
 
 import numpy as np
 
+from .records import *  # noqa: F401,F403  the records, their dtypes and the enumerators of the header: declared there, used under these names
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "lib", "libaloam_mi355x.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "aloam_mi355x.h")
 
-CLOUD_FULL, CLOUD_SHARP, CLOUD_LESS_SHARP, CLOUD_FLAT, CLOUD_LESS_FLAT, CLOUD_CORNER_LAST, CLOUD_SURF_LAST = range(7)
-E_ARG, E_SCAN_LINES, E_EMPTY, E_CAPACITY, E_HIP, E_STATE = -1, -2, -3, -4, -5, -6
-MAP_REGISTERED, MAP_CORNER_STACK, MAP_SURF_STACK, MAP_SURROUND, MAP_FULL = 2, 3, 4, 5, 6
-EXPORT_MAP, EXPORT_MAX_IDS = 16, 12                 # export ids: CLOUD_* or EXPORT_MAP + MAP_*
-STAGE_REGISTRATION, STAGE_ODOMETRY, STAGE_MAPPING, STAGE_ALL = 1, 2, 4, 7
-SEQ_RECORD_MAGIC, SEQ_RECORD_VERSION = 0x51534C41, 1
-SEQ_PART_ODOMETRY, SEQ_PART_MAP = 1, 2
 MAP_INFO_KEYS = ("cenW", "cenH", "cenD", "frame_count", "from_map_corner", "from_map_surf", "corner_stack", "surf_stack",
                  "corner_num0", "corner_num1", "surf_num0", "surf_num1", "lm_iterations0", "lm_iterations1", "termination0", "compactions")
-
-
-class AloamConfig(C.Structure):
-    _fields_ = [("n_scans", C.c_int), ("min_range", C.c_float), ("ring_from_field", C.c_int), ("batch", C.c_int),
-                ("max_points", C.c_int), ("max_ring_points", C.c_int), ("device", C.c_int), ("lm_max_iterations", C.c_int),
-                ("outer_iterations", C.c_int), ("distortion", C.c_int)]
-
-
-class AloamOdomStats(C.Structure):
-    _fields_ = [("corner_corr", C.c_int * 2), ("plane_corr", C.c_int * 2), ("lm_iterations", C.c_int * 2),
-                ("lm_successful", C.c_int * 2), ("initial_cost", C.c_double * 2), ("final_cost", C.c_double * 2),
-                ("termination", C.c_int * 2)]
-
-
-class AloamPoseRecord(C.Structure):
-    _fields_ = [("q_w", C.c_double * 4), ("t_w", C.c_double * 3), ("q_last_curr", C.c_double * 4), ("t_last_curr", C.c_double * 3),
-                ("map_q_w", C.c_double * 4), ("map_t_w", C.c_double * 3), ("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3),
-                ("inited", C.c_int), ("map_frames", C.c_int), ("pad", C.c_int * 2)]
-
-
-class AloamPoseInformation(C.Structure):
-    """The information matrix of one solve (aloam_pose_information, 1048 bytes); a-loam_amd/information.py holds the definition."""
-    _fields_ = [("info", C.c_double * 36), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36),
-                ("trans_info", C.c_double * 9), ("trans_eigenvalues", C.c_double * 3), ("trans_eigenvectors", C.c_double * 9),
-                ("rot_info", C.c_double * 9), ("rot_eigenvalues", C.c_double * 3), ("rot_eigenvectors", C.c_double * 9),
-                ("gradient", C.c_double * 6), ("cost", C.c_double), ("n_line", C.c_int), ("n_plane", C.c_int), ("rows", C.c_int),
-                ("status", C.c_int), ("frame", C.c_int), ("pad", C.c_int * 3)]
-
-
-INFO_ODOMETRY, INFO_MAPPING = 0, 1
-INFO_OK, INFO_NONE, INFO_NO_FACTORS, INFO_SINGULAR = 0, 1, 2, 3
-POSE_INFORMATION_DTYPE = np.dtype([
-    ("info", np.float64, (6, 6)), ("eigenvalues", np.float64, 6), ("eigenvectors", np.float64, (6, 6)),
-    ("trans_info", np.float64, (3, 3)), ("trans_eigenvalues", np.float64, 3), ("trans_eigenvectors", np.float64, (3, 3)),
-    ("rot_info", np.float64, (3, 3)), ("rot_eigenvalues", np.float64, 3), ("rot_eigenvectors", np.float64, (3, 3)),
-    ("gradient", np.float64, 6), ("cost", np.float64), ("n_line", np.int32), ("n_plane", np.int32), ("rows", np.int32),
-    ("status", np.int32), ("frame", np.int32), ("pad", np.int32, 3)])
-
-
-class AloamGraphNode(C.Structure):
-    """One keyframe of a pose graph (aloam_graph_node, 128 bytes); a-loam_amd/posegraph.py holds the definitions of this section."""
-    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("q_opt", C.c_double * 4), ("t_opt", C.c_double * 3), ("frame", C.c_int),
-                ("pad", C.c_int * 3)]
-
-
-class AloamGraphEdge(C.Structure):
-    """One edge (aloam_graph_edge, 240 bytes): i = -1 is an anchor; info is the upper triangle, row-major."""
-    _fields_ = [("seq", C.c_int), ("i", C.c_int), ("j", C.c_int), ("flags", C.c_int), ("q", C.c_double * 4), ("t", C.c_double * 3),
-                ("info", C.c_double * 21)]
-
-
-class AloamGraphOptions(C.Structure):
-    _fields_ = [("max_iterations", C.c_int), ("pcg_max_iterations", C.c_int), ("function_tolerance", C.c_double),
-                ("gradient_tolerance", C.c_double), ("pcg_tolerance", C.c_double), ("huber_delta", C.c_double)]
-
-
-class AloamGraphResult(C.Structure):
-    """The outcome of one sequence's solve (aloam_graph_result, 64 bytes)."""
-    _fields_ = [("status", C.c_int), ("termination", C.c_int), ("lm_iterations", C.c_int), ("accepted_steps", C.c_int),
-                ("pcg_iterations", C.c_int), ("nodes", C.c_int), ("edges", C.c_int), ("pad", C.c_int), ("initial_cost", C.c_double),
-                ("final_cost", C.c_double), ("gradient_max", C.c_double), ("reserved", C.c_double)]
-
-
-class AloamGraphMapRequest(C.Structure):
-    """Nodes [first, first + count) of one sequence at the entered or the optimised poses (aloam_graph_map_request, 16 bytes)."""
-    _fields_ = [("seq", C.c_int), ("first", C.c_int), ("count", C.c_int), ("pose", C.c_int)]
-
-
-class AloamGraphMapStats(C.Structure):
-    """What aloam_graph_export_map made of one request (aloam_graph_map_stats, 32 bytes)."""
-    _fields_ = [("tiles", C.c_int * 2), ("points", C.c_int * 2), ("raw_points", C.c_int * 2), ("outside", C.c_int), ("written", C.c_int)]
-
-
-class AloamGraphApplyRequest(C.Structure):
-    """The map of nodes [first, first + count) of one sequence carried into its live state (aloam_graph_apply_request, 16 bytes)."""
-    _fields_ = [("seq", C.c_int), ("first", C.c_int), ("count", C.c_int), ("flags", C.c_int)]
-
-
-class AloamGraphApplyResult(C.Structure):
-    """What aloam_graph_apply did to one sequence (aloam_graph_apply_result, 104 bytes)."""
-    _fields_ = [("status", C.c_int), ("nodes", C.c_int), ("cen", C.c_int * 3), ("cubes", C.c_int * 2), ("points", C.c_int * 2),
-                ("raw_points", C.c_int * 2), ("outside_window", C.c_int), ("q_corr", C.c_double * 4), ("t_corr", C.c_double * 3)]
-
-
-class AloamGraphLoopRequest(C.Structure):
-    """Node j registered against nodes [first, first + count) in the frame of node i (aloam_graph_loop_request, 96 bytes)."""
-    _fields_ = [("seq", C.c_int), ("i", C.c_int), ("j", C.c_int), ("first", C.c_int), ("count", C.c_int), ("pose", C.c_int), ("pad", C.c_int * 2),
-                ("q", C.c_double * 4), ("t", C.c_double * 3), ("reserved", C.c_double)]
-
-
-class AloamGraphLoopOptions(C.Structure):
-    _fields_ = [("outer_iterations", C.c_int), ("lm_max_iterations", C.c_int)]
-
-
-class AloamGraphLoopResult(C.Structure):
-    """The measured loop edge of one request (aloam_graph_loop_result, 448 bytes); a-loam_amd/loopreg.py holds the definitions."""
-    _fields_ = [("status", C.c_int), ("n_line", C.c_int), ("n_plane", C.c_int), ("lm_iterations", C.c_int), ("lm_termination", C.c_int), ("pad", C.c_int),
-                ("target_points", C.c_int * 2), ("target_raw", C.c_int * 2), ("source_points", C.c_int * 2), ("cost", C.c_double),
-                ("q", C.c_double * 4), ("t", C.c_double * 3), ("info", C.c_double * 21), ("info_left", C.c_double * 21)]
-
-
-class AloamMapScore(C.Structure):
-    """What one pose counts against a bucketed target: a (sequence, candidate) pair, a node of a loop search (aloam_map_score, 32 bytes)."""
-    _fields_ = [("corner_factors", C.c_int), ("surf_factors", C.c_int), ("corner_found", C.c_int), ("surf_found", C.c_int), ("cost", C.c_double), ("pad", C.c_int * 2)]
-
-
-class AloamGraphLoopSearch(C.Structure):
-    """The pose grid around every request's guess (aloam_graph_loop_search, 32 bytes)."""
-    _fields_ = [("radius_m", C.c_double), ("step_m", C.c_double), ("yaw_deg", C.c_double), ("yaw_step_deg", C.c_double)]
-
-
-class AloamGraphLoopSearchResult(C.Structure):
-    """The node a searched registration started from (aloam_graph_loop_search_result, 160 bytes); a-loam_amd/loopreg.py holds the definitions."""
-    _fields_ = [("status", C.c_int), ("nodes", C.c_int), ("best", C.c_int), ("ix", C.c_int), ("iy", C.c_int), ("iyaw", C.c_int), ("pad", C.c_int * 2),
-                ("q", C.c_double * 4), ("t", C.c_double * 3), ("reserved", C.c_double), ("best_score", AloamMapScore), ("guess_score", AloamMapScore)]
-
-
-class AloamGraphMarginalRequest(C.Structure):
-    """A candidate edge whose residual covariance and chi-square are wanted (aloam_graph_marginal_request, 248 bytes)."""
-    _fields_ = [("edge", AloamGraphEdge), ("mode", C.c_int), ("pad", C.c_int)]
-
-
-class AloamGraphMarginalOptions(C.Structure):
-    _fields_ = [("pcg_max_iterations", C.c_int), ("pad", C.c_int), ("pcg_tolerance", C.c_double), ("huber_delta", C.c_double)]
-
-
-class AloamGraphMarginalResult(C.Structure):
-    """Sigma_r, s_edge and chi2 of one request (aloam_graph_marginal_result, 440 bytes); a-loam_amd/posegraph.py marginals() holds the definitions."""
-    _fields_ = [("status", C.c_int), ("mode", C.c_int), ("seq", C.c_int), ("i", C.c_int), ("j", C.c_int), ("pcg_iterations", C.c_int), ("nodes", C.c_int),
-                ("edges", C.c_int), ("chi2", C.c_double), ("s_edge", C.c_double), ("r", C.c_double * 6), ("q", C.c_double * 4), ("t", C.c_double * 3),
-                ("cov", C.c_double * 36)]
-
-
-class AloamGraphRobustOptions(C.Structure):
-    """The outer loop of aloam_graph_optimize_robust (aloam_graph_robust_options, 32 bytes)."""
-    _fields_ = [("max_outer_iterations", C.c_int), ("pad", C.c_int), ("inlier_chi2", C.c_double), ("mu_step", C.c_double), ("reserved", C.c_double)]
-
-
-class AloamGraphRobustResult(C.Structure):
-    """The outcome of one sequence's robust solve (aloam_graph_robust_result, 128 bytes); a-loam_amd/posegraph.py optimize_robust() holds the definitions."""
-    _fields_ = [("solve", AloamGraphResult), ("outer_iterations", C.c_int), ("robust_edges", C.c_int), ("inliers", C.c_int), ("outliers", C.c_int),
-                ("mu", C.c_double), ("s_max", C.c_double), ("truncated_cost", C.c_double), ("reserved", C.c_double * 3)]
-
-
-LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
-GRAPH_LOOP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32),
-                                     ("pad", np.int32, 2), ("q", np.float64, 4), ("t", np.float64, 3), ("reserved", np.float64)])
-GRAPH_LOOP_RESULT_DTYPE = np.dtype([("status", np.int32), ("n_line", np.int32), ("n_plane", np.int32), ("lm_iterations", np.int32),
-                                    ("lm_termination", np.int32), ("pad", np.int32), ("target_points", np.int32, 2), ("target_raw", np.int32, 2),
-                                    ("source_points", np.int32, 2), ("cost", np.float64), ("q", np.float64, 4), ("t", np.float64, 3),
-                                    ("info", np.float64, 21), ("info_left", np.float64, 21)])
-GRAPH_APPLY_POSE, GRAPH_APPLY_MAP = 1, 2
-GRAPH_APPLIED, GRAPH_APPLY_NO_NODES, GRAPH_APPLY_NO_ROOM = 0, 1, 2
-GRAPH_APPLY_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("first", np.int32), ("count", np.int32), ("flags", np.int32)])
-GRAPH_APPLY_RESULT_DTYPE = np.dtype([("status", np.int32), ("nodes", np.int32), ("cen", np.int32, 3), ("cubes", np.int32, 2), ("points", np.int32, 2),
-                                     ("raw_points", np.int32, 2), ("outside_window", np.int32), ("q_corr", np.float64, 4), ("t_corr", np.float64, 3)])
-GRAPH_POSE_ENTERED, GRAPH_POSE_OPTIMIZED = 0, 1
-GRAPH_MAP_REQUEST_DTYPE = np.dtype([("seq", np.int32), ("first", np.int32), ("count", np.int32), ("pose", np.int32)])
-GRAPH_MAP_STATS_DTYPE = np.dtype([("tiles", np.int32, 2), ("points", np.int32, 2), ("raw_points", np.int32, 2), ("outside", np.int32),
-                                  ("written", np.int32)])
-GRAPH_EDGE_ROBUST = 1
-GRAPH_OK, GRAPH_NO_EDGES, GRAPH_FAILED = 0, 1, 2
-GRAPH_NODE_DTYPE = np.dtype([("q", np.float64, 4), ("t", np.float64, 3), ("q_opt", np.float64, 4), ("t_opt", np.float64, 3),
-                             ("frame", np.int32), ("pad", np.int32, 3)])
-GRAPH_EDGE_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("flags", np.int32), ("q", np.float64, 4),
-                             ("t", np.float64, 3), ("info", np.float64, 21)])
-GRAPH_RESULT_DTYPE = np.dtype([("status", np.int32), ("termination", np.int32), ("lm_iterations", np.int32), ("accepted_steps", np.int32),
-                               ("pcg_iterations", np.int32), ("nodes", np.int32), ("edges", np.int32), ("pad", np.int32),
-                               ("initial_cost", np.float64), ("final_cost", np.float64), ("gradient_max", np.float64), ("reserved", np.float64)])
-GRAPH_ROBUST_RESULT_DTYPE = np.dtype([("solve", GRAPH_RESULT_DTYPE), ("outer_iterations", np.int32), ("robust_edges", np.int32), ("inliers", np.int32),
-                                      ("outliers", np.int32), ("mu", np.float64), ("s_max", np.float64), ("truncated_cost", np.float64),
-                                      ("reserved", np.float64, 3)])
-GRAPH_MARGINAL_MEASURED, GRAPH_MARGINAL_AT_ESTIMATE = 0, 1
-GRAPH_MARGINAL_OK, GRAPH_MARGINAL_NO_EDGES, GRAPH_MARGINAL_NOT_CONVERGED, GRAPH_MARGINAL_FAILED = 0, 1, 2, 3
-GRAPH_MARGINAL_REQUEST_DTYPE = np.dtype([("edge", GRAPH_EDGE_DTYPE), ("mode", np.int32), ("pad", np.int32)])
-GRAPH_MARGINAL_RESULT_DTYPE = np.dtype([("status", np.int32), ("mode", np.int32), ("seq", np.int32), ("i", np.int32), ("j", np.int32),
-                                        ("pcg_iterations", np.int32), ("nodes", np.int32), ("edges", np.int32), ("chi2", np.float64),
-                                        ("s_edge", np.float64), ("r", np.float64, 6), ("q", np.float64, 4), ("t", np.float64, 3),
-                                        ("cov", np.float64, (6, 6))])
-
-
-class AloamMapCorrection(C.Structure):
-    """One candidate map <- odometry correction (aloam_map_correction, 64 bytes)."""
-    _fields_ = [("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3), ("pad", C.c_double)]
-
-
-class AloamMapTile(C.Structure):
-    """One cube of one class with absolute cube coordinates (aloam_map_tile, 32 bytes)."""
-    _fields_ = [("cube", C.c_int * 3), ("feature_class", C.c_int), ("count", C.c_int), ("frame", C.c_int), ("first_point", C.c_longlong)]
-
-
-class AloamPlace(C.Structure):
-    """One stored place (aloam_place, 4880 bytes): the 60 x 20 sector-major cells of its descriptor and the tag."""
-    _fields_ = [("cells", (C.c_float * 20) * 60), ("q", C.c_double * 4), ("t", C.c_double * 3), ("slot", C.c_int), ("frame", C.c_int),
-                ("n_points", C.c_int), ("pad", C.c_int * 3)]
-
-
-class AloamPlaceMatch(C.Structure):
-    """One result of aloam_places_match (aloam_place_match, 16 bytes)."""
-    _fields_ = [("entry", C.c_int), ("shift", C.c_int), ("distance", C.c_float), ("pad", C.c_int)]
-
-
-PLACE_RINGS, PLACE_SECTORS = 20, 60
-PLACE_DTYPE = np.dtype([("cells", np.float32, (60, 20)), ("q", np.float64, 4), ("t", np.float64, 3), ("slot", np.int32), ("frame", np.int32),
-                        ("n_points", np.int32), ("pad", np.int32, 3)])
-PLACE_MATCH_DTYPE = np.dtype([("entry", np.int32), ("shift", np.int32), ("distance", np.float32), ("pad", np.int32)])
-MAP_TILE_DTYPE = np.dtype([("cube", np.int32, 3), ("feature_class", np.int32), ("count", np.int32), ("frame", np.int32), ("first_point", np.int64)])
-MAP_CORRECTION_DTYPE = np.dtype([("q_wmap_wodom", np.float64, 4), ("t_wmap_wodom", np.float64, 3), ("pad", np.float64)])
-MAP_SCORE_DTYPE = np.dtype([("corner_factors", np.int32), ("surf_factors", np.int32), ("corner_found", np.int32), ("surf_found", np.int32),
-                            ("cost", np.float64), ("pad", np.int32, 2)])
-GRAPH_LOOP_SEARCH_DTYPE = np.dtype([("radius_m", np.float64), ("step_m", np.float64), ("yaw_deg", np.float64), ("yaw_step_deg", np.float64)])
-GRAPH_LOOP_SEARCH_RESULT_DTYPE = np.dtype([("status", np.int32), ("nodes", np.int32), ("best", np.int32), ("ix", np.int32), ("iy", np.int32), ("iyaw", np.int32),
-                                           ("pad", np.int32, 2), ("q", np.float64, 4), ("t", np.float64, 3), ("reserved", np.float64),
-                                           ("best_score", MAP_SCORE_DTYPE), ("guess_score", MAP_SCORE_DTYPE)])
-
-
-def map_corrections(q, t):
-    """Candidates as the C ABI takes them: q [K, 4] (x, y, z, w) and t [K, 3] -> structured array [K] of MAP_CORRECTION_DTYPE."""
-    q, t = np.asarray(q, np.float64).reshape(-1, 4), np.asarray(t, np.float64).reshape(-1, 3)
-    assert len(q) == len(t)
-    c = np.zeros(len(q), MAP_CORRECTION_DTYPE)
-    c["q_wmap_wodom"], c["t_wmap_wodom"] = q, t
-    return c
-
-
-class AloamRangeDecoder(C.Structure):
-    """aloam_range_decoder: how a 16-bit range image becomes points (a-loam_amd/range_input.py holds the definition)."""
-    _fields_ = [("rows", C.c_int), ("n_az", C.c_int), ("order", C.c_int), ("range_scale", C.c_float),
-                ("az_x", C.POINTER(C.c_float)), ("az_y", C.POINTER(C.c_float)), ("cos_el", C.POINTER(C.c_float)), ("sin_el", C.POINTER(C.c_float)),
-                ("range_off", C.POINTER(C.c_float)), ("z_off", C.POINTER(C.c_float)), ("az_off", C.POINTER(C.c_int)), ("ring_id", C.POINTER(C.c_int))]
-
-
-RANGE_COLUMN_MAJOR, RANGE_ROW_MAJOR = 0, 1
-
-
-def range_decoder_struct(dec):
-    """The C struct of a range_input.RangeDecoder (or anything with its fields); the second value keeps the arrays it points to alive."""
-    keep = {k: np.ascontiguousarray(getattr(dec, k), dtype=np.float32) for k in ("az_x", "az_y", "cos_el", "sin_el", "range_off", "z_off")}
-    keep.update({k: np.ascontiguousarray(getattr(dec, k), dtype=np.int32) for k in ("az_off", "ring_id")})
-    d = AloamRangeDecoder(int(dec.rows), int(dec.n_az), int(dec.order), float(dec.range_scale))
-    for k, a in keep.items():
-        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_float if a.dtype == np.float32 else C.c_int)))
-    return d, keep
-
-
-class AloamSeqRecordHeader(C.Structure):
-    """The first 128 bytes of a sequence record (aloam_seq_record_header)."""
-    _fields_ = [("magic", C.c_uint), ("version", C.c_uint), ("bytes", C.c_longlong), ("parts", C.c_int), ("n_scans", C.c_int),
-                ("ring_from_field", C.c_int), ("min_range_bits", C.c_uint), ("distortion", C.c_int), ("lm_max_iterations", C.c_int),
-                ("outer_iterations", C.c_int), ("sum_order", C.c_int), ("line_res_bits", C.c_uint), ("plane_res_bits", C.c_uint),
-                ("inited", C.c_int), ("n_corner_last", C.c_int), ("n_surf_last", C.c_int), ("n_cubes", C.c_int * 2),
-                ("map_points", C.c_int * 2), ("err_events", C.c_int), ("seq_meta_bytes", C.c_int), ("odom_bytes", C.c_int),
-                ("map_seq_bytes", C.c_int), ("pad", C.c_int * 6)]
-
-
-class AloamGraphRecordHeader(C.Structure):
-    """The first 128 bytes of a graph record (aloam_graph_record_header)."""
-    _fields_ = [("magic", C.c_uint), ("version", C.c_uint), ("bytes", C.c_longlong), ("parts", C.c_int), ("nodes", C.c_int), ("edges", C.c_int),
-                ("kf_points", C.c_int * 2), ("seq", C.c_int), ("line_res_bits", C.c_uint), ("plane_res_bits", C.c_uint), ("node_bytes", C.c_int),
-                ("edge_bytes", C.c_int), ("desc_bytes", C.c_int), ("point_bytes", C.c_int), ("pad", C.c_int * 16)]
-
-
-GRAPH_RECORD_MAGIC, GRAPH_RECORD_VERSION = 0x52474C41, 1
-GRAPH_PART_GRAPH, GRAPH_PART_KEYFRAMES = 1, 2
-GRAPH_RECORD_HEADER_DTYPE = np.dtype([("magic", np.uint32), ("version", np.uint32), ("bytes", np.int64), ("parts", np.int32), ("nodes", np.int32),
-                                      ("edges", np.int32), ("kf_points", np.int32, 2), ("seq", np.int32), ("line_res_bits", np.uint32),
-                                      ("plane_res_bits", np.uint32), ("node_bytes", np.int32), ("edge_bytes", np.int32), ("desc_bytes", np.int32),
-                                      ("point_bytes", np.int32), ("pad", np.int32, 16)])
 
 
 class AloamError(RuntimeError):
@@ -454,6 +181,45 @@ def _f32(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _vp(x):
+    """An address as a pointer argument; 0 is NULL."""
+    return C.c_void_p(x) if x else None
+
+
+def _ids(seqs):
+    return np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+
+
+def _ids_arg(ids):
+    return _p(ids) if len(ids) else None
+
+
+def _where(pinned):
+    """Where a destination is allocated (torch's keywords): pinned host memory, or this process's device."""
+    return {"pin_memory": True} if pinned else {"device": "cuda"}
+
+
+def _out_bytes(n, dtype, pinned):
+    """Zeroed room for n records (for one where n is 0): a uint8 tensor in pinned host memory, or on the device."""
+    import torch
+    return torch.zeros(max(1, n) * dtype.itemsize, dtype=torch.uint8, **_where(pinned))
+
+
+def _records(buf, n, dtype):
+    """The first n records of such a buffer as a structured array of the host's own."""
+    return buf.cpu().numpy()[:n * dtype.itemsize].view(dtype).copy()
+
+
+def _options(cls, default_fn, kw):
+    """The library's defaults of an options record with the fields of kw replaced."""
+    o = cls()
+    default_fn(C.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
 
 
 class Aloam:
@@ -623,8 +389,8 @@ class Aloam:
 
     def reset_sequences(self, seqs):
         """Put the listed sequences back to the state of a fresh context, in stream order (no synchronisation)."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_reset_sequences(self.h, _p(ids) if len(ids) else None, len(ids)))
+        ids = _ids(seqs)
+        self._check(lib().aloam_reset_sequences(self.h, _ids_arg(ids), len(ids)))
 
     def set_map_frozen(self, mask=None):
         """Which sequences localize against their map instead of extending it in the mapping steps that follow (one truthy value per
@@ -640,9 +406,8 @@ class Aloam:
     def score_map_corrections_into(self, seqs, cand_ptr, K, scores_ptr, best_ptr=0):
         """Queue the scoring of the K candidates at cand_ptr (device, pinned or pageable host memory) for `seqs`; scores_ptr receives
         len(seqs) * K aloam_map_score records, best_ptr (0 = not wanted) len(seqs) int32 - both device memory or pinned host memory."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_score_map_corrections(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(cand_ptr) if cand_ptr else None, int(K),
-                                                      C.c_void_p(scores_ptr) if scores_ptr else None, C.c_void_p(best_ptr) if best_ptr else None))
+        ids = _ids(seqs)
+        self._check(lib().aloam_score_map_corrections(self.h, _ids_arg(ids), len(ids), _vp(cand_ptr), int(K), _vp(scores_ptr), _vp(best_ptr)))
 
     def score_map_corrections(self, seqs, cand, pinned=True):
         """Scores of the candidates `cand` (structured array of MAP_CORRECTION_DTYPE, see map_corrections) for `seqs`, after a synchronise.
@@ -651,19 +416,17 @@ class Aloam:
         import torch
         cand = np.ascontiguousarray(cand, dtype=MAP_CORRECTION_DTYPE)
         n, K = len(seqs), len(cand)
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        sc = torch.zeros(max(1, n * K) * 32, dtype=torch.uint8, **where)
-        best = torch.zeros(max(1, n), dtype=torch.int32, **where)
+        sc = _out_bytes(n * K, MAP_SCORE_DTYPE, pinned)
+        best = torch.zeros(max(1, n), dtype=torch.int32, **_where(pinned))
         self.score_map_corrections_into(seqs, cand.ctypes.data, K, sc.data_ptr(), best.data_ptr())
         self.synchronize()
-        return sc.cpu().numpy()[:n * K * 32].view(MAP_SCORE_DTYPE).reshape(n, K).copy(), best.cpu().numpy()[:n].copy()
+        return _records(sc, n * K, MAP_SCORE_DTYPE).reshape(n, K), best.cpu().numpy()[:n].copy()
 
     def apply_map_corrections_from(self, seqs, cand_ptr, K, choice_ptr):
         """Queue q_wmap_wodom, t_wmap_wodom := cand[choice[i]] for seqs[i]; choice_ptr: int32 in device memory or pinned host memory, read
         on the device in stream order (the `best` of a scoring call queued before this one may be passed straight in)."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_apply_map_corrections(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(cand_ptr) if cand_ptr else None, int(K),
-                                                      C.c_void_p(choice_ptr) if choice_ptr else None))
+        ids = _ids(seqs)
+        self._check(lib().aloam_apply_map_corrections(self.h, _ids_arg(ids), len(ids), _vp(cand_ptr), int(K), _vp(choice_ptr)))
 
     def apply_map_corrections(self, seqs, cand, choice):
         """Install cand[choice[i]] as the correction of seqs[i] (choice: one int per listed sequence), in stream order."""
@@ -682,10 +445,9 @@ class Aloam:
         """Queue the drain of the spills of `seqs`: tiles_ptr receives up to cap_tiles aloam_map_tile records, points_ptr up to cap_points
         float4 points, offsets_ptr 2 * (len(seqs) + 1) int64 (tile offsets, then point offsets) - device memory or pinned host memory; 0
         pointers with caps of 0 = the size query.  clear: empty the sequences that were written."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_export_map_spill(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(tiles_ptr) if tiles_ptr else None, int(cap_tiles),
-                                                 C.c_void_p(points_ptr) if points_ptr else None, int(cap_points),
-                                                 C.c_void_p(offsets_ptr) if offsets_ptr else None, 1 if clear else 0))
+        ids = _ids(seqs)
+        self._check(lib().aloam_export_map_spill(self.h, _ids_arg(ids), len(ids), _vp(tiles_ptr), int(cap_tiles), _vp(points_ptr), int(cap_points),
+                                                 _vp(offsets_ptr), 1 if clear else 0))
 
     def export_map_spill(self, seqs, clear=True, pinned=True):
         """The spills of `seqs`: a size query, one allocation (pinned host memory, or device memory with pinned=False), the drain and a
@@ -696,12 +458,11 @@ class Aloam:
         self.export_map_spill_into(seqs, 0, 0, 0, 0, off.data_ptr(), clear=False)
         self.synchronize()
         nt, npts = int(off[n]), int(off[2 * n + 1])
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, **where)
-        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **where)
+        tiles = _out_bytes(nt, MAP_TILE_DTYPE, pinned)
+        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **_where(pinned))
         self.export_map_spill_into(seqs, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), clear=clear)
         self.synchronize()
-        return (tiles.cpu().numpy()[:nt * 32].view(MAP_TILE_DTYPE).copy(), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy())
+        return (_records(tiles, nt, MAP_TILE_DTYPE), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy())
 
     def map_spill_info(self, seq=0):
         v = np.zeros(8, np.int32)
@@ -743,46 +504,41 @@ class Aloam:
     def places_add(self, seqs):
         """Append the place of each listed sequence (descriptor of the sweep it holds + its pose at this point of the stream).  Returns the
         store index of the first one; the others follow in listed order."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        ids = _ids(seqs)
         first = self.places_info()["count"]
-        self._check(lib().aloam_places_add(self.h, _p(ids) if len(ids) else None, len(ids)))
+        self._check(lib().aloam_places_add(self.h, _ids_arg(ids), len(ids)))
         return first
 
     def places_match_into(self, seqs, ranges, T, dst_ptr):
         """Queue the match of the listed sequences' descriptors, each against the store entries [ranges[i][0], ranges[i][1]); dst_ptr
         receives len(seqs) * T aloam_place_match records (device memory or pinned host memory)."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        ids = _ids(seqs)
         rg = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 2)
         assert len(rg) == len(ids)
-        self._check(lib().aloam_places_match(self.h, _p(ids) if len(ids) else None, len(ids), _p(rg) if len(ids) else None, int(T),
-                                             C.c_void_p(dst_ptr) if dst_ptr else None))
+        self._check(lib().aloam_places_match(self.h, _ids_arg(ids), len(ids), _p(rg) if len(ids) else None, int(T), _vp(dst_ptr)))
 
     def places_match(self, seqs, ranges=None, T=1, pinned=True):
         """The T best stored places for each listed sequence, after a synchronise: a structured array [len(seqs), T] of PLACE_MATCH_DTYPE.
         ranges: one (lo, hi) per sequence, or None = the whole store."""
-        import torch
         n = len(seqs)
         if ranges is None:
             ranges = [(0, self.places_info()["count"])] * n
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        dst = torch.zeros(max(1, n * T) * 16, dtype=torch.uint8, **where)
+        dst = _out_bytes(n * T, PLACE_MATCH_DTYPE, pinned)
         self.places_match_into(seqs, ranges, T, dst.data_ptr())
         self.synchronize()
-        return dst.cpu().numpy()[:n * T * 16].view(PLACE_MATCH_DTYPE).reshape(n, T).copy()
+        return _records(dst, n * T, PLACE_MATCH_DTYPE).reshape(n, T)
 
     def places_export_into(self, first, count, dst_ptr):
-        self._check(lib().aloam_places_export(self.h, int(first), int(count), C.c_void_p(dst_ptr) if dst_ptr else None))
+        self._check(lib().aloam_places_export(self.h, int(first), int(count), _vp(dst_ptr)))
 
     def places_export(self, first=0, count=None, pinned=True):
         """Store entries [first, first + count) (default: all that follow first) as a structured array of PLACE_DTYPE, after a synchronise."""
-        import torch
         if count is None:
             count = self.places_info()["count"] - first
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        dst = torch.zeros(max(1, count) * PLACE_DTYPE.itemsize, dtype=torch.uint8, **where)
+        dst = _out_bytes(count, PLACE_DTYPE, pinned)
         self.places_export_into(first, count, dst.data_ptr())
         self.synchronize()
-        return dst.cpu().numpy()[:count * PLACE_DTYPE.itemsize].view(PLACE_DTYPE).copy()
+        return _records(dst, count, PLACE_DTYPE)
 
     def places_load(self, places):
         """Append stored places: a structured array of PLACE_DTYPE (pageable host memory), or a torch uint8 tensor on this device or pinned.
@@ -813,13 +569,13 @@ class Aloam:
     def graph_add_nodes(self, seqs, odom_info):
         """Enter the pose each listed sequence holds at this point of the stream as its next node; odom_info: one 6 x 6 information (or its
         21-element upper triangle) for all, or one per sequence, for the odometry edge to the node before.  Returns the new nodes' indices."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
+        ids = _ids(seqs)
         info = np.asarray(odom_info, dtype=np.float64)
         if info.shape[-2:] == (6, 6):
             info = info[..., np.triu_indices(6)[0], np.triu_indices(6)[1]]
         info = np.ascontiguousarray(np.broadcast_to(info, (len(ids), 21)))
         index = [self.graph_info(int(b))["nodes"] for b in ids]
-        self._check(lib().aloam_graph_add_nodes(self.h, _p(ids) if len(ids) else None, len(ids), _p(info) if len(ids) else None))
+        self._check(lib().aloam_graph_add_nodes(self.h, _ids_arg(ids), len(ids), _p(info) if len(ids) else None))
         return index
 
     def graph_add_edges(self, edges):
@@ -828,46 +584,37 @@ class Aloam:
         self._check(lib().aloam_graph_add_edges(self.h, _p(e) if len(e) else None, len(e)))
 
     def graph_options(self, **kw):
-        o = AloamGraphOptions()
-        lib().aloam_graph_default_options(C.byref(o))
-        for k, v in kw.items():
-            assert hasattr(o, k), k
-            setattr(o, k, v)
-        return o
+        return _options(AloamGraphOptions, lib().aloam_graph_default_options, kw)
 
     def graph_optimize_into(self, seqs, dst_ptr, options=None):
         """Queue the solve of the listed sequences' graphs; dst_ptr receives one aloam_graph_result each (device or pinned memory)."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_graph_optimize(self.h, _p(ids) if len(ids) else None, len(ids), C.byref(options) if options is not None else None,
-                                               C.c_void_p(dst_ptr) if dst_ptr else None))
+        ids = _ids(seqs)
+        self._check(lib().aloam_graph_optimize(self.h, _ids_arg(ids), len(ids), C.byref(options) if options is not None else None, _vp(dst_ptr)))
 
     def graph_optimize(self, seqs, pinned=True, **options):
         """Solve and wait: a structured array [len(seqs)] of GRAPH_RESULT_DTYPE.  Keyword arguments are fields of aloam_graph_options."""
-        import torch
-        n = len(seqs)
-        buf = torch.zeros(max(1, n) * 64, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        buf = _out_bytes(len(seqs), GRAPH_RESULT_DTYPE, pinned)
         self.graph_optimize_into(seqs, buf.data_ptr(), self.graph_options(**options))
         self.synchronize()
-        return buf.cpu().numpy()[:n * 64].view(GRAPH_RESULT_DTYPE).copy()
+        return _records(buf, len(seqs), GRAPH_RESULT_DTYPE)
 
     def graph_export_into(self, seq, first, count, dst_ptr, edges=False):
         f = lib().aloam_graph_export_edges if edges else lib().aloam_graph_export
-        self._check(f(self.h, int(seq), int(first), int(count), C.c_void_p(dst_ptr) if dst_ptr else None))
+        self._check(f(self.h, int(seq), int(first), int(count), _vp(dst_ptr)))
 
     def graph_export(self, seq=0, first=0, count=None, edges=False, pinned=True):
         """Nodes (or edges) [first, first + count) of one sequence after a synchronise, as a structured array."""
-        import torch
         dt = GRAPH_EDGE_DTYPE if edges else GRAPH_NODE_DTYPE
         if count is None:
             count = self.graph_info(seq)["edges" if edges else "nodes"] - first
-        buf = torch.zeros(max(1, count) * dt.itemsize, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        buf = _out_bytes(count, dt, pinned)
         self.graph_export_into(seq, first, count, buf.data_ptr(), edges)
         self.synchronize()
-        return buf.cpu().numpy()[:count * dt.itemsize].view(dt).copy()
+        return _records(buf, count, dt)
 
     def graph_clear(self, seqs):
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_graph_clear(self.h, _p(ids) if len(ids) else None, len(ids)))
+        ids = _ids(seqs)
+        self._check(lib().aloam_graph_clear(self.h, _ids_arg(ids), len(ids)))
 
     def graph_info(self, seq=0):
         v = np.zeros(4, np.int32)
@@ -880,8 +627,8 @@ class Aloam:
         self._check(lib().aloam_graph_keyframes_enable(self.h, int(max_corner_points), int(max_surf_points)))
 
     def graph_export_keyframes_into(self, seq, first, count, feature_class, points_ptr, cap_points, offsets_ptr):
-        self._check(lib().aloam_graph_export_keyframes(self.h, int(seq), int(first), int(count), int(feature_class), C.c_void_p(points_ptr) if points_ptr else None,
-                                                       int(cap_points), C.c_void_p(offsets_ptr) if offsets_ptr else None))
+        self._check(lib().aloam_graph_export_keyframes(self.h, int(seq), int(first), int(count), int(feature_class), _vp(points_ptr),
+                                                       int(cap_points), _vp(offsets_ptr)))
 
     def graph_export_keyframes(self, seq=0, first=0, count=None, feature_class=0, pinned=True):
         """The clouds of nodes [first, first + count) of one class: a size query, one allocation, the export and a synchronise.  Returns
@@ -893,7 +640,7 @@ class Aloam:
         self.graph_export_keyframes_into(seq, first, count, feature_class, 0, 0, off.data_ptr())
         self.synchronize()
         n = int(off[count])
-        pts = torch.zeros((max(1, n), 4), dtype=torch.float32, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        pts = torch.zeros((max(1, n), 4), dtype=torch.float32, **_where(pinned))
         self.graph_export_keyframes_into(seq, first, count, feature_class, pts.data_ptr(), n, off.data_ptr())
         self.synchronize()
         return pts.cpu().numpy()[:n].copy(), off.numpy().copy()
@@ -917,9 +664,8 @@ class Aloam:
         aloam_graph_map_stats per request - device memory or pinned host memory; 0 pointers with caps of 0 = the size query."""
         r = requests if isinstance(requests, np.ndarray) else self.graph_map_requests(requests)
         r = np.ascontiguousarray(r, dtype=GRAPH_MAP_REQUEST_DTYPE)
-        self._check(lib().aloam_graph_export_map(self.h, _p(r) if len(r) else None, len(r), C.c_void_p(tiles_ptr) if tiles_ptr else None, int(cap_tiles),
-                                                 C.c_void_p(points_ptr) if points_ptr else None, int(cap_points),
-                                                 C.c_void_p(offsets_ptr) if offsets_ptr else None, C.c_void_p(stats_ptr) if stats_ptr else None))
+        self._check(lib().aloam_graph_export_map(self.h, _p(r) if len(r) else None, len(r), _vp(tiles_ptr), int(cap_tiles),
+                                                 _vp(points_ptr), int(cap_points), _vp(offsets_ptr), _vp(stats_ptr)))
 
     def graph_export_map(self, requests, pinned=True):
         """The maps of `requests` ((seq, first, count, pose) each): a size query, pinned destinations (device memory with pinned=False), then
@@ -931,14 +677,13 @@ class Aloam:
         self.graph_export_map_into(requests, 0, 0, 0, 0, off.data_ptr())
         self.synchronize()
         nt, npts = int(off[n]), int(off[2 * n + 1])
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, **where)
-        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **where)
-        stats = torch.zeros(max(1, n) * 32, dtype=torch.uint8, pin_memory=True)
+        tiles = _out_bytes(nt, MAP_TILE_DTYPE, pinned)
+        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **_where(pinned))
+        stats = _out_bytes(n, GRAPH_MAP_STATS_DTYPE, True)
         self.graph_export_map_into(requests, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), stats.data_ptr())
         self.synchronize()
-        return (tiles.cpu().numpy()[:nt * 32].view(MAP_TILE_DTYPE).copy(), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy(),
-                stats.numpy()[:n * 32].view(GRAPH_MAP_STATS_DTYPE).copy())
+        return (_records(tiles, nt, MAP_TILE_DTYPE), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy(),
+                _records(stats, n, GRAPH_MAP_STATS_DTYPE))
 
     # ---- a solved graph carried into the live state (posegraph.apply_correction, atlas.window_from_keyframes hold the definition) ------------
     @staticmethod
@@ -954,16 +699,14 @@ class Aloam:
         aloam_graph_apply_result per request, device memory or pinned host memory."""
         r = requests if isinstance(requests, np.ndarray) else self.graph_apply_requests(requests)
         r = np.ascontiguousarray(r, dtype=GRAPH_APPLY_REQUEST_DTYPE)
-        self._check(lib().aloam_graph_apply(self.h, _p(r) if len(r) else None, len(r), C.c_void_p(dst_ptr) if dst_ptr else None))
+        self._check(lib().aloam_graph_apply(self.h, _p(r) if len(r) else None, len(r), _vp(dst_ptr)))
 
     def graph_apply(self, requests, pinned=True):
         """Apply and wait: a structured array [len(requests)] of GRAPH_APPLY_RESULT_DTYPE."""
-        import torch
-        n, size = len(requests), GRAPH_APPLY_RESULT_DTYPE.itemsize
-        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        buf = _out_bytes(len(requests), GRAPH_APPLY_RESULT_DTYPE, pinned)
         self.graph_apply_into(requests, buf.data_ptr())
         self.synchronize()
-        return buf.cpu().numpy()[:n * size].view(GRAPH_APPLY_RESULT_DTYPE).copy()
+        return _records(buf, len(requests), GRAPH_APPLY_RESULT_DTYPE)
 
     # ---- loop edges measured on the device (a-loam_amd/loopreg.py holds the definition) -----------------------------------------------------
     def graph_loops_enable(self, max_requests, max_target_corner_points, max_target_surf_points):
@@ -980,12 +723,7 @@ class Aloam:
         return r
 
     def graph_loop_options(self, **kw):
-        o = AloamGraphLoopOptions()
-        lib().aloam_graph_loop_default_options(C.byref(o))
-        for k, v in kw.items():
-            assert hasattr(o, k), k
-            setattr(o, k, v)
-        return o
+        return _options(AloamGraphLoopOptions, lib().aloam_graph_loop_default_options, kw)
 
     def graph_register_loops_into(self, requests, dst_ptr, options=None):
         """Queue the registration of each request (no host synchronisation): dst_ptr receives one aloam_graph_loop_result per request, device
@@ -993,26 +731,19 @@ class Aloam:
         r = requests if isinstance(requests, np.ndarray) else self.graph_loop_requests(requests)
         r = np.ascontiguousarray(r, dtype=GRAPH_LOOP_REQUEST_DTYPE)
         self._check(lib().aloam_graph_register_loops(self.h, _p(r) if len(r) else None, len(r), C.byref(options) if options is not None else None,
-                                                     C.c_void_p(dst_ptr) if dst_ptr else None))
+                                                     _vp(dst_ptr)))
 
     def graph_register_loops(self, requests, pinned=True, **options):
         """Register and wait: a structured array [len(requests)] of GRAPH_LOOP_RESULT_DTYPE.  Keyword arguments are fields of
         aloam_graph_loop_options."""
-        import torch
-        n, size = len(requests), GRAPH_LOOP_RESULT_DTYPE.itemsize
-        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        buf = _out_bytes(len(requests), GRAPH_LOOP_RESULT_DTYPE, pinned)
         self.graph_register_loops_into(requests, buf.data_ptr(), self.graph_loop_options(**options))
         self.synchronize()
-        return buf.cpu().numpy()[:n * size].view(GRAPH_LOOP_RESULT_DTYPE).copy()
+        return _records(buf, len(requests), GRAPH_LOOP_RESULT_DTYPE)
 
     def graph_loop_search(self, **kw):
         """The default grid of aloam_graph_search_loops (3 m in 0.5 m steps, 12.5 degrees in 2.5 degree steps) with the given fields replaced."""
-        g = AloamGraphLoopSearch()
-        lib().aloam_graph_loop_default_search(C.byref(g))
-        for k, v in kw.items():
-            assert hasattr(g, k), k
-            setattr(g, k, v)
-        return g
+        return _options(AloamGraphLoopSearch, lib().aloam_graph_loop_default_search, kw)
 
     def graph_search_loops_into(self, requests, dst_ptr, search_dst_ptr, scores_ptr=0, search=None, options=None):
         """Queue the searched registration of each request (no host synchronisation): dst_ptr receives one aloam_graph_loop_result and
@@ -1021,8 +752,7 @@ class Aloam:
         r = requests if isinstance(requests, np.ndarray) else self.graph_loop_requests(requests)
         r = np.ascontiguousarray(r, dtype=GRAPH_LOOP_REQUEST_DTYPE)
         self._check(lib().aloam_graph_search_loops(self.h, _p(r) if len(r) else None, len(r), C.byref(search) if search is not None else None,
-                                                   C.byref(options) if options is not None else None, C.c_void_p(dst_ptr) if dst_ptr else None,
-                                                   C.c_void_p(search_dst_ptr) if search_dst_ptr else None, C.c_void_p(scores_ptr) if scores_ptr else None))
+                                                   C.byref(options) if options is not None else None, _vp(dst_ptr), _vp(search_dst_ptr), _vp(scores_ptr)))
 
     def graph_search_loops(self, requests, search=None, scores=False, pinned=True, **options):
         """Search, register and wait: (results [n] of GRAPH_LOOP_RESULT_DTYPE, search results [n] of GRAPH_LOOP_SEARCH_RESULT_DTYPE[, scores
@@ -1033,15 +763,13 @@ class Aloam:
         g = self.graph_loop_search(**search) if isinstance(search, dict) else search if search is not None else self.graph_loop_search()
         lin, yaw = grid_axes(g.radius_m, g.step_m, g.yaw_deg, g.yaw_step_deg)
         n, K = len(requests), len(yaw) * len(lin) * len(lin)
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        bufs = [torch.zeros(max(1, n) * size, dtype=torch.uint8, **where)
-                for size in (GRAPH_LOOP_RESULT_DTYPE.itemsize, GRAPH_LOOP_SEARCH_RESULT_DTYPE.itemsize, K * MAP_SCORE_DTYPE.itemsize if scores else 8)]
-        self.graph_search_loops_into(requests, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr() if scores else 0, g, self.graph_loop_options(**options))
+        res, found = _out_bytes(n, GRAPH_LOOP_RESULT_DTYPE, pinned), _out_bytes(n, GRAPH_LOOP_SEARCH_RESULT_DTYPE, pinned)
+        sc = torch.zeros(max(1, n) * (K * MAP_SCORE_DTYPE.itemsize if scores else 8), dtype=torch.uint8, **_where(pinned))
+        self.graph_search_loops_into(requests, res.data_ptr(), found.data_ptr(), sc.data_ptr() if scores else 0, g, self.graph_loop_options(**options))
         self.synchronize()
-        out = (bufs[0].cpu().numpy()[:n * GRAPH_LOOP_RESULT_DTYPE.itemsize].view(GRAPH_LOOP_RESULT_DTYPE).copy(),
-               bufs[1].cpu().numpy()[:n * GRAPH_LOOP_SEARCH_RESULT_DTYPE.itemsize].view(GRAPH_LOOP_SEARCH_RESULT_DTYPE).copy())
+        out = (_records(res, n, GRAPH_LOOP_RESULT_DTYPE), _records(found, n, GRAPH_LOOP_SEARCH_RESULT_DTYPE))
         if scores:
-            out += (bufs[2].cpu().numpy()[:n * K * MAP_SCORE_DTYPE.itemsize].view(MAP_SCORE_DTYPE).reshape(n, K).copy(),)
+            out += (_records(sc, n * K, MAP_SCORE_DTYPE).reshape(n, K),)
         return out
 
     def graph_loop_target(self, slot=0, feature_class=0):
@@ -1058,48 +786,35 @@ class Aloam:
 
     # ---- pose-graph marginals (posegraph.marginals holds the definition) -------------------------------------------------------------------
     def graph_marginal_options(self, **kw):
-        o = AloamGraphMarginalOptions()
-        lib().aloam_graph_marginal_default_options(C.byref(o))
-        for k, v in kw.items():
-            assert hasattr(o, k), k
-            setattr(o, k, v)
-        return o
+        return _options(AloamGraphMarginalOptions, lib().aloam_graph_marginal_default_options, kw)
 
     def graph_marginals_into(self, requests, dst_ptr, options=None):
         """Queue the marginals of each request (a structured array of GRAPH_MARGINAL_REQUEST_DTYPE, posegraph.marginal_request builds one; no
         host synchronisation): dst_ptr receives one aloam_graph_marginal_result per request, device memory or pinned host memory."""
         r = np.ascontiguousarray(requests, dtype=GRAPH_MARGINAL_REQUEST_DTYPE)
         self._check(lib().aloam_graph_marginals(self.h, _p(r) if len(r) else None, len(r), C.byref(options) if options is not None else None,
-                                                C.c_void_p(dst_ptr) if dst_ptr else None))
+                                                _vp(dst_ptr)))
 
     def graph_marginals(self, requests, options=None, pinned=True):
         """Compute and wait: a structured array [len(requests)] of GRAPH_MARGINAL_RESULT_DTYPE.  options: None (the defaults), an
         AloamGraphMarginalOptions, or a dict of its fields."""
-        import torch
         if isinstance(options, dict):
             options = self.graph_marginal_options(**options)
-        n, size = len(requests), GRAPH_MARGINAL_RESULT_DTYPE.itemsize
-        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        buf = _out_bytes(len(requests), GRAPH_MARGINAL_RESULT_DTYPE, pinned)
         self.graph_marginals_into(requests, buf.data_ptr(), options)
         self.synchronize()
-        return buf.cpu().numpy()[:n * size].view(GRAPH_MARGINAL_RESULT_DTYPE).copy()
+        return _records(buf, len(requests), GRAPH_MARGINAL_RESULT_DTYPE)
 
     # ---- the robust solve (posegraph.optimize_robust holds the definition) ----------------------------------------------------------------
     def graph_robust_options(self, **kw):
-        o = AloamGraphRobustOptions()
-        lib().aloam_graph_robust_default_options(C.byref(o))
-        for k, v in kw.items():
-            assert hasattr(o, k), k
-            setattr(o, k, v)
-        return o
+        return _options(AloamGraphRobustOptions, lib().aloam_graph_robust_default_options, kw)
 
     def graph_optimize_robust_into(self, seqs, dst_ptr, options=None, robust=None, weights_ptr=0, weights_stride=0):
         """Queue the robust solve of the listed sequences' graphs (no host synchronisation): dst_ptr receives one aloam_graph_robust_result
         each, weights_ptr (or 0) one row of weights_stride doubles each; device memory or pinned host memory."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_graph_optimize_robust(self.h, _p(ids) if len(ids) else None, len(ids), C.byref(options) if options is not None else None,
-                                                      C.byref(robust) if robust is not None else None, C.c_void_p(dst_ptr) if dst_ptr else None,
-                                                      C.c_void_p(weights_ptr) if weights_ptr else None, int(weights_stride)))
+        ids = _ids(seqs)
+        self._check(lib().aloam_graph_optimize_robust(self.h, _ids_arg(ids), len(ids), C.byref(options) if options is not None else None,
+                                                      C.byref(robust) if robust is not None else None, _vp(dst_ptr), _vp(weights_ptr), int(weights_stride)))
 
     def graph_optimize_robust(self, seqs, robust=None, pinned=True, weights_stride=None, sentinel=np.nan, **options):
         """Solve and wait: (a structured array [len(seqs)] of GRAPH_ROBUST_RESULT_DTYPE, the weights [len(seqs), weights_stride]: a row holds
@@ -1108,23 +823,21 @@ class Aloam:
         import torch
         if isinstance(robust, dict):
             robust = self.graph_robust_options(**robust)
-        n, size = len(seqs), GRAPH_ROBUST_RESULT_DTYPE.itemsize
+        n = len(seqs)
         if weights_stride is None:
             weights_stride = max([self.graph_info(int(b))["edges"] for b in seqs] + [1])
-        where = {"pin_memory": True} if pinned else {"device": "cuda"}
-        buf = torch.zeros(max(1, n) * size, dtype=torch.uint8, **where)
-        wts = torch.full((max(1, n), int(weights_stride)), float(sentinel), dtype=torch.float64, **where)
+        buf = _out_bytes(n, GRAPH_ROBUST_RESULT_DTYPE, pinned)
+        wts = torch.full((max(1, n), int(weights_stride)), float(sentinel), dtype=torch.float64, **_where(pinned))
         self.graph_optimize_robust_into(seqs, buf.data_ptr(), self.graph_options(**options), robust, wts.data_ptr(), weights_stride)
         self.synchronize()
-        return buf.cpu().numpy()[:n * size].view(GRAPH_ROBUST_RESULT_DTYPE).copy(), wts.cpu().numpy()[:n].copy()
+        return _records(buf, n, GRAPH_ROBUST_RESULT_DTYPE), wts.cpu().numpy()[:n].copy()
 
     # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
     def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):
         """Queue the graph records of `seqs` into dst_ptr (device memory or pinned host memory; 0 with cap_bytes 0 = the size query);
         offsets_ptr receives len(seqs) + 1 int64 byte offsets.  Stream-ordered: wait with synchronize()."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_graph_save(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None,
-                                           int(cap_bytes), C.c_void_p(offsets_ptr) if offsets_ptr else None))
+        ids = _ids(seqs)
+        self._check(lib().aloam_graph_save(self.h, _ids_arg(ids), len(ids), _vp(dst_ptr), int(cap_bytes), _vp(offsets_ptr)))
 
     def graph_save(self, seqs, pinned=True):
         """Graph records of `seqs`: a size query, one allocation (pinned host memory, or device memory with pinned=False), the save and a
@@ -1134,7 +847,7 @@ class Aloam:
         self.graph_save_into(seqs, 0, 0, off.data_ptr())
         self.synchronize()
         total = int(off[-1])
-        blob = torch.empty(max(total, 16), dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        blob = torch.empty(max(total, 16), dtype=torch.uint8, **_where(pinned))
         self.graph_save_into(seqs, blob.data_ptr(), total, off.data_ptr())
         self.synchronize()
         return (blob[:total].numpy() if pinned else blob[:total]), off.numpy().copy()
@@ -1143,19 +856,18 @@ class Aloam:
         """Graph record i of blob (numpy array - pageable or a pinned view - or torch tensor on this device or pinned), at
         [offsets[i], offsets[i + 1]), into the empty graph of slots[i].  The blob is kept referenced until the next load (the copy is
         stream-ordered)."""
-        ids = np.ascontiguousarray([int(v) for v in slots], dtype=np.int32)
+        ids = _ids(slots)
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         ptr = blob.data_ptr() if hasattr(blob, "data_ptr") else blob.ctypes.data
         self._graph_load_keep = (blob, off)
-        self._check(lib().aloam_graph_load(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(ptr) if ptr else None, _p(off)))
+        self._check(lib().aloam_graph_load(self.h, _ids_arg(ids), len(ids), _vp(ptr), _p(off)))
 
     # ---- sequence records ------------------------------------------------------------------------------------------------------------
     def save_sequences_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):
         """Queue the records of `seqs` into dst_ptr (device memory or pinned host memory; 0 with cap_bytes 0 = the size query); offsets_ptr
         receives len(seqs) + 1 int64 byte offsets.  Stream-ordered: wait with synchronize()."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_save_sequences(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None,
-                                               int(cap_bytes), C.c_void_p(offsets_ptr) if offsets_ptr else None))
+        ids = _ids(seqs)
+        self._check(lib().aloam_save_sequences(self.h, _ids_arg(ids), len(ids), _vp(dst_ptr), int(cap_bytes), _vp(offsets_ptr)))
 
     def save_sequences(self, seqs, pinned=True):
         """Records of `seqs`: a size query, one allocation (pinned host memory, or device memory with pinned=False), the save and a
@@ -1165,7 +877,7 @@ class Aloam:
         self.save_sequences_into(seqs, 0, 0, off.data_ptr())
         self.synchronize()
         total = int(off[-1])
-        blob = torch.empty(max(total, 16), dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        blob = torch.empty(max(total, 16), dtype=torch.uint8, **_where(pinned))
         self.save_sequences_into(seqs, blob.data_ptr(), total, off.data_ptr())
         self.synchronize()
         return (blob[:total].numpy() if pinned else blob[:total]), off.numpy().copy()
@@ -1173,11 +885,11 @@ class Aloam:
     def load_sequences(self, slots, blob, offsets):
         """Record i of blob (numpy array - pageable or a pinned view - or torch tensor on this device or pinned), at
         [offsets[i], offsets[i + 1]), into slots[i].  The blob is kept referenced until the next load (the copy is stream-ordered)."""
-        ids = np.ascontiguousarray([int(v) for v in slots], dtype=np.int32)
+        ids = _ids(slots)
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         ptr = blob.data_ptr() if hasattr(blob, "data_ptr") else blob.ctypes.data
         self._load_keep = (blob, off)
-        self._check(lib().aloam_load_sequences(self.h, _p(ids) if len(ids) else None, len(ids), C.c_void_p(ptr) if ptr else None, _p(off)))
+        self._check(lib().aloam_load_sequences(self.h, _ids_arg(ids), len(ids), _vp(ptr), _p(off)))
 
     def odometry_step(self):
         self._check(lib().aloam_odometry_step(self.h))
@@ -1286,23 +998,21 @@ class Aloam:
         """Clouds `ids` (CLOUD_* or EXPORT_MAP + MAP_*) of every sequence packed into dst_ptr (16-byte points, at most cap_points of
         them), segment (i, b) at [offsets[i * batch + b], offsets[i * batch + b + 1]); offsets_ptr receives len(ids) * batch + 1 int64."""
         a = (C.c_int * max(1, len(ids)))(*[int(v) for v in ids])
-        self._check(lib().aloam_export_clouds(self.h, a, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None, int(cap_points), C.c_void_p(offsets_ptr)))
+        self._check(lib().aloam_export_clouds(self.h, a, len(ids), _vp(dst_ptr), int(cap_points), C.c_void_p(offsets_ptr)))
 
     def export_pose_information_into(self, which, seqs, dst_ptr):
         """Queue one aloam_pose_information per listed sequence (INFO_ODOMETRY / INFO_MAPPING) into dst_ptr: device memory of this
         context's device, or pinned host memory."""
-        ids = np.ascontiguousarray([int(v) for v in seqs], dtype=np.int32)
-        self._check(lib().aloam_export_pose_information(self.h, int(which), _p(ids) if len(ids) else None, len(ids), C.c_void_p(dst_ptr) if dst_ptr else None))
+        ids = _ids(seqs)
+        self._check(lib().aloam_export_pose_information(self.h, int(which), _ids_arg(ids), len(ids), _vp(dst_ptr)))
 
     def export_pose_information(self, which, seqs, pinned=True):
         """The records of `seqs` after a synchronise: a structured array [len(seqs)] of POSE_INFORMATION_DTYPE (information.py says what a
         caller does with one); with pinned=False the destination is device memory, copied back afterwards."""
-        import torch
-        n = len(seqs)
-        buf = torch.zeros(max(1, n) * POSE_INFORMATION_DTYPE.itemsize, dtype=torch.uint8, **({"pin_memory": True} if pinned else {"device": "cuda"}))
+        buf = _out_bytes(len(seqs), POSE_INFORMATION_DTYPE, pinned)
         self.export_pose_information_into(which, seqs, buf.data_ptr())
         self.synchronize()
-        return buf.cpu().numpy()[:n * POSE_INFORMATION_DTYPE.itemsize].view(POSE_INFORMATION_DTYPE).copy()
+        return _records(buf, len(seqs), POSE_INFORMATION_DTYPE)
 
     def map_factors(self, seq=0):
         """The factor records the last mapping solve of `seq` read: (lines [n, 9] cp, a, b; planes [m, 7] cp, n, d), float64, in the solver's order."""

@@ -9,11 +9,8 @@ from __future__ import annotations
 import numpy as np
 
 from .posegraph import EDGE_DTYPE, EDGE_ROBUST, NODE_DTYPE
+from .records import GRAPH_RECORD_HEADER_DTYPE as HEADER_DTYPE                    # aloam_graph_record_header, 128 bytes
 
-HEADER_DTYPE = np.dtype([("magic", np.uint32), ("version", np.uint32), ("bytes", np.int64), ("parts", np.int32), ("nodes", np.int32),
-                         ("edges", np.int32), ("kf_points", np.int32, 2), ("seq", np.int32), ("line_res_bits", np.uint32),
-                         ("plane_res_bits", np.uint32), ("node_bytes", np.int32), ("edge_bytes", np.int32), ("desc_bytes", np.int32),
-                         ("point_bytes", np.int32), ("pad", np.int32, 16)])    # aloam_graph_record_header, 128 bytes
 DESC_DTYPE = np.dtype([("first", np.int32, 2), ("count", np.int32, 2)])          # KfDesc: where a node's clouds lie in the point sections
 MAGIC, VERSION = 0x52474C41, 1                                                    # the bytes "ALGR"
 PART_GRAPH, PART_KEYFRAMES = 1, 2

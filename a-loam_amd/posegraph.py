@@ -18,11 +18,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from .records import GRAPH_EDGE_DTYPE as EDGE_DTYPE, GRAPH_MARGINAL_REQUEST_DTYPE as MARGINAL_REQUEST_DTYPE, GRAPH_NODE_DTYPE as NODE_DTYPE
+
 EDGE_ROBUST = 1
-NODE_DTYPE = np.dtype([("q", np.float64, 4), ("t", np.float64, 3), ("q_opt", np.float64, 4), ("t_opt", np.float64, 3),
-                       ("frame", np.int32), ("pad", np.int32, 3)])
-EDGE_DTYPE = np.dtype([("seq", np.int32), ("i", np.int32), ("j", np.int32), ("flags", np.int32), ("q", np.float64, 4), ("t", np.float64, 3),
-                       ("info", np.float64, 21)])
 _IU = np.triu_indices(6)
 
 
@@ -434,7 +432,6 @@ def optimize_robust(q, t, edges, inlier_chi2=22.46, mu_step=1.4, max_outer_itera
 # ---- marginals: the covariance of an edge's residual under the graph, and the chi-square gate ----------------------
 MARGINAL_MEASURED, MARGINAL_AT_ESTIMATE = 0, 1
 MARGINAL_OK, MARGINAL_NO_EDGES, MARGINAL_NOT_CONVERGED, MARGINAL_FAILED = 0, 1, 2, 3
-MARGINAL_REQUEST_DTYPE = np.dtype([("edge", EDGE_DTYPE), ("mode", np.int32), ("pad", np.int32)])
 MARGINAL_DEFAULTS = dict(pcg_max_iterations=200, pcg_tolerance=1e-10, huber_delta=1.0)
 INFO_PIVOT_TOL = 1e-12               # kInfoPivotTol: a Cholesky pivot counts as positive when it exceeds this times its diagonal entry
 

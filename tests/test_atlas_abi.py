@@ -44,20 +44,13 @@ def test_header_documents_the_contract():
         assert word in block, word
 
 
-def test_tile_layout_in_c_and_in_the_binding(binding, tmp_path):
+def test_tile_offsets_and_the_models_dtype(binding):
+    """(test_abi_records.py holds the tile against the C compiler's layout; the offsets are written out here once more.)"""
     fields = ("cube", "feature_class", "count", "frame", "first_point")
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aloam_mi355x.h"\nint main(void) { printf("%zu'
-                   + " %zu" * len(fields) + '\\n", sizeof(aloam_map_tile), ' + ", ".join(f"offsetof(aloam_map_tile, {f})" for f in fields) + "); return 0; }\n")
-    exe = tmp_path / "sizes"
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr                                    # the header is plain C
-    in_c = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    assert in_c == [32, 0, 12, 16, 20, 24]
     atlas = importlib.import_module("a-loam_amd.atlas")
     assert C.sizeof(binding.AloamMapTile) == 32 and binding.MAP_TILE_DTYPE.itemsize == 32 and atlas.TILE_DTYPE == binding.MAP_TILE_DTYPE
-    assert [getattr(binding.AloamMapTile, f).offset for f in fields] == in_c[1:]
-    assert [binding.MAP_TILE_DTYPE.fields[f][1] for f in fields] == in_c[1:]
+    assert [getattr(binding.AloamMapTile, f).offset for f in fields] == [0, 12, 16, 20, 24]
+    assert [binding.MAP_TILE_DTYPE.fields[f][1] for f in fields] == [0, 12, 16, 20, 24]
 
 
 def test_binding_and_library_export_the_calls(binding):

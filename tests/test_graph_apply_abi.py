@@ -1,41 +1,17 @@
 """aloam_graph_apply, host side (no GPU): the entry point, the enums and the two records in the header, the binding and the library; the
 event in capi_seq.hip and its row in DESIGN §7b; what the header says about the map, the rebase and the stored places."""
-import ctypes as C
 import os
 import re
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "aloam_mi355x.h")
-RECORDS = (("aloam_graph_apply_request", "AloamGraphApplyRequest", "GRAPH_APPLY_REQUEST_DTYPE", 16),
-           ("aloam_graph_apply_result", "AloamGraphApplyResult", "GRAPH_APPLY_RESULT_DTYPE", 104))
 
 
-@pytest.mark.parametrize("c_name,cls_name,dtype_name,size", RECORDS)
-def test_records_have_the_header_layout(binding, tmp_path, c_name, cls_name, dtype_name, size):
-    cls = getattr(binding, cls_name)
-    names = [n for n, _ in cls._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "aloam_mi355x.h"', "int main(void) {", f'  printf("%zu", sizeof({c_name}));']
-    src += [f'  printf(" {n}:%zu", offsetof({c_name}, {n}));' for n in names]
-    src += ['  printf("\\n");', "  return 0;", "}"]
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(c), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    parts = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-    dt = getattr(binding, dtype_name)
-    assert int(parts[0]) == size == C.sizeof(cls) == dt.itemsize and size % 8 == 0
-    for tok, name in zip(parts[1:], names):
-        n, off = tok.split(":")
-        assert n == name and int(off) == getattr(cls, name).offset == dt.fields[name][1], tok
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (c_name, c_name), hdr, flags=re.S).group(1)
-    declared = [re.sub(r"\[.*", "", v.strip()) for stmt in body.split(";") if stmt.strip() for v in re.sub(r"^\s*(double|int)\s+", "", stmt.strip()).split(",")]
-    assert declared == names, declared
+def test_the_records_are_whole_doubles(binding):
+    """(Their layouts are rows of test_abi_records.py.)"""
+    assert binding.GRAPH_APPLY_REQUEST_DTYPE.itemsize % 8 == 0 and binding.GRAPH_APPLY_RESULT_DTYPE.itemsize % 8 == 0
 
 
 def test_the_call_is_declared_exported_and_bound(binding):

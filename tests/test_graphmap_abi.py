@@ -8,16 +8,9 @@ import sys
 
 import pytest
 
-from test_posegraph_abi import HEADER, ROOT, test_records_have_the_header_layout as _layout
+from test_posegraph_abi import HEADER, ROOT
 
 CALLS = ("aloam_graph_keyframes_enable", "aloam_graph_export_keyframes", "aloam_graph_keyframe_info", "aloam_graph_export_map")
-RECORDS = (("aloam_graph_map_request", "AloamGraphMapRequest", "GRAPH_MAP_REQUEST_DTYPE", 16),
-           ("aloam_graph_map_stats", "AloamGraphMapStats", "GRAPH_MAP_STATS_DTYPE", 32))
-
-
-@pytest.mark.parametrize("c_name,cls_name,dtype_name,size", RECORDS)
-def test_records_match_the_header(binding, tmp_path, c_name, cls_name, dtype_name, size):
-    _layout(binding, tmp_path, c_name, cls_name, dtype_name, size)
 
 
 def test_calls_are_declared_exported_and_bound(binding):

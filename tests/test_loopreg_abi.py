@@ -6,16 +6,9 @@ import re
 
 import pytest
 
-from test_posegraph_abi import HEADER, ROOT, test_records_have_the_header_layout as _layout
+from test_posegraph_abi import HEADER, ROOT
 
 CALLS = ("aloam_graph_loops_enable", "aloam_graph_loop_default_options", "aloam_graph_register_loops", "aloam_graph_loop_export_target")
-RECORDS = (("aloam_graph_loop_request", "AloamGraphLoopRequest", "GRAPH_LOOP_REQUEST_DTYPE", 96),
-           ("aloam_graph_loop_result", "AloamGraphLoopResult", "GRAPH_LOOP_RESULT_DTYPE", 448))
-
-
-@pytest.mark.parametrize("c_name,cls_name,dtype_name,size", RECORDS)
-def test_records_match_the_header(binding, tmp_path, c_name, cls_name, dtype_name, size):
-    _layout(binding, tmp_path, c_name, cls_name, dtype_name, size)
 
 
 def test_calls_are_declared_exported_and_bound(binding):

@@ -34,14 +34,8 @@ def test_header_documents_the_contract():
         assert word in block, word
 
 
-def test_record_sizes_in_c_and_in_the_binding(binding, tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aloam_mi355x.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", sizeof(aloam_map_correction), '
-                   'sizeof(aloam_map_score), offsetof(aloam_map_correction, t_wmap_wodom), offsetof(aloam_map_score, cost)); return 0; }\n')
-    exe = tmp_path / "sizes"
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr                                    # the header is plain C
-    assert subprocess.run([str(exe)], capture_output=True, text=True).stdout.split() == ["64", "32", "32", "16"]
+def test_record_offsets_and_the_candidates_bytes(binding):
+    """(test_abi_records.py holds both records against the C compiler's layout; two offsets are written out here once more.)"""
     assert C.sizeof(binding.AloamMapCorrection) == 64 and C.sizeof(binding.AloamMapScore) == 32
     assert binding.MAP_CORRECTION_DTYPE.itemsize == 64 and binding.MAP_SCORE_DTYPE.itemsize == 32
     assert binding.MAP_CORRECTION_DTYPE.fields["t_wmap_wodom"][1] == 32 and binding.MAP_SCORE_DTYPE.fields["cost"][1] == 16
