@@ -161,6 +161,8 @@ def lib():
         L.aloam_graph_marginals.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphMarginalOptions), vp]
         L.aloam_graph_robust_default_options.argtypes = [C.POINTER(AloamGraphRobustOptions)]; L.aloam_graph_robust_default_options.restype = None
         L.aloam_graph_optimize_robust.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphOptions), C.POINTER(AloamGraphRobustOptions), vp, vp, C.c_longlong]
+        if hasattr(L, "aloam_graph_propose_loops"):        # absent from an A/B variant built from an older tree (ALOAM_MI355X_LIB)
+            L.aloam_graph_propose_loops.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
         L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -831,6 +833,27 @@ class Aloam:
         self.graph_optimize_robust_into(seqs, buf.data_ptr(), self.graph_options(**options), robust, wts.data_ptr(), weights_stride)
         self.synchronize()
         return _records(buf, n, GRAPH_ROBUST_RESULT_DTYPE), wts.cpu().numpy()[:n].copy()
+
+    # ---- loop candidates by pose proximity (posegraph.propose_loops holds the definition) ----------------------------------------------------
+    def graph_propose_loops_into(self, queries, dst_ptr, counts_ptr, dist2_ptr=0, *, radius_m, growth_m_per_node=0.0, min_gap, half_window=0,
+                                 separation=0, K=1, pose=GRAPH_POSE_OPTIMIZED):
+        """Queue the radius search of each query ((seq, j) pairs; no host synchronisation): dst_ptr receives K aloam_graph_loop_request per
+        query, counts_ptr one int, dist2_ptr (or 0) K doubles; device memory or pinned host memory."""
+        qs = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 2)
+        self._check(lib().aloam_graph_propose_loops(self.h, _p(qs) if len(qs) else None, len(qs), int(pose), float(radius_m), float(growth_m_per_node),
+                                                    int(min_gap), int(half_window), int(separation), int(K), _vp(dst_ptr), _vp(counts_ptr), _vp(dist2_ptr)))
+
+    def graph_propose_loops(self, queries, pinned=True, **parameters):
+        """Propose and wait: (requests [n, K] of GRAPH_LOOP_REQUEST_DTYPE, counts int32 [n], dist2 float64 [n, K]).  Keyword arguments are
+        the parameters of aloam_graph_propose_loops (radius_m, growth_m_per_node, min_gap, half_window, separation, K, pose)."""
+        import torch
+        n, K = len(np.asarray(queries).reshape(-1, 2)), int(parameters.get("K", 1))
+        dst = _out_bytes(n * K, GRAPH_LOOP_REQUEST_DTYPE, pinned)
+        cnt = torch.zeros(max(1, n), dtype=torch.int32, **_where(pinned))
+        d2 = torch.zeros(max(1, n * K), dtype=torch.float64, **_where(pinned))
+        self.graph_propose_loops_into(queries, dst.data_ptr(), cnt.data_ptr(), d2.data_ptr(), **parameters)
+        self.synchronize()
+        return _records(dst, n * K, GRAPH_LOOP_REQUEST_DTYPE).reshape(n, K), cnt.cpu().numpy()[:n].copy(), d2.cpu().numpy()[:n * K].reshape(n, K).copy()
 
     # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
     def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

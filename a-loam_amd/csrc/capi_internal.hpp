@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, staging of input counts, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphpropose.hip (loop candidates by pose proximity), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 // Stated once here for all of them: the pinned staging ring (StageRing), a scratch buffer with its capacity (Scratch), and one struct per
 // graph-family feature (GraphStore ... MarginalScratch) that its enable builds fresh and commits with one move, as MapPool.
@@ -23,6 +23,7 @@
 #include "graphapply_kernels.hpp"
 #include "graphmap_kernels.hpp"
 #include "graphmarginal_kernels.hpp"
+#include "graphpropose_kernels.hpp"
 #include "graphrecord_kernels.hpp"
 #include "loopreg_kernels.hpp"
 #include "loopsearch_kernels.hpp"
@@ -184,6 +185,10 @@ struct MarginalScratch {             // pose-graph marginals (aloam_graph_margin
   Scratch<double> f64; Scratch<int> i32;                            // the scratch rows, one per request of a round
   long long last_nodes = 0, last_edges = 0; int last_n = 0;         // the last call (algorithmic bytes)
 };
+struct ProposeScratch {              // loop candidates by pose proximity (aloam_graph_propose_loops): nothing is allocated before the first call; used in stream order
+  DevBuf<GraphProposeQuery> queries;                                // [kProposeStageItems] the round's queries
+  StageRing<kProposeStageSlots> ring;                               // a slot holds kProposeStageItems queries
+};
 
 struct GraphRecordScratch {          // graph records (aloam_graph_save / aloam_graph_load): sized for `batch` records on first use, used in stream order
   DevBuf<GraphRecItem> items;                                       // [B] the records of one call
@@ -324,6 +329,7 @@ struct aloam_ctx {
   GraphApplyScratch ga;
   LoopScratch lr;
   MarginalScratch mg;
+  ProposeScratch pp;
   GraphRecordScratch gr;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;

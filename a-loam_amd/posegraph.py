@@ -19,6 +19,7 @@ from __future__ import annotations
 import numpy as np
 
 from .records import GRAPH_EDGE_DTYPE as EDGE_DTYPE, GRAPH_MARGINAL_REQUEST_DTYPE as MARGINAL_REQUEST_DTYPE, GRAPH_NODE_DTYPE as NODE_DTYPE
+from .records import GRAPH_LOOP_REQUEST_DTYPE as LOOP_REQUEST_DTYPE, GRAPH_POSE_ENTERED as POSE_ENTERED, GRAPH_POSE_OPTIMIZED as POSE_OPTIMIZED
 
 EDGE_ROBUST = 1
 _IU = np.triu_indices(6)
@@ -612,6 +613,57 @@ def loop_from_localization(i, q_place, t_place, j, q_reloc, t_reloc, info, seq=0
     info = T^T info_left T with T = blockdiag(R_Z, R_Z): that matters in a corridor whose weak direction is not the sensor's x axis."""
     qz, tz = relative_pose(q_place, t_place, q_reloc, t_reloc)
     return make_edges(seq, i, j, qz[None], tz[None], np.asarray(info)[None], robust)
+
+
+# ---- loop candidates by pose proximity (aloam_graph_propose_loops) -------------------------------------------------------------------
+PROPOSE_MAX_K = 16
+
+
+def propose_loops(q, t, j, radius_m, growth_m_per_node, min_gap, half_window, separation, K, seq=0, pose=POSE_OPTIMIZED):
+    """aloam_graph_propose_loops for one query (seq, j), operation by operation: (q, t) are the poses the call reads (the entered ones
+    or the estimates, as `pose` says; `pose` itself only goes into the records).  A node i in [0, j - min_gap] is a hit when
+    d2 = (dx dx + dy dy) + dz dz of t_i - t_j is <= r r, r = (j - i) growth_m_per_node + radius_m.  At most K rounds: the live hit with
+    the least (d2, i) is taken and every hit within `separation` indices of it dies.  Returns (requests [K] of GRAPH_LOOP_REQUEST_DTYPE
+    with first = max(0, i - half_window), count = i + half_window - first + 1 and the guess relative_pose(X_i, X_j); count; dist2 [K]);
+    rows behind the count are zero."""
+    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    j, K = int(j), int(K)
+    req, dist2 = np.zeros(K, LOOP_REQUEST_DTYPE), np.zeros(K, np.float64)
+    i = np.arange(max(0, j - int(min_gap) + 1))
+    d = t[i] - t[j]
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    r = (j - i).astype(np.float64) * np.float64(growth_m_per_node) + np.float64(radius_m)
+    with np.errstate(over="ignore"):
+        live = d2 <= r * r
+    taken = 0
+    while taken < K and live.any():
+        cand = i[live]
+        best = d2[cand].min()
+        w = int(cand[d2[cand] == best][0])
+        live &= np.abs(i - w) > int(separation)
+        first = max(0, w - int(half_window))
+        qd, td = relative_pose(q[w], t[w], q[j], t[j])
+        rec = req[taken]
+        rec["seq"], rec["i"], rec["j"], rec["first"], rec["count"], rec["pose"] = int(seq), w, j, first, w + int(half_window) - first + 1, int(pose)
+        rec["q"], rec["t"] = qd, td
+        dist2[taken] = d2[w]
+        taken += 1
+    return req, taken, dist2
+
+
+def unclosed(requests, edges, gap):
+    """The proposals (i, j) of `requests` next to which the graph holds no loop edge yet: a proposal is dropped when some edge (a, b) of
+    `edges` (EDGE_DTYPE records of the same sequence, or pairs) has |a - i| <= gap and |b - j| <= gap.  The host added the edges, so it is
+    the host that knows them."""
+    requests = np.asarray(requests)
+    if getattr(getattr(edges, "dtype", None), "names", None):
+        ab = np.stack([edges["i"], edges["j"]], 1).astype(np.int64)
+    else:
+        ab = np.asarray(edges, np.int64).reshape(-1, 2)
+    keep = np.ones(len(requests), bool)
+    for k, rq in enumerate(requests):
+        keep[k] = not np.any((np.abs(ab[:, 0] - int(rq["i"])) <= gap) & (np.abs(ab[:, 1] - int(rq["j"])) <= gap))
+    return requests[keep]
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------------

@@ -1192,6 +1192,42 @@ void aloam_graph_robust_default_options(aloam_graph_robust_options* opt);
 int aloam_graph_optimize_robust(aloam_ctx* ctx, const int* seqs, int n, const aloam_graph_options* opt, const aloam_graph_robust_options* robust,
                                 aloam_graph_robust_result* dst /* [n] */, double* weights_dst /* [n][weights_stride] or NULL */, long long weights_stride);
 
+/* ---- loop candidates by pose proximity -------------------------------------------------------------------------------------------------
+ * aloam_places_match answers "which stored sweep looks like this one"; this section answers "which keyframes does the graph itself say I am
+ * next to": a radius search over the positions of a sequence's own nodes, as the LOAM-family back ends propose loops (a radius and a
+ * minimum age), for a batch of queries in one stream-ordered call.  It writes aloam_graph_loop_request records, guess and target window
+ * filled in, ready for aloam_graph_search_loops / aloam_graph_register_loops: propose -> search and register -> gate -> add -> solve.  It
+ * needs neither the place store nor the keyframe store.  Opt-in and beside the reference: a context that never calls it allocates nothing for
+ * it and launches exactly what it launched before.  a-loam_amd/posegraph.py restates the definition as propose_loops(); DESIGN.md §7v.
+ *
+ * Definition of a query (seq, j), every f64 operation separately rounded:
+ *   1. X_k is node k's entered pose (q, t) or its estimate (q_opt, t_opt), chosen by pose.
+ *   2. The eligible nodes are i in [0, j - min_gap]; none when j < min_gap.
+ *   3. For each eligible i: (dx, dy, dz) = t_i - t_j, d2 = (dx*dx + dy*dy) + dz*dz, r = (double)(j - i) * growth_m_per_node + radius_m;
+ *      i is a hit when d2 <= r*r.  The growth term lets the radius follow the drift between two nodes far apart on the chain.
+ *   4. Selection is greedy, at most K rounds: each round takes, among the hits still live, the one with the least (d2, i) - lower d2 first,
+ *      then lower i - and removes every hit i' with |i' - i| <= separation (one pass by the same place fills many consecutive nodes; this
+ *      keeps one candidate per pass).  counts[q] is the number taken.
+ *   5. The record of the k-th node taken: seq, i, j and pose as given; first = max(0, i - half_window); count = i + half_window - first + 1;
+ *      the guess (q, t) = X_i^-1 o X_j as this header defines a relative pose, q_d = conj(q_i) q_j, t_d = conj(q_i) (t_j - t_i); pad and
+ *      reserved are zero.  dist2[q][k] = d2.
+ *   6. Rows k >= counts[q] of dst are all-zero bytes and their dist2 entries are 0.0.  Every byte of dst[0 .. n*K) and of counts[0 .. n) is
+ *      written (and of dist2[0 .. n*K) unless it is NULL); nothing outside them is written.
+ *
+ * aloam_graph_propose_loops: queries is host memory, n pairs (seq, j), read during the call; everything is checked before anything is
+ *   queued, ALOAM_E_ARG with nothing changed: seq in range; 0 <= j < the sequence's nodes (host state); pose 0 or 1; radius_m and
+ *   growth_m_per_node finite and >= 0; min_gap >= 1; 0 <= half_window < min_gap, so the window never reaches j, which
+ *   aloam_graph_register_loops requires; separation >= 0; 1 <= K <= 16; dst, counts and dist2 (which may be NULL) device memory of the
+ *   context's device or pinned host memory, classified like the exports, dst and dist2 8-byte aligned and counts 4-byte aligned.
+ *   ALOAM_E_STATE before aloam_graph_enable.  n = 0 is ALOAM_OK.  A sequence, and a (seq, j), may be listed any number of times.
+ *   Stream-ordered, no host synchronisation: the queries go through a pinned staging ring, and a large n runs in rounds.  The call reads
+ *   the graph and writes nothing in it.  Every bit of a query's outputs is independent of n, of its position in the list, of the round and
+ *   of the other queries.  Which edges the graph already holds is the caller's knowledge (it added them): posegraph.unclosed() drops the
+ *   proposals next to one.  Timed under the profiling slot pose_graph. */
+int aloam_graph_propose_loops(aloam_ctx* ctx, const int* queries /* [n][2]: seq, j */, int n, int pose,
+                              double radius_m, double growth_m_per_node, int min_gap, int half_window, int separation, int K,
+                              aloam_graph_loop_request* dst /* [n][K] */, int* counts /* [n] */, double* dist2 /* [n][K] or NULL */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

@@ -2,6 +2,7 @@
 edge inside a drive").
 
     python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]] [--false-loops K] [--resume-at K]
+                                         [--device-loops --proximity RADIUS]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -24,6 +25,13 @@ route's: the default path is unchanged.
 
 With --device-loops --search the match's guess is also searched (aloam_graph_search_loops, the default grid): the best node, its score and
 the guess's, and the edge's error are printed as device_loop_search beside device_loop_edge, the unsearched call from the same guess.
+
+With --device-loops --proximity RADIUS the loop candidate of the last keyframe comes from the graph itself instead of the place match:
+aloam_graph_propose_loops over the estimates, nodes at least --gap keyframes old within RADIUS metres, --neighbours either side as the
+target window.  No place store is enabled and steps 1 to 3 do not run.  The first proposal - a ready aloam_graph_loop_request, its guess
+X_i^-1 o X_j of the estimates - goes through the --device-loops route (with --search through the grid search), and its edge, measured by
+the last of those calls, is the one that enters the graph.  Printed as proposal: the proposed (i, j) and their distance in the graph,
+beside the ground-truth revisit (the nearest keyframe in ground truth among those at least --gap older).
 
 With --false-loops K the measured edge goes into the graph flagged ALOAM_GRAPH_EDGE_ROBUST beside K copies of itself displaced by up to
 8 m and 0.5 rad per axis (what a place-recognition alias looks like to the graph), flagged too.  The graph is solved by aloam_graph_optimize
@@ -82,11 +90,15 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--device-loops", action="store_true", help="also measure the edge with aloam_graph_register_loops from the same match, and print it beside the spare-slot route's")
     ap.add_argument("--search", action="store_true", help="with --device-loops: also search a pose grid around the match's guess (aloam_graph_search_loops) and print it beside the unsearched call")
+    ap.add_argument("--proximity", type=float, default=None, metavar="RADIUS", help="with --device-loops: take the loop candidate of the last keyframe from aloam_graph_propose_loops "
+                    "(nodes within RADIUS metres in the graph's estimates) instead of the place match; no place store, no spare slot")
     ap.add_argument("--false-loops", type=int, default=0, metavar="K", help="enter K displaced copies of the measured edge beside it, all flagged robust, and print the distance to ground truth "
                     "after aloam_graph_optimize and after aloam_graph_optimize_robust, with the weights")
     ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
     ap.add_argument("--resume-at", type=int, default=None, metavar="K", help="only drive: at keyframe K save the sequence record and the graph record to a temporary file, load both into a fresh context, drive on in both and compare")
     args = ap.parse_args()
+    if args.proximity is not None and not (args.device_loops and 0 <= args.neighbours < args.gap):
+        ap.error("--proximity needs --device-loops and --neighbours below --gap")
 
     import torch
     binding = importlib.import_module("a-loam_amd.binding")
@@ -180,7 +192,9 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
     gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)
     gpu.graph_enable(n_key + 4, n_key + 8)
     gpu.graph_keyframes_enable(n_key * 2048, n_key * 16384)
-    gpu.places_enable(n_key + 4, max_range=40.0, sensor_height=syn.SENSOR_HEIGHT)
+    proximity = args.proximity is not None
+    if not proximity:
+        gpu.places_enable(n_key + 4, max_range=40.0, sensor_height=syn.SENSOR_HEIGHT)
     if args.device_loops:
         gpu.graph_loops_enable(1, (2 * args.neighbours + 1) * 2048, (2 * args.neighbours + 1) * 16384)
     info = np.diag([1.0 / 5e-3 ** 2] * 3 + [1.0 / 5e-2 ** 2] * 3)
@@ -195,7 +209,8 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
             gpu.mapping_step()
             if k % every == 0 or k == frames - 1:
                 gpu.graph_add_nodes([0], info)
-                gpu.places_add([0])
+                if not proximity:
+                    gpu.places_add([0])
                 key_frames.append(k)
         gpu.synchronize()
         out["keyframes"] = len(key_frames)
@@ -204,21 +219,39 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
         truth_q, truth_t = q_true[key_frames], t_true[key_frames]
         out["ate_before"] = pg.ate(nodes["t_opt"], truth_t)
 
-        stage = "places_match"
-        m = gpu.places_match([0], [(0, max(1, j - args.gap))])[0, 0]
-        i = int(m["entry"])
-        out["match"] = {"entry": i, "shift": int(m["shift"]), "distance": float(m["distance"]), "truth_distance_m": float(np.linalg.norm(truth_t[i] - truth_t[j]))}
-        if i < 0:
-            raise RuntimeError("no stored place matches the last sweep")
+        if proximity:
+            # the candidate from the graph itself: the nearest node at least --gap keyframes old, one per pass, as a ready request
+            stage = "graph_propose_loops"
+            t0 = time.perf_counter()
+            prop, count, dist2 = gpu.graph_propose_loops([(0, j)], radius_m=args.proximity, min_gap=args.gap, half_window=args.neighbours,
+                                                         separation=args.neighbours, K=4, pose=binding.GRAPH_POSE_OPTIMIZED)
+            propose_ms = 1e3 * (time.perf_counter() - t0)
+            older = np.arange(0, max(1, j - args.gap + 1))
+            i_true = int(older[np.argmin(np.linalg.norm(truth_t[older] - truth_t[j], axis=1))])
+            out["proposal"] = {"count": int(count[0]), "proposed": [[int(r["i"]), int(r["j"])] for r in prop[0][:count[0]]], "graph_distance_m": np.sqrt(dist2[0][:count[0]]).tolist(),
+                               "truth_revisit": [i_true, j], "truth_distance_m": float(np.linalg.norm(truth_t[i_true] - truth_t[j])), "call_and_synchronize_ms": propose_ms}
+            if count[0] < 1:
+                raise RuntimeError("no node within --proximity of the last keyframe")
+            first = prop[0][0]
+            i, lo, hi = int(first["i"]), int(first["first"]), int(first["first"] + first["count"])
+            qg, tg = first["q"].copy(), first["t"].copy()
+        else:
+            stage = "places_match"
+            m = gpu.places_match([0], [(0, max(1, j - args.gap))])[0, 0]
+            i = int(m["entry"])
+            out["match"] = {"entry": i, "shift": int(m["shift"]), "distance": float(m["distance"]), "truth_distance_m": float(np.linalg.norm(truth_t[i] - truth_t[j]))}
+            if i < 0:
+                raise RuntimeError("no stored place matches the last sweep")
+            lo, hi = max(0, i - args.neighbours), min(j - args.gap, i + args.neighbours + 1)
 
         stage = "graph_export_map (local)"
-        lo, hi = max(0, i - args.neighbours), min(j - args.gap, i + args.neighbours + 1)
         req = [(0, lo, hi - lo, binding.GRAPH_POSE_OPTIMIZED)]
         if args.device_loops:
-            # the one-call route: node j against nodes lo .. hi - 1 in the frame of node i, the guess from the match's yaw shift
+            # the one-call route: node j against nodes lo .. hi - 1 in the frame of node i, the guess from the match's yaw shift (or the proposal's)
             stage = "graph_register_loops"
             lr = importlib.import_module("a-loam_amd.loopreg")
-            qg, tg = lr.guess_from_match(nodes["q_opt"][i], nodes["t_opt"][i], nodes["q_opt"][i], nodes["t_opt"][i], int(m["shift"]), nodes["q_opt"][j], nodes["t_opt"][j])
+            if not proximity:
+                qg, tg = lr.guess_from_match(nodes["q_opt"][i], nodes["t_opt"][i], nodes["q_opt"][i], nodes["t_opt"][i], int(m["shift"]), nodes["q_opt"][j], nodes["t_opt"][j])
             t0 = time.perf_counter()
             r = gpu.graph_register_loops([(0, i, j, lo, hi - lo, binding.GRAPH_POSE_OPTIMIZED, qg, tg)])[0]
             call_ms = 1e3 * (time.perf_counter() - t0)
@@ -241,7 +274,8 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
                                              "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dqs[:3]))))), "call_and_synchronize_ms": search_ms}
             # the gate: the measured edge, and a copy displaced by 1.5 m, against the graph's own uncertainty about X_i^-1 o X_j
             stage = "graph_marginals"
-            rq = lr.request_from_result(r, i, j, 0)
+            measured = rs if args.search and proximity else r                     # --proximity: the edge that enters the graph
+            rq = lr.request_from_result(measured, i, j, 0)
             if rq is not None:
                 moved = rq.copy()
                 moved["edge"]["t"][0, 0] += 1.5
@@ -252,50 +286,56 @@ def drive(args, mods, scans, q_true, t_true, frames, more, every, apply):
                      "accepted": bool(g["status"] == pg.MARGINAL_OK and g["chi2"] < gate)} for d, g in zip((0.0, 1.5), mg)]}
             stage = "graph_export_map (local)"
             t_spare = time.perf_counter()
-        off = torch.zeros(4, dtype=torch.int64, pin_memory=True)
-        gpu.graph_export_map_into(req, 0, 0, 0, 0, off.data_ptr())
-        gpu.synchronize()
-        nt, npts = int(off[1]), int(off[3])
-        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, device="cuda")
-        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, device="cuda")
-        gpu.graph_export_map_into(req, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr())
-        out["local_atlas"] = {"nodes": [lo, hi], "tiles": nt, "points": npts}
+        if proximity:
+            stage = "loop edge"
+            edge = lr.edge_from_result(measured, 0, i, j, robust=False)            # the edge of the last registration call above
+            if edge is None:
+                raise RuntimeError("the registration of the proposal ended with status %d" % int(measured["status"]))
+        else:
+            off = torch.zeros(4, dtype=torch.int64, pin_memory=True)
+            gpu.graph_export_map_into(req, 0, 0, 0, 0, off.data_ptr())
+            gpu.synchronize()
+            nt, npts = int(off[1]), int(off[3])
+            tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, device="cuda")
+            pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, device="cuda")
+            gpu.graph_export_map_into(req, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr())
+            out["local_atlas"] = {"nodes": [lo, hi], "tiles": nt, "points": npts}
 
-        stage = "atlas_load"
-        gpu.atlas_load(tiles[:nt * 32], pts[:npts])
+            stage = "atlas_load"
+            gpu.atlas_load(tiles[:nt * 32], pts[:npts])
 
-        stage = "spare slot"
-        gpu.reset_sequences([1])
-        gpu.set_active([0, 1])
-        gpu.scan_register([nan_row, scans[key_frames[j]]], check=False)
-        gpu.odometry_step()
-        odom = gpu.pose(1)
-        gq, gt = places.guess_from_match(nodes["q_opt"][i], nodes["t_opt"][i], int(m["shift"]), odom["q_w"], odom["t_w"])
-        gpu.set_map_frozen([0, 1])
-        gpu.atlas_attach([0, 1])
-        gpu.set_map_frame((10, 10, 5), gq, gt, 0, seq=1)
-        gpu.mapping_step()
-        stage = "relocalize"
-        r = reloc.relocalize(gpu, [1])
-        out["relocalize"] = {"best_node": r[1]["nodes"][r[1]["best"]].tolist()}
-        stage = "frozen steps"
-        for _ in range(args.frozen_steps):
+            stage = "spare slot"
+            gpu.reset_sequences([1])
+            gpu.set_active([0, 1])
+            gpu.scan_register([nan_row, scans[key_frames[j]]], check=False)
+            gpu.odometry_step()
+            odom = gpu.pose(1)
+            gq, gt = places.guess_from_match(nodes["q_opt"][i], nodes["t_opt"][i], int(m["shift"]), odom["q_w"], odom["t_w"])
+            gpu.set_map_frozen([0, 1])
+            gpu.atlas_attach([0, 1])
+            gpu.set_map_frame((10, 10, 5), gq, gt, 0, seq=1)
             gpu.mapping_step()
-        gpu.synchronize()
-        mp = gpu.map_pose(1)
-        pi = gpu.export_pose_information(binding.INFO_MAPPING, [1])[0]
-        if args.device_loops:
-            out["spare_slot_route_ms"] = 1e3 * (time.perf_counter() - t_spare)
-        out["localization"] = {"status": int(pi["status"]), "n_line": int(pi["n_line"]), "n_plane": int(pi["n_plane"]),
-                               "error_m": float(np.linalg.norm(mp["t_w"] - truth_t[j])), "drive_error_m": float(np.linalg.norm(nodes["t_opt"][j] - truth_t[j]))}
-        gpu.atlas_attach(None)
-        gpu.set_map_frozen(None)
-        gpu.set_active([1, 0])
-        if pi["status"] != binding.INFO_OK:
-            raise RuntimeError("the frozen steps of the spare slot ended without a usable solve")
+            stage = "relocalize"
+            r = reloc.relocalize(gpu, [1])
+            out["relocalize"] = {"best_node": r[1]["nodes"][r[1]["best"]].tolist()}
+            stage = "frozen steps"
+            for _ in range(args.frozen_steps):
+                gpu.mapping_step()
+            gpu.synchronize()
+            mp = gpu.map_pose(1)
+            pi = gpu.export_pose_information(binding.INFO_MAPPING, [1])[0]
+            if args.device_loops:
+                out["spare_slot_route_ms"] = 1e3 * (time.perf_counter() - t_spare)
+            out["localization"] = {"status": int(pi["status"]), "n_line": int(pi["n_line"]), "n_plane": int(pi["n_plane"]),
+                                   "error_m": float(np.linalg.norm(mp["t_w"] - truth_t[j])), "drive_error_m": float(np.linalg.norm(nodes["t_opt"][j] - truth_t[j]))}
+            gpu.atlas_attach(None)
+            gpu.set_map_frozen(None)
+            gpu.set_active([1, 0])
+            if pi["status"] != binding.INFO_OK:
+                raise RuntimeError("the frozen steps of the spare slot ended without a usable solve")
 
-        stage = "loop edge"
-        edge = pg.loop_from_localization(i, nodes["q_opt"][i], nodes["t_opt"][i], j, mp["q_w"], mp["t_w"], pi["info"])
+            stage = "loop edge"
+            edge = pg.loop_from_localization(i, nodes["q_opt"][i], nodes["t_opt"][i], j, mp["q_w"], mp["t_w"], pi["info"])
         qz, tz = pg.relative_pose(truth_q[i], truth_t[i], truth_q[j], truth_t[j])
         dq = pg.qmul(pg.qconj(qz), edge["q"][0])
         out["loop_edge"] = {"i": i, "j": j, "translation_error_m": float(np.linalg.norm(edge["t"][0] - tz)),
