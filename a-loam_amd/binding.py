@@ -163,6 +163,8 @@ def lib():
         L.aloam_graph_optimize_robust.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphOptions), C.POINTER(AloamGraphRobustOptions), vp, vp, C.c_longlong]
         if hasattr(L, "aloam_graph_propose_loops"):        # absent from an A/B variant built from an older tree (ALOAM_MI355X_LIB)
             L.aloam_graph_propose_loops.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+        if hasattr(L, "aloam_graph_trim"):                 # likewise
+            L.aloam_graph_trim.argtypes = [vp, vp, vp, C.c_int, vp]
         L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -854,6 +856,17 @@ class Aloam:
         self.graph_propose_loops_into(queries, dst.data_ptr(), cnt.data_ptr(), d2.data_ptr(), **parameters)
         self.synchronize()
         return _records(dst, n * K, GRAPH_LOOP_REQUEST_DTYPE).reshape(n, K), cnt.cpu().numpy()[:n].copy(), d2.cpu().numpy()[:n * K].reshape(n, K).copy()
+
+    # ---- trimming a graph in place (posegraph.trim and graph_records.trim_keyframes hold the definition) -----------------------------------
+    def graph_trim(self, seqs, first):
+        """Drop nodes [0, first[k]) of every listed sequence's graph on the device; edges from a dropped node to a kept one become anchors.
+        Synchronises the stream once.  Returns int32 [n, 8]: nodes, edges, anchored, removed_fixed, removed_reverse, corner / surf points
+        freed, 0."""
+        ids = _ids(seqs)
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(first, dtype=np.int32), (len(ids),)))
+        out = np.zeros((len(ids), 8), np.int32)
+        self._check(lib().aloam_graph_trim(self.h, _ids_arg(ids), _p(f) if len(ids) else None, len(ids), _p(out) if len(ids) else None))
+        return out
 
     # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
     def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

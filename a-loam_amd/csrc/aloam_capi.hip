@@ -391,8 +391,10 @@ int aloam_profile_get(aloam_ctx* c, int kernel, double* total_ms, long long* lau
         else if (c->map_on) bytes += (double)sizeof(MapEdgeRec) * ms[b].factor_num[1][0] + (double)sizeof(MapNormRec) * ms[b].factor_num[1][1];
       }
     }
-    // the last aloam_graph_optimize: nodes and edges read once, the estimates and one result written (the iterations run out of L2)
+    // the last aloam_graph_optimize: nodes and edges read once, the estimates and one result written (the iterations run out of L2); or the last
+    // aloam_graph_trim: the rows it moved, read and written
     if (kernel == K_POSE_GRAPH) bytes = (double)(sizeof(aloam_graph_node) + 56) * c->pg.last_nodes + (double)sizeof(aloam_graph_edge) * c->pg.last_edges;
+    if (kernel == K_POSE_GRAPH && c->pg.last_trim_bytes >= 0) bytes = (double)c->pg.last_trim_bytes;
     // the last aloam_graph_marginals: per request its graph's estimates and edges read once, one request read and one result written (the
     // linearisation and the iterations run out of the request's scratch row)
     if (kernel == K_GRAPH_MARGINALS)

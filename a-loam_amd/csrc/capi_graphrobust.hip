@@ -75,7 +75,7 @@ int aloam_graph_optimize_robust(aloam_ctx* c, const int* seqs, int n, const aloa
     launch_graph_robust(a, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
-  c->pg.last_nodes = nodes; c->pg.last_edges = edges;
+  c->pg.last_nodes = nodes; c->pg.last_edges = edges; c->pg.last_trim_bytes = -1;
   return ALOAM_OK;
 }
 

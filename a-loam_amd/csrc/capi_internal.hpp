@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, staging of input counts, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphpropose.hip (loop candidates by pose proximity), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphpropose.hip (loop candidates by pose proximity), capi_graphtrim.hip (pose graphs trimmed in place), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 // Stated once here for all of them: the pinned staging ring (StageRing), a scratch buffer with its capacity (Scratch), and one struct per
 // graph-family feature (GraphStore ... MarginalScratch) that its enable builds fresh and commits with one move, as MapPool.
@@ -25,6 +25,7 @@
 #include "graphmarginal_kernels.hpp"
 #include "graphpropose_kernels.hpp"
 #include "graphrecord_kernels.hpp"
+#include "graphtrim_kernels.hpp"
 #include "loopreg_kernels.hpp"
 #include "loopsearch_kernels.hpp"
 #include "mapping_kernels.hpp"
@@ -138,6 +139,7 @@ struct GraphStore {                  // pose graphs (aloam_graph_enable): one ro
   StageRing<kGraphStageSlots> ring;                                 // a slot holds the B items of one add / optimize
   Scratch<double> f64; Scratch<int> i32;                            // the solve's scratch rows, grown on first use
   long long last_nodes = 0, last_edges = 0;                         // the last solve (algorithmic bytes)
+  long long last_trim_bytes = -1;                                   // >= 0: the last call timed under pose_graph was aloam_graph_trim, and moved this much
 };
 struct KeyframeStore {               // keyframe clouds (aloam_graph_keyframes_enable): per sequence and class a row of sensor-frame points, per node a descriptor
   bool on = false;
@@ -188,6 +190,11 @@ struct MarginalScratch {             // pose-graph marginals (aloam_graph_margin
 struct ProposeScratch {              // loop candidates by pose proximity (aloam_graph_propose_loops): nothing is allocated before the first call; used in stream order
   DevBuf<GraphProposeQuery> queries;                                // [kProposeStageItems] the round's queries
   StageRing<kProposeStageSlots> ring;                               // a slot holds kProposeStageItems queries
+};
+struct TrimScratch {                 // pose graphs trimmed in place (aloam_graph_trim): nothing is allocated before the first call; used in stream order
+  DevBuf<GraphTrimItem> items;                                      // [B] the listed sequences of one call
+  StageRing<kTrimStageSlots> ring;                                  // a slot holds B items
+  PinnedBuf<int> h_out; int* d_out = nullptr;                       // [B][kTrimRecordInts] what k_graph_trim reports (pinned, mapped)
 };
 
 struct GraphRecordScratch {          // graph records (aloam_graph_save / aloam_graph_load): sized for `batch` records on first use, used in stream order
@@ -330,6 +337,7 @@ struct aloam_ctx {
   LoopScratch lr;
   MarginalScratch mg;
   ProposeScratch pp;
+  TrimScratch tr;
   GraphRecordScratch gr;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
@@ -531,6 +539,7 @@ void on_graph_edges_added(aloam_ctx* c, int seq, int count);
 void on_graph_cleared(aloam_ctx* c, const int* seqs, int n);
 int on_graph_applied(aloam_ctx* c, const int* seqs, int n);
 void on_graph_loaded(aloam_ctx* c, int seq, int nodes, int edges);
+void on_graph_trimmed(aloam_ctx* c, int seq, int nodes, int edges);
 long long on_pool_events_reported(aloam_ctx* c, int seq, long long events);
 // capi_posegraph.hip
 int require_graph(aloam_ctx* c);

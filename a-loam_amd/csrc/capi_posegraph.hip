@@ -219,7 +219,7 @@ int aloam_graph_optimize(aloam_ctx* c, const int* seqs, int n, const aloam_graph
     launch_pose_graph(a, c->stream);
   }
   HIP_TRY(c, hipGetLastError());
-  c->pg.last_nodes = nodes; c->pg.last_edges = edges;
+  c->pg.last_nodes = nodes; c->pg.last_edges = edges; c->pg.last_trim_bytes = -1;
   return ALOAM_OK;
 }
 

@@ -135,6 +135,8 @@ void on_graph_edges_added(aloam_ctx* c, int seq, int count) { c->seq[seq].graph_
 void on_graph_cleared(aloam_ctx* c, const int* seqs, int n) { for (int i = 0; i < n; ++i) { c->seq[seqs[i]].graph_nodes = 0; c->seq[seqs[i]].graph_edges = 0; } }
 // aloam_graph_load has queued the unpack of a checked record into an empty slot: its rows hold the record's nodes and edges.
 void on_graph_loaded(aloam_ctx* c, int seq, int nodes, int edges) { c->seq[seq].graph_nodes = nodes; c->seq[seq].graph_edges = edges; }
+// aloam_graph_trim has run and the stream has drained: the slot's rows hold what k_graph_trim reported (the kept nodes, the compacted edges).
+void on_graph_trimmed(aloam_ctx* c, int seq, int nodes, int edges) { c->seq[seq].graph_nodes = nodes; c->seq[seq].graph_edges = edges; }
 // aloam_graph_apply has been queued for the listed sequences: another frame and, with its map rebuilt, another submap, so their grids are built
 // anew, there is nothing to score against and the pose of their last mapping solve is gone.  The graph's counts stay, and so does has_stacks:
 // the stacks are in the sensor frame.

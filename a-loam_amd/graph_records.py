@@ -3,7 +3,8 @@ DESIGN.md §7r), stated once more without the device.
 
 A record is `header | nodes[N] | edges[E] [ | descriptors[N] | corner points | surf points ] | zeros up to a multiple of 256`; every
 section is a whole number of 16-byte units.  pack() builds one from what Aloam.graph_export, graph_export(edges=True) and
-graph_export_keyframes return, parse() takes one apart into those arrays, check() names what aloam_graph_load would refuse."""
+graph_export_keyframes return, parse() takes one apart into those arrays, check() names what aloam_graph_load would refuse.
+trim_keyframes() is the keyframe store's part of aloam_graph_trim, on the same descriptors."""
 from __future__ import annotations
 
 import numpy as np
@@ -62,11 +63,7 @@ def pack(nodes, edges, keyframes=None, resolutions=None, seq=0):
     if keyframes is not None:
         h["kf_points"] = kf_points
         h["line_res_bits"], h["plane_res_bits"] = _bits(resolutions[0]), _bits(resolutions[1])
-        d = np.zeros(N, DESC_DTYPE)
-        for cls in (0, 1):
-            d["first"][:, cls] = offs[cls][:-1]
-            d["count"][:, cls] = np.diff(offs[cls])
-        rec[L["desc"]:L["corner"]] = d.view(np.uint8).reshape(-1)
+        rec[L["desc"]:L["corner"]] = descriptors(keyframes).view(np.uint8).reshape(-1)
         rec[L["corner"]:L["surf"]] = pts[0].view(np.uint8).reshape(-1)
         rec[L["surf"]:L["end"]] = pts[1].view(np.uint8).reshape(-1)
     return rec
@@ -95,6 +92,31 @@ def parse(blob, offset=0):
         out["keyframes"] = tuple((pts[cls], np.concatenate([d["first"][:, cls], [len(pts[cls])]]).astype(np.int64)) for cls in (0, 1))
         out["resolutions"] = tuple(float(np.array([h[k]], np.uint32).view(np.float32)[0]) for k in ("line_res_bits", "plane_res_bits"))
     return out
+
+
+def descriptors(keyframes):
+    """The descriptor row of the N nodes from the per-class (points, offsets [N + 1]) pairs that graph_export_keyframes returns."""
+    offs = [np.asarray(o, np.int64) for _, o in keyframes]
+    d = np.zeros(len(offs[0]) - 1, DESC_DTYPE)
+    for cls in (0, 1):
+        d["first"][:, cls] = offs[cls][:-1]
+        d["count"][:, cls] = np.diff(offs[cls])
+    return d
+
+
+def trim_keyframes(desc, corner, surf, first):
+    """The keyframe store of one sequence behind aloam_graph_trim(first).  desc: DESC_DTYPE [N]; corner / surf: the points
+    the rows hold, [cursor, 4] each.  Per class d = desc[first].first and m = cursor - d: points [d, d + m) move to [0, m), descriptor
+    n >= first moves to n - first with first -= d and its counts unchanged, the cursor becomes m.  Returns (desc', corner', surf', freed)
+    with freed = [d corner, d surf] (copies; points as bits)."""
+    desc = np.ascontiguousarray(desc, DESC_DTYPE)
+    f = int(first)
+    assert 0 <= f < len(desc), "0 <= first < nodes"
+    d = desc["first"][f].astype(np.int64)
+    out = desc[f:].copy()
+    out["first"] -= d.astype(np.int32)
+    pts = [np.ascontiguousarray(p, np.float32).reshape(-1, 4)[int(d[cls]):].copy() for cls, p in enumerate((corner, surf))]
+    return out, pts[0], pts[1], d
 
 
 def check(blob, offset=0, length=None, max_nodes=None, max_edges=None, kf_capacity=None, resolutions=None):

@@ -11,8 +11,8 @@ A pose X = (q, t) maps a point of the node's frame into the frame the graph live
 
 Everything here is float64 numpy on the host: the definition the device is tested against, a dense Levenberg-Marquardt reference
 (optimize), the chain-preconditioned conjugate gradients of the device restated (chain_pcg), the robust solve over the flagged edges
-(optimize_robust: GNC-TLS), the two lines of algebra that turn a relocalized pose into an edge, and the fixture generators of the tests
-(drifted_laps, false_loops).
+(optimize_robust: GNC-TLS), the two lines of algebra that turn a relocalized pose into an edge, the loop proposal by pose proximity
+(propose_loops), the sliding window (trim: aloam_graph_trim restated), and the fixture generators of the tests (drifted_laps, false_loops).
 """
 from __future__ import annotations
 
@@ -664,6 +664,51 @@ def unclosed(requests, edges, gap):
     for k, rq in enumerate(requests):
         keep[k] = not np.any((np.abs(ab[:, 0] - int(rq["i"])) <= gap) & (np.abs(ab[:, 1] - int(rq["j"])) <= gap))
     return requests[keep]
+
+
+# ---- the sliding window ----------------------------------------------------------------------------------------------------------------
+TRIM_KEPT, TRIM_ANCHORED, TRIM_KEPT_ON_FIRST, TRIM_REVERSE, TRIM_FIXED = 0, 1, 2, 3, 4
+
+
+def trim_classes(i, j, first):
+    """What aloam_graph_trim does with an edge (i, j) when node `first` > 0 becomes node 0, as TRIM_* codes, the rules in the header's order:
+    1 j > f and (i >= f or i == -1): kept;  2 j > f and 0 <= i < f: anchored;  3 i > f and j == f: kept;  4 i > f and 0 <= j < f: removed, a
+    reverse edge;  5 everything else touches no node above f: removed, a constant."""
+    i, j, f = np.asarray(i, np.int64), np.asarray(j, np.int64), int(first)
+    code = np.full(i.shape, TRIM_FIXED, np.int32)
+    code[(i > f) & (j >= 0) & (j < f)] = TRIM_REVERSE
+    code[(i > f) & (j == f)] = TRIM_KEPT_ON_FIRST
+    code[(j > f) & (i >= 0) & (i < f)] = TRIM_ANCHORED
+    code[(j > f) & ((i >= f) | (i == -1))] = TRIM_KEPT
+    return code
+
+
+def trim(nodes, edges, first):
+    """aloam_graph_trim restated (include/aloam_mi355x.h, "trimming a graph in place"): nodes [0, first) are dropped, old node
+    n >= first becomes node n - first as a bit copy, and the edges are compacted in their stored order - kept ones with their indices shifted,
+    the ones from a dropped node i to a kept node j turned into anchors with Z' = X_opt[i] o Z (compose, operation by operation; stored as
+    computed), info and flags copied.  The dropped nodes and node `first` are conditioned on at their estimates, not marginalised.
+    first = 0 changes nothing.  Returns (nodes', edges', stats) with stats = [nodes', edges', anchored, removed_fixed, removed_reverse]."""
+    nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
+    edges = np.ascontiguousarray(edges, EDGE_DTYPE)
+    f = int(first)
+    assert 0 <= f < len(nodes), "0 <= first < nodes"
+    if f == 0:
+        return nodes.copy(), edges.copy(), np.array([len(nodes), len(edges), 0, 0, 0], np.int64)
+    code = trim_classes(edges["i"], edges["j"], f)
+    keep = code <= TRIM_KEPT_ON_FIRST
+    out = edges[keep].copy()
+    anchored = code[keep] == TRIM_ANCHORED
+    out["i"] = np.where(anchored | (out["i"] < 0), -1, out["i"] - f)
+    out["j"] -= f
+    src = edges[code == TRIM_ANCHORED]
+    if len(src):
+        qz, tz = compose(nodes["q_opt"][src["i"]], nodes["t_opt"][src["i"]], src["q"], src["t"])
+        q, t = out["q"], out["t"]
+        q[anchored], t[anchored] = qz, tz
+        out["q"], out["t"] = q, t
+    stats = np.array([len(nodes) - f, len(out), int(anchored.sum()), int((code == TRIM_FIXED).sum()), int((code == TRIM_REVERSE).sum())], np.int64)
+    return nodes[f:].copy(), out, stats
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------------

@@ -1228,6 +1228,47 @@ int aloam_graph_propose_loops(aloam_ctx* ctx, const int* queries /* [n][2]: seq,
                               double radius_m, double growth_m_per_node, int min_gap, int half_window, int separation, int K,
                               aloam_graph_loop_request* dst /* [n][K] */, int* counts /* [n] */, double* dist2 /* [n][K] or NULL */);
 
+/* ---- trimming a graph in place: a sliding window over the keyframes -------------------------------------------------------------------------
+ * The rows of aloam_graph_enable and aloam_graph_keyframes_enable are fixed; when they fill, aloam_graph_add_nodes returns ALOAM_E_CAPACITY or
+ * keeps the node without clouds, and aloam_graph_clear throws the whole graph away.  aloam_graph_trim drops the oldest nodes of the listed
+ * sequences on the device, compacts the node, edge, descriptor and point rows in place, and turns every constraint from a dropped node to a
+ * kept one into an anchor edge with the same residual.  Everything behind it - the solves, the marginals, the proposal, the registration,
+ * aloam_graph_export_map, aloam_graph_apply, aloam_graph_save / aloam_graph_load and the next aloam_graph_add_nodes - runs on the trimmed
+ * graph unchanged: anchors (i = -1) and a fixed node 0 exist in every kernel.  Opt-in and beside the reference: a context that never calls
+ * it allocates nothing for it and launches exactly what it launched before.  a-loam_amd/posegraph.py restates the definition as trim(),
+ * a-loam_amd/graph_records.py the keyframe store's part as trim_keyframes(); the device reproduces them byte for byte.  DESIGN.md §7x.
+ *
+ * Definition, for one listed sequence; f = first[k] is the old index of the node that becomes node 0.
+ *   Nodes.  Nodes [0, f) are dropped.  Old node n >= f becomes node n - f, a bit copy of its 128 bytes: entered pose, estimate, frame.  New
+ *     node 0 (old f) is the node every solver holds fixed.  The trim conditions on the dropped nodes and on node f at their current
+ *     estimates; it does not marginalise them: no dense prior among the kept nodes is formed, and what the dropped nodes' uncertainty would
+ *     have added to the kept ones is not carried over.  Solve before trimming.
+ *   Edges, in their stored order (a stable compaction), the first rule that applies:
+ *     1. j > f and (i >= f or i == -1): kept.  i' = i - f (or -1), j' = j - f; Z, info and flags are bit copies.
+ *     2. j > f and 0 <= i < f: anchored.  i' = -1, j' = j - f, Z' = X_opt[i] o Z, computed as (quat_mul(q_opt_i, q_Z),
+ *        quat_rotate(q_opt_i, t_Z) + t_opt_i), every f64 operation rounded on its own; the result is stored as computed, not renormalised.
+ *        info and flags are bit copies.  With X_i the identity, E = Z'^-1 o X_j is the old Z^-1 o X_i^-1 o X_j: residual, tangent, Huber
+ *        weight and information are unchanged.
+ *     3. i > f and j == f: kept, i' = i - f, j' = 0.
+ *     4. i > f and 0 <= j < f: removed and counted as removed_reverse; no exact anchor form exists for it.  aloam_graph_add_nodes and
+ *        aloam_graph_propose_loops only ever produce i < j.
+ *     5. Everything else touches no node above f and is a constant of the problem: removed and counted as removed_fixed.
+ *   Keyframe store, when enabled, per class: d = desc[f].first[cls] and m = cursor[cls] - d.  Points [d, d + m) move to [0, m); descriptor
+ *     n >= f moves to n - f with first -= d, counts unchanged; the cursor becomes m.  The counters of nodes kept without clouds stay.
+ *
+ * aloam_graph_trim: seqs and first are host memory, read during the call.  out (plain host memory, may be NULL) receives per listed sequence
+ *   {nodes, edges, anchored, removed_fixed, removed_reverse, corner points freed, surf points freed, 0} after the trim.  Checked before
+ *   anything is queued, ALOAM_E_ARG with nothing queued and nothing changed: seqs distinct and in range; 0 <= first[k] < nodes of that
+ *   sequence (host state), so a graph with 0 nodes admits no value; NULL lists with n > 0; n < 0.  first[k] == 0 is allowed and changes
+ *   nothing in that sequence.  ALOAM_E_STATE before aloam_graph_enable.  n = 0 is ALOAM_OK.
+ *   Stream-ordered behind what was queued before; the items go through a pinned staging ring.  The call then SYNCHRONISES the context's
+ *   stream once, behind its kernels, as aloam_graph_export_map does: the edge counts are host state and the host holds no copy of the
+ *   edge endpoints, so it reads back the eight integers per sequence and sets the counts (aloam_graph_info) from them.  Meant to be called
+ *   once per many keyframes, not once per sweep.  What an application wants of the dropped part it takes first, with
+ *   aloam_graph_export_map or aloam_graph_save.  A listed sequence's bytes do not depend on n, on its position in the list or on the other
+ *   sequences; unlisted sequences are untouched.  Timed under the profiling slot pose_graph, with the rows moved as algorithmic bytes. */
+int aloam_graph_trim(aloam_ctx* ctx, const int* seqs, const int* first, int n, int* out /* [n][8] or NULL */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

@@ -2,7 +2,7 @@
 edge inside a drive").
 
     python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]] [--false-loops K] [--resume-at K]
-                                         [--device-loops --proximity RADIUS]
+                                         [--device-loops --proximity RADIUS] [--window N [--proximity RADIUS]]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -46,6 +46,12 @@ With --resume-at K nothing of the above runs: the drive alone, and when keyframe
 of slot 0 (aloam_save_sequences, aloam_graph_save) are written to a temporary file, read back and loaded into a fresh context
 (aloam_load_sequences, aloam_graph_load).  Both contexts then drive on over the same sweeps.  Printed: the bytes of the two records, and
 whether the final nodes, edges and the tiles and points of the map at the entered poses are byte-equal.
+
+With --window N nothing of the above runs either: the drive twice over the same sweeps, in two contexts.  Both propose a loop candidate from
+the graph at every keyframe (--proximity metres, default 3; --gap, --neighbours), register it on the device, enter the edge and solve.  One
+keeps every keyframe; the other, once it holds more than N, exports the map tiles of the nodes about to go, trims to N (aloam_graph_trim)
+and drives on.  Printed: the ATE over all keyframes of both (a dropped keyframe counts where it was when it left), the loops entered, what
+the window holds at the end, the last trim's eight integers, the tiles and points exported on the way.
 """
 from __future__ import annotations
 
@@ -96,8 +102,12 @@ def main():
                     "after aloam_graph_optimize and after aloam_graph_optimize_robust, with the weights")
     ap.add_argument("--apply", action="store_true", help="carry the solve into the live state (aloam_graph_apply) and drive on for a quarter lap, beside a run that does not")
     ap.add_argument("--resume-at", type=int, default=None, metavar="K", help="only drive: at keyframe K save the sequence record and the graph record to a temporary file, load both into a fresh context, drive on in both and compare")
+    ap.add_argument("--window", type=int, default=None, metavar="N", help="only drive, twice: one graph keeps every keyframe, the other is trimmed to N (aloam_graph_trim) once it holds more, the map "
+                    "tiles of the nodes about to go exported first; loops are proposed by proximity and registered on the device in both; prints the two ATEs")
     args = ap.parse_args()
-    if args.proximity is not None and not (args.device_loops and 0 <= args.neighbours < args.gap):
+    if args.window is not None and not (args.window >= 1 and 0 <= args.neighbours < args.gap):
+        ap.error("--window needs N >= 1 and --neighbours below --gap")
+    if args.window is None and args.proximity is not None and not (args.device_loops and 0 <= args.neighbours < args.gap):
         ap.error("--proximity needs --device-loops and --neighbours below --gap")
 
     import torch
@@ -122,6 +132,9 @@ def main():
     mods = (torch, binding, pg, places, reloc, syn, model)
     if args.resume_at is not None:
         print(json.dumps(resume(args, mods, scans, frames, every)))
+        return
+    if args.window is not None:
+        print(json.dumps(window(args, mods, scans, q_true, t_true, frames, every)))
         return
     if not args.apply:
         print(json.dumps(drive(args, mods, scans, q_true, t_true, frames, 0, every, False)))
@@ -180,6 +193,77 @@ def resume(args, mods, scans, frames, every):
         out["byte_equal"] = same
         out["map"] = {"tiles": len(ma[0]), "points": len(ma[1])}
     for g in ctx:
+        g.close()
+    return out
+
+
+def window(args, mods, scans, q_true, t_true, frames, every):
+    """Two drives over the same sweeps, slot 0 of a context each: `whole` keeps every keyframe, `window` holds at most --window of them.  In
+    both, every new keyframe asks the graph for a loop candidate (aloam_graph_propose_loops), registers the first one that is not next to an
+    edge already entered (aloam_graph_register_loops), enters the edge and solves.  When `window` holds more than N keyframes, the map tiles
+    of the nodes about to go are exported at their estimates (aloam_graph_export_map), their positions are kept for the trajectory, and the
+    graph is trimmed to N (aloam_graph_trim).  The ATE of each run is over all keyframes: dropped ones where they were when they left."""
+    torch, binding, pg, places, reloc, syn, model = mods
+    lr = importlib.import_module("a-loam_amd.loopreg")
+    nan_row = np.full((1, 4), np.nan, np.float32)
+    n_key = (frames + every - 1) // every + 1
+    info = np.diag([1.0 / 5e-3 ** 2] * 3 + [1.0 / 5e-2 ** 2] * 3)
+    radius = 3.0 if args.proximity is None else args.proximity
+    span = 2 * args.neighbours + 1
+
+    def make():
+        g = binding.Aloam(n_scans=16, min_range=model.min_range, batch=2, max_points=max(len(s) for s in scans) + 64)
+        g.mapping_enable(0.4, 0.8, pool_points=1 << 17)
+        g.graph_enable(n_key + 4, 2 * n_key + 8)
+        g.graph_keyframes_enable(n_key * 2048, n_key * 16384)
+        g.graph_loops_enable(1, span * 2048, span * 16384)
+        g.set_active([1, 0])
+        return g
+    runs = {name: {"gpu": make(), "limit": limit, "base": 0, "left": [], "pairs": [], "loops": 0, "trims": [], "tiles": 0, "points": 0}
+            for name, limit in (("whole", None), ("window", args.window))}
+    key_frames = []
+    for k in range(frames):
+        key = k % every == 0 or k == frames - 1
+        if key:
+            key_frames.append(k)
+        for run in runs.values():
+            g = run["gpu"]
+            g.scan_register([scans[k], nan_row], check=False)
+            g.odometry_step()
+            g.mapping_step()
+            if not key:
+                continue
+            g.graph_add_nodes([0], info)
+            j = g.graph_info(0)["nodes"] - 1
+            if j >= args.gap:
+                prop, count, _ = g.graph_propose_loops([(0, j)], radius_m=radius, min_gap=args.gap, half_window=args.neighbours, separation=args.neighbours, K=1)
+                fresh = pg.unclosed(prop[0][:count[0]], np.array(run["pairs"], np.int64).reshape(-1, 2), args.neighbours)
+                if len(fresh):
+                    c = fresh[0]
+                    r = g.graph_register_loops([(0, int(c["i"]), j, int(c["first"]), int(c["count"]), binding.GRAPH_POSE_OPTIMIZED, c["q"].copy(), c["t"].copy())])[0]
+                    edge = lr.edge_from_result(r, 0, int(c["i"]), j, robust=False)
+                    if edge is not None:
+                        g.graph_add_edges(edge)
+                        g.graph_optimize([0])
+                        run["pairs"].append((int(c["i"]), j))
+                        run["loops"] += 1
+            held = j + 1
+            if run["limit"] is not None and held > run["limit"]:
+                drop = held - run["limit"]
+                run["left"].append(g.graph_export(0, 0, drop)["t_opt"].copy())
+                tiles, pts, _, _ = g.graph_export_map([(0, 0, drop, binding.GRAPH_POSE_OPTIMIZED)], pinned=False)
+                run["tiles"] += len(tiles); run["points"] += len(pts)
+                run["trims"].append(g.graph_trim([0], [drop])[0].tolist())
+                run["base"] += drop
+                run["pairs"] = [(a - drop, b - drop) for a, b in run["pairs"] if a >= drop]   # an edge from a dropped node is an anchor now
+    truth_t = t_true[key_frames]
+    out = {"frames": frames, "keyframes": len(key_frames), "window": args.window, "proximity_m": radius}
+    for name, run in runs.items():
+        g = run["gpu"]
+        t = np.concatenate(run["left"] + [g.graph_export(0)["t_opt"]])
+        i = g.graph_info(0)
+        out[name] = {"nodes_held": i["nodes"], "edges_held": i["edges"], "loops_entered": run["loops"], "ate_m": pg.ate(t, truth_t), "trims": len(run["trims"]),
+                     "last_trim": run["trims"][-1] if run["trims"] else None, "tiles_exported": run["tiles"], "points_exported": run["points"]}
         g.close()
     return out
 
