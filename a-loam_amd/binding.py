@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 
 from .records import *  # noqa: F401,F403  the records, their dtypes and the enumerators of the header: declared there, used under these names
+from .joint_records import AloamGraphJointGroup, AloamGraphLink, GRAPH_JOINT_GROUP_DTYPE, GRAPH_LINK_DTYPE  # noqa: F401  the records of the joined graphs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -165,6 +166,11 @@ def lib():
             L.aloam_graph_propose_loops.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
         if hasattr(L, "aloam_graph_trim"):                 # likewise
             L.aloam_graph_trim.argtypes = [vp, vp, vp, C.c_int, vp]
+        if hasattr(L, "aloam_graph_optimize_joint"):       # likewise
+            L.aloam_graph_optimize_joint.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(AloamGraphOptions), vp]
+            L.aloam_graph_optimize_joint_robust.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(AloamGraphOptions),
+                                                            C.POINTER(AloamGraphRobustOptions), vp, vp, C.c_longlong]
+            L.aloam_graph_joint_export.argtypes = [vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp]
         L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -867,6 +873,65 @@ class Aloam:
         out = np.zeros((len(ids), 8), np.int32)
         self._check(lib().aloam_graph_trim(self.h, _ids_arg(ids), _p(f) if len(ids) else None, len(ids), _p(out) if len(ids) else None))
         return out
+
+    # ---- joined graphs: links between sequences and a joint solve (posegraph.join / optimize_joint hold the definition) ---------------------
+    @staticmethod
+    def joint_lists(groups):
+        """The four host lists of a joint call from groups = [(members, links) or (members, links, align), ...]: members int32, align int32,
+        links (GRAPH_LINK_DTYPE), groups (GRAPH_JOINT_GROUP_DTYPE)."""
+        members, align, links, n_links, recs = [], [], [], 0, np.zeros(len(groups), GRAPH_JOINT_GROUP_DTYPE)
+        for g, group in enumerate(groups):
+            m, l = group[0], np.ascontiguousarray(group[1] if group[1] is not None else [], dtype=GRAPH_LINK_DTYPE).reshape(-1)
+            a = group[2] if len(group) > 2 and group[2] is not None else [0] * len(m)
+            recs[g] = (len(members), len(m), n_links, len(l))
+            members += [int(v) for v in m]; align += [int(v) for v in a]; links.append(l)
+            n_links += len(l)
+        links = np.concatenate(links) if links else np.zeros(0, GRAPH_LINK_DTYPE)
+        return np.array(members, np.int32), np.array(align, np.int32), np.ascontiguousarray(links), recs
+
+    def graph_optimize_joint_into(self, groups, dst_ptr, options=None, robust=None, weights_ptr=0, weights_stride=0, robust_call=False):
+        """Queue the joint solve of every group (no host synchronisation; groups as for graph_optimize_joint, or the tuple joint_lists
+        made of them, for a caller that repeats a call): dst_ptr receives one aloam_graph_result per group - with
+        robust_call one aloam_graph_robust_result, and weights_ptr (or 0) one row of weights_stride doubles; device or pinned memory."""
+        m, a, l, g = groups if isinstance(groups, tuple) else self.joint_lists(groups)      # (a tuple: the four lists, built once by joint_lists)
+        lists = (_p(m) if len(m) else None, _p(a) if len(a) else None, len(m), _p(l) if len(l) else None, len(l), _p(g) if len(g) else None, len(g))
+        opt = C.byref(options) if options is not None else None
+        if robust_call:
+            self._check(lib().aloam_graph_optimize_joint_robust(self.h, *lists, opt, C.byref(robust) if robust is not None else None, _vp(dst_ptr),
+                                                                _vp(weights_ptr), int(weights_stride)))
+        else:
+            self._check(lib().aloam_graph_optimize_joint(self.h, *lists, opt, _vp(dst_ptr)))
+
+    def graph_optimize_joint(self, groups, pinned=True, **options):
+        """Join, solve, write back and wait: a structured array [len(groups)] of GRAPH_RESULT_DTYPE.  groups = [(members, links) or
+        (members, links, align), ...]; keyword arguments are fields of aloam_graph_options."""
+        buf = _out_bytes(len(groups), GRAPH_RESULT_DTYPE, pinned)
+        self.graph_optimize_joint_into(groups, buf.data_ptr(), self.graph_options(**options))
+        self.synchronize()
+        return _records(buf, len(groups), GRAPH_RESULT_DTYPE)
+
+    def graph_optimize_joint_robust(self, groups, robust=None, pinned=True, weights_stride=None, sentinel=np.nan, **options):
+        """The same with the robust solve: (a structured array [len(groups)] of GRAPH_ROBUST_RESULT_DTYPE, the weights
+        [len(groups), weights_stride]: one per joined edge - the members' edges in member order, then the links - and `sentinel` behind them)."""
+        import torch
+        if isinstance(robust, dict):
+            robust = self.graph_robust_options(**robust)
+        n = len(groups)
+        if weights_stride is None:
+            weights_stride = max([sum(self.graph_info(int(b))["edges"] for b in g[0]) + (len(g[1]) if g[1] is not None else 0) for g in groups] + [1])
+        buf = _out_bytes(n, GRAPH_ROBUST_RESULT_DTYPE, pinned)
+        wts = torch.full((max(1, n), int(weights_stride)), float(sentinel), dtype=torch.float64, **_where(pinned))
+        self.graph_optimize_joint_into(groups, buf.data_ptr(), self.graph_options(**options), robust, wts.data_ptr(), weights_stride, robust_call=True)
+        self.synchronize()
+        return _records(buf, n, GRAPH_ROBUST_RESULT_DTYPE), wts.cpu().numpy()[:n].copy()
+
+    def graph_joint_export(self, group):
+        """The joined rows of one group of the last joint call (synchronises): (nodes, edges, counts = [nodes, edges, member edges, links])."""
+        counts = np.zeros(4, np.int32)
+        self._check(lib().aloam_graph_joint_export(self.h, int(group), None, 0, None, 0, _p(counts)))
+        nodes, edges = np.zeros(max(1, counts[0]), GRAPH_NODE_DTYPE), np.zeros(max(1, counts[1]), GRAPH_EDGE_DTYPE)
+        self._check(lib().aloam_graph_joint_export(self.h, int(group), _p(nodes), len(nodes), _p(edges), len(edges), _p(counts)))
+        return nodes[:counts[0]], edges[:counts[1]], counts
 
     # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
     def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

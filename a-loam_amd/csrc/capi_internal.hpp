@@ -1,7 +1,7 @@
 // a-loam_amd/csrc/capi_internal.hpp — what the host files of libaloam_mi355x.so share: the context and the owners of its buffers, the
 // error and scope guards, and the helpers that more than one of them calls.  The host side is split by stage like the kernels:
 // aloam_capi.hip (context, staging of input counts, lifecycle, profiling), capi_odometry.hip (registration, odometry, the sequence getters and
-// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphpropose.hip (loop candidates by pose proximity), capi_graphtrim.hip (pose graphs trimmed in place), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
+// setters), capi_mapping.hip (scan-to-map refinement and its pools), capi_records.hip (batched export, sequence records), capi_information.hip (pose information), capi_posegraph.hip (pose graphs), capi_graphmap.hip (keyframe clouds, the map at the graph's poses), capi_graphapply.hip (a solved graph carried into the live state), capi_loopreg.hip (loop edges: batched keyframe registration), capi_graphmarginal.hip (pose-graph marginals), capi_graphpropose.hip (loop candidates by pose proximity), capi_graphtrim.hip (pose graphs trimmed in place), capi_graphjoint.hip (joined pose graphs: links between sequences and a joint solve), capi_graphrecords.hip (graph records: save / load of pose graphs with their keyframe clouds), capi_relocalize.hip (map-pose hypotheses), capi_atlas.hip (map spill and atlas),
 // capi_places.hip (place recognition), capi_range.hip (range-image input), capi_seq.hip (what the host knows about each sequence, SeqHost: the events that change it, the stage masks).
 // Stated once here for all of them: the pinned staging ring (StageRing), a scratch buffer with its capacity (Scratch), and one struct per
 // graph-family feature (GraphStore ... MarginalScratch) that its enable builds fresh and commits with one move, as MapPool.
@@ -21,6 +21,7 @@
 #include "checkpoint_kernels.hpp"
 #include "export_kernels.hpp"
 #include "graphapply_kernels.hpp"
+#include "graphjoint_kernels.hpp"
 #include "graphmap_kernels.hpp"
 #include "graphmarginal_kernels.hpp"
 #include "graphpropose_kernels.hpp"
@@ -196,6 +197,15 @@ struct TrimScratch {                 // pose graphs trimmed in place (aloam_grap
   StageRing<kTrimStageSlots> ring;                                  // a slot holds B items
   PinnedBuf<int> h_out; int* d_out = nullptr;                       // [B][kTrimRecordInts] what k_graph_trim reports (pinned, mapped)
 };
+struct JointScratch {                // joined pose graphs (aloam_graph_optimize_joint): nothing is allocated before the first call; used in stream order
+  StageRing<kJointStageSlots> ring;                                 // a slot holds one call's items, groups, members and links, back to back
+  size_t slot_bytes = 0;                                            // what a slot holds; a call that needs more waits for the stream and builds a larger ring
+  Scratch<char> staged;                                             // the device copy of one call's slot
+  Scratch<aloam_graph_node> nodes;                                  // [n_groups][row_nodes] the joined node rows
+  Scratch<aloam_graph_edge> edges;                                  // [n_groups][row_edges] the joined edge rows
+  int row_nodes = 0, row_edges = 0;                                 // the rows' strides as the last call laid them out
+  std::vector<JointGroup> last;                                     // the last call's groups (aloam_graph_joint_export)
+};
 
 struct GraphRecordScratch {          // graph records (aloam_graph_save / aloam_graph_load): sized for `batch` records on first use, used in stream order
   DevBuf<GraphRecItem> items;                                       // [B] the records of one call
@@ -338,6 +348,7 @@ struct aloam_ctx {
   MarginalScratch mg;
   ProposeScratch pp;
   TrimScratch tr;
+  JointScratch jt;
   GraphRecordScratch gr;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;

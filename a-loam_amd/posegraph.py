@@ -12,13 +12,15 @@ A pose X = (q, t) maps a point of the node's frame into the frame the graph live
 Everything here is float64 numpy on the host: the definition the device is tested against, a dense Levenberg-Marquardt reference
 (optimize), the chain-preconditioned conjugate gradients of the device restated (chain_pcg), the robust solve over the flagged edges
 (optimize_robust: GNC-TLS), the two lines of algebra that turn a relocalized pose into an edge, the loop proposal by pose proximity
-(propose_loops), the sliding window (trim: aloam_graph_trim restated), and the fixture generators of the tests (drifted_laps, false_loops).
+(propose_loops), the sliding window (trim: aloam_graph_trim restated), the joined graphs of several sequences (join, align_member, split,
+optimize_joint: aloam_graph_optimize_joint restated), and the fixture generators of the tests (drifted_laps, false_loops, cut_drive).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .records import GRAPH_EDGE_DTYPE as EDGE_DTYPE, GRAPH_MARGINAL_REQUEST_DTYPE as MARGINAL_REQUEST_DTYPE, GRAPH_NODE_DTYPE as NODE_DTYPE
+from .joint_records import GRAPH_LINK_DTYPE as LINK_DTYPE
 from .records import GRAPH_LOOP_REQUEST_DTYPE as LOOP_REQUEST_DTYPE, GRAPH_POSE_ENTERED as POSE_ENTERED, GRAPH_POSE_OPTIMIZED as POSE_OPTIMIZED
 
 EDGE_ROBUST = 1
@@ -711,6 +713,133 @@ def trim(nodes, edges, first):
     return nodes[f:].copy(), out, stats
 
 
+# ---- joined graphs: links between sequences and a joint solve ---------------------------------------------------------
+def make_links(seq_i, i, seq_j, j, q, t, info, robust=False):
+    """A structured array of LINK_DTYPE: node j of seq_j measured in the frame of node i of seq_i; info as make_edges takes it."""
+    i = np.atleast_1d(np.asarray(i, np.int32))
+    l = np.zeros(len(i), LINK_DTYPE)
+    info = np.asarray(info, np.float64)
+    if info.shape[-1] == 6:
+        info = info_upper(info)
+    l["seq_i"], l["i"], l["seq_j"], l["j"], l["q"], l["t"], l["info"] = seq_i, i, seq_j, j, q, t, info
+    l["flags"] = np.where(np.broadcast_to(robust, i.shape), EDGE_ROBUST, 0)
+    return l
+
+
+def stored_q(q):
+    """A measurement's rotation as the C ABI stores it (aloam_graph_add_edges, the links of a joint call): divided by its norm, the
+    squares summed in index order."""
+    q = np.asarray(q, np.float64)
+    nn = np.zeros(q.shape[:-1])
+    for a in range(4):
+        nn = nn + q[..., a] * q[..., a]
+    return q / np.sqrt(nn)[..., None]
+
+
+def tree_links(seqs, links):
+    """Per member of a group (its sequences `seqs` in member order) the index of its tree link in `links`, -1 for the first member: the
+    first link, in list order, that joins the member to a member earlier in the list."""
+    at = {int(s): m for m, s in enumerate(seqs)}
+    tree = np.full(len(seqs), -1, np.int64)
+    for k, l in enumerate(links):
+        later = max(at[int(l["seq_i"])], at[int(l["seq_j"])])
+        if tree[later] < 0:
+            tree[later] = k
+    assert (tree[1:] >= 0).all(), "every member after the first needs a link to an earlier member"
+    return tree
+
+
+def align_member(nodes, edges, q_g, t_g, link, own, seq_i_side):
+    """A member that is still in its own frame, moved into its group's: (q_g, t_g) is the estimate Xg of the tree link's node in the earlier
+    member as placed in the joined row, `link` the tree link, `own` the member's node of it, `seq_i_side` true when the member is the link's
+    seq_i side.  A = (Xg o Z) o X[own]^-1, with Z inverted first for the seq_i side; compose and inverse operation by operation, then q_A divided
+    by its norm (stored_q); nothing else is renormalised.  Every (q_opt, t_opt) becomes A o X_opt and every anchor A o Z; q, t, frame, relative edges, info and flags are untouched.
+    Returns (nodes', edges', (q_A, t_A))."""
+    nodes, edges = np.array(nodes, NODE_DTYPE), np.array(edges, EDGE_DTYPE)
+    qz, tz = np.array(link["q"], np.float64), np.array(link["t"], np.float64)
+    if seq_i_side:
+        qz, tz = inverse(qz, tz)
+    qa, ta = compose(*compose(q_g, t_g, qz, tz), *inverse(nodes["q_opt"][own], nodes["t_opt"][own]))
+    qa = stored_q(qa)                                  # a rigid transform whatever the norms of the chained estimates it is built from
+    nodes["q_opt"], nodes["t_opt"] = compose(qa, ta, nodes["q_opt"], nodes["t_opt"])
+    anchor = edges["i"] < 0
+    if anchor.any():
+        q, t = edges["q"], edges["t"]
+        q[anchor], t[anchor] = compose(qa, ta, q[anchor], t[anchor])
+        edges["q"], edges["t"] = q, t
+    return nodes, edges, (qa, ta)
+
+
+def join(members, links, seqs=None, align=None):
+    """The joined graph of one group (include/aloam_mi355x.h, "joined graphs").  members: [(nodes, edges), ...] in member order; links:
+    LINK_DTYPE records whose seq_i / seq_j name members by `seqs` (the members' sequence indices; their positions by default); align: per
+    member, non-zero for one that is still in its own frame (never the first).
+      nodes: the members' rows end to end, bit copies; off[m] = the nodes of the members before m.
+      edges: every member's edges in member order and stored order, i >= 0 and j shifted by off[m], anchors keep i = -1, seq and the rest
+             bit copies; then the links in list order as (off[seq_i] + i, off[seq_j] + j, Z, info, flags) with seq = seq_i, q of Z as
+             stored_q makes it (the call checks a link like aloam_graph_add_edges checks an edge and stores q normalised).
+    An aligned member goes through align_member with Xg read from the rows joined so far, so chains of new members work.
+    Returns (nodes, edges, off) with off of length members + 1."""
+    seqs = list(range(len(members))) if seqs is None else [int(s) for s in seqs]
+    at = {s: m for m, s in enumerate(seqs)}
+    links = np.array(links, LINK_DTYPE)
+    links["q"] = stored_q(links["q"]) if len(links) else links["q"]
+    align = np.zeros(len(members), np.int32) if align is None else np.asarray(align, np.int32)
+    assert len(at) == len(members) and not align[0], "distinct members; the first member defines the frame"
+    off = np.concatenate([[0], np.cumsum([len(n) for n, _ in members])]).astype(np.int64)
+    tree = tree_links(seqs, links) if len(members) > 1 else np.full(1, -1, np.int64)
+    out_n, out_e = np.zeros(off[-1], NODE_DTYPE), []
+    for m, (nodes, edges) in enumerate(members):
+        nodes, edges = np.ascontiguousarray(nodes, NODE_DTYPE), np.ascontiguousarray(edges, EDGE_DTYPE).copy()
+        if align[m]:
+            l = links[tree[m]]
+            inv = at[int(l["seq_i"])] == m
+            other = off[at[int(l["seq_j"])]] + int(l["j"]) if inv else off[at[int(l["seq_i"])]] + int(l["i"])
+            nodes, edges, _ = align_member(nodes, edges, out_n["q_opt"][other], out_n["t_opt"][other], l, int(l["i"]) if inv else int(l["j"]), inv)
+        out_n[off[m]:off[m + 1]] = nodes
+        edges["i"] = np.where(edges["i"] >= 0, edges["i"] + off[m], edges["i"])
+        edges["j"] += off[m]
+        out_e.append(edges)
+    tail = np.zeros(len(links), EDGE_DTYPE)
+    for k, l in enumerate(links):
+        tail[k] = (l["seq_i"], off[at[int(l["seq_i"])]] + l["i"], off[at[int(l["seq_j"])]] + l["j"], l["flags"], l["q"], l["t"], l["info"])
+    return out_n, np.concatenate(out_e + [tail]), off
+
+
+def split(members, nodes, edges, off, align=None):
+    """The write-back of a joint solve: every member's q_opt / t_opt are the joined row's; an aligned member's anchors take the joined
+    row's Z'.  Everything else of a member is what it was.  Returns [(nodes, edges), ...]."""
+    align = np.zeros(len(members), np.int32) if align is None else np.asarray(align, np.int32)
+    out, e0 = [], 0
+    for m, (n, e) in enumerate(members):
+        n, e = np.array(n, NODE_DTYPE), np.array(e, EDGE_DTYPE)
+        n["q_opt"], n["t_opt"] = nodes["q_opt"][off[m]:off[m + 1]], nodes["t_opt"][off[m]:off[m + 1]]
+        if align[m]:
+            je = edges[e0:e0 + len(e)]
+            anchor = e["i"] < 0
+            q, t = e["q"], e["t"]
+            q[anchor], t[anchor] = je["q"][anchor], je["t"][anchor]
+            e["q"], e["t"] = q, t
+        e0 += len(e)
+        out.append((n, e))
+    return out
+
+
+def optimize_joint(members, links, seqs=None, align=None, robust=None, solve=None, **options):
+    """aloam_graph_optimize_joint (robust = None) / aloam_graph_optimize_joint_robust (robust = a dict of optimize_robust's options)
+    restated for one group: join, optimize or optimize_robust on the joined graph (its node 0 fixed), split.  With a joined graph of fewer
+    than two nodes or no edge nothing is written back.  Returns ([(nodes, edges), ...], the result dict, (joined nodes, joined edges))."""
+    nodes, edges, off = join(members, links, seqs, align)
+    if robust is None:
+        q, t, res = optimize(nodes["q_opt"], nodes["t_opt"], edges, solve=solve, **options)
+    else:
+        q, t, res = optimize_robust(nodes["q_opt"], nodes["t_opt"], edges, solve=solve, **dict(options, **robust))
+    if res["status"] == 1:
+        return [(np.array(n, NODE_DTYPE), np.array(e, EDGE_DTYPE)) for n, e in members], res, (nodes, edges)
+    nodes["q_opt"], nodes["t_opt"] = q, t
+    return split(members, nodes, edges, off, align), res, (nodes, edges)
+
+
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------------
 def drifted_laps(seed, nodes, loops, radius=10.0, per_lap=None, sigma_theta=5e-3, sigma_t=5e-2, yaw_bias=1.5e-3, noise=1.0):
     """Ground-truth laps of a circle (with a slow climb), odometry edges with seeded noise and a yaw bias, `loops` loop edges between
@@ -761,6 +890,35 @@ def false_loops(g, n, seed):
     tz = tz + rng.uniform(-8, 8, (n, 3))
     qz = qmul(qz, qexp(rng.uniform(-0.5, 0.5, (n, 3))))
     return make_edges(0, fi, fj, qz, tz, g["info"], robust=True)
+
+
+def graph_nodes(q, t, q_opt=None, t_opt=None, frame=-1):
+    """NODE_DTYPE records with the entered poses (q, t) and the estimates (the entered poses by default)."""
+    n = np.zeros(len(q), NODE_DTYPE)
+    n["q"], n["t"], n["q_opt"], n["t_opt"], n["frame"] = q, t, q if q_opt is None else q_opt, t if t_opt is None else t_opt, frame
+    return n
+
+
+def cut_drive(g, c, frame, seqs=(0, 1)):
+    """The graph g of drifted_laps cut at node c into two sessions: nodes [0, c) with the edges among them, and nodes [c, N) renumbered
+    from 0 and expressed in another rigid frame, X' = F o X with F = frame = (q_F, t_F).  The edges that cross the cut become links, the
+    cut odometry edge (c - 1, c) first, then the others in their order.  Returns dict(members = [(nodes, edges)] * 2, links,
+    whole = (nodes, edges) of the uncut graph, seqs)."""
+    edges = np.concatenate([g["odom"], g["loop"]])
+    i, j = edges["i"], edges["j"]
+    first, second = edges[(i < c) & (j < c)].copy(), edges[(i >= c) & (j >= c)].copy()
+    second["i"] -= c; second["j"] -= c
+    first["seq"], second["seq"] = seqs
+    cross = np.flatnonzero((i < c) != (j < c))
+    cut = [k for k in cross if (i[k], j[k]) == (c - 1, c)]
+    x = edges[np.array(cut + [k for k in cross if k not in cut], np.int64)]
+    low = x["i"] < c
+    links = make_links(np.where(low, seqs[0], seqs[1]), np.where(low, x["i"], x["i"] - c), np.where(x["j"] < c, seqs[0], seqs[1]),
+                       np.where(x["j"] < c, x["j"], x["j"] - c), x["q"], x["t"], x["info"], x["flags"] != 0)
+    qf, tf = np.asarray(frame[0], np.float64), np.asarray(frame[1], np.float64)
+    q2, t2 = compose(qf, tf, g["q"][c:], g["t"][c:])
+    return dict(members=[(graph_nodes(g["q"][:c], g["t"][:c]), first), (graph_nodes(q2, t2), second)], links=links,
+                whole=(graph_nodes(g["q"], g["t"]), edges), seqs=tuple(seqs))
 
 
 def apply_correction(q, t, q_opt, t_opt, live):

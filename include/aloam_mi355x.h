@@ -1269,6 +1269,81 @@ int aloam_graph_propose_loops(aloam_ctx* ctx, const int* queries /* [n][2]: seq,
  *   sequences; unlisted sequences are untouched.  Timed under the profiling slot pose_graph, with the rows moved as algorithmic bytes. */
 int aloam_graph_trim(aloam_ctx* ctx, const int* seqs, const int* first, int n, int* out /* [n][8] or NULL */);
 
+/* ---- joined graphs: links between sequences and a joint solve ------------------------------------------------------------------------------
+ * Every call above stops at the boundary of one sequence: an aloam_graph_edge carries one seq, aloam_graph_optimize solves one graph per
+ * workgroup.  This section joins sessions: a link is a measurement between a node of one sequence and a node of another, a group is a set
+ * of sequences (its members) with the links among them, and a joint solve optimises a group as ONE graph in one frame - a fleet on one
+ * site, the same vehicle on different days - so that two sessions correct each other.  The joined graph is laid out in scratch rows and
+ * solved by the kernels of aloam_graph_optimize / aloam_graph_optimize_robust as they are; what is new is the gather, the alignment and the
+ * write-back.  Opt-in and beside the reference: a context that never calls it allocates nothing for it and launches exactly what it launched
+ * before.  a-loam_amd/posegraph.py restates the definition as join(), align_member(), split() and optimize_joint(); DESIGN.md §7y.
+ *
+ * The links are NOT STORED.  The host owns them, as it owns loop requests, and passes them on every call; no record of a sequence changes
+ * shape.  After an aloam_graph_trim of a member at `first` the host shifts its own link indices of that member by -first and drops the
+ * links whose node was dropped.
+ *
+ * The joined graph of a group.
+ *   Nodes: the members' rows laid end to end in member order, as bit copies; off[m] is the sum of the node counts of the members before m.
+ *   Edges, first part: every member's edges in member order and stored order, with i >= 0 shifted by off[m] and j shifted by off[m];
+ *     anchors keep i = -1; seq, Z, info and flags are bit copies.
+ *   Edges, second part: the group's links in list order as edges (off[seq_i] + i, off[seq_j] + j, Z, info, flags) with seq = seq_i.
+ *   This edge order is also the order of weights_dst.
+ *   Joined node 0, which is node 0 of the group's first member, is the fixed one; every other member's node 0 is free.
+ * Alignment.  align[m] != 0 (never for the first member of a group) says that this member's estimates and anchors are still in its own
+ *   frame; it is moved into the group's frame before the solve.  The member's tree link is the first link, in the group's list order, that
+ *   joins it to a member earlier in the group's member list.  If the member is the seq_j side, A = (Xg[seq_i][i] o Z) o X[j]^-1; if it is
+ *   the seq_i side, A = (Xg[seq_j][j] o Z^-1) o X[i]^-1.  X is the member's own estimate, Xg the earlier member's estimate as placed in
+ *   the joined row, so chains of newly joined members work.  compose(a, b) = (quat_mul(q_a, q_b), quat_rotate(q_a, t_b) + t_a) and
+ *   inverse(a) = (q*, -quat_rotate(q*, t)), every f64 operation rounded on its own; q_A is then divided by its norm (the squares summed
+ *   in index order): the estimates it is built from are chained products that nothing renormalises, and A must be a rigid transform.
+ *   Nothing else is renormalised.  Every node's (q_opt, t_opt)
+ *   becomes A o X_opt; every anchor edge of the member becomes Z' = A o Z with residual, information and flags unchanged (a left
+ *   multiplication of both cancels in Z^-1 o X_j); q, t, frame and relative edges are untouched.  Alignment is applied ONCE, when a
+ *   sequence first joins: aligning a member again re-composes its anchors and its estimates with a transform that is then close to, but
+ *   not exactly, the identity.  With align NULL or all zeros the gather is a pure copy.
+ * Write-back.  After the solve every member's q_opt / t_opt are the joined row's, and an aligned member's anchors hold Z' - whatever the
+ *   solve's status, except ALOAM_GRAPH_NO_EDGES (fewer than two joined nodes or no joined edge), where nothing is written.  From then on
+ *   the member's estimates live in the group's frame and the existing calls run on it unchanged: aloam_graph_add_nodes (the next node is
+ *   X_opt[k-1] o Z), aloam_graph_trim, aloam_graph_export_map, aloam_graph_apply, and a solo aloam_graph_optimize.
+ *
+ * aloam_graph_optimize_joint / aloam_graph_optimize_joint_robust: members (sequence indices), align (may be NULL), links and groups are host
+ *   memory, read during the call.  groups[g] = {member_first, member_count, link_first, link_count} indexes members / align and links.
+ *   dst receives one result per group, weights_dst (may be NULL) the final weights of a group's joined edges at
+ *   weights_dst[g * weights_stride + e].  Options and results are those of aloam_graph_optimize / aloam_graph_optimize_robust.
+ *   Checked before anything is queued, ALOAM_E_ARG with nothing queued and nothing changed, the field named in aloam_last_error: members in
+ *   range and distinct over the whole call; the groups tile members and links contiguously and in order; member_count >= 1 and every
+ *   member holds at least one node; align of a group's first member is 0; a link's two sequences are distinct members of the link's own
+ *   group; its node indices lie inside the members' counts; q, t, info, flags by the rules of aloam_graph_add_edges (q is stored
+ *   normalised); every member after the first has a link to an earlier member of its group (the gauge, and the tree link); a group's
+ *   summed nodes do not exceed 2^20 and its summed edges plus links 2^22; the options as for the per-sequence solves; dst and weights_dst
+ *   device memory of the context's device or pinned host memory; weights_stride at least the largest joined edge count; NULL lists;
+ *   negative counts.  ALOAM_E_STATE before aloam_graph_enable.  n_groups = 0 is ALOAM_OK.
+ *   Stream-ordered, no host synchronisation: one pinned staging ring, three launches (gather, the solve, scatter), one workgroup per
+ *   group in the first two, so a group costs what one graph of the summed size costs.  (A call whose lists outgrow the ring, or whose
+ *   groups outgrow the joined rows, waits for the stream once while they are rebuilt.)  Scratch: the joined rows, n_groups x the largest
+ *   group, beside the rows of the solve.  The bits of a group's result and of its members' rows do not depend on the other groups, on the
+ *   group's position or on n_groups; sequences that are no member are untouched.  A group of one member with no links is byte for byte
+ *   aloam_graph_optimize (or aloam_graph_optimize_robust) of that sequence.  Timed under the profiling slot pose_graph. */
+struct aloam_graph_link {                     /* 256 bytes                                                                              */
+  int seq_i, i, seq_j, j;                     /* node j of seq_j measured in the frame of node i of seq_i; seq_i != seq_j               */
+  int flags, pad[3];                          /* 0 or ALOAM_GRAPH_EDGE_ROBUST                                                           */
+  double q[4], t[3];                          /* Z                                                                                      */
+  double info[21];                            /* as aloam_graph_edge.info (right tangent of Z)                                          */
+};
+typedef struct aloam_graph_link aloam_graph_link;
+struct aloam_graph_joint_group {              /* 16 bytes                                                                               */
+  int member_first, member_count, link_first, link_count;
+};
+typedef struct aloam_graph_joint_group aloam_graph_joint_group;
+int aloam_graph_optimize_joint(aloam_ctx* ctx, const int* members, const int* align /* [n_members] or NULL */, int n_members,
+                               const aloam_graph_link* links, int n_links, const aloam_graph_joint_group* groups, int n_groups,
+                               const aloam_graph_options* opt, aloam_graph_result* dst /* [n_groups] */);
+int aloam_graph_optimize_joint_robust(aloam_ctx* ctx, const int* members, const int* align /* [n_members] or NULL */, int n_members,
+                                      const aloam_graph_link* links, int n_links, const aloam_graph_joint_group* groups, int n_groups,
+                                      const aloam_graph_options* opt, const aloam_graph_robust_options* robust,
+                                      aloam_graph_robust_result* dst /* [n_groups] */, double* weights_dst /* [n_groups][weights_stride] or NULL */,
+                                      long long weights_stride);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */
@@ -1287,6 +1362,12 @@ int aloam_get_map_factors(aloam_ctx* ctx, int seq, double* lines, int cap_lines,
  * (request r of a call ran in slot r % max_requests).  Stream-ordered; dst_xyzw and count are classified like the exports' destinations;
  * count is always written, the points only when they fit cap (0 with dst NULL: the size query). */
 int aloam_graph_loop_export_target(aloam_ctx* ctx, int slot, int feature_class, float* dst_xyzw, long long cap, int* count);
+/* The joined rows of group `group` of the last aloam_graph_optimize_joint / aloam_graph_optimize_joint_robust as that call left them: the
+ * nodes with the solved estimates, the edges as gathered.  Synchronises.  nodes_dst and edges_dst are plain host memory and may be NULL;
+ * counts = {nodes, edges, of these the members' edges, links} is always written, a row only when its dst is given and it fits its cap.
+ * ALOAM_E_STATE before the first joint call, ALOAM_E_ARG for a group the last call did not have. */
+int aloam_graph_joint_export(aloam_ctx* ctx, int group, aloam_graph_node* nodes_dst, long long cap_nodes, aloam_graph_edge* edges_dst, long long cap_edges,
+                             int counts[4]);
 
 /* How the ring ids of the clouds the last aloam_odometry_step searched (laserCloudCornerLast, laserCloudSurfLast of that step) are ordered, as
  * found when their kd-tree stand-ins were built (src/laserOdometry.cpp:567-568): 0 = int(intensity) never decreases with the index; 1 = it decreases, but never by more than 2 below an earlier
