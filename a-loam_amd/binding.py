@@ -14,6 +14,7 @@ import numpy as np
 
 from .records import *  # noqa: F401,F403  the records, their dtypes and the enumerators of the header: declared there, used under these names
 from .joint_records import AloamGraphJointGroup, AloamGraphLink, GRAPH_JOINT_GROUP_DTYPE, GRAPH_LINK_DTYPE  # noqa: F401  the records of the joined graphs
+from .link_records import AloamGraphLinkRequest, GRAPH_LINK_REQUEST_DTYPE  # noqa: F401  the record of the links measured on the device
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -171,6 +172,10 @@ def lib():
             L.aloam_graph_optimize_joint_robust.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(AloamGraphOptions),
                                                             C.POINTER(AloamGraphRobustOptions), vp, vp, C.c_longlong]
             L.aloam_graph_joint_export.argtypes = [vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp]
+        if hasattr(L, "aloam_graph_register_links"):       # likewise
+            L.aloam_graph_register_links.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopOptions), vp]
+            L.aloam_graph_search_links.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopSearch), C.POINTER(AloamGraphLoopOptions), vp, vp, vp]
+            L.aloam_graph_propose_links.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp]
         L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -932,6 +937,78 @@ class Aloam:
         nodes, edges = np.zeros(max(1, counts[0]), GRAPH_NODE_DTYPE), np.zeros(max(1, counts[1]), GRAPH_EDGE_DTYPE)
         self._check(lib().aloam_graph_joint_export(self.h, int(group), _p(nodes), len(nodes), _p(edges), len(edges), _p(counts)))
         return nodes[:counts[0]], edges[:counts[1]], counts
+
+    # ---- links measured on the device (loopreg.link_request / posegraph.propose_links hold the definitions) ----------------------------------
+    @staticmethod
+    def graph_link_requests(requests):
+        """[(seq_i, i, first, count, seq_j, j, pose, q_guess, t_guess), ...] -> structured array of GRAPH_LINK_REQUEST_DTYPE."""
+        r = np.zeros(len(requests), GRAPH_LINK_REQUEST_DTYPE)
+        for k, (seq_i, i, first, count, seq_j, j, pose, q, t) in enumerate(requests):
+            r[k]["seq_i"], r[k]["i"], r[k]["first"], r[k]["count"] = int(seq_i), int(i), int(first), int(count)
+            r[k]["seq_j"], r[k]["j"], r[k]["pose"] = int(seq_j), int(j), int(pose)
+            r[k]["q"], r[k]["t"] = np.asarray(q, np.float64), np.asarray(t, np.float64)
+        return r
+
+    def graph_register_links_into(self, requests, dst_ptr, options=None):
+        """Queue the registration of each link request (no host synchronisation): dst_ptr receives one aloam_graph_loop_result per request,
+        device memory or pinned host memory."""
+        r = requests if isinstance(requests, np.ndarray) else self.graph_link_requests(requests)
+        r = np.ascontiguousarray(r, dtype=GRAPH_LINK_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_register_links(self.h, _p(r) if len(r) else None, len(r), C.byref(options) if options is not None else None,
+                                                     _vp(dst_ptr)))
+
+    def graph_register_links(self, requests, pinned=True, **options):
+        """Register and wait: a structured array [len(requests)] of GRAPH_LOOP_RESULT_DTYPE.  Keyword arguments are fields of
+        aloam_graph_loop_options."""
+        buf = _out_bytes(len(requests), GRAPH_LOOP_RESULT_DTYPE, pinned)
+        self.graph_register_links_into(requests, buf.data_ptr(), self.graph_loop_options(**options))
+        self.synchronize()
+        return _records(buf, len(requests), GRAPH_LOOP_RESULT_DTYPE)
+
+    def graph_search_links_into(self, requests, dst_ptr, search_dst_ptr, scores_ptr=0, search=None, options=None):
+        """Queue the searched registration of each link request (no host synchronisation); the outputs are those of graph_search_loops_into."""
+        r = requests if isinstance(requests, np.ndarray) else self.graph_link_requests(requests)
+        r = np.ascontiguousarray(r, dtype=GRAPH_LINK_REQUEST_DTYPE)
+        self._check(lib().aloam_graph_search_links(self.h, _p(r) if len(r) else None, len(r), C.byref(search) if search is not None else None,
+                                                   C.byref(options) if options is not None else None, _vp(dst_ptr), _vp(search_dst_ptr), _vp(scores_ptr)))
+
+    def graph_search_links(self, requests, search=None, scores=False, pinned=True, **options):
+        """Search, register and wait: what graph_search_loops returns, for link requests."""
+        import torch
+        from .relocalize import grid_axes
+        g = self.graph_loop_search(**search) if isinstance(search, dict) else search if search is not None else self.graph_loop_search()
+        lin, yaw = grid_axes(g.radius_m, g.step_m, g.yaw_deg, g.yaw_step_deg)
+        n, K = len(requests), len(yaw) * len(lin) * len(lin)
+        res, found = _out_bytes(n, GRAPH_LOOP_RESULT_DTYPE, pinned), _out_bytes(n, GRAPH_LOOP_SEARCH_RESULT_DTYPE, pinned)
+        sc = torch.zeros(max(1, n) * (K * MAP_SCORE_DTYPE.itemsize if scores else 8), dtype=torch.uint8, **_where(pinned))
+        self.graph_search_links_into(requests, res.data_ptr(), found.data_ptr(), sc.data_ptr() if scores else 0, g, self.graph_loop_options(**options))
+        self.synchronize()
+        out = (_records(res, n, GRAPH_LOOP_RESULT_DTYPE), _records(found, n, GRAPH_LOOP_SEARCH_RESULT_DTYPE))
+        if scores:
+            out += (_records(sc, n * K, MAP_SCORE_DTYPE).reshape(n, K),)
+        return out
+
+    def graph_propose_links_into(self, queries, dst_ptr, counts_ptr, dist2_ptr=0, *, frames=None, radius_m, half_window=0, separation=0, K=1,
+                                 pose=GRAPH_POSE_OPTIMIZED):
+        """Queue the radius search of each query ((seq_j, j, seq_i) triples; frames: [n, 7] = q_A, t_A per query, or None; no host
+        synchronisation): dst_ptr receives K aloam_graph_link_request per query, counts_ptr one int, dist2_ptr (or 0) K doubles; device
+        memory or pinned host memory."""
+        qs = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, 3)
+        fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.float64).reshape(len(qs), 7)
+        self._check(lib().aloam_graph_propose_links(self.h, _p(qs) if len(qs) else None, _p(fr) if fr is not None and len(qs) else None, len(qs), int(pose),
+                                                    float(radius_m), int(half_window), int(separation), int(K), _vp(dst_ptr), _vp(counts_ptr), _vp(dist2_ptr)))
+
+    def graph_propose_links(self, queries, pinned=True, **parameters):
+        """Propose and wait: (requests [n, K] of GRAPH_LINK_REQUEST_DTYPE, counts int32 [n], dist2 float64 [n, K]).  Keyword arguments are
+        the parameters of aloam_graph_propose_links (frames, radius_m, half_window, separation, K, pose)."""
+        import torch
+        n, K = len(np.asarray(queries).reshape(-1, 3)), int(parameters.get("K", 1))
+        dst = _out_bytes(n * K, GRAPH_LINK_REQUEST_DTYPE, pinned)
+        cnt = torch.zeros(max(1, n), dtype=torch.int32, **_where(pinned))
+        d2 = torch.zeros(max(1, n * K), dtype=torch.float64, **_where(pinned))
+        self.graph_propose_links_into(queries, dst.data_ptr(), cnt.data_ptr(), d2.data_ptr(), **parameters)
+        self.synchronize()
+        return _records(dst, n * K, GRAPH_LINK_REQUEST_DTYPE).reshape(n, K), cnt.cpu().numpy()[:n].copy(), d2.cpu().numpy()[:n * K].reshape(n, K).copy()
 
     # ---- graph records (a-loam_amd/graph_records.py holds the format) ------------------------------------------------------------------
     def graph_save_into(self, seqs, dst_ptr, cap_bytes, offsets_ptr):

@@ -22,6 +22,7 @@
 #include "export_kernels.hpp"
 #include "graphapply_kernels.hpp"
 #include "graphjoint_kernels.hpp"
+#include "graphlink_kernels.hpp"
 #include "graphmap_kernels.hpp"
 #include "graphmarginal_kernels.hpp"
 #include "graphpropose_kernels.hpp"
@@ -206,6 +207,14 @@ struct JointScratch {                // joined pose graphs (aloam_graph_optimize
   int row_nodes = 0, row_edges = 0;                                 // the rows' strides as the last call laid them out
   std::vector<JointGroup> last;                                     // the last call's groups (aloam_graph_joint_export)
 };
+// Links measured on the device (aloam_graph_register_links / aloam_graph_search_links / aloam_graph_propose_links): nothing is allocated
+// before the first call that needs it; used in stream order.  The registrations run in the scratch of LoopScratch.
+struct LinkScratch {
+  DevBuf<aloam_graph_link_request> req;                             // [LoopScratch::slots] the round's link records, read by k_link_gather
+  StageRing<kLoopStageSlots> ring;                                  // a slot holds `slots` link records; acquired in step with LoopScratch::ring
+  DevBuf<LinkProposeQuery> queries;                                 // [kProposeStageItems] the round's queries with their frames
+  StageRing<kProposeStageSlots> query_ring;                         // a slot holds kProposeStageItems staged queries
+};
 
 struct GraphRecordScratch {          // graph records (aloam_graph_save / aloam_graph_load): sized for `batch` records on first use, used in stream order
   DevBuf<GraphRecItem> items;                                       // [B] the records of one call
@@ -349,6 +358,7 @@ struct aloam_ctx {
   ProposeScratch pp;
   TrimScratch tr;
   JointScratch jt;
+  LinkScratch lk;
   GraphRecordScratch gr;
   // map spill (aloam_map_spill_enable): what the window shifts of the mapping steps empty, kept as tiles until the host drains them
   bool spill_on = false;
@@ -557,6 +567,11 @@ int require_graph(aloam_ctx* c);
 // What aloam_graph_add_edges asks of an edge, for it and for the candidates of aloam_graph_marginals: seq, i and j always; with `measurement`
 // also flags, Z (q is normalised in place) and info.  nullptr, or what is wrong.
 const char* graph_edge_check(const aloam_ctx* c, aloam_graph_edge& e, bool measurement);
+// capi_loopreg.hip: the one body behind aloam_graph_register_loops / _search_loops (links == nullptr) and aloam_graph_register_links /
+// _search_links (req == nullptr, links given: the round's gather is k_link_gather, and the link records are staged beside the requests)
+int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, const aloam_graph_link_request* links, int n, const aloam_graph_loop_options* opt,
+                   aloam_graph_loop_result* dst, const aloam_graph_loop_search* search_or_default, bool searched, aloam_graph_loop_search_result* search_dst,
+                   aloam_map_score* scores);
 // capi_mapping.hip
 VoxArgs vox_args(aloam_ctx* c, int n_segs, int levels);
 // capi_records.hip

@@ -135,13 +135,70 @@ static int loop_search_grid(aloam_ctx* c, const aloam_graph_loop_search& s, Loop
   return ALOAM_OK;
 }
 
+}  // extern "C"
+
+// What a loop request and a link request share: the target window and node i against the node count of the sequence that holds the
+// target (seq for a loop, seq_i for a link, which the message names), a loop's node j (a link's lives in seq_j: check_link), pose, and
+// the guess, whose q is normalised in place as aloam_graph_add_edges does.  nullptr, or what is wrong.
+static const char* check_target_and_guess(int first, int count, int i, int j, long long nodes, int pose, double q[4], const double t[3], bool link) {
+  if (first < 0 || count < 1 || first + (long long)count > nodes)
+    return link ? "need count >= 1 and [first, first + count) inside what seq_i's graph holds" : "need count >= 1 and [first, first + count) inside what the sequence's graph holds";
+  if (i < first || i >= first + (long long)count) return "node i must be one of the target nodes (first <= i < first + count)";
+  if (!link && (j < 0 || j >= nodes || (j >= first && j < first + (long long)count))) return "node j must be a node outside [first, first + count)";
+  if (pose != ALOAM_GRAPH_POSE_ENTERED && pose != ALOAM_GRAPH_POSE_OPTIMIZED) return "pose must be ALOAM_GRAPH_POSE_ENTERED or ALOAM_GRAPH_POSE_OPTIMIZED";
+  double nn = 0.0;
+  for (int a = 0; a < 4; ++a) { if (!std::isfinite(q[a])) return "the guess q is not finite"; nn += q[a] * q[a]; }
+  nn = std::sqrt(nn);
+  if (!(std::fabs(nn - 1.0) <= 1e-6)) return "the guess q is not within 1e-6 of unit norm";
+  for (int a = 0; a < 3; ++a) if (!std::isfinite(t[a])) return "the guess t is not finite";
+  for (int a = 0; a < 4; ++a) q[a] /= nn;
+  return nullptr;
+}
+
+// A link request: both sequences, j against seq_j's nodes, the rest against seq_i's; there is no "j outside the window" rule.  On success
+// the record is as it is staged for k_link_gather: the guess normalised, pad and reserved zero.
+static const char* check_link(const aloam_ctx* c, aloam_graph_link_request& l) {
+  if (l.seq_i < 0 || l.seq_i >= c->B) return "seq_i out of range";
+  if (l.seq_j < 0 || l.seq_j >= c->B) return "seq_j out of range";
+  if (l.seq_i == l.seq_j) return "seq_i and seq_j must differ (for one sequence there is aloam_graph_register_loops)";
+  if (l.j < 0 || l.j >= c->seq[l.seq_j].graph_nodes) return "node j must be a node of seq_j's graph";
+  if (const char* what = check_target_and_guess(l.first, l.count, l.i, l.j, c->seq[l.seq_i].graph_nodes, l.pose, l.q, l.t, true)) return what;
+  l.pad = 0; l.reserved = 0.0;
+  return nullptr;
+}
+
+// The loop request the kernels behind the gather read for a checked link: the frame's sequence, the indices and the normalised guess.
+static aloam_graph_loop_request loop_request_of(const aloam_graph_link_request& l) {
+  aloam_graph_loop_request q{};
+  q.seq = l.seq_i; q.i = l.i; q.j = l.j; q.first = l.first; q.count = l.count; q.pose = l.pose;
+  for (int a = 0; a < 4; ++a) q.q[a] = l.q[a];
+  for (int a = 0; a < 3; ++a) q.t[a] = l.t[a];
+  return q;
+}
+
+// The staging of a link call's records (aloam_graph_register_links / aloam_graph_search_links), on first use: a ring whose slots hold as many
+// records as the request ring's, and the round's device copy.  Nothing stays allocated behind a refusal.
+static int link_staging(aloam_ctx* c) {
+  if (c->lk.req) return ALOAM_OK;
+  if (dalloc(c->lk.req, (size_t)c->lr.slots) == hipSuccess && !c->lk.ring.create(sizeof(aloam_graph_link_request) * (size_t)c->lr.slots)) return ALOAM_OK;
+  (void)hipGetLastError();
+  c->lk.req.reset();
+  c->err = "link registration: allocating the staging of " + std::to_string(c->lr.slots) + " link records failed";
+  return ALOAM_E_HIP;
+}
+
 // aloam_graph_register_loops (search == nullptr) and aloam_graph_search_loops: checks, ring, gather, filter, grid, then search and pick when a
 // grid is given, rounds, information, result.  The plain call queues exactly the launches it queued before the search existed.
-static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst,
-                          const aloam_graph_loop_search* search_or_default, bool searched, aloam_graph_loop_search_result* search_dst, aloam_map_score* scores) {
+// aloam_graph_register_links / aloam_graph_search_links (capi_graphlink.hip) come through here with `links` in place of `req`: a link round
+// differs in its checks, in which gather is launched and in what is staged - the link records for k_link_gather, and plain loop requests
+// (seq = seq_i, the normalised guess) for the kernels behind it, which read nothing of a request but its guess.
+int aloam::register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, const aloam_graph_link_request* links, int n, const aloam_graph_loop_options* opt,
+                          aloam_graph_loop_result* dst, const aloam_graph_loop_search* search_or_default, bool searched, aloam_graph_loop_search_result* search_dst,
+                          aloam_map_score* scores) {
   if (const int rc = require_loops(c)) return rc;
   // ---- everything is checked before anything is queued
-  if (n < 0 || (n > 0 && !req)) { c->err = "bad request list"; return ALOAM_E_ARG; }
+  const bool linked = links != nullptr;
+  if (n < 0 || (n > 0 && !req && !linked)) { c->err = "bad request list"; return ALOAM_E_ARG; }
   aloam_graph_loop_options o;
   aloam_graph_loop_default_options(&o);
   if (opt) o = *opt;
@@ -154,31 +211,30 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
     if (const int rc = loop_search_grid(c, g, &sc.grid)) return rc;
   }
   if (n == 0) return ALOAM_OK;
-  if (const int rc = require_host_list(c, req, "req")) return rc;
+  if (const int rc = require_host_list(c, linked ? (const void*)links : (const void*)req, "req")) return rc;
   void* d_dst = nullptr;
   if (const int rc = export_target(c, dst, 8, "dst", &d_dst)) return rc;
   if (searched) {
     if (const int rc = export_target(c, search_dst, 8, "search_dst", &sc.d_search)) return rc;
     if (scores) if (const int rc = export_target(c, scores, 8, "scores", &sc.d_scores)) return rc;
   }
-  std::vector<aloam_graph_loop_request> checked(req, req + n);
+  std::vector<aloam_graph_loop_request> checked(linked ? (size_t)n : 0);
+  if (!linked) checked.assign(req, req + n);
+  std::vector<aloam_graph_link_request> checked_links(links, links + (linked ? n : 0));
   for (int r = 0; r < n; ++r) {
-    aloam_graph_loop_request& q = checked[r];
-    auto fail = [&](const char* what) { c->err = "request " + std::to_string(r) + ": " + what; return ALOAM_E_ARG; };
-    if (q.seq < 0 || q.seq >= c->B) return fail("seq out of range");
-    const long long nodes = c->seq[q.seq].graph_nodes;
-    if (q.first < 0 || q.count < 1 || q.first + (long long)q.count > nodes) return fail("need count >= 1 and [first, first + count) inside what the sequence's graph holds");
-    if (q.i < q.first || q.i >= q.first + (long long)q.count) return fail("node i must be one of the target nodes (first <= i < first + count)");
-    if (q.j < 0 || q.j >= nodes || (q.j >= q.first && q.j < q.first + (long long)q.count)) return fail("node j must be a node outside [first, first + count)");
-    if (q.pose != ALOAM_GRAPH_POSE_ENTERED && q.pose != ALOAM_GRAPH_POSE_OPTIMIZED) return fail("pose must be ALOAM_GRAPH_POSE_ENTERED or ALOAM_GRAPH_POSE_OPTIMIZED");
-    double nn = 0.0;
-    for (int a = 0; a < 4; ++a) { if (!std::isfinite(q.q[a])) return fail("the guess q is not finite"); nn += q.q[a] * q.q[a]; }
-    nn = std::sqrt(nn);
-    if (!(std::fabs(nn - 1.0) <= 1e-6)) return fail("the guess q is not within 1e-6 of unit norm");
-    for (int a = 0; a < 4; ++a) q.q[a] /= nn;
-    for (int a = 0; a < 3; ++a) if (!std::isfinite(q.t[a])) return fail("the guess t is not finite");
-    q.pad[0] = 0; q.pad[1] = 0; q.reserved = 0.0;
+    const char* what = nullptr;
+    if (linked) {
+      what = check_link(c, checked_links[r]);
+      if (!what) checked[r] = loop_request_of(checked_links[r]);
+    } else {
+      aloam_graph_loop_request& q = checked[r];
+      if (q.seq < 0 || q.seq >= c->B) what = "seq out of range";
+      else what = check_target_and_guess(q.first, q.count, q.i, q.j, c->seq[q.seq].graph_nodes, q.pose, q.q, q.t, false);
+      q.pad[0] = 0; q.pad[1] = 0; q.reserved = 0.0;
+    }
+    if (what) { c->err = "request " + std::to_string(r) + ": " + what; return ALOAM_E_ARG; }
   }
+  if (linked) if (const int rc = link_staging(c)) return rc;
   // ---- rounds of at most lr_slots requests (searched: and at most 2^18 (slot, node) pairs) over the same scratch, in stream order
   const int per_round = searched ? (int)std::min<long long>(c->lr.slots, kLoopSearchMaxPairs / sc.grid.K) : c->lr.slots;
   if (searched)
@@ -191,13 +247,20 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
   // A slot of the pinned ring holds lr_slots requests: one round of the plain call, as many whole rounds of a searched call as fit (its
   // rounds are the shorter of the two bounds), so that a searched call waits for the ring no sooner than a plain call of the same n.
   aloam_graph_loop_request* ring_slot = nullptr; int ns = 0, ring_at = 0, ring_left = 0;
+  aloam_graph_link_request* link_slot = nullptr; int link_ns = 0;           // a link call's second ring, acquired in step with the first
   for (int r0 = 0; r0 < n; r0 += per_round) {
     const int m = std::min(per_round, n - r0);
     if (ring_left < m) {
       if (const int rc = c->lr.ring.acquire(c, &ring_slot, &ns)) return rc;
+      if (linked) if (const int rc = c->lk.ring.acquire(c, &link_slot, &link_ns)) return rc;
       ring_at = 0; ring_left = c->lr.slots;
     }
     aloam_graph_loop_request* slot = ring_slot + ring_at;
+    if (linked) {
+      aloam_graph_link_request* ls = link_slot + ring_at;
+      std::copy(checked_links.begin() + r0, checked_links.begin() + r0 + m, ls);
+      if (const int rc = c->lk.ring.queue(c, link_ns, ls, sizeof(aloam_graph_link_request) * (size_t)m, c->lk.req.get(), c->stream)) return rc;
+    }
     ring_at += m; ring_left -= m;
     std::copy(checked.begin() + r0, checked.begin() + r0 + m, slot);
     if (const int rc = c->lr.ring.queue(c, ns, slot, sizeof(aloam_graph_loop_request) * (size_t)m, c->lr.req.get(), c->stream)) return rc;
@@ -211,7 +274,15 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
     a.info = c->lr.info.get(); a.dst = static_cast<aloam_graph_loop_result*>(d_dst) + r0;
     const VoxArgs v = loop_vox_args(c, 2 * m);
     HIP_TRY(c, hipMemsetAsync(c->lr.vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));   // general-path count, the three LDS-filter lists
-    launch_loop_gather(a, v, c->stream);
+    if (linked) {
+      LinkGatherArgs g{};
+      g.n = m; g.req = c->lk.req.get(); g.kf = a.kf; g.nodes = a.nodes; g.max_nodes = a.max_nodes; g.map = a.map;
+      for (int k = 0; k < 2; ++k) { g.raw[k] = a.raw[k]; g.raw_cap[k] = a.raw_cap[k]; g.target[k] = a.target[k]; }
+      g.plan = a.plan; g.plan_ints = kLoopPlanInts;
+      launch_link_gather(g, v, c->stream);
+    } else {
+      launch_loop_gather(a, v, c->stream);
+    }
     launch_voxel_filter(v, c->lr.tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
     launch_loop_grid(a, c->stream);
     if (searched) {
@@ -235,17 +306,19 @@ static int register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int
   return ALOAM_OK;
 }
 
+extern "C" {
+
 int aloam_graph_register_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  return register_loops(c, req, n, opt, dst, nullptr, false, nullptr, nullptr);
+  return register_loops(c, req, nullptr, n, opt, dst, nullptr, false, nullptr, nullptr);
 }
 
 int aloam_graph_search_loops(aloam_ctx* c, const aloam_graph_loop_request* req, int n, const aloam_graph_loop_search* search, const aloam_graph_loop_options* opt,
                              aloam_graph_loop_result* dst, aloam_graph_loop_search_result* search_dst, aloam_map_score* scores) {
   DeviceScope device_scope(c);
   if (!c) return ALOAM_E_ARG;
-  return register_loops(c, req, n, opt, dst, search, true, search_dst, scores);
+  return register_loops(c, req, nullptr, n, opt, dst, search, true, search_dst, scores);
 }
 
 int aloam_graph_loop_export_target(aloam_ctx* c, int slot, int feature_class, float* dst_xyzw, long long cap, int* count) {

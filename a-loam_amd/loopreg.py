@@ -25,6 +25,7 @@ from . import places
 from .atlas import associate_to_map
 from .relocalize import grid_axes
 from .posegraph import EDGE_ROBUST, MARGINAL_MEASURED, MARGINAL_REQUEST_DTYPE, compose, info_full, info_upper, inverse, make_edges, qrot, relative_pose, rotmat
+from .posegraph import LINK_REQUEST_DTYPE, POSE_OPTIMIZED, make_links
 
 LOOP_OK, LOOP_NO_CLOUDS, LOOP_TARGET_TOO_SMALL, LOOP_TOO_LARGE, LOOP_SOLVE_FAILED = 0, 1, 2, 3, 4
 GATE_CORNER, GATE_SURF = 10, 50                  # the filtered targets must hold MORE points than these (src/laserMapping.cpp:554)
@@ -99,6 +100,25 @@ def request_from_result(result, i, j, seq):
     r = np.zeros(1, MARGINAL_REQUEST_DTYPE)
     r["edge"], r["mode"] = e, MARGINAL_MEASURED
     return r
+
+
+def link_request(seq_i, i, first, count, seq_j, j, q, t, pose=POSE_OPTIMIZED):
+    """The aloam_graph_link_request (posegraph.LINK_REQUEST_DTYPE, one element) that registers node j of seq_j against nodes
+    [first, first + count) of seq_i in the frame of node i, from the guess (q, t) of Z."""
+    r = np.zeros(1, LINK_REQUEST_DTYPE)
+    r["seq_i"], r["i"], r["first"], r["count"], r["seq_j"], r["j"], r["pose"] = int(seq_i), int(i), int(first), int(count), int(seq_j), int(j), int(pose)
+    r["q"], r["t"] = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    return r
+
+
+def link_from_result(result, seq_i, i, seq_j, j, robust=True):
+    """The aloam_graph_link (posegraph.LINK_DTYPE, one element) of an ALOAM_LOOP_OK result record of aloam_graph_register_links /
+    aloam_graph_search_links; None for every other status.  Its info is the result's right-tangent `info`, which is what a link wants.
+    Whether an OK link is a good one is the caller's decision: hence robust by default."""
+    if int(result["status"]) != LOOP_OK:
+        return None
+    q = np.asarray(result["q"], np.float64)
+    return make_links(seq_i, i, seq_j, j, (q / np.linalg.norm(q))[None], np.asarray(result["t"], np.float64)[None], np.asarray(result["info"], np.float64)[None], robust)
 
 
 SEARCH_MAX_YAW, SEARCH_MAX_NODES = 31, 1 << 14   # yaw steps to either side, nodes of one grid (aloam_graph_search_loops)

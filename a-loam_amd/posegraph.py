@@ -21,6 +21,7 @@ import numpy as np
 
 from .records import GRAPH_EDGE_DTYPE as EDGE_DTYPE, GRAPH_MARGINAL_REQUEST_DTYPE as MARGINAL_REQUEST_DTYPE, GRAPH_NODE_DTYPE as NODE_DTYPE
 from .joint_records import GRAPH_LINK_DTYPE as LINK_DTYPE
+from .link_records import GRAPH_LINK_REQUEST_DTYPE as LINK_REQUEST_DTYPE
 from .records import GRAPH_LOOP_REQUEST_DTYPE as LOOP_REQUEST_DTYPE, GRAPH_POSE_ENTERED as POSE_ENTERED, GRAPH_POSE_OPTIMIZED as POSE_OPTIMIZED
 
 EDGE_ROBUST = 1
@@ -651,6 +652,52 @@ def propose_loops(q, t, j, radius_m, growth_m_per_node, min_gap, half_window, se
         dist2[taken] = d2[w]
         taken += 1
     return req, taken, dist2
+
+
+def propose_links(q_i, t_i, q_j, t_j, j, frame, radius_m, half_window, separation, K, seq_i=0, seq_j=1, pose=POSE_OPTIMIZED):
+    """aloam_graph_propose_links for one query (seq_j, j, seq_i), operation by operation: (q_i, t_i) are the poses of seq_i's nodes the call
+    reads and (q_j, t_j) those of seq_j's (the entered ones or the estimates, as `pose` says; `pose` itself only goes into the records).
+    X_j' = X_j when `frame` is None (its bits), else compose(A, X_j) with A = frame = (q_A, t_A) or the seven numbers, q_A stored normalised
+    (stored_q).  EVERY node i of seq_i is eligible and is a hit when d2 = (dx dx + dy dy) + dz dz of t_i - t_j' is <= radius_m radius_m.  At
+    most K rounds of propose_loops' greedy rule.  Returns (requests [K] of LINK_REQUEST_DTYPE with first = max(0, i - half_window),
+    count = min(i + half_window, nodes - 1) - first + 1 and the guess relative_pose(X_i, X_j'); count; dist2 [K]); rows behind the count
+    are zero."""
+    q_i, t_i = np.asarray(q_i, np.float64).reshape(-1, 4), np.asarray(t_i, np.float64).reshape(-1, 3)
+    q_j, t_j = np.asarray(q_j, np.float64), np.asarray(t_j, np.float64)
+    j, K, nodes = int(j), int(K), len(t_i)
+    req, dist2 = np.zeros(K, LINK_REQUEST_DTYPE), np.zeros(K, np.float64)
+    qj, tj = q_j[j], t_j[j]
+    if frame is not None:
+        f = np.concatenate([np.asarray(x, np.float64).reshape(-1) for x in frame]) if isinstance(frame, tuple) else np.asarray(frame, np.float64).reshape(7)
+        qj, tj = compose(stored_q(f[:4]), f[4:], qj, tj)
+    i = np.arange(nodes)
+    d = t_i - tj
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    with np.errstate(over="ignore"):
+        live = d2 <= np.float64(radius_m) * np.float64(radius_m)
+    taken = 0
+    while taken < K and live.any():
+        cand = i[live]
+        best = d2[cand].min()
+        w = int(cand[d2[cand] == best][0])
+        live &= np.abs(i - w) > int(separation)
+        first = max(0, w - int(half_window))
+        qd, td = relative_pose(q_i[w], t_i[w], qj, tj)
+        rec = req[taken]
+        rec["seq_i"], rec["i"], rec["first"], rec["count"] = int(seq_i), w, first, min(w + int(half_window), nodes - 1) - first + 1
+        rec["seq_j"], rec["j"], rec["pose"] = int(seq_j), j, int(pose)
+        rec["q"], rec["t"] = qd, td
+        dist2[taken] = d2[w]
+        taken += 1
+    return req, taken, dist2
+
+
+def frame_from_link(q_i, t_i, link, q_j, t_j):
+    """The pose A of seq_j's frame in seq_i's frame that a link (node j of seq_j measured in the frame of node i of seq_i) stands for:
+    A = (X_i o Z) o X_j^-1 with X_i = (q_i, t_i) the estimate of the link's node i and X_j = (q_j, t_j) that of its node j, q_A divided by its
+    norm - align_member's transform for the seq_j side, without its side effects.  Returns (q_A, t_A)."""
+    qa, ta = compose(*compose(q_i, t_i, np.array(link["q"], np.float64).reshape(4), np.array(link["t"], np.float64).reshape(3)), *inverse(q_j, t_j))
+    return stored_q(qa), ta
 
 
 def unclosed(requests, edges, gap):

@@ -1344,6 +1344,79 @@ int aloam_graph_optimize_joint_robust(aloam_ctx* ctx, const int* members, const 
                                       aloam_graph_robust_result* dst /* [n_groups] */, double* weights_dst /* [n_groups][weights_stride] or NULL */,
                                       long long weights_stride);
 
+/* ---- links measured on the device: register, search and propose between sequences ----------------------------------------------------------
+ * aloam_graph_optimize_joint consumes links; this section measures them.  The chain propose -> search and register -> gate -> link ->
+ * joint solve runs between two sequences with the same stream-ordered, batched calls that run it inside one: no atlas, no spare sequence
+ * slot, no host synchronisation.  Opt-in and beside the reference: a context that never calls a function of this section allocates and
+ * launches exactly what it launched before, and aloam_graph_register_loops / aloam_graph_search_loops / aloam_graph_propose_loops queue
+ * exactly the launches they queued before.  a-loam_amd/posegraph.py (propose_links, frame_from_link) and a-loam_amd/loopreg.py
+ * (link_request, link_from_result) restate the definitions; DESIGN.md §7z.
+ *
+ * A link request names a frame (node i of seq_i), a target (nodes [first, first + count) of seq_i, i among them), a source (node j of
+ * seq_j, seq_j != seq_i) and a guess of Z, the pose of node j of seq_j in the frame of node i of seq_i.  The guess sits at byte 32, as in
+ * aloam_graph_loop_request.
+ *
+ * aloam_graph_register_links(ctx, req, n, opt, dst) writes aloam_graph_loop_result dst[n].  Its definition is that of
+ *   aloam_graph_register_loops, word for word, with two substitutions: the target is built from seq_i's nodes, descriptors and point rows
+ *   (X_k, T_k = X_i^-1 o X_k and the poses chosen by `pose` are seq_i's), and the source is node j's two clouds from seq_j's rows.  No pose
+ *   of seq_j is read: the two sessions need not share a frame, because the guess carries everything about their relation.  The statuses
+ *   (ALOAM_LOOP_NO_CLOUDS: node j of seq_j or every target node of seq_i was kept without clouds), the options, the result record, the
+ *   rounds of n > max_requests and the determinism clause (dst[r] does not depend on n, on the position, on the round or on the other
+ *   requests) are unchanged.  Z is the pose of node j of seq_j in the frame of node i of seq_i and `info` its right-tangent information:
+ *   what an aloam_graph_link wants.
+ * aloam_graph_search_links(ctx, req, n, search, opt, dst, search_dst, scores) is the same call with the pose grid of
+ *   aloam_graph_search_loops scored around every guess first; grid, score, ranking, records and limits are unchanged.
+ * Checked before anything is queued, ALOAM_E_ARG with the field named in aloam_last_error and nothing changed, by the rules of the
+ *   per-sequence calls with these differences: seq_i and seq_j both in range and seq_i != seq_j (for one sequence the loop calls exist);
+ *   count >= 1, [first, first + count) and first <= i < first + count are held against seq_i's node count; 0 <= j < seq_j's node count;
+ *   there is no "j outside the window" rule.  ALOAM_E_STATE before aloam_graph_loops_enable.  n = 0 is ALOAM_OK.  Timed under the profiling
+ *   slot loop_register.  The staging of the link records (a pinned ring and a device array of max_requests records) is made by the first
+ *   link call that needs it; when it cannot be had it is ALOAM_E_HIP and nothing of it stays allocated.  aloam_graph_loop_export_target
+ *   returns a slot's filtered target after a link call as after a loop call.
+ *
+ * aloam_graph_propose_links: for every query (seq_j, j, seq_i) the nodes of seq_i near node j of seq_j, as link requests.  Every f64
+ *   operation is rounded on its own.
+ *   1. X_k = (q, t) or its estimate (q_opt, t_opt), chosen by pose, for both sequences.
+ *   2. X_j' = X_j when frames is NULL (no arithmetic: the bits are X_j's); otherwise X_j' = A o X_j with A = frames[query] = (q_A, t_A), the
+ *      pose of seq_j's frame in seq_i's frame: compose of the joined-graphs section, q_j' = quat_mul(q_A, q_j),
+ *      t_j' = quat_rotate(q_A, t_j) + t_A.  q_A is stored normalised by the host, as a link's q is.
+ *   3. The eligible nodes are all nodes [0, nodes(seq_i)): no minimum gap and no growth term, an index distance between two chains means
+ *      nothing.
+ *   4. (dx, dy, dz) = t_i - t_j'; d2 = (dx*dx + dy*dy) + dz*dz; i is a hit when d2 <= radius_m * radius_m.
+ *   5. At most K rounds of the greedy rule of aloam_graph_propose_loops: the live hit with the least (d2, i) - lower d2 first, then lower i -
+ *      is taken, and every hit i' with |i' - i| <= separation dies.  counts[q] is the number taken.
+ *   6. Record k: seq_i, i, first = max(0, i - half_window), count = min(i + half_window, nodes(seq_i) - 1) - first + 1 (the window is
+ *      clamped at BOTH ends: no minimum gap keeps it off the end of the chain), seq_j, j, pose, and the guess X_i^-1 o X_j',
+ *      q_d = conj(q_i) q_j', t_d = conj(q_i) (t_j' - t_i); pad and reserved are zero; dist2[q][k] = d2.
+ *   7. Rows behind counts[q] are all-zero bytes; every byte of the three outputs is written and nothing outside them is written.
+ *   frames NULL is for members already joined and aligned; before that A comes from the first link,
+ *   A = (X_i o Z) o X_j^-1 (align_member's transform; posegraph.frame_from_link).
+ *   queries (n triples) and frames (n x 7 doubles, or NULL) are host memory, read during the call.  Checked before anything is queued,
+ *   ALOAM_E_ARG with nothing changed: both sequences in range and distinct; 0 <= j < seq_j's nodes; pose 0 or 1; radius_m finite and >= 0;
+ *   half_window >= 0; separation >= 0; 1 <= K <= 16; frames finite and q_A unit to 1e-6; dst and dist2 (may be NULL) 8-byte aligned and
+ *   counts 4-byte aligned, device memory of the context's device or pinned host memory, classified like the exports.  ALOAM_E_STATE before
+ *   aloam_graph_enable.  n = 0 is ALOAM_OK.  Stream-ordered, no host synchronisation: the queries go through a pinned staging ring made
+ *   by the first call, and n > 2048 runs in rounds.  It reads the graphs and writes nothing in them; a query's bytes are independent of n,
+ *   of its position in the list, of the round and of the other queries.  Timed under the profiling slot pose_graph. */
+struct aloam_graph_link_request {             /* 96 bytes; the guess at byte 32, as in aloam_graph_loop_request                          */
+  int seq_i, i;                               /* the frame: node i of sequence seq_i                                                    */
+  int first, count;                           /* the target: nodes [first, first + count) of seq_i, i among them                        */
+  int seq_j, j;                               /* the source: the clouds of node j of sequence seq_j, seq_j != seq_i                     */
+  int pose;                                   /* ALOAM_GRAPH_POSE_ENTERED / _OPTIMIZED: which poses of seq_i place the target           */
+  int pad;
+  double q[4], t[3];                          /* the guess of Z: node j of seq_j in the frame of node i of seq_i                        */
+  double reserved;
+};
+typedef struct aloam_graph_link_request aloam_graph_link_request;
+int aloam_graph_register_links(aloam_ctx* ctx, const aloam_graph_link_request* req, int n, const aloam_graph_loop_options* opt,
+                               aloam_graph_loop_result* dst /* [n] */);
+int aloam_graph_search_links(aloam_ctx* ctx, const aloam_graph_link_request* req, int n, const aloam_graph_loop_search* search,
+                             const aloam_graph_loop_options* opt, aloam_graph_loop_result* dst /* [n] */,
+                             aloam_graph_loop_search_result* search_dst /* [n] */, aloam_map_score* scores /* [n][K] or NULL */);
+int aloam_graph_propose_links(aloam_ctx* ctx, const int* queries /* [n][3]: seq_j, j, seq_i */, const double* frames /* [n][7]: q, t, or NULL */,
+                              int n, int pose, double radius_m, int half_window, int separation, int K,
+                              aloam_graph_link_request* dst /* [n][K] */, int* counts /* [n] */, double* dist2 /* [n][K] or NULL */);
+
 /* ---- intermediate arrays, for parity tests ----------------------------------------------------------------- */
 /* cloudCurvature / cloudLabel are kept by the aloam_scan_register* entries only; after aloam_process_device / aloam_process_host
  * (which skip those 5 bytes per point) the two getters fail with ALOAM_E_STATE. */

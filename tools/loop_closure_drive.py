@@ -2,7 +2,7 @@
 edge inside a drive").
 
     python tools/loop_closure_drive.py [--radius 12] [--step 0.5] [--laps 1.25] [--keyframe-spacing 2] [--gap 20] [--neighbours 6] [--apply] [--device-loops [--search]] [--false-loops K] [--resume-at K]
-                                         [--device-loops --proximity RADIUS] [--window N [--proximity RADIUS]]
+                                         [--device-loops --proximity RADIUS] [--window N [--proximity RADIUS]] [--two-sessions [--proximity RADIUS]]
 
 A synthetic VLP-16 drives a lap and a quarter of a small circle (synthetic.trajectory) in slot 0: odometry, mapping, a keyframe (graph
 node with its clouds) and a place every few metres.  At the last keyframe:
@@ -52,6 +52,17 @@ the graph at every keyframe (--proximity metres, default 3; --gap, --neighbours)
 keeps every keyframe; the other, once it holds more than N, exports the map tiles of the nodes about to go, trims to N (aloam_graph_trim)
 and drives on.  Printed: the ATE over all keyframes of both (a dropped keyframe counts where it was when it left), the loops entered, what
 the window holds at the end, the last trim's eight integers, the tiles and points exported on the way.
+
+With --two-sessions nothing of the above runs: the drive is cut after its first lap into two sessions in two slots.  Slot 1 starts the
+second session from the identity, so it lives in a frame of its own.  Then, with nothing leaving the device but records:
+  1. the first link: aloam_places_match of the second session's last sweep against the first session's places, the guess of the match's yaw
+     shift (loopreg.guess_from_match), aloam_graph_search_links of that keyframe against the nodes around the matched one;
+  2. aloam_graph_optimize_joint of both sessions with that link and align = [0, 1]: the second session moves into the first one's frame;
+  3. more links: aloam_graph_propose_links of every keyframe of the second session against the first (--proximity metres, default 3; frames
+     NULL, the sessions share a frame now), aloam_graph_register_links of all candidates in one call; a link is kept when its status is OK
+     and Z moved less than a metre from the proposal's guess (aloam_graph_marginals works inside one sequence and does not apply across two);
+  4. the second joint solve, all links, no alignment;
+  5. printed against ground truth: the first link's error, the ATE of both sessions after each solve, the links kept.
 """
 from __future__ import annotations
 
@@ -104,10 +115,14 @@ def main():
     ap.add_argument("--resume-at", type=int, default=None, metavar="K", help="only drive: at keyframe K save the sequence record and the graph record to a temporary file, load both into a fresh context, drive on in both and compare")
     ap.add_argument("--window", type=int, default=None, metavar="N", help="only drive, twice: one graph keeps every keyframe, the other is trimmed to N (aloam_graph_trim) once it holds more, the map "
                     "tiles of the nodes about to go exported first; loops are proposed by proximity and registered on the device in both; prints the two ATEs")
+    ap.add_argument("--two-sessions", action="store_true", help="only drive: the drive cut into two sessions in two slots, the second in a frame of its own; a first link from a place match "
+                    "and aloam_graph_search_links, a joint solve with align, more links from aloam_graph_propose_links and aloam_graph_register_links, a second joint solve; prints both ATEs")
     args = ap.parse_args()
+    if args.two_sessions and args.neighbours < 0:
+        ap.error("--two-sessions needs --neighbours >= 0")
     if args.window is not None and not (args.window >= 1 and 0 <= args.neighbours < args.gap):
         ap.error("--window needs N >= 1 and --neighbours below --gap")
-    if args.window is None and args.proximity is not None and not (args.device_loops and 0 <= args.neighbours < args.gap):
+    if args.window is None and not args.two_sessions and args.proximity is not None and not (args.device_loops and 0 <= args.neighbours < args.gap):
         ap.error("--proximity needs --device-loops and --neighbours below --gap")
 
     import torch
@@ -132,6 +147,9 @@ def main():
     mods = (torch, binding, pg, places, reloc, syn, model)
     if args.resume_at is not None:
         print(json.dumps(resume(args, mods, scans, frames, every)))
+        return
+    if args.two_sessions:
+        print(json.dumps(two_sessions(args, mods, scans, q_true, t_true, frames, every)))
         return
     if args.window is not None:
         print(json.dumps(window(args, mods, scans, q_true, t_true, frames, every)))
@@ -265,6 +283,113 @@ def window(args, mods, scans, q_true, t_true, frames, every):
         out[name] = {"nodes_held": i["nodes"], "edges_held": i["edges"], "loops_entered": run["loops"], "ate_m": pg.ate(t, truth_t), "trims": len(run["trims"]),
                      "last_trim": run["trims"][-1] if run["trims"] else None, "tiles_exported": run["tiles"], "points_exported": run["points"]}
         g.close()
+    return out
+
+
+def two_sessions(args, mods, scans, q_true, t_true, frames, every):
+    """The drive cut after its first lap: session one in slot 0, session two in slot 1 from the identity.  Links are measured on the device
+    between the slots (aloam_graph_search_links, aloam_graph_propose_links, aloam_graph_register_links) and solved jointly."""
+    torch, binding, pg, places, reloc, syn, model = mods
+    lr = importlib.import_module("a-loam_amd.loopreg")
+    nan_row = np.full((1, 4), np.nan, np.float32)
+    cut = min(frames - 2 * every, int(round(frames / max(args.laps, 1e-9))))      # the first lap; at least two keyframes are left for session two
+    n_key = (frames + every - 1) // every + 2
+    radius = 3.0 if args.proximity is None else args.proximity
+    span = 2 * args.neighbours + 1
+    info = np.diag([1.0 / 5e-3 ** 2] * 3 + [1.0 / 5e-2 ** 2] * 3)
+    gpu = binding.Aloam(n_scans=16, min_range=model.min_range, batch=2, max_points=max(len(s) for s in scans) + 64)
+    gpu.mapping_enable(0.4, 0.8, pool_points=1 << 17)
+    gpu.graph_enable(n_key + 4, n_key + 8)
+    gpu.graph_keyframes_enable(n_key * 2048, n_key * 16384)
+    gpu.places_enable(n_key + 4, max_range=40.0, sensor_height=syn.SENSOR_HEIGHT)
+    gpu.graph_loops_enable(8, span * 2048, span * 16384)
+    out = {"frames": frames, "cut_at_sweep": cut, "proximity_m": radius}
+    keys = [[], []]
+    stage = "drive"
+    try:
+        for k in range(frames):
+            b = 0 if k < cut else 1
+            gpu.set_active([1, 0] if b == 0 else [0, 1])
+            gpu.scan_register([scans[k], nan_row] if b == 0 else [nan_row, scans[k]], check=False)
+            gpu.odometry_step()
+            gpu.mapping_step()
+            if (k - (cut if b else 0)) % every == 0 or k in (cut - 1, frames - 1):
+                gpu.graph_add_nodes([b], info)
+                if b == 0:
+                    gpu.places_add([0])
+                keys[b].append(k)
+        gpu.synchronize()
+        n0, n1 = len(keys[0]), len(keys[1])
+        truth = np.concatenate([t_true[keys[0]], t_true[keys[1]]])
+        truth_q = np.concatenate([q_true[keys[0]], q_true[keys[1]]])
+        out["keyframes"] = [n0, n1]
+        nodes = [gpu.graph_export(b) for b in (0, 1)]
+        out["second_session_frame_offset_m"] = float(np.linalg.norm(nodes[1]["t_opt"][0] - t_true[keys[1][0]]))
+
+        stage = "places_match"
+        j = n1 - 1
+        m = gpu.places_match([1], [(0, n0)])[0, 0]
+        i = int(m["entry"])
+        if i < 0:
+            raise RuntimeError("no place of the first session matches the second session's last sweep")
+        out["match"] = {"entry": i, "shift": int(m["shift"]), "distance": float(m["distance"]), "truth_distance_m": float(np.linalg.norm(t_true[keys[0][i]] - t_true[keys[1][j]]))}
+        lo, hi = max(0, i - args.neighbours), min(n0, i + args.neighbours + 1)
+        stage = "graph_search_links"
+        qg, tg = lr.guess_from_match(nodes[0]["q_opt"][i], nodes[0]["t_opt"][i], nodes[0]["q_opt"][i], nodes[0]["t_opt"][i], int(m["shift"]), nodes[1]["q_opt"][j], nodes[1]["t_opt"][j])
+        t0 = time.perf_counter()
+        rs, ss = gpu.graph_search_links(lr.link_request(0, i, lo, hi - lo, 1, j, qg, tg))
+        search_ms = 1e3 * (time.perf_counter() - t0)
+        rs, ss = rs[0], ss[0]
+        qz, tz = pg.relative_pose(q_true[keys[0][i]], t_true[keys[0][i]], q_true[keys[1][j]], t_true[keys[1][j]])
+        dq = pg.qmul(pg.qconj(qz), rs["q"])
+        out["first_link"] = {"i": i, "j": j, "status": int(rs["status"]), "best": int(ss["best"]), "n_line": int(rs["n_line"]), "n_plane": int(rs["n_plane"]),
+                             "guess_error_m": float(np.linalg.norm(tg - tz)), "translation_error_m": float(np.linalg.norm(rs["t"] - tz)),
+                             "rotation_error_deg": float(np.degrees(2 * math.asin(min(1.0, np.linalg.norm(dq[:3]))))), "call_and_synchronize_ms": search_ms}
+        first = lr.link_from_result(rs, 0, i, 1, j)
+        if first is None:
+            raise RuntimeError("the first link's registration ended with status %d" % int(rs["status"]))
+
+        stage = "graph_optimize_joint (align)"
+        res = gpu.graph_optimize_joint([([0, 1], first, [0, 1])])[0]
+        after = [gpu.graph_export(b) for b in (0, 1)]
+        out["first_solve"] = {"status": int(res["status"]), "lm_iterations": int(res["lm_iterations"]), "final_cost": float(res["final_cost"]),
+                              "ate_m": pg.ate(np.concatenate([a["t_opt"] for a in after]), truth)}
+
+        stage = "graph_propose_links"
+        t0 = time.perf_counter()
+        prop, count, dist2 = gpu.graph_propose_links([(1, jj, 0) for jj in range(n1)], radius_m=radius, half_window=args.neighbours, separation=args.neighbours, K=1)
+        propose_ms = 1e3 * (time.perf_counter() - t0)
+        cand = np.ascontiguousarray(np.concatenate([prop[jj][:count[jj]] for jj in range(n1)]))
+        out["proposals"] = {"queries": n1, "candidates": len(cand), "call_and_synchronize_ms": propose_ms}
+        links = [first]
+        if len(cand):
+            stage = "graph_register_links"
+            t0 = time.perf_counter()
+            reg = gpu.graph_register_links(cand)
+            register_ms = 1e3 * (time.perf_counter() - t0)
+            kept, errors = 0, []
+            for c, r in zip(cand, reg):
+                l = lr.link_from_result(r, 0, int(c["i"]), 1, int(c["j"]))
+                if l is None or np.linalg.norm(r["t"] - c["t"]) >= 1.0:
+                    continue
+                _, tz = pg.relative_pose(truth_q[int(c["i"])], truth[int(c["i"])], truth_q[n0 + int(c["j"])], truth[n0 + int(c["j"])])
+                errors.append(float(np.linalg.norm(r["t"] - tz)))
+                links.append(l)
+                kept += 1
+            out["more_links"] = {"registered": len(cand), "kept": kept, "statuses": {int(s): int(n) for s, n in zip(*np.unique(reg["status"], return_counts=True))},
+                                 "mean_translation_error_m": float(np.mean(errors)) if errors else None, "call_and_synchronize_ms": register_ms}
+
+        stage = "graph_optimize_joint (all links)"
+        res = gpu.graph_optimize_joint([([0, 1], np.concatenate(links))])[0]
+        last = [gpu.graph_export(b) for b in (0, 1)]
+        out["second_solve"] = {"status": int(res["status"]), "links": len(links), "lm_iterations": int(res["lm_iterations"]), "final_cost": float(res["final_cost"]),
+                               "ate_m": pg.ate(np.concatenate([a["t_opt"] for a in last]), truth)}
+        stage = "done"
+    except Exception as e:  # noqa: BLE001 - the tool reports how far the chain got
+        out["failed_at"] = stage
+        out["error"] = str(e)
+    out["stage"] = stage
+    gpu.close()
     return out
 
 

@@ -1,6 +1,6 @@
 """tools/loop_register_rate.py — what one aloam_graph_register_loops call costs.
 
-    python tools/loop_register_rate.py [--shapes 1,256,2048] [--sequences 16] [--repeats 5] [--search R STEP YAW YAWSTEP] [--out FILE.json]
+    python tools/loop_register_rate.py [--shapes 1,256,2048] [--sequences 16] [--repeats 5] [--search R STEP YAW YAWSTEP] [--links] [--out FILE.json]
 
 Every sequence holds 14 hand-made keyframes of a room (loopreg.room_sample: a floor, two walls, four poles, two edges; about 300 corner and 1500 surf points fed
 per keyframe, VLP-16-sized, down-sampled by a mapping step with the solver off): 13 target nodes along 8 m and one source node entered
@@ -18,6 +18,11 @@ rocprofv3 --kernel-trace --stats.  Prints one JSON object.
 aloam_graph_search_loops with that grid (metres, metres, degrees, degrees).  Per shape, under "search": queue_ms, call_ms and stream_ms of
 the searched call, nodes per request, us_per_request_node, the mean error, and beside them ("plain") the plain call from the same far
 guesses.
+
+--links: the same shapes with every source node in ANOTHER sequence (request r: target and frame in sequence r mod B, source node 13 of
+sequence (r + 1) mod B) through aloam_graph_register_links.  The per-sequence call and the link call alternate in one process, repeat by
+repeat; per shape, under "loops" and "links": queue_ms, call_ms and stream_ms side by side, the statuses, the mean factor counts and the
+mean error.
 """
 from __future__ import annotations
 
@@ -45,6 +50,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="timed calls per shape (median, min and max are reported)")
     ap.add_argument("--search", nargs=4, type=float, metavar=("R", "STEP", "YAW", "YAWSTEP"), default=None,
                     help="time aloam_graph_search_loops with this grid (m, m, deg, deg) from far guesses, the plain call beside it")
+    ap.add_argument("--links", action="store_true",
+                    help="time aloam_graph_register_links (every source node in another sequence) alternated with the per-sequence call")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -127,6 +134,40 @@ def main():
                          best=sorted({int(b) for b in sout["best"]}), statuses={int(s): int(c) for s, c in zip(*np.unique(out["status"], return_counts=True))},
                          factors=[float(out["n_line"].mean()), float(out["n_plane"].mean())])
             res["shapes"].append({"requests": n, "search": found, "plain": plain})
+        shapes = []
+    if args.links:
+        assert B >= 2, "--links needs two sequences"
+        for n in shapes:
+            loops = gpu.graph_loop_requests([(r % B, i, j, 0, TARGETS, binding.GRAPH_POSE_ENTERED, qg, tg) for r in range(n)])
+            links = gpu.graph_link_requests([(r % B, i, 0, TARGETS, (r + 1) % B, j, binding.GRAPH_POSE_ENTERED, qg, tg) for r in range(n)])
+            dst = {k: torch.zeros(n * size, dtype=torch.uint8, device="cuda") for k in ("loops", "links")}
+            opt = gpu.graph_loop_options()
+            calls = {"loops": lambda: gpu.graph_register_loops_into(loops, dst["loops"].data_ptr(), opt),
+                     "links": lambda: gpu.graph_register_links_into(links, dst["links"].data_ptr(), opt)}
+            for call in calls.values():                                    # (warm-up: the first launch of every kernel, the link staging)
+                call()
+            gpu.synchronize()
+            times = {k: {"queue_ms": [], "call_ms": [], "stream_ms": []} for k in calls}
+            for _ in range(args.repeats):
+                for k, call in calls.items():                              # alternated: both see the same clocks and the same neighbours
+                    gpu.profile_enable(True)
+                    t0 = time.perf_counter()
+                    call()
+                    t1 = time.perf_counter()
+                    gpu.synchronize()
+                    t2 = time.perf_counter()
+                    times[k]["queue_ms"].append(1e3 * (t1 - t0)); times[k]["call_ms"].append(1e3 * (t2 - t0))
+                    times[k]["stream_ms"].append(gpu.profile()["loop_register"]["total_ms"])
+            gpu.profile_enable(False)
+            shape = {"requests": n}
+            for k in calls:
+                out = dst[k].cpu().numpy().view(binding.GRAPH_LOOP_RESULT_DTYPE)
+                shape[k] = {m: stat(v) for m, v in times[k].items()}
+                shape[k].update(statuses={int(s): int(c) for s, c in zip(*np.unique(out["status"], return_counts=True))},
+                                factors=[float(out["n_line"].mean()), float(out["n_plane"].mean())], error_m=float(np.linalg.norm(out["t"] - tz, axis=1).mean()),
+                                ms_per_request=float(np.median(times[k]["stream_ms"])) / n)
+            shape["links_over_loops_stream"] = shape["links"]["stream_ms"]["median"] / shape["loops"]["stream_ms"]["median"]
+            res["shapes"].append(shape)
         shapes = []
     for n in shapes:
         reqs = gpu.graph_loop_requests([(r % B, i, j, 0, TARGETS, binding.GRAPH_POSE_ENTERED, qg, tg) for r in range(n)])
