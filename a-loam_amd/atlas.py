@@ -201,6 +201,25 @@ def tiles_from_keyframes(q, t, clouds, leaves, voxel_filter, stats=None):
     return (np.array(tiles, TILE_DTYPE) if tiles else np.zeros(0, TILE_DTYPE)), (np.concatenate(pts) if pts else np.zeros((0, 4), np.float32))
 
 
+def tiles_from_parts(parts, leaves, voxel_filter, frames=None, stats=None):
+    """The map of a group of parts (aloam_graph_export_map_joint).  parts = [(q[k], t[k], clouds[k], frame), ...]: the poses
+    and sensor-frame clouds of a run of nodes and the frame they stand under, -1 (or None) for the poses as they are, else an index into
+    frames = [(q_A xyzw, t_A) as seven numbers, ...], in which case every pose becomes posegraph.compose(A, X_k), nothing renormalised.  The
+    result is tiles_from_keyframes of the concatenation, in part order: that is the whole definition."""
+    from .posegraph import compose
+    q, t, clouds = [], [], []
+    for pq, pt, pc, frame in parts:
+        for k in range(len(pc)):
+            qk, tk = np.asarray(pq[k], np.float64), np.asarray(pt[k], np.float64)
+            if frame is not None and frame >= 0:
+                A = np.asarray(frames[frame], np.float64).reshape(7)
+                qk, tk = compose(A[:4], A[4:], qk, tk)
+            q.append(qk)
+            t.append(tk)
+            clouds.append(pc[k])
+    return tiles_from_keyframes(q, t, clouds, leaves, voxel_filter, stats)
+
+
 def window_centre(t_w_curr):
     """The window centre that puts the sensor's cube at the middle of the window: (10, 10, 5) - cube of the f64 position."""
     s = np.asarray(t_w_curr, np.float64) + 25.0

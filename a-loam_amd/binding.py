@@ -15,6 +15,7 @@ import numpy as np
 from .records import *  # noqa: F401,F403  the records, their dtypes and the enumerators of the header: declared there, used under these names
 from .joint_records import AloamGraphJointGroup, AloamGraphLink, GRAPH_JOINT_GROUP_DTYPE, GRAPH_LINK_DTYPE  # noqa: F401  the records of the joined graphs
 from .link_records import AloamGraphLinkRequest, GRAPH_LINK_REQUEST_DTYPE  # noqa: F401  the record of the links measured on the device
+from .map_joint_records import AloamGraphMapGroup, AloamGraphMapPart, GRAPH_MAP_GROUP_DTYPE, GRAPH_MAP_PART_DTYPE  # noqa: F401  the records of the map of joined sequences
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -176,6 +177,8 @@ def lib():
             L.aloam_graph_register_links.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopOptions), vp]
             L.aloam_graph_search_links.argtypes = [vp, vp, C.c_int, C.POINTER(AloamGraphLoopSearch), C.POINTER(AloamGraphLoopOptions), vp, vp, vp]
             L.aloam_graph_propose_links.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+        if hasattr(L, "aloam_graph_export_map_joint"):     # likewise
+            L.aloam_graph_export_map_joint.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_longlong, vp, C.c_longlong, vp, vp]
         L.aloam_graph_save.argtypes = [vp, vp, C.c_int, vp, C.c_longlong, vp]
         L.aloam_graph_load.argtypes = [vp, vp, C.c_int, vp, vp]
         L.aloam_profile_enable.argtypes = [vp, C.c_int]
@@ -696,6 +699,54 @@ class Aloam:
         pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **_where(pinned))
         stats = _out_bytes(n, GRAPH_MAP_STATS_DTYPE, True)
         self.graph_export_map_into(requests, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), stats.data_ptr())
+        self.synchronize()
+        return (_records(tiles, nt, MAP_TILE_DTYPE), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy(),
+                _records(stats, n, GRAPH_MAP_STATS_DTYPE))
+
+    # ---- the map of joined sequences (atlas.tiles_from_parts holds the definition) ---------------------------------------------------------
+    @staticmethod
+    def graph_map_groups(groups):
+        """[(parts, pose), ...] with parts = [(seq, first, count, frame), ...] -> (parts of GRAPH_MAP_PART_DTYPE, groups of
+        GRAPH_MAP_GROUP_DTYPE): the parts of all groups laid end to end, every group indexing its run."""
+        parts = [tuple(int(v) for v in p) for g in groups for p in g[0]]
+        pr = np.zeros(len(parts), GRAPH_MAP_PART_DTYPE)
+        for i, p in enumerate(parts):
+            pr[i] = p
+        gr = np.zeros(len(groups), GRAPH_MAP_GROUP_DTYPE)
+        at = 0
+        for i, (ps, pose) in enumerate(groups):
+            gr[i] = (at, len(ps), int(pose), 0)
+            at += len(ps)
+        return pr, gr
+
+    def graph_export_map_joint_into(self, groups, tiles_ptr, cap_tiles, points_ptr, cap_points, offsets_ptr, stats_ptr=0, frames=None):
+        """Queue the map of each group of parts (synchronises the stream once on the way).  groups: [(parts, pose), ...] or a pair of
+        record arrays (parts, groups); frames: [n_frames, 7] = (q_A xyzw, t_A) or None.  The destinations are those of
+        graph_export_map_into, with one offset pair and one aloam_graph_map_stats per group."""
+        if isinstance(groups, tuple) and len(groups) == 2 and isinstance(groups[0], np.ndarray) and isinstance(groups[1], np.ndarray):
+            pr, gr = groups
+        else:
+            pr, gr = self.graph_map_groups(groups)
+        pr, gr = np.ascontiguousarray(pr, dtype=GRAPH_MAP_PART_DTYPE), np.ascontiguousarray(gr, dtype=GRAPH_MAP_GROUP_DTYPE)
+        fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.float64).reshape(-1, 7)
+        self._check(lib().aloam_graph_export_map_joint(self.h, _p(pr) if len(pr) else None, len(pr), _p(fr) if fr is not None and len(fr) else None,
+                                                       0 if fr is None else len(fr), _p(gr) if len(gr) else None, len(gr), _vp(tiles_ptr), int(cap_tiles),
+                                                       _vp(points_ptr), int(cap_points), _vp(offsets_ptr), _vp(stats_ptr)))
+
+    def graph_export_map_joint(self, groups, frames=None, pinned=True):
+        """The maps of `groups` ([(parts, pose), ...], parts = [(seq, first, count, frame), ...]): a size query, pinned destinations (device
+        memory with pinned=False), then the call and a synchronise.  Returns (tiles, points, offsets, stats) as graph_export_map does, with
+        one row of offsets and stats per group."""
+        import torch
+        n = len(groups)
+        off = torch.zeros(2 * (n + 1), dtype=torch.int64, pin_memory=True)
+        self.graph_export_map_joint_into(groups, 0, 0, 0, 0, off.data_ptr(), frames=frames)
+        self.synchronize()
+        nt, npts = int(off[n]), int(off[2 * n + 1])
+        tiles = _out_bytes(nt, MAP_TILE_DTYPE, pinned)
+        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, **_where(pinned))
+        stats = _out_bytes(n, GRAPH_MAP_STATS_DTYPE, True)
+        self.graph_export_map_joint_into(groups, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), stats.data_ptr(), frames=frames)
         self.synchronize()
         return (_records(tiles, nt, MAP_TILE_DTYPE), pts.cpu().numpy()[:npts].copy(), off.numpy().reshape(2, n + 1).copy(),
                 _records(stats, n, GRAPH_MAP_STATS_DTYPE))

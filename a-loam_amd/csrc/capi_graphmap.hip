@@ -8,7 +8,7 @@
 
 #include "capi_internal.hpp"
 
-static int require_keyframes(aloam_ctx* c) {
+int aloam::require_keyframes(aloam_ctx* c) {
   if (!c->kf.on) { c->err = "keyframe clouds are not enabled (aloam_graph_keyframes_enable)"; return ALOAM_E_STATE; }
   return ALOAM_OK;
 }
@@ -74,6 +74,134 @@ int keyframes_dropped_since(aloam_ctx* c, long long* fresh) {
   for (int b = 0; b < c->B; ++b) dropped += cnt[(size_t)b * kKfInts + kKfDroppedNodes];
   *fresh = dropped - c->kf.dropped_reported;
   c->kf.dropped_reported = dropped;
+  return ALOAM_OK;
+}
+
+// The point scratch of a map export, sized for the host's bounds: transformed points, grouped points, directory slots.
+int graph_map_scratch(aloam_ctx* c, long long bound_points) {
+  if (const int rc = grow_together(c, c->gm.world, c->gm.grouped, std::max<long long>(bound_points, 1))) return rc;
+  return c->gm.slot.grow(c, std::max<long long>(bound_points, 1));
+}
+
+// The half of a map export that does not care whether a key's group came from a request or from a group of parts: the directory grown
+// until the transform fits it, its read-back and sort, the segment and job layout, the rounds, the pool growth, the grouping pass, the
+// filter and the emit.  n groups (requests, or groups of parts) of n_pieces pieces; `passes` launches the two passes over the piece table.
+int graph_map_run(aloam_ctx* c, int n, int n_pieces, int* d_outside, int* d_flags, const GmPasses& passes, const GmDst& dst, const char* unit) {
+  // The directory starts at 128 slots per piece (a sweep's points fall into about a dozen cubes), or where an earlier call had to grow it
+  // to; a call whose pieces scatter over more cubes than that runs the transform again with the directory doubled, up to kGmDirMax.
+  long long dir_size = std::max<long long>(4096, c->gm.dir_hint);
+  while (dir_size < 128LL * n_pieces && dir_size < kGmDirMax) dir_size <<= 1;
+  int rc;
+  std::vector<unsigned long long> keys;
+  std::vector<int> counts;
+  for (;;) {
+    if ((rc = c->gm.dir_key.grow(c, dir_size))) return rc;
+    if ((rc = c->gm.dir_count.grow(c, dir_size))) return rc;
+    if ((rc = c->gm.dir_base.grow(c, dir_size))) return rc;
+    HIP_TRY(c, hipMemsetAsync(d_outside, 0, sizeof(int) * ((size_t)n + 1), c->stream));   // (and the flag behind it)
+    HIP_TRY(c, hipMemsetAsync(c->gm.dir_key.get(), 0xff, sizeof(unsigned long long) * (size_t)dir_size, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->gm.dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
+    {
+      ProfScope p(c, K_GRAPH_MAP);
+      passes.transform((unsigned)(dir_size - 1));
+    }
+    HIP_TRY(c, hipGetLastError());
+    // ---- the synchronisation: the directory comes back, the points stay where they are
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int overflow = 0;
+    HIP_TRY(c, hipMemcpy(&overflow, d_flags, sizeof(int), hipMemcpyDeviceToHost));
+    if (!overflow) break;
+    if (dir_size >= kGmDirMax) {
+      c->err = "the keyframes fall into more (cube, piece) pairs than the largest directory (2^22 entries) holds: export fewer nodes per call";
+      return ALOAM_E_CAPACITY;
+    }
+    dir_size <<= 1;
+  }
+  c->gm.dir_hint = dir_size;
+  keys.resize((size_t)dir_size); counts.resize((size_t)dir_size);
+  HIP_TRY(c, hipMemcpy(keys.data(), c->gm.dir_key.get(), sizeof(unsigned long long) * keys.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(counts.data(), c->gm.dir_count.get(), sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
+  struct Entry { unsigned long long key; int slot; };
+  std::vector<Entry> ent;
+  for (long long h = 0; h < dir_size; ++h) if (keys[(size_t)h] != kGmEmpty) ent.push_back(Entry{keys[(size_t)h], (int)h});
+  std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) { return a.key < b.key; });
+  // one segment per (request, class, cube): its pieces follow each other in member order
+  std::vector<AtlasMergeJob> jobs;
+  std::vector<GmSegInfo> segs;
+  std::vector<long long> dir_base((size_t)dir_size, 0);
+  std::vector<GmRequestOut> out((size_t)n + 1, GmRequestOut{0, 0, {0, 0}});
+  long long total = 0, largest = 0;
+  {
+    size_t e = 0;
+    for (int grp = 0; grp < 2 * n; ++grp) {
+      const int r = grp >> 1, cls = grp & 1;
+      if (cls == 0) out[r].seg_first = (int)jobs.size(); else out[r].surf_first = (int)jobs.size();
+      long long raw = 0;
+      while (e < ent.size() && (int)(ent[e].key >> 46) == grp) {
+        const unsigned long long cube = ent[e].key >> 16;                    // (group, cube)
+        long long seg_n = 0;
+        const long long first = total;
+        for (; e < ent.size() && (ent[e].key >> 16) == cube; ++e) { dir_base[(size_t)ent[e].slot] = total; total += counts[(size_t)ent[e].slot]; seg_n += counts[(size_t)ent[e].slot]; }
+        if (seg_n > 0x7fffffffLL) { c->err = "more than 2^31 points in one cube"; return ALOAM_E_CAPACITY; }
+        jobs.push_back(AtlasMergeJob{first, 0, (int)seg_n, cls, (int)jobs.size(), 0});
+        segs.push_back(GmSegInfo{(int)(cube & 0x3fffffffULL), r});
+        raw += seg_n; largest = std::max(largest, seg_n);
+      }
+      if (raw > 0x7fffffffLL) { c->err = std::string("more than 2^31 points of one class in a ") + unit; return ALOAM_E_CAPACITY; }
+      out[r].raw[cls] = (int)raw;
+    }
+  }
+  const int n_segs = (int)jobs.size();
+  out[(size_t)n].seg_first = n_segs; out[(size_t)n].surf_first = n_segs;
+  // a (cube, class) is filtered through the scratch of the per-cube filter, which holds a pool row: larger ones grow the pools first
+  if (largest > c->map.points && (rc = grow_map_pool(c, largest, false))) { c->err = "a cube of the exported map exceeds the pool limit"; return rc; }
+  // rounds of at most map_nsegs_max segments that fit the key scratch and the tile lists, as aloam_atlas_load plans them
+  std::vector<int> round_end;
+  for (size_t j0 = 0; j0 < jobs.size();) {
+    size_t j1 = j0; long long nkeys = 0, vtiles = 0;
+    while (j1 < jobs.size() && (long long)(j1 - j0) < c->map_nsegs_max && nkeys + jobs[j1].n <= c->map.key_cap && vtiles + (jobs[j1].n + kVoxTile - 1) / kVoxTile <= c->map.tile_cap) {
+      jobs[j1].tmp_off = nkeys; nkeys += jobs[j1].n; vtiles += (jobs[j1].n + kVoxTile - 1) / kVoxTile; ++j1;
+    }
+    if (j1 == j0) { c->err = "a cube of the exported map does not fit the voxel-filter scratch"; return ALOAM_E_CAPACITY; }
+    round_end.push_back((int)j1);
+    j0 = j1;
+  }
+  if ((rc = c->gm.jobs.grow(c, (long long)std::max(n_segs, 1)))) return rc;
+  if ((rc = c->gm.seg.grow(c, (long long)std::max(n_segs, 1)))) return rc;
+  if ((rc = c->gm.counts.grow(c, (long long)std::max(n_segs, 1)))) return rc;
+  if ((rc = c->gm.point_off.grow(c, (long long)n_segs + 1))) return rc;
+  // ---- from here everything is stream-ordered
+  HIP_TRY(c, hipMemcpyAsync(c->gm.dir_base.get(), dir_base.data(), sizeof(long long) * dir_base.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->gm.dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->gm.req_out.get(), out.data(), sizeof(GmRequestOut) * out.size(), hipMemcpyHostToDevice, c->stream));
+  if (n_segs > 0) {
+    HIP_TRY(c, hipMemcpyAsync(c->gm.jobs.get(), jobs.data(), sizeof(AtlasMergeJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->gm.seg.get(), segs.data(), sizeof(GmSegInfo) * segs.size(), hipMemcpyHostToDevice, c->stream));
+  }
+  {
+    ProfScope p(c, K_GRAPH_MAP);
+    passes.group();
+    int j0 = 0;
+    for (const int j1 : round_end) {
+      const VoxArgs v = vox_args(c, j1 - j0, c->map.cube_levels);
+      AtlasMergeArgs m{};
+      m.jobs = c->gm.jobs.get() + j0; m.n_jobs = j1 - j0; m.points[0] = c->gm.grouped.get(); m.points[1] = c->gm.grouped.get(); m.counts = c->gm.counts.get();
+      m.leaf[0] = c->map_line_res; m.leaf[1] = c->map_plane_res;
+      HIP_TRY(c, hipMemsetAsync(c->d_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));
+      launch_atlas_merge_segments(m, v, c->stream);
+      launch_voxel_filter(v, c->map.tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
+      j0 = j1;
+    }
+    GmEmitArgs e{};
+    e.n = n; e.n_segs = n_segs; e.req = c->gm.req_out.get(); e.jobs = c->gm.jobs.get(); e.seg = c->gm.seg.get(); e.counts = c->gm.counts.get();
+    e.point_off = c->gm.point_off.get(); e.outside = d_outside; e.grouped = c->gm.grouped.get();
+    e.tiles_dst = static_cast<aloam_map_tile*>(dst.tiles); e.cap_tiles = dst.tiles ? dst.cap_tiles : 0;
+    e.points_dst = static_cast<float4*>(dst.points); e.cap_points = dst.points ? dst.cap_points : 0;
+    e.dst_off = static_cast<long long*>(dst.offsets); e.stats = static_cast<aloam_graph_map_stats*>(dst.stats);
+    launch_graph_map_emit(e, c->stream);
+  }
+  HIP_TRY(c, hipGetLastError());
+  c->gm.last_raw = total; c->gm.last_segs = n_segs;
   return ALOAM_OK;
 }
 
@@ -183,8 +311,7 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
   }
   piece_first[2 * (size_t)n] = n_pieces;
   int rc;
-  if ((rc = grow_together(c, c->gm.world, c->gm.grouped, std::max<long long>(bound_points, 1)))) return rc;
-  if ((rc = c->gm.slot.grow(c, std::max<long long>(bound_points, 1)))) return rc;
+  if ((rc = graph_map_scratch(c, bound_points))) return rc;
   if ((rc = c->gm.req.grow(c, (long long)std::max(n, 1)))) return rc;
   if ((rc = c->gm.req_out.grow(c, (long long)n + 1))) return rc;
   if ((rc = c->gm.ints.grow(c, 3LL * n + 2))) return rc;   // piece_first [2 n + 1], outside [n], flags [1]
@@ -194,128 +321,20 @@ int aloam_graph_export_map(aloam_ctx* c, const aloam_graph_map_request* req, int
   if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->gm.req.get(), rq.data(), sizeof(GmRequest) * (size_t)n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(d_piece_first, piece_first.data(), sizeof(int) * piece_first.size(), hipMemcpyHostToDevice, c->stream));
   c->gm.last_segs = -1;                                    // the scratch of the last call's algorithmic bytes is about to be reused
-  // The directory starts at 128 slots per piece (a sweep's points fall into about a dozen cubes), or where an earlier call had to grow it
-  // to; a call whose pieces scatter over more cubes than that runs the transform again with the directory doubled, up to kGmDirMax.
-  long long dir_size = std::max<long long>(4096, c->gm.dir_hint);
-  while (dir_size < 128LL * n_pieces && dir_size < kGmDirMax) dir_size <<= 1;
   GmArgs g{};
-  std::vector<unsigned long long> keys;
-  std::vector<int> counts;
-  for (;;) {
-    if ((rc = c->gm.dir_key.grow(c, dir_size))) return rc;
-    if ((rc = c->gm.dir_count.grow(c, dir_size))) return rc;
-    if ((rc = c->gm.dir_base.grow(c, dir_size))) return rc;
-    HIP_TRY(c, hipMemsetAsync(d_outside, 0, sizeof(int) * ((size_t)n + 1), c->stream));   // (and the flag behind it)
-    HIP_TRY(c, hipMemsetAsync(c->gm.dir_key.get(), 0xff, sizeof(unsigned long long) * (size_t)dir_size, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->gm.dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
+  GmPasses passes;
+  passes.transform = [&](unsigned dir_mask) {
     g = GmArgs{};
     g.n = n; g.req = c->gm.req.get(); g.piece_first = d_piece_first; g.n_pieces = n_pieces; g.kf = kf_store(c);
     g.nodes = c->pg.nodes.get(); g.max_nodes = c->pg.max_nodes;
     g.world = c->gm.world.get(); g.slot = c->gm.slot.get(); g.grouped = c->gm.grouped.get();
-    g.dir_key = c->gm.dir_key.get(); g.dir_count = c->gm.dir_count.get(); g.dir_base = c->gm.dir_base.get(); g.dir_mask = (unsigned)(dir_size - 1);
+    g.dir_key = c->gm.dir_key.get(); g.dir_count = c->gm.dir_count.get(); g.dir_base = c->gm.dir_base.get(); g.dir_mask = dir_mask;
     g.outside = d_outside; g.flags = d_flags;
-    {
-      ProfScope p(c, K_GRAPH_MAP);
-      launch_graph_map_transform(g, c->stream);
-    }
-    HIP_TRY(c, hipGetLastError());
-    // ---- the synchronisation: the directory comes back, the points stay where they are
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int overflow = 0;
-    HIP_TRY(c, hipMemcpy(&overflow, d_flags, sizeof(int), hipMemcpyDeviceToHost));
-    if (!overflow) break;
-    if (dir_size >= kGmDirMax) {
-      c->err = "the keyframes fall into more (cube, piece) pairs than the largest directory (2^22 entries) holds: export fewer nodes per call";
-      return ALOAM_E_CAPACITY;
-    }
-    dir_size <<= 1;
-  }
-  c->gm.dir_hint = dir_size;
-  keys.resize((size_t)dir_size); counts.resize((size_t)dir_size);
-  HIP_TRY(c, hipMemcpy(keys.data(), c->gm.dir_key.get(), sizeof(unsigned long long) * keys.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(counts.data(), c->gm.dir_count.get(), sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
-  struct Entry { unsigned long long key; int slot; };
-  std::vector<Entry> ent;
-  for (long long h = 0; h < dir_size; ++h) if (keys[(size_t)h] != kGmEmpty) ent.push_back(Entry{keys[(size_t)h], (int)h});
-  std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) { return a.key < b.key; });
-  // one segment per (request, class, cube): its pieces follow each other in member order
-  std::vector<AtlasMergeJob> jobs;
-  std::vector<GmSegInfo> segs;
-  std::vector<long long> dir_base((size_t)dir_size, 0);
-  std::vector<GmRequestOut> out((size_t)n + 1, GmRequestOut{0, 0, {0, 0}});
-  long long total = 0, largest = 0;
-  {
-    size_t e = 0;
-    for (int grp = 0; grp < 2 * n; ++grp) {
-      const int r = grp >> 1, cls = grp & 1;
-      if (cls == 0) out[r].seg_first = (int)jobs.size(); else out[r].surf_first = (int)jobs.size();
-      long long raw = 0;
-      while (e < ent.size() && (int)(ent[e].key >> 46) == grp) {
-        const unsigned long long cube = ent[e].key >> 16;                    // (group, cube)
-        long long seg_n = 0;
-        const long long first = total;
-        for (; e < ent.size() && (ent[e].key >> 16) == cube; ++e) { dir_base[(size_t)ent[e].slot] = total; total += counts[(size_t)ent[e].slot]; seg_n += counts[(size_t)ent[e].slot]; }
-        if (seg_n > 0x7fffffffLL) { c->err = "more than 2^31 points in one cube"; return ALOAM_E_CAPACITY; }
-        jobs.push_back(AtlasMergeJob{first, 0, (int)seg_n, cls, (int)jobs.size(), 0});
-        segs.push_back(GmSegInfo{(int)(cube & 0x3fffffffULL), r});
-        raw += seg_n; largest = std::max(largest, seg_n);
-      }
-      if (raw > 0x7fffffffLL) { c->err = "more than 2^31 points of one class in a request"; return ALOAM_E_CAPACITY; }
-      out[r].raw[cls] = (int)raw;
-    }
-  }
-  const int n_segs = (int)jobs.size();
-  out[(size_t)n].seg_first = n_segs; out[(size_t)n].surf_first = n_segs;
-  // a (cube, class) is filtered through the scratch of the per-cube filter, which holds a pool row: larger ones grow the pools first
-  if (largest > c->map.points && (rc = grow_map_pool(c, largest, false))) { c->err = "a cube of the exported map exceeds the pool limit"; return rc; }
-  // rounds of at most map_nsegs_max segments that fit the key scratch and the tile lists, as aloam_atlas_load plans them
-  std::vector<int> round_end;
-  for (size_t j0 = 0; j0 < jobs.size();) {
-    size_t j1 = j0; long long nkeys = 0, vtiles = 0;
-    while (j1 < jobs.size() && (long long)(j1 - j0) < c->map_nsegs_max && nkeys + jobs[j1].n <= c->map.key_cap && vtiles + (jobs[j1].n + kVoxTile - 1) / kVoxTile <= c->map.tile_cap) {
-      jobs[j1].tmp_off = nkeys; nkeys += jobs[j1].n; vtiles += (jobs[j1].n + kVoxTile - 1) / kVoxTile; ++j1;
-    }
-    if (j1 == j0) { c->err = "a cube of the exported map does not fit the voxel-filter scratch"; return ALOAM_E_CAPACITY; }
-    round_end.push_back((int)j1);
-    j0 = j1;
-  }
-  if ((rc = c->gm.jobs.grow(c, (long long)std::max(n_segs, 1)))) return rc;
-  if ((rc = c->gm.seg.grow(c, (long long)std::max(n_segs, 1)))) return rc;
-  if ((rc = c->gm.counts.grow(c, (long long)std::max(n_segs, 1)))) return rc;
-  if ((rc = c->gm.point_off.grow(c, (long long)n_segs + 1))) return rc;
-  // ---- from here everything is stream-ordered
-  HIP_TRY(c, hipMemcpyAsync(c->gm.dir_base.get(), dir_base.data(), sizeof(long long) * dir_base.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->gm.dir_count.get(), 0, sizeof(int) * (size_t)dir_size, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->gm.req_out.get(), out.data(), sizeof(GmRequestOut) * out.size(), hipMemcpyHostToDevice, c->stream));
-  if (n_segs > 0) {
-    HIP_TRY(c, hipMemcpyAsync(c->gm.jobs.get(), jobs.data(), sizeof(AtlasMergeJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->gm.seg.get(), segs.data(), sizeof(GmSegInfo) * segs.size(), hipMemcpyHostToDevice, c->stream));
-  }
-  {
-    ProfScope p(c, K_GRAPH_MAP);
-    launch_graph_map_group(g, c->stream);
-    int j0 = 0;
-    for (const int j1 : round_end) {
-      const VoxArgs v = vox_args(c, j1 - j0, c->map.cube_levels);
-      AtlasMergeArgs m{};
-      m.jobs = c->gm.jobs.get() + j0; m.n_jobs = j1 - j0; m.points[0] = c->gm.grouped.get(); m.points[1] = c->gm.grouped.get(); m.counts = c->gm.counts.get();
-      m.leaf[0] = c->map_line_res; m.leaf[1] = c->map_plane_res;
-      HIP_TRY(c, hipMemsetAsync(c->d_vox_counters.get() + 4, 0, 4 * sizeof(int), c->stream));
-      launch_atlas_merge_segments(m, v, c->stream);
-      launch_voxel_filter(v, c->map.tile_bound, c->stream);   // always the input-order sum, whatever aloam_set_voxel_sum_order says
-      j0 = j1;
-    }
-    GmEmitArgs e{};
-    e.n = n; e.n_segs = n_segs; e.req = c->gm.req_out.get(); e.jobs = c->gm.jobs.get(); e.seg = c->gm.seg.get(); e.counts = c->gm.counts.get();
-    e.point_off = c->gm.point_off.get(); e.outside = d_outside; e.grouped = c->gm.grouped.get();
-    e.tiles_dst = static_cast<aloam_map_tile*>(d_tiles); e.cap_tiles = d_tiles ? cap_tiles : 0;
-    e.points_dst = static_cast<float4*>(d_pts); e.cap_points = d_pts ? cap_points : 0;
-    e.dst_off = static_cast<long long*>(d_off); e.stats = static_cast<aloam_graph_map_stats*>(d_stats);
-    launch_graph_map_emit(e, c->stream);
-  }
-  HIP_TRY(c, hipGetLastError());
-  c->gm.last_raw = total; c->gm.last_segs = n_segs;
-  return ALOAM_OK;
+    launch_graph_map_transform(g, c->stream);
+  };
+  passes.group = [&] { launch_graph_map_group(g, c->stream); };
+  GmDst dst{d_tiles, cap_tiles, d_pts, cap_points, d_off, d_stats};
+  return graph_map_run(c, n, n_pieces, d_outside, d_flags, passes, dst, "request");
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include "graphjoint_kernels.hpp"
 #include "graphlink_kernels.hpp"
 #include "graphmap_kernels.hpp"
+#include "graphmapjoint_kernels.hpp"
 #include "graphmarginal_kernels.hpp"
 #include "graphpropose_kernels.hpp"
 #include "graphrecord_kernels.hpp"
@@ -156,6 +157,7 @@ struct GraphMapScratch {             // the map at the graph's poses (aloam_grap
   Scratch<int> slot;                                                // directory slot of every transformed point
   Scratch<unsigned long long> dir_key; Scratch<int> dir_count; Scratch<long long> dir_base;   // the directory of (request, class, cube, piece): keys, counts / cursors, bases
   Scratch<GmRequest> req; Scratch<GmRequestOut> req_out;
+  Scratch<GmPart> parts; Scratch<double> frames;                    // aloam_graph_export_map_joint: the parts of its groups and the frames they name
   Scratch<int> ints;                                                // first piece per (request, class), points outside per request, the overflow flag
   Scratch<AtlasMergeJob> jobs;                                      // one per (request, class, cube), with its filtered size and point offset
   Scratch<GmSegInfo> seg; Scratch<int> counts; Scratch<long long> point_off;
@@ -531,6 +533,14 @@ int keyframe_add_check(aloam_ctx* c, const int* seqs, int n);        // ALOAM_E_
 void queue_keyframe_capture(aloam_ctx* c, int n);                    // k_keyframe_capture behind k_graph_add_nodes, for the items in pg.add
 int queue_keyframe_rewind(aloam_ctx* c, const int* seqs, int n);     // aloam_graph_clear: the listed cursors back to 0, in stream order
 int keyframes_dropped_since(aloam_ctx* c, long long* fresh);
+int require_keyframes(aloam_ctx* c);                                 // ALOAM_E_STATE before aloam_graph_keyframes_enable
+int graph_map_scratch(aloam_ctx* c, long long bound_points);         // world / grouped / slot of a map export, sized for the host's bounds
+// What aloam_graph_export_map and aloam_graph_export_map_joint share: everything behind the layout of the piece table.  The two passes
+// over that table are the caller's (per request, or per part); the transform is handed the directory's mask and reads the directory's
+// arrays from c->gm at that moment (they grow), the grouping pass runs with what the last transform ran with.
+struct GmPasses { std::function<void(unsigned dir_mask)> transform; std::function<void()> group; };
+struct GmDst { void* tiles; long long cap_tiles; void* points; long long cap_points; void* offsets; void* stats; };   // classified destinations (nullptr: not given)
+int graph_map_run(aloam_ctx* c, int n, int n_pieces, int* d_outside, int* d_flags, const GmPasses& passes, const GmDst& dst, const char* unit);
 // capi_seq.hip: the one "does sequence b take part in this step", a stage's mask, and what happens to a sequence, each with its whole consequence
 inline bool takes_part(const aloam_ctx* c, int b) { return c->all_active || c->seq[b].active; }
 struct StageMask {

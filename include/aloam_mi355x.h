@@ -1344,6 +1344,55 @@ int aloam_graph_optimize_joint_robust(aloam_ctx* ctx, const int* members, const 
                                       aloam_graph_robust_result* dst /* [n_groups] */, double* weights_dst /* [n_groups][weights_stride] or NULL */,
                                       long long weights_stride);
 
+/* ---- the map of joined sequences ---------------------------------------------------------------------------------------------------------------
+ * aloam_graph_optimize_joint puts the estimates of several sequences into one frame; aloam_graph_export_map still builds a map from the
+ * nodes of ONE sequence, so two sessions that share a frame come out as two maps, with every (cube, class) they both reach present twice
+ * and filtered twice.  This call makes the one map: tiles from the keyframes of several sequences, every (cube, class) filtered once over
+ * all of its members.  Opt-in and beside the reference: a context that never calls it allocates nothing for it and launches exactly what
+ * it launched before, and aloam_graph_export_map queues exactly the launches it queued before.  a-loam_amd/atlas.py (tiles_from_parts)
+ * restates the definition; DESIGN.md §7za.
+ *
+ * A part is nodes [first, first + count) of sequence seq under a frame; a group is a run of parts, in the caller's order, with one choice of
+ * pose.  The call reads no group membership and nothing about joins is stored on the device: a part is any node range of any sequence, a
+ * sequence may appear in several parts and in several groups, ranges may overlap, count = 0 is allowed.
+ *
+ * The map of group g is the map aloam_graph_export_map defines, made of the concatenation of its parts' nodes in part order, nodes in node
+ * order inside each part: every point through associate-to-map with its node's pose X_k ((q, t) or (q_opt, t_opt), by the group's pose),
+ * the cube of the result, the members of a (cube, class) in that order, one pcl::VoxelGrid pass with the class's leaf and the input-order
+ * sum - always, also when only one node contributes -, corner tiles first, then surf tiles, each ascending in cube, frame 0; points whose
+ * cube lies outside -512 .. 511 on some axis are left out and counted.  Offsets, both caps and the size query, written, raw_points and
+ * outside, the single synchronisation after the transform pass, the growing directory and the growing pools are those of
+ * aloam_graph_export_map with "request" read as "group": dst_offsets[0 .. n_groups] holds the tile offsets, dst_offsets[n_groups + 1 ..
+ * 2 n_groups + 1] the point offsets.
+ * Frames.  frame = -1: the part's poses are used as stored, no arithmetic is applied, the bits are X_k's.  frame = f >= 0: X_k' = A o X_k
+ *   with A = frames[f] = (q_A xyzw, t_A), the compose of the joined-graphs section: q' = quat_mul(q_A, q_k), t' = quat_rotate(q_A, t_k) + t_A,
+ *   every f64 operation rounded on its own, nothing renormalised.  Use -1 for members that a joint solve has already aligned, an index for
+ *   a session that is not aligned yet (A from a first link, as in aloam_graph_propose_links).
+ * The bytes written for a group do not depend on n_groups, on its position, on the other groups or on the directory's size.  A group of one
+ *   part with frame = -1 is byte for byte aloam_graph_export_map of (seq, first, count, pose); a group whose parts are adjacent ranges of
+ *   one sequence ([a, b) then [b, c), frame = -1) is the group of the single part [a, c).
+ * Checked before anything is queued, ALOAM_E_ARG with nothing changed and the field named in aloam_last_error: seq in range; 0 <= first,
+ *   0 <= count, first + count <= the sequence's nodes; frame in [-1, n_frames); frames finite with q_A unit to 1e-6; pose 0 or 1 and pad 0;
+ *   the groups tile parts contiguously and in order; part_count >= 0; n_groups <= 32768; NULL lists and negative counts; the destinations
+ *   as for the exports.  ALOAM_E_STATE before aloam_graph_keyframes_enable.  n_groups = 0 is ALOAM_OK, with the offsets written.  A
+ *   (group, class) whose parts are bounded, on the host, by more than 65536 pieces of 4096 points is ALOAM_E_CAPACITY before anything is
+ *   queued, with the group named.  Timed under the profiling slot graph_map. */
+struct aloam_graph_map_part {                 /* 16 bytes: nodes [first, first + count) of sequence seq                                 */
+  int seq, first, count, frame;               /* frame: -1 = the poses as stored, else an index into frames                             */
+};
+typedef struct aloam_graph_map_part aloam_graph_map_part;
+struct aloam_graph_map_group {                /* 16 bytes: parts [part_first, part_first + part_count) make one map                     */
+  int part_first, part_count, pose, pad;      /* pose: ALOAM_GRAPH_POSE_ENTERED or ALOAM_GRAPH_POSE_OPTIMIZED; pad: 0                   */
+};
+typedef struct aloam_graph_map_group aloam_graph_map_group;
+int aloam_graph_export_map_joint(aloam_ctx* ctx, const aloam_graph_map_part* parts, int n_parts,
+                                 const double* frames /* [n_frames][7] or NULL */, int n_frames,
+                                 const aloam_graph_map_group* groups, int n_groups,
+                                 aloam_map_tile* tiles_dst, long long cap_tiles,
+                                 float* points_dst_xyzw, long long cap_points,
+                                 long long* dst_offsets /* [2][n_groups + 1] */,
+                                 aloam_graph_map_stats* stats_dst /* [n_groups] or NULL */);
+
 /* ---- links measured on the device: register, search and propose between sequences ----------------------------------------------------------
  * aloam_graph_optimize_joint consumes links; this section measures them.  The chain propose -> search and register -> gate -> link ->
  * joint solve runs between two sequences with the same stream-ordered, batched calls that run it inside one: no atlas, no spare sequence

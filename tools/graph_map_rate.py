@@ -1,6 +1,6 @@
 """tools/graph_map_rate.py — what one aloam_graph_export_map call costs.
 
-    python tools/graph_map_rate.py [--cases 64x256,8x2048,1x8192] [--repeats 5] [--host-keyframes 64] [--out FILE.json]
+    python tools/graph_map_rate.py [--cases 64x256,8x2048,1x8192] [--repeats 5] [--host-keyframes 64] [--joint M] [--out FILE.json]
 
 Per case (sequences x keyframes): every sequence drives a straight line, one keyframe every --spacing metres; each keyframe is a synthetic
 HDL-64 stack of about 1.5 k corner and 6 k surf points (random returns in an 80 m square, fed with aloam_set_last, down-sampled by a frozen
@@ -9,6 +9,9 @@ poses, into device memory: a size query, and --repeats timed calls.  Reported pe
   call_ms    host clock around aloam_graph_export_map + aloam_synchronize (the whole call, its one synchronisation and read-back included)
   stream_ms  hipEvent intervals of the graph_map profiling slot: the stream-ordered parts (transform; grouping, voxel filter and emit)
   hbm_ms     the call's algorithmic bytes at the 8 TB/s HBM peak
+With --joint M the sequences are also taken M at a time as one group of M parts (aloam_graph_export_map_joint, frame -1; the last group
+takes what is left), timed the same way and alternated, call by call, with the per-request call over the same nodes: the pieces are the
+same, so the two differ by the filter seeing merged cubes (neighbouring sequences drive 60 m apart and share cubes).  Reported under "joint".
 The host time of the model (atlas.tiles_from_keyframes with a numpy voxel filter) on --host-keyframes keyframes of one sequence is printed
 beside them.  Prints one JSON object.
 """
@@ -57,6 +60,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="timed calls per case (median, min and max are reported)")
     ap.add_argument("--spacing", type=float, default=2.0, help="metres between keyframes")
     ap.add_argument("--host-keyframes", type=int, default=64, help="keyframes of one sequence the numpy model is timed on (0 = skip)")
+    ap.add_argument("--joint", type=int, default=0, metavar="M", help="also time aloam_graph_export_map_joint with the sequences taken M at a time as one group of M parts (0 = off)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -87,32 +91,45 @@ def main():
         gpu.synchronize()
         held = gpu.graph_keyframe_info(0)
         reqs = gpu.graph_map_requests([(b, 0, frames, binding.GRAPH_POSE_ENTERED) for b in ids])
-        off = torch.zeros(2 * (batch + 1), dtype=torch.int64, pin_memory=True)
-        t0 = time.perf_counter()
-        gpu.graph_export_map_into(reqs, 0, 0, 0, 0, off.data_ptr())
-        gpu.synchronize()
-        query_ms = 1e3 * (time.perf_counter() - t0)         # (the first call also allocates the scratch)
-        nt, npts = int(off[batch]), int(off[2 * batch + 1])
-        tiles = torch.zeros(max(1, nt) * 32, dtype=torch.uint8, device="cuda")
-        pts = torch.zeros((max(1, npts), 4), dtype=torch.float32, device="cuda")
-        stats = torch.zeros(batch * 32, dtype=torch.uint8, pin_memory=True)
-        call_ms, stream_ms, bytes_ = [], [], 0.0
-        for _ in range(args.repeats):
-            gpu.profile_enable(True)
+        calls = [("request", batch, lambda *dst: gpu.graph_export_map_into(reqs, *dst))]
+        if args.joint > 0:
+            lists = gpu.graph_map_groups([([(b, 0, frames, -1) for b in ids[g:g + args.joint]], binding.GRAPH_POSE_ENTERED) for g in range(0, batch, args.joint)])
+            calls.append(("joint", len(lists[1]), lambda *dst: gpu.graph_export_map_joint_into(lists, *dst)))
+        sized = []
+        for name, n, call in calls:                         # a size query each, then the destinations in device memory
+            off = torch.zeros(2 * (n + 1), dtype=torch.int64, pin_memory=True)
             t0 = time.perf_counter()
-            gpu.graph_export_map_into(reqs, tiles.data_ptr(), nt, pts.data_ptr(), npts, off.data_ptr(), stats.data_ptr())
+            call(0, 0, 0, 0, off.data_ptr())
             gpu.synchronize()
-            call_ms.append(1e3 * (time.perf_counter() - t0))
-            prof = gpu.profile()["graph_map"]
-            stream_ms.append(prof["total_ms"])
-            bytes_ = prof["bytes_per_launch"]
+            query_ms = 1e3 * (time.perf_counter() - t0)     # (the first call also allocates the scratch)
+            nt, npts = int(off[n]), int(off[2 * n + 1])
+            sized.append({"name": name, "n": n, "call": call, "off": off, "query_ms": query_ms, "nt": nt, "npts": npts,
+                          "tiles": torch.zeros(max(1, nt) * 32, dtype=torch.uint8, device="cuda"), "pts": torch.zeros((max(1, npts), 4), dtype=torch.float32, device="cuda"),
+                          "stats": torch.zeros(n * 32, dtype=torch.uint8, pin_memory=True), "call_ms": [], "stream_ms": [], "bytes": 0.0})
+        for _ in range(args.repeats):                       # alternated, call by call, in this one process
+            for c in sized:
+                gpu.profile_enable(True)
+                t0 = time.perf_counter()
+                c["call"](c["tiles"].data_ptr(), c["nt"], c["pts"].data_ptr(), c["npts"], c["off"].data_ptr(), c["stats"].data_ptr())
+                gpu.synchronize()
+                c["call_ms"].append(1e3 * (time.perf_counter() - t0))
+                prof = gpu.profile()["graph_map"]
+                c["stream_ms"].append(prof["total_ms"])
+                c["bytes"] = prof["bytes_per_launch"]
         gpu.profile_enable(False)
-        st = stats.numpy().view(binding.GRAPH_MAP_STATS_DTYPE)
-        res["cases"].append({"sequences": batch, "keyframes": frames, "points_per_keyframe": [held["points"][0] / frames, held["points"][1] / frames],
-                             "raw_points": int(st["raw_points"].sum()), "tiles": nt, "points": npts, "written": int(st["written"].sum()),
-                             "size_query_ms": query_ms, "call_ms": {"median": float(np.median(call_ms)), "min": min(call_ms), "max": max(call_ms)},
-                             "stream_ms": {"median": float(np.median(stream_ms)), "min": min(stream_ms), "max": max(stream_ms)},
-                             "algorithmic_bytes": bytes_, "hbm_ms": 1e3 * bytes_ / HBM_PEAK, "pool_points": gpu.map_pool_info()["pool_points"]})
+
+        def figures(c):
+            st = c["stats"].numpy().view(binding.GRAPH_MAP_STATS_DTYPE)
+            return {"raw_points": int(st["raw_points"].sum()), "tiles": c["nt"], "points": c["npts"], "written": int(st["written"].sum()), "size_query_ms": c["query_ms"],
+                    "call_ms": {"median": float(np.median(c["call_ms"])), "min": min(c["call_ms"]), "max": max(c["call_ms"])},
+                    "stream_ms": {"median": float(np.median(c["stream_ms"])), "min": min(c["stream_ms"]), "max": max(c["stream_ms"])},
+                    "algorithmic_bytes": c["bytes"], "hbm_ms": 1e3 * c["bytes"] / HBM_PEAK}
+        row = {"sequences": batch, "keyframes": frames, "points_per_keyframe": [held["points"][0] / frames, held["points"][1] / frames]}
+        row.update(figures(sized[0]))
+        if args.joint > 0:
+            row["joint"] = dict(figures(sized[1]), groups=sized[1]["n"], parts_per_group=min(args.joint, batch))
+        row["pool_points"] = gpu.map_pool_info()["pool_points"]
+        res["cases"].append(row)
         if args.host_keyframes and "host_model" not in res:
             n = min(args.host_keyframes, frames)
             nodes = gpu.graph_export(0, 0, n)

@@ -62,6 +62,8 @@ second session from the identity, so it lives in a frame of its own.  Then, with
      NULL, the sessions share a frame now), aloam_graph_register_links of all candidates in one call; a link is kept when its status is OK
      and Z moved less than a metre from the proposal's guess (aloam_graph_marginals works inside one sequence and does not apply across two);
   4. the second joint solve, all links, no alignment;
+  after each joint solve, the joined map (aloam_graph_export_map_joint of both sessions as one group at the optimised poses: tiles, points)
+  beside the two per-session maps laid end to end, and the number of (cube, class) keys both sessions reach;
   5. printed against ground truth: the first link's error, the ATE of both sessions after each solve, the links kept.
 """
 from __future__ import annotations
@@ -116,7 +118,7 @@ def main():
     ap.add_argument("--window", type=int, default=None, metavar="N", help="only drive, twice: one graph keeps every keyframe, the other is trimmed to N (aloam_graph_trim) once it holds more, the map "
                     "tiles of the nodes about to go exported first; loops are proposed by proximity and registered on the device in both; prints the two ATEs")
     ap.add_argument("--two-sessions", action="store_true", help="only drive: the drive cut into two sessions in two slots, the second in a frame of its own; a first link from a place match "
-                    "and aloam_graph_search_links, a joint solve with align, more links from aloam_graph_propose_links and aloam_graph_register_links, a second joint solve; prints both ATEs")
+                    "and aloam_graph_search_links, a joint solve with align, more links from aloam_graph_propose_links and aloam_graph_register_links, a second joint solve; prints both ATEs and, after each solve, the joined map (aloam_graph_export_map_joint) beside the two per-session maps")
     args = ap.parse_args()
     if args.two_sessions and args.neighbours < 0:
         ap.error("--two-sessions needs --neighbours >= 0")
@@ -286,6 +288,16 @@ def window(args, mods, scans, q_true, t_true, frames, every):
     return out
 
 
+def joined_map_figures(gpu, binding, n0, n1):
+    """After a joint solve both sessions' estimates share a frame: the joined map (aloam_graph_export_map_joint, one group of the two
+    sessions, every (cube, class) filtered once) beside the two per-session maps laid end to end, and the keys both sessions reach."""
+    P = binding.GRAPH_POSE_OPTIMIZED
+    jt, jp, _, _ = gpu.graph_export_map_joint([([(0, 0, n0, -1), (1, 0, n1, -1)], P)])
+    st, sp, off, _ = gpu.graph_export_map([(0, 0, n0, P), (1, 0, n1, P)])
+    keys = [{(tuple(t["cube"].tolist()), int(t["feature_class"])) for t in st[off[0, r]:off[0, r + 1]]} for r in (0, 1)]
+    return {"joined": {"tiles": len(jt), "points": len(jp)}, "per_session_concatenated": {"tiles": len(st), "points": len(sp)}, "keys_both_sessions_reach": len(keys[0] & keys[1])}
+
+
 def two_sessions(args, mods, scans, q_true, t_true, frames, every):
     """The drive cut after its first lap: session one in slot 0, session two in slot 1 from the identity.  Links are measured on the device
     between the slots (aloam_graph_search_links, aloam_graph_propose_links, aloam_graph_register_links) and solved jointly."""
@@ -354,6 +366,8 @@ def two_sessions(args, mods, scans, q_true, t_true, frames, every):
         after = [gpu.graph_export(b) for b in (0, 1)]
         out["first_solve"] = {"status": int(res["status"]), "lm_iterations": int(res["lm_iterations"]), "final_cost": float(res["final_cost"]),
                               "ate_m": pg.ate(np.concatenate([a["t_opt"] for a in after]), truth)}
+        stage = "graph_export_map_joint (first solve)"
+        out["first_solve"]["map"] = joined_map_figures(gpu, binding, n0, n1)
 
         stage = "graph_propose_links"
         t0 = time.perf_counter()
@@ -384,6 +398,8 @@ def two_sessions(args, mods, scans, q_true, t_true, frames, every):
         last = [gpu.graph_export(b) for b in (0, 1)]
         out["second_solve"] = {"status": int(res["status"]), "links": len(links), "lm_iterations": int(res["lm_iterations"]), "final_cost": float(res["final_cost"]),
                                "ate_m": pg.ate(np.concatenate([a["t_opt"] for a in last]), truth)}
+        stage = "graph_export_map_joint (all links)"
+        out["second_solve"]["map"] = joined_map_figures(gpu, binding, n0, n1)
         stage = "done"
     except Exception as e:  # noqa: BLE001 - the tool reports how far the chain got
         out["failed_at"] = stage
